@@ -10,7 +10,9 @@ One process per GPU; frames are independent, so ranks share nothing on the data 
 torch.distributed (RCCL) is used for the barriers and the max-over-ranks time only (plus the optional descriptor
 all-gather of config C5, --config C5).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step =
+the wall time of one timed step, ...).  A plain run does only that: set up, warm up, time --steps steps, print the line
+(--dump-outputs DIR: and write what the last timed step computed).  With --full the line also holds
   "roofline":      dominant kernel: algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak (the contract's fraction),
                    roofline.valu = the same launch against the chip's VALU issue rate (what actually limits it),
                    roofline.streaming = the three streaming kernels of SURVEY 8d against the HBM peak
@@ -72,10 +74,10 @@ def parse(argv=None):
     ap.add_argument("--cpu-cores", type=int, default=0, help="worker processes of the CPU baseline (0 = all cores)")
     ap.add_argument("--cpu-mt-frames", type=int, default=200,
                     help="frames of the cpu_mt leg (one pipeline with the reference's thread structure; SURVEY 8d: mean +- std over >= 200)")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--no-profile", action="store_true", help="--full: do not bracket kernels with HIP events")
     ap.add_argument("--sustain-ms", type=float, default=6000.0,
                     help="extras: repeat the timed step back to back for this long and report the sustained rate (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip latency / H2D-inclusive / cpu legs (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip latency / H2D-inclusive / cpu legs (profiling runs)")
     ap.add_argument("--latency-frames", type=int, default=200)
     ap.add_argument("--h2d-steps", type=int, default=30)
     ap.add_argument("--other-steps", type=int, default=400,
@@ -103,6 +105,14 @@ def parse(argv=None):
                          "of an N-GPU launch up to the first HIP call, testable on a CPU box (tests/test_bench_contract.py)")
     ap.add_argument("--allgather", action="store_true",
                     help="RCCL all-gather of every rank's descriptor blocks after each step (implied by --config C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the HIP-event stage table and rooflines, the shader clock probe, "
+                         "and (stereo, one rank, unless --no-extras) the sustained, natural-image, latency, H2D-inclusive, "
+                         "other-configuration, default-queue and CPU-baseline legs.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (keypoints, descriptors, stereo / "
+                         "fisheye association, C5 all-gather blocks) as DIR/<name>.npy in float32, at most 64 MB in all")
     a = ap.parse_args(argv)
     if a.config == "C5":
         a.mode, a.allgather, a.distinct = "stereo", True, 8
@@ -279,9 +289,11 @@ class Workload:
 
 
 def self_launch(a):
-    """Started without a launcher but asked for N > 1 ranks (or --self-launch): become `python -m torch.distributed.run
-    --nnodes=1 --nproc-per-node N bench.py ...` -- one process per GPU, RCCL rendezvous on 127.0.0.1.  Refuses (exit 2)
-    when the node does not show N devices: a single process must never print an n_gpus = N line."""
+    """Started without a launcher but asked for N > 1 ranks (or --self-launch): run `python -m torch.distributed.run
+    --nnodes=1 --nproc-per-node N bench.py ...` as a child -- one process per GPU, RCCL rendezvous on 127.0.0.1 -- and exit
+    with its status.  A child, not an exec: the device count below has already initialised the HIP runtime in this process.
+    Refuses (exit 2) when the node does not show N devices: a single process must never print an n_gpus = N line."""
+    import subprocess
     import socket
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -298,13 +310,70 @@ def self_launch(a):
     env = dict(os.environ, ORBX_BENCH_SELF_LAUNCHED="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
+
+
+def dump_outputs(a, wl, out_dir, budget=64 << 20):
+    """--dump-outputs: what the LAST timed step computed, as a caller of that path receives it (the handle that ran it, read
+    before any further step): per image the keypoints and descriptors (images 0..B-1 left eyes, B..2B-1 right eyes), per pair
+    the stereo (uRight, depth) or fisheye association, with config C5 the gathered descriptor blocks.  float32 throughout
+    (keypoint fields x y size angle response octave class_id, descriptor bytes as 0..255); variable-length rows of all images
+    are concatenated in image order, `counts` holds the rows per image.  If the pairs of the step exceed the byte budget, a
+    fixed prefix of pairs (the same for every run with the same arguments) is written and `dump_pairs` says how many."""
+    np, orbx = wl.np, wl.orbx
+    B = a.pairs
+    h = step_plan(wl.step_no - 1, len(wl.exs), a.ring)[0]
+    ex = wl.exs[h]
+    cap = ex.capacity
+    world = wl.dist.get_world_size() if wl.dist is not None else 1
+    per_pair = 2 * cap * (7 + 32) * 4 + cap * 6 * 4 + (world * 2 * cap * 32 * 4 if wl.gathered[h] is not None else 0)
+    P = max(1, min(B, budget // per_pair))
+    imgs = list(range(P)) + list(range(B, B + P))
+    arrays = {"counts": [], "mono_left": [], "keypoints": [], "descriptors": []}
+    for i in imgs:
+        mono, kps, desc = ex.download(i)
+        arrays["counts"].append(len(kps))
+        arrays["mono_left"].append(mono)
+        arrays["keypoints"].append(np.stack([kps[f].astype(np.float32) for f in orbx.KP_DTYPE.names], 1).reshape(-1, 7))
+        arrays["descriptors"].append(desc.astype(np.float32).reshape(-1, 32))
+    out = {"counts": np.asarray(arrays["counts"], np.float32), "mono_left": np.asarray(arrays["mono_left"], np.float32),
+           "keypoints": np.concatenate(arrays["keypoints"]), "descriptors": np.concatenate(arrays["descriptors"]),
+           "dump_pairs": np.asarray([P, B], np.float32)}
+    n_left = [int(c) for c in out["counts"][:P]]
+    if a.mode == "stereo":
+        u, dep = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        us, ds = [], []
+        for p in range(P):
+            orbx._check(orbx.lib().orbx_stereo_download(ex._h, p, orbx._p(u), orbx._p(dep), cap))
+            us.append(u[:n_left[p]].copy())
+            ds.append(dep[:n_left[p]].copy())
+        out["uright"], out["depth"] = np.concatenate(us), np.concatenate(ds)
+    elif a.mode == "fisheye":
+        res = {"fisheye_matches": [], "fisheye_l2r": [], "fisheye_r2l": [], "fisheye_depth": [], "fisheye_points3d": []}
+        for p in range(P):
+            n, nd, l2r, r2l, depth, pts = orbx.fisheye_download(ex, ex, p)
+            nr = int(out["counts"][P + p])
+            res["fisheye_matches"].append(np.asarray([n, nd], np.float32))
+            res["fisheye_l2r"].append(l2r[:n_left[p]].astype(np.float32))
+            res["fisheye_r2l"].append(r2l[:nr].astype(np.float32))
+            res["fisheye_depth"].append(depth[:n_left[p]].astype(np.float32))
+            res["fisheye_points3d"].append(pts[:n_left[p]].astype(np.float32).reshape(-1, 3))
+        out.update({k: np.stack(v) if k == "fisheye_matches" else np.concatenate(v) for k, v in res.items()})
+    if wl.gathered[h] is not None:
+        wl.torch.cuda.synchronize()
+        cnt, desc = wl.gathered[h][0].cpu().numpy(), wl.gathered[h][1].cpu().numpy()
+        rows = [r * 2 * B + i for r in range(world) for i in imgs]   # rank r's block holds rows r*2B .. r*2B+2B-1
+        out["allgather_counts"] = cnt[rows].astype(np.float32)
+        out["allgather_descriptors"] = np.concatenate([desc[r, :int(cnt[r])].reshape(-1, 32) for r in rows]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, np.float32))
 
 
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or a.self_launch):
-        self_launch(a)   # does not return
+        self_launch(a)   # exits with the launcher's status
     # Exactly ONE line on stdout: libraries (RCCL prints a version banner when NCCL_DEBUG=VERSION is set, HIP /
     # libdrm print warnings) must not interleave with it, so fd 1 is pointed at stderr for the run and the JSON
     # line is written to the saved descriptor at the end.
@@ -370,7 +439,8 @@ def main():
     # alone: under overlap the small resize launches stretch more than the one FAST launch).  From here on only
     # that kernel is bracketed.
     dom = None
-    if not a.no_profile:
+    profile = a.full and not a.no_profile   # HIP-event brackets: the stage table and rooflines of --full
+    if profile:
         exs[0].profile_enable(True)
         for i in range(3):
             wl.step_no = i * len(exs)
@@ -382,7 +452,7 @@ def main():
         dom = max(wprof, key=lambda k: wprof[k][0])
         wl.step_no = 0
     for e in exs:
-        e.profile_enable(not a.no_profile, stage=dom)
+        e.profile_enable(profile, stage=dom)
     # Preheat: a step is 0.5 ms of GPU work, so W warm-up steps are over before the GPU has left its idle power state
     # (measured: 20 timed steps take 0.576 ms each after 5 warm-up steps and 0.522 ms after 60).  Untimed steps of the same
     # workload run for --preheat-ms first; the W warm-up steps follow, then the timed region, with no host-side pause.
@@ -397,10 +467,13 @@ def main():
                 step()
             preheat_steps += len(exs)
             exs[0].sync()   # keeps the host within one round of the GPU
+    # the preheat runs for a time, so its step count varies: restart the (handle, ring slot) plan behind it, so that the
+    # warm-up and timed steps -- the last one's inputs above all (--dump-outputs) -- are the same in every run
+    wl.step_no = 0
     for _ in range(max(a.warmup, len(exs))):
         step()
     barrier()
-    if not a.no_profile:
+    if profile:
         collect()   # drop the untimed launches: the timed region's events only
     barrier()
     t0 = time.perf_counter()
@@ -412,23 +485,26 @@ def main():
     elapsed = t1 - t0
     if dist is not None:
         elapsed = sharding.max_over_ranks(elapsed, device="cuda")
-    dom_prof = collect() if not a.no_profile else {}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a, wl, a.dump_outputs)   # before any further step overwrites the last timed step's results
+    dom_prof = collect() if profile else {}
     # shader clock under THIS load: a one-wave probe spins for 2 ms on its own stream while further steps run
     shader_ghz = None
-    try:
-        probe = orbx.clock_probe_start(local_rank, 2000)
-        for _ in range(2 * len(exs)):
-            step()
-        wl.sync()
-        shader_ghz = orbx.clock_probe_finish(probe)
-    except Exception:
-        shader_ghz = None
+    if a.full:
+        try:
+            probe = orbx.clock_probe_start(local_rank, 2000)
+            for _ in range(2 * len(exs)):
+                step()
+            wl.sync()
+            shader_ghz = orbx.clock_probe_finish(probe)
+        except Exception:
+            shader_ghz = None
     # per-stage table: a short extra pass outside the timed region with every kernel bracketed, on ONE handle with a
     # sync after every step, so that the durations are those of the kernels alone (in the timed region the batches
     # of the two handles overlap on the GPU, which stretches every individual launch)
     prof = {}
     nprof = max(3, min(a.steps, 10))
-    if not a.no_profile:
+    if profile:
         collect()   # drop the dominant kernel's events of the clock-probe steps above: the stage table covers nprof steps exactly
         exs[0].profile_enable(True)
         for i in range(nprof):
@@ -615,7 +691,7 @@ def main():
         a_pair = 2 * (2 * P + 60 * nsel_mean) + 120 * nsel_mean + 352 * nmatch
         out["end_to_end_algorithmic_GBps"] = round(a_pair * value / n_ranks / 1e9, 2)
 
-    extras = rank == 0 and n_ranks == 1 and a.mode == "stereo" and not a.no_extras and not c5
+    extras = a.full and rank == 0 and n_ranks == 1 and a.mode == "stereo" and not a.no_extras and not c5
     if extras and a.sustain_ms > 0:
         # The timed region of the default run is ~10 - 50 ms: too short for an outside sampler (the driver polls GPU activity every
         # few seconds) and open to the question whether it is a burst.  The same steps, back to back, for --sustain-ms of wall time
@@ -964,7 +1040,7 @@ def default_queue_leg(a):
     env.pop("GPU_MAX_HW_QUEUES", None)
     env["ORBX_BENCH_KEEP_QUEUES"] = "1"
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--handles", "3", "--steps", str(a.steps),
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--handles", "3", "--steps", str(a.steps),
                             "--warmup", str(a.warmup)], capture_output=True, text=True, timeout=300, env=env)
         d = json.loads(r.stdout.strip().splitlines()[-1])
         return {"value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "handles": 3,

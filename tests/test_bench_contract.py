@@ -51,7 +51,7 @@ def test_gpus_n_never_comes_from_one_process():
 def test_self_launch_path_prints_the_contract_line():
     """--self-launch: bench.py re-executes itself under torch.distributed.run (here with ONE rank) and rank 0 prints the
     same single contract line; n_gpus / rccl_ranks are the size of the RCCL group that ran."""
-    r = _run(["--self-launch", "--steps", "3", "--warmup", "1", "--pairs", "2", "--width", "320", "--height", "240",
+    r = _run(["--self-launch", "--full", "--steps", "3", "--warmup", "1", "--pairs", "2", "--width", "320", "--height", "240",
               "--nfeatures", "300", "--cpu-pairs", "0", "--no-extras"])
     assert r.returncode == 0, r.stderr[-800:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -64,7 +64,7 @@ def test_self_launch_path_prints_the_contract_line():
 @pytest.mark.parametrize("mode", ["stereo", "mono", "fisheye"])
 def test_bench_prints_one_contract_line(mode):
     size = ["--width", "256", "--height", "256"] if mode == "fisheye" else ["--width", "320", "--height", "240"]
-    r = _run(["--mode", mode, "--steps", "3", "--warmup", "1", "--pairs", "2", "--nfeatures", "300", "--cpu-pairs",
+    r = _run(["--full", "--mode", mode, "--steps", "3", "--warmup", "1", "--pairs", "2", "--nfeatures", "300", "--cpu-pairs",
               "4" if mode == "stereo" else "0", "--latency-frames", "12", "--h2d-steps", "4"] + size)
     assert r.returncode == 0, r.stderr[-600:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -102,7 +102,7 @@ def test_bench_prints_one_contract_line(mode):
 
 @pytest.mark.gpu
 def test_bench_c5_mode_prints_one_contract_line():
-    r = _run(["--config", "C5", "--inflight", "2", "--steps", "4", "--warmup", "1", "--nfeatures", "300", "--width", "320",
+    r = _run(["--full", "--config", "C5", "--inflight", "2", "--steps", "4", "--warmup", "1", "--nfeatures", "300", "--width", "320",
               "--height", "240", "--ring", "2"])
     assert r.returncode == 0, r.stderr[-600:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -114,6 +114,53 @@ def test_bench_c5_mode_prints_one_contract_line():
     # a collective inside the step: the preheat runs a FIXED number of steps (all ranks must issue the same all-gathers)
     nh = d["config"]["handles"]
     assert d["preheat_steps"] == nh * ((int(40.0 / 0.55 / nh) + 1))
+
+
+def test_full_and_dump_outputs_are_options():
+    """--full (everything beyond the headline) is off by default; --dump-outputs takes a directory.  No GPU touched."""
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run prints the headline line only (the legs and rooflines are --full's); --dump-outputs writes the last timed
+    step's results as float32 .npy files, the same in two runs, and equal to the CPU oracle on that step's inputs."""
+    import numpy as np
+    import bench
+    import orb_slam3_fast_amd as orbx
+    from orb_slam3_fast_amd import synth
+    from oracle import cpu_bench
+    W, H, B, NF = 320, 240, 2, 300
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run(["--steps", "3", "--warmup", "1", "--pairs", str(B), "--width", str(W), "--height", str(H), "--nfeatures", str(NF),
+                  "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-600:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+        assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["n_gpus"] == 1
+        assert not {"roofline", "stages", "cpu_baseline", "latency_ms", "h2d_inclusive_value", "other_configs"} & set(line)
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrs = {f[:-4]: np.load(d / f) for f in files if f.endswith(".npy")}
+        assert all(v.dtype in (np.float32, np.float64) for v in arrs.values())
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    # the last timed step: max(warm-up 1, 4 handles) warm-up steps + 3 timed steps -> step 6, ring slot 6 mod 3 = 0
+    gl, gr = synth.stereo_ring(W, H, bench.rank_streams(0, B), [0, 1, 2])
+    ref = cpu_bench.oracle_pairs(gl[0], gr[0], NF, bench.BF, bench.BASE)
+    kp = lambda k: np.stack([np.ascontiguousarray(k).view(orbx.KP_DTYPE)[f].astype(np.float32) for f in orbx.KP_DTYPE.names], 1)
+    got = dumps[0]
+    assert got["counts"].tolist() == [len(x[0]) for x in ref] + [len(x[2]) for x in ref]
+    assert np.array_equal(got["keypoints"], np.concatenate([kp(x[0]) for x in ref] + [kp(x[2]) for x in ref]))
+    assert np.array_equal(got["descriptors"], np.concatenate([x[1] for x in ref] + [x[3] for x in ref]).astype(np.float32))
+    assert np.array_equal(got["uright"].view(np.uint32), np.concatenate([x[4] for x in ref]).view(np.uint32))
+    assert np.array_equal(got["depth"].view(np.uint32), np.concatenate([x[5] for x in ref]).view(np.uint32))
 
 
 def test_two_rank_launch_rank_logic_on_gloo():

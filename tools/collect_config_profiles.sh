@@ -13,7 +13,7 @@ run_cfg() {
   local cfg=$1; shift
   local args="$@"
   rm -rf /tmp/cp_kt /tmp/cp_f /tmp/cp_w /tmp/cp_i
-  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/cp_kt -o kt -- python $R/bench.py --no-extras --handles 1 $args > $O/${TAG}_${cfg}_bench_1handle_under_rocprof.json 2> /dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/cp_kt -o kt -- python $R/bench.py --full --no-extras --handles 1 $args > $O/${TAG}_${cfg}_bench_1handle_under_rocprof.json 2> /dev/null
   timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/cp_f -o pmc -- python $R/bench.py --no-extras --handles 1 --steps 5 --warmup 2 --no-profile $args > /dev/null 2>&1
   timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d /tmp/cp_w -o pmc -- python $R/bench.py --no-extras --handles 1 --steps 5 --warmup 2 --no-profile $args > /dev/null 2>&1
   timeout 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --kernel-trace -d /tmp/cp_i -o pmc -- python $R/bench.py --no-extras --handles 1 --steps 5 --warmup 2 --no-profile $args > /dev/null 2>&1
