@@ -244,6 +244,45 @@ int orbx_stereo_results_device(const orbx_extractor* left, const float** d_urigh
 /* Host copy of pair `pair` (synchronises): n = keypoint count of the left image. */
 int orbx_stereo_download(orbx_extractor* left, int pair, float* uright, float* depth, int cap);
 
+/* ---- RGB-D frames ----------------------------------------------------------------------------------------------------------
+ * Depth image types: OpenCV's CV_16U and CV_32F (single channel).  Any other type is ORBX_E_UNSUPPORTED. */
+#define ORBX_DEPTH_U16 2
+#define ORBX_DEPTH_F32 5
+/* Replaces Frame::ComputeStereoFromRGBD (src/Frame.cc:1086-1104) -- with Tracking::GrabImageRGBD's depth conversion
+ * (src/Tracking.cc:1490-1547) folded in -- for n_frames device-resident depth images: frame f is image first_image + f of ex's
+ * last extraction, its depth image (depth_type, the size of that extraction, rows row_pitch bytes apart) starts at
+ * d_depth + f * image_pitch; base and pitches are multiples of the element size.  depth_scale = Tracking::mDepthMapFactor
+ * (1 / RGBD.DepthMapFactor, or 1 when |factor| < 1e-5: src/Tracking.cc:610-614); the library applies the reference's skip
+ * rule itself (a CV_32F image with |depth_scale - 1| <= 1e-5 is used unscaled; every other image is scaled by one float
+ * multiply per read pixel).  Per keypoint i: d = depth at row (int)mvKeys[i].pt.y, column (int)mvKeys[i].pt.x (the DISTORTED
+ * point); d > 0 gives mvDepth = d and mvuRight = mvKeysUn[i].pt.x - bf / d (bf = mbf), anything else (0, negative, -0, NaN,
+ * and points whose truncated coordinates fall outside the image) gives -1 for both.  mvKeysUn is computed inside the kernel
+ * (Frame::UndistortKeyPoints, src/Frame.cc:853-885: K = fx fy cx cy, dist = mDistCoef, n_dist <= 14 with terms 12, 13 zero; K may be NULL when
+ * n_dist == 0 or dist[0] == 0, where mvKeysUn = mvKeys); d_kps_un, a caller-owned DEVICE array [n_frames][cap] (cap =
+ * orbx_batch_results_device's), receives it when not NULL.
+ * The results land in the handle's stereo result arrays: pair f = frame f, so orbx_stereo_results_device,
+ * orbx_stereo_download, orbx_batch_download_async(..., n_pairs <= n_frames) and every batched matcher's stereo_pair0 read
+ * them as they read ComputeStereoMatches' results; rows past a frame's keypoint count are left untouched, as the stereo
+ * association leaves them.  The next extraction invalidates them.  Enqueued on the handle's stream, no synchronisation: the
+ * depth images must stay valid until orbx_sync. */
+int orbx_rgbd_depth_batch(orbx_extractor* ex, int first_image, int n_frames, const void* d_depth, int depth_type,
+                          ptrdiff_t row_pitch, ptrdiff_t image_pitch, float depth_scale, float bf, const float K[4],
+                          const float* dist, int n_dist, orbx_keypoint* d_kps_un);
+/* ONE RGB-D frame with one synchronisation: replaces the RGB-D Frame constructor's ExtractORB(0, imGray, 0, 0);
+ * UndistortKeyPoints(); ComputeStereoFromRGBD(imDepth) (src/Frame.cc:281-348) and GrabImageRGBD's depth conversion.  The
+ * extraction is orbx_extract's (kps / desc / cap / n_out / return value as there, lapping area {0, 0}; *mono receives
+ * monoIndex); mvKeysUn is computed on the device from the handle's keypoints and travels back in the same result gather.
+ * The depth lookup runs on the HOST, from the caller's host depth image (depth_type, w x h, rows depth_stride bytes apart)
+ * with the rule of orbx_rgbd_depth_batch: the frame reads ~N pixels of a depth image the Frame never keeps, and uploading
+ * the whole image (1.8 MB at 1280x720 u16) would cost about as much as the extraction, where reading N pixels on the host
+ * costs microseconds.  Any of kps, desc, kps_un, uright, depth_out may be NULL; orbx_host_results(ex, 0, ...) hands out
+ * keypoints, descriptors, uright and depth in place afterwards, as after orbx_extract_stereo.  Returns monoIndex (>= 0),
+ * ORBX_E_EMPTY for an empty image, or another negative error. */
+int orbx_extract_rgbd(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t stride, const void* depth,
+                      int depth_type, ptrdiff_t depth_stride, float depth_scale, float bf, const float K[4], const float* dist,
+                      int n_dist, orbx_keypoint* kps, uint8_t* desc, int cap, int* n_out, int* mono, orbx_keypoint* kps_un,
+                      float* uright, float* depth_out);
+
 /* Replaces cv::BFMatcher(NORM_HAMMING).knnMatch(Q, T, k=2) + Lowe ratio of
  * Frame::ComputeStereoFishEyeMatches (src/Frame.cc:46,1293-1302).  Host descriptor rows in, host results
  * out: idx2 / dist2 [nQ][2] (-1 when the train set has fewer rows), ratio_ok[nQ] = d0 < d1*0.7. */

@@ -93,6 +93,9 @@ def lib():
         L.orbx_stereo_match_batch.argtypes = [vp, i, vp, i, i, f, f]
         L.orbx_stereo_results_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.orbx_stereo_download.argtypes = [vp, i, vp, vp, i]
+        L.orbx_rgbd_depth_batch.argtypes = [vp, i, i, vp, i, C.c_ssize_t, C.c_ssize_t, f, f, vp, vp, i, vp]
+        L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
+                                        C.POINTER(i), vp, vp, vp]
         L.orbx_bf_knn2.argtypes = [i, vp, i, vp, i, vp, vp, vp]
         L.orbx_fisheye_stereo_match.argtypes = [i, vp, vp, i, i, vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_fisheye_stereo_match_batch.argtypes = [vp, i, vp, i, i, vp]
@@ -340,6 +343,38 @@ class ORBextractor:
         v = self._result_views(hb, 2, bf > 0)
         out = ((ml.value,) + self._take(v[0], nl.value), (mr.value,) + self._take(v[1], nr.value))
         return out + ((v["ur"][:nl.value].copy(), v["dp"][:nl.value].copy()),) if bf > 0 else out
+
+    def extract_rgbd(self, gray, depth, K, dist, bf, depth_scale):
+        """One RGB-D frame (orbx_extract_rgbd): ExtractORB + UndistortKeyPoints + ComputeStereoFromRGBD of the RGB-D Frame
+        constructor (src/Frame.cc:281-348) with GrabImageRGBD's depth conversion folded in.  depth = uint16 (CV_16U) or float32
+        (CV_32F) image of the gray image's size; depth_scale = Tracking::mDepthMapFactor (depth_scale_from_settings).  Returns
+        (mono, kps, desc, kpsUn, uRight, depth)."""
+        g = np.asarray(gray)
+        if g.ndim != 2 or g.dtype != np.uint8:
+            raise ValueError("CV_8UC1 image expected")
+        if g.strides[1] != 1:
+            g = np.ascontiguousarray(g)
+        D = np.asarray(depth)
+        if D.shape != g.shape:
+            raise ValueError("depth image must have the gray image's size")
+        dtype = _DEPTH_TYPES.get(D.dtype.type)
+        if dtype is None:
+            raise ValueError("depth image must be uint16 (CV_16U) or float32 (CV_32F)")
+        if D.strides[1] != D.itemsize or D.strides[0] % D.itemsize:
+            D = np.ascontiguousarray(D)
+        h, w = g.shape
+        K = np.ascontiguousarray(K, np.float32) if K is not None else None
+        d = np.ascontiguousarray(dist if dist is not None else [], np.float32).ravel()
+        hb = self._host_bufs()
+        cap = self.capacity
+        kun = np.zeros(cap, KP_DTYPE)
+        mono = _check(lib().orbx_extract_rgbd(self._h, g.ctypes.data, w, h, g.strides[0], D.ctypes.data, dtype, D.strides[0],
+                                              float(depth_scale), float(bf), None if K is None else _p(K),
+                                              _p(d) if len(d) else None, len(d), None, None, cap, hb["nref"][0], hb["nref"][1],
+                                              _p(kun), None, None))
+        n = hb["n"][0].value
+        v = self._result_views(hb, 1, True)
+        return (mono,) + self._take(v[0], n) + (kun[:n].copy(), v["ur"][:n].copy(), v["dp"][:n].copy())
 
     def map_upload(self, world_pos, normal, min_distance, max_distance, desc, flags):
         """The local map as structure-of-arrays, resident on the device (orbx_map_upload): GetWorldPos / GetNormal [n][3],
@@ -623,6 +658,50 @@ def ComputeStereoMatches(left, right, bf, b, first_left=0, first_right=0, n_pair
 
 def stereo_match_async(left, right, bf, b, first_left=0, first_right=0, n_pairs=1):
     _check(lib().orbx_stereo_match_batch(left._h, first_left, right._h, first_right, n_pairs, bf, b))
+
+
+_DEPTH_TYPES = {np.uint16: 2, np.float32: 5}   # ORBX_DEPTH_U16 (CV_16U), ORBX_DEPTH_F32 (CV_32F)
+DEPTH_U16, DEPTH_F32 = 2, 5
+
+
+def depth_scale_from_settings(DepthMapFactor):
+    """Tracking::mDepthMapFactor from the settings' RGBD.DepthMapFactor (src/Tracking.cc:610-614): 1 when |factor| < 1e-5,
+    else 1.0f / factor -- as np.float32."""
+    f = np.float32(DepthMapFactor)
+    if abs(float(f)) < 1e-5:
+        return np.float32(1.0)
+    return np.float32(np.float32(1.0) / f)
+
+
+def _rgbd_enqueue(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, depth_scale, K, dist, first_image, n_frames,
+                  d_kps_un_ptr):
+    K = None if K is None else np.ascontiguousarray(K, np.float32)
+    d = np.ascontiguousarray(dist if dist is not None else [], np.float32).ravel()
+    _check(lib().orbx_rgbd_depth_batch(ex._h, first_image, n_frames, C.c_void_p(d_depth_ptr), int(depth_type), row_pitch,
+                                       image_pitch, float(depth_scale), float(bf), None if K is None else _p(K),
+                                       _p(d) if len(d) else None, len(d),
+                                       None if d_kps_un_ptr is None else C.c_void_p(d_kps_un_ptr)))
+
+
+def ComputeStereoFromRGBD(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, depth_scale, K=None, dist=None, first_image=0,
+                          n_frames=1, d_kps_un_ptr=None):
+    """Frame::ComputeStereoFromRGBD (src/Frame.cc:1086-1104) for images [first_image, first_image + n_frames) of ex's last
+    extraction, from device-resident depth images (orbx_rgbd_depth_batch; depth_type DEPTH_U16 / DEPTH_F32, frame f at
+    d_depth_ptr + f * image_pitch).  The results land in the handle's stereo result arrays (pair f = frame f: a matcher's
+    stereo_pair0 reads them).  Returns (mvuRight, mvDepth) arrays [n_frames][capacity]."""
+    _rgbd_enqueue(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, depth_scale, K, dist, first_image, n_frames,
+                  d_kps_un_ptr)
+    out_u = np.zeros((n_frames, ex.capacity), np.float32)
+    out_d = np.zeros((n_frames, ex.capacity), np.float32)
+    for p in range(n_frames):
+        _check(lib().orbx_stereo_download(ex._h, p, _p(out_u[p]), _p(out_d[p]), ex.capacity))
+    return out_u, out_d
+
+
+def rgbd_depth_async(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, depth_scale, K=None, dist=None, first_image=0,
+                     n_frames=1, d_kps_un_ptr=None):
+    _rgbd_enqueue(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, depth_scale, K, dist, first_image, n_frames,
+                  d_kps_un_ptr)
 
 
 def debug_sincos(angles, fused=True, device=0):

@@ -46,8 +46,13 @@ class Mat {
   int rows = 0, cols = 0;
   size_t step = 0;
   uint8_t* data = nullptr;
+  int flags = 0;   // element type of a header made by the typed constructor (CV_8U = 0, CV_16U = 2, CV_32F = 5)
   Mat() {}
   Mat(int r, int c, uint8_t* ext, size_t step_) : rows(r), cols(c), step(step_), data(ext) {}
+  Mat(int r, int c, int type, void* ext, size_t step_)
+      : rows(r), cols(c), step(step_), data(static_cast<uint8_t*>(ext)), flags(type) {}
+  int depth() const { return flags & 7; }
+  int channels() const { return 1; }
   void create(int r, int c) {
     buf_ = std::shared_ptr<uint8_t>(new uint8_t[(size_t)r * c], std::default_delete<uint8_t[]>());
     rows = r;
@@ -229,6 +234,53 @@ class ORBextractor {
       ViewImagePyramid(0);
       ViewImagePyramid(1);
     }
+  }
+
+  // The RGB-D Frame constructor's ExtractORB(0, imGray, 0, 0); UndistortKeyPoints(); ComputeStereoFromRGBD(imDepth)
+  // (src/Frame.cc:281-348) in one call and one synchronisation (orbx_extract_rgbd), with Tracking::GrabImageRGBD's depth
+  // conversion folded in: imDepth is the RAW depth image (CV_16U or CV_32F, single channel, imGray's size) and depthScale is
+  // mDepthMapFactor (src/Tracking.cc:610-614; the library applies the reference's skip rule).  K = fx fy cx cy and distCoef =
+  // mDistCoef as UndistortKeyPoints (ORBmatcher.h) takes them; bf = mbf.  keys / descriptors as operator(), keysUn = mvKeysUn,
+  // uRight / depth = mvuRight / mvDepth.  The depth lookup runs on the host (include/orbx.h).  Returns monoIndex, -1 for an
+  // empty image; throws on errors as ExtractStereo does.
+  int ExtractRGBD(ocv::InputArray imGray, ocv::InputArray imDepth, float depthScale, const float K[4],
+                  const std::vector<float>& distCoef, float bf, std::vector<ocv::KeyPoint>& keys, ocv::OutputArray descriptors,
+                  std::vector<ocv::KeyPoint>& keysUn, std::vector<float>& uRight, std::vector<float>& depth) {
+    const int kDepthU16 = 2, kDepthF32 = 5;   // CV_16U, CV_32F (ORBX_DEPTH_U16 / _F32)
+#ifdef ORBX_HAVE_OPENCV
+    if (imGray.empty()) return -1;
+    cv::Mat G = imGray.getMat(), D = imDepth.getMat();
+    CV_Assert(G.type() == CV_8UC1);
+#else
+    if (imGray.empty()) return -1;
+    const ocv::Mat& G = imGray;
+    const ocv::Mat& D = imDepth;
+#endif
+    if (D.empty() || D.rows != G.rows || D.cols != G.cols || D.channels() != 1 ||
+        (D.depth() != kDepthU16 && D.depth() != kDepthF32))
+      throw std::invalid_argument("ORBextractor::ExtractRGBD: the depth image must be CV_16U or CV_32F of the gray image's size");
+    ApplyHostPyramidMode();
+    const int cap = capacity_;
+    keysUn.resize((size_t)cap);
+    uRight.resize((size_t)cap);
+    depth.resize((size_t)cap);
+    int n = 0, mono = 0;
+    const int rc = orbx_extract_rgbd(h_, G.data, G.cols, G.rows, (ptrdiff_t)G.step, D.data, D.depth(), (ptrdiff_t)D.step,
+                                     depthScale, bf, K, distCoef.empty() ? nullptr : distCoef.data(), (int)distCoef.size(), nullptr,
+                                     nullptr, cap, &n, &mono, reinterpret_cast<orbx_keypoint*>(keysUn.data()), uRight.data(),
+                                     depth.data());
+    if (rc == ORBX_E_EMPTY) return -1;
+    if (rc < 0) throw std::runtime_error(std::string("ORBextractor::ExtractRGBD: ") + orbx_last_error());
+    const orbx_keypoint* rk = nullptr;
+    const uint8_t* rd = nullptr;
+    if (orbx_host_results(h_, 0, &rk, &rd, nullptr, nullptr, nullptr, nullptr) != ORBX_OK)
+      throw std::runtime_error(std::string("ORBextractor::ExtractRGBD: ") + orbx_last_error());
+    FillOutputs(keys, descriptors, rk, rd, n);
+    keysUn.resize((size_t)n);
+    uRight.resize((size_t)n);
+    depth.resize((size_t)n);
+    if (mbKeepHostPyramid) ViewImagePyramid(0);
+    return mono;
   }
 
   // Not in the reference (its OpenCV is chosen at link time): which OpenCV's GaussianBlur taps the descriptors follow --

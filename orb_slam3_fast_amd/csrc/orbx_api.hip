@@ -2,6 +2,7 @@
 // Host-side restatement of the ORBextractor constructor tables (src/ORBextractor.cc:408-469) and of the
 // OpenCV resize coefficient tables; all pixel/bit work is in orbx_kernels.hip.
 #include "orbx_host.h"
+#include "orbx_rgbd.h"
 
 namespace orbx_host {
 thread_local std::string g_err;
@@ -1035,9 +1036,10 @@ int orbx_host_pyramid_level(const orbx_extractor* ex, int image, int level, cons
   return ORBX_OK;
 }
 
-int orbx_extract(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t stride, int lap0, int lap1,
-                 orbx_keypoint* kps, uint8_t* desc, int cap, int* n_out) {
-  if (!ex) return fail(ORBX_E_BADARG, "null handle");
+// orbx_extract, and orbx_extract_rgbd's extraction: with `un`, k_rgbd_depth writes mvKeysUn of the frame's keypoints into the
+// second keypoint section of the host block (unused by a single image) before the result gather
+static int extract_single(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t stride, int lap0, int lap1,
+                          orbx_keypoint* kps, uint8_t* desc, int cap, int* n_out, const RgbdArgs* un) {
   if (n_out) *n_out = 0;
   if (!img || w <= 0 || h <= 0) return fail(ORBX_E_EMPTY, "empty image");  // :1021
   if (w > ex->maxW || h > ex->maxH) return fail(ORBX_E_CAPACITY, "image larger than the handle's maximum");
@@ -1056,6 +1058,15 @@ int orbx_extract(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t
   if (rc != ORBX_OK) return rc;
   const size_t oc = (size_t)ex->gmax.outCap;  // results through pinned memory: async copies, one synchronisation
   uint8_t* H = ex->hostResults;
+  if (un) {
+    RgbdArgs a = *un;
+    uint8_t* hd = nullptr;
+    HIPC(hipHostGetDevicePointer(reinterpret_cast<void**>(&hd), ex->hostResults, 0));
+    a.kps = ex->d_kps.p; a.nOut = ex->d_nOut.p; a.cap = (int)oc; a.first = 0;
+    a.depth = nullptr; a.uR = a.dep = nullptr;
+    a.kpsUn = reinterpret_cast<orbx_keypoint*>(hd + hr_kps(oc)) + oc;
+    HIPC(launch_rgbd_depth(a, 1, st));
+  }
   HIPC(enqueue_result_pack(ex, 1, false));   // one gather kernel writes the pinned block (count-trimmed), no D2H copies
   if (ex->keepHostPyr) {
     const ptrdiff_t hs[1] = {stride};
@@ -1073,6 +1084,74 @@ int orbx_extract(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t
   if (n > 0 && kps) std::memcpy(kps, H + hr_kps(oc), (size_t)n * sizeof(orbx_keypoint));
   if (n > 0 && desc) std::memcpy(desc, H + hr_desc(oc), (size_t)n * 32);
   return mono;
+}
+
+int orbx_extract(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t stride, int lap0, int lap1,
+                 orbx_keypoint* kps, uint8_t* desc, int cap, int* n_out) {
+  if (!ex) return fail(ORBX_E_BADARG, "null handle");
+  return extract_single(ex, img, w, h, stride, lap0, lap1, kps, desc, cap, n_out, nullptr);
+}
+
+// ---- RGB-D frames (Frame::ComputeStereoFromRGBD, src/Frame.cc:1086-1104) ----------------------------------------------------
+// The camera of Frame::UndistortKeyPoints (src/Frame.cc:853-885) into the kernel's arguments: mvKeysUn = mvKeys when
+// mDistCoef(0) == 0 (or there are no coefficients), the cv::undistortPoints iteration otherwise.
+static int rgbd_camera(RgbdArgs& a, const float K[4], const float* dist, int n_dist) {
+  if (n_dist < 0 || n_dist > 14 || (n_dist && !dist)) return fail(ORBX_E_BADARG, "bad distortion arguments");
+  for (int i = 12; i < n_dist; i++)
+    if (dist[i] != 0.f) return fail(ORBX_E_UNSUPPORTED, "tilted-sensor distortion terms are not supported");
+  a.undist = n_dist > 0 && dist[0] != 0.0f;
+  if (a.undist) {
+    if (!K) return fail(ORBX_E_BADARG, "K is required with a non-zero distortion");
+    if (!(K[0] != 0.f) || !(K[1] != 0.f)) return fail(ORBX_E_BADARG, "fx / fy must be non-zero");
+  }
+  for (int i = 0; i < 4; i++) a.K[i] = K ? K[i] : 0.f;
+  for (int i = 0; i < 12; i++) a.k[i] = i < n_dist ? dist[i] : 0.f;
+  return ORBX_OK;
+}
+static int rgbd_depth_type(int depth_type, size_t* elem) {
+  if (depth_type != ORBX_DEPTH_U16 && depth_type != ORBX_DEPTH_F32)
+    return fail(ORBX_E_UNSUPPORTED, "depth images are ORBX_DEPTH_U16 (CV_16U) or ORBX_DEPTH_F32 (CV_32F)");
+  *elem = depth_type == ORBX_DEPTH_U16 ? 2 : 4;
+  return ORBX_OK;
+}
+
+int orbx_extract_rgbd(orbx_extractor* ex, const uint8_t* img, int w, int h, ptrdiff_t stride, const void* depth,
+                      int depth_type, ptrdiff_t depth_stride, float depth_scale, float bf, const float K[4], const float* dist,
+                      int n_dist, orbx_keypoint* kps, uint8_t* desc, int cap, int* n_out, int* mono, orbx_keypoint* kps_un,
+                      float* uright, float* depth_out) {
+  if (!ex) return fail(ORBX_E_BADARG, "null handle");
+  if (n_out) *n_out = 0;
+  if (mono) *mono = 0;
+  if (!n_out || !mono) return fail(ORBX_E_BADARG, "null argument");
+  if (!img || w <= 0 || h <= 0) return fail(ORBX_E_EMPTY, "empty image");
+  size_t es = 0;
+  int rc = rgbd_depth_type(depth_type, &es);
+  if (rc != ORBX_OK) return rc;
+  if (!depth || depth_stride < (ptrdiff_t)(w * es) || depth_stride % (ptrdiff_t)es || reinterpret_cast<uintptr_t>(depth) % es)
+    return fail(ORBX_E_BADARG, "depth image: null, rows shorter than the image, or misaligned");
+  RgbdArgs a{};
+  rc = rgbd_camera(a, K, dist, n_dist);
+  if (rc != ORBX_OK) return rc;
+  const int m = extract_single(ex, img, w, h, stride, 0, 0, kps, desc, cap, n_out, &a);
+  if (m < 0) return m;
+  const int n = *n_out;
+  *mono = m;
+  const size_t oc = (size_t)ex->gmax.outCap;
+  uint8_t* H = ex->hostResults;
+  const orbx_keypoint* kp = reinterpret_cast<const orbx_keypoint*>(H + hr_kps(oc));
+  const orbx_keypoint* kun = kp + oc;
+  float* ur = reinterpret_cast<float*>(H + hr_ur(oc));
+  float* dp = reinterpret_cast<float*>(H + hr_depth(oc));
+  // the lookup on the host: N pixels of the caller's image (orbx_rgbd.h, the kernel's own rule)
+  const bool sc = rgbd_scales(depth_type, depth_scale);
+  const uint8_t* D = static_cast<const uint8_t*>(depth);
+  for (int i = 0; i < n; i++) rgbd_lookup(D, depth_type, depth_stride, w, h, sc, depth_scale, bf, kp[i].x, kp[i].y, kun[i].x, ur[i], dp[i]);
+  ex->hostResStereo = true;
+  if ((kps_un || uright || depth_out) && n > cap) return fail(ORBX_E_CAPACITY, "keypoint buffer too small");
+  if (n > 0 && kps_un) std::memcpy(kps_un, kun, (size_t)n * sizeof(orbx_keypoint));
+  if (n > 0 && uright) std::memcpy(uright, ur, (size_t)n * sizeof(float));
+  if (n > 0 && depth_out) std::memcpy(depth_out, dp, (size_t)n * sizeof(float));
+  return m;
 }
 
 int orbx_extract_stereo(orbx_extractor* ex, const uint8_t* img_left, const uint8_t* img_right, int w, int h,
@@ -1362,8 +1441,11 @@ static int enqueue_stereo_match(orbx_extractor* left, int first_left, orbx_extra
   const size_t capL = (size_t)left->gmax.outCap;
   if (left->stereoPairs < n_pairs) {
     HIPC(hipStreamSynchronize(left->stream));
-    HIPC(left->d_uR.alloc((size_t)n_pairs * capL));
-    HIPC(left->d_depth.alloc((size_t)n_pairs * capL));
+    if (left->uRPairs < n_pairs) {
+      HIPC(left->d_uR.alloc((size_t)n_pairs * capL));
+      HIPC(left->d_depth.alloc((size_t)n_pairs * capL));
+      left->uRPairs = n_pairs;
+    }
     HIPC(left->d_sad.alloc((size_t)n_pairs * capL));
     const size_t capS = std::max(capL, (size_t)right->gmax.outCap);
     HIPC(left->d_rowStart.alloc((size_t)n_pairs * 2 * (left->maxH + 2)));
@@ -1451,6 +1533,44 @@ int orbx_stereo_download(orbx_extractor* left, int pair, float* uright, float* d
   HIPC(hipStreamSynchronize(left->stream));
   if (uright && n) std::memcpy(uright, left->hostResults + hr_ur(capL), n * sizeof(float));
   if (depth && n) std::memcpy(depth, left->hostResults + hr_depth(capL), n * sizeof(float));
+  return ORBX_OK;
+}
+
+int orbx_rgbd_depth_batch(orbx_extractor* ex, int first_image, int n_frames, const void* d_depth, int depth_type,
+                          ptrdiff_t row_pitch, ptrdiff_t image_pitch, float depth_scale, float bf, const float K[4],
+                          const float* dist, int n_dist, orbx_keypoint* d_kps_un) {
+  if (!ex) return fail(ORBX_E_BADARG, "null handle");
+  if (n_frames <= 0 || first_image < 0 || first_image + n_frames > ex->lastN)
+    return fail(ORBX_E_BADARG, "frame range outside the last extraction");
+  size_t es = 0;
+  int rc = rgbd_depth_type(depth_type, &es);
+  if (rc != ORBX_OK) return rc;
+  const int w = ex->curW, h = ex->curH;
+  const ptrdiff_t e = (ptrdiff_t)es;
+  if (!d_depth || row_pitch < (ptrdiff_t)w * e || row_pitch % e || image_pitch % e || reinterpret_cast<uintptr_t>(d_depth) % es ||
+      (n_frames > 1 && image_pitch < row_pitch * h))
+    return fail(ORBX_E_BADARG, "depth images: null, rows or images overlapping, or misaligned");
+  RgbdArgs a{};
+  rc = rgbd_camera(a, K, dist, n_dist);
+  if (rc != ORBX_OK) return rc;
+  HIPC(hipSetDevice(ex->device));
+  const size_t cap = (size_t)ex->gmax.outCap;
+  if (ex->uRPairs < n_frames) {   // (its own counter: the association's other buffers stay guarded by stereoPairs)
+    HIPC(hipStreamSynchronize(ex->stream));
+    HIPC(ex->d_uR.alloc((size_t)n_frames * cap));
+    HIPC(ex->d_depth.alloc((size_t)n_frames * cap));
+    ex->uRPairs = n_frames;
+  }
+  a.kps = ex->d_kps.p; a.nOut = ex->d_nOut.p; a.cap = (int)cap; a.first = first_image;
+  a.depth = static_cast<const uint8_t*>(d_depth); a.rowPitch = row_pitch; a.imgPitch = image_pitch;
+  a.w = w; a.h = h; a.type = depth_type; a.scale = rgbd_scales(depth_type, depth_scale) ? 1 : 0;
+  a.depthScale = depth_scale; a.bf = bf;
+  a.uR = ex->d_uR.p; a.dep = ex->d_depth.p; a.kpsUn = d_kps_un;
+  {
+    StageTimer t(ex, ex->stream, ORBX_STAGE_STEREO_MATCH);
+    HIPC(launch_rgbd_depth(a, n_frames, ex->stream));
+  }
+  ex->lastStereoPairs = n_frames;
   return ORBX_OK;
 }
 

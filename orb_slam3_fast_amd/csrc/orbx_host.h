@@ -273,6 +273,8 @@ struct orbx_extractor {
   int stagePitch = 0;
   int stereoPairs = 0;             // high-water allocation of d_uR / d_depth / d_sad (pairs)
   int lastStereoPairs = 0;         // pairs of the stereo association run since the last extraction (0: none)
+  int uRPairs = 0;                 // allocation of d_uR / d_depth alone (pairs): grown by the stereo association and the RGB-D
+                                   // lookup (orbx_rgbd_depth_batch), which needs none of the association's other buffers
   // device-resident local map (orbx_map_upload) and the views orbx_project_map_points_batch made of it
   DevBuf<float> d_mapPos, d_mapNormal, d_mapMinD, d_mapMaxD;
   DevBuf<uint8_t> d_mapDesc, d_mapFlags, d_mapSkip;

@@ -196,6 +196,25 @@ struct UndistortArgs {
 };
 hipError_t launch_undistort(const UndistortArgs& a, hipStream_t s);
 
+// Frame::ComputeStereoFromRGBD (src/Frame.cc:1086-1104) on frames [first, first + n) of the last extraction (orbx_rgbd.hip):
+// grid (ceil(cap / 256), n), one thread per keypoint slot, counts from nOut.  depth == nullptr: only kpsUn is written.
+struct RgbdArgs {
+  const orbx_keypoint* kps;  // [image][cap] (mvKeys)
+  const int* nOut;           // per image counts
+  int cap, first;
+  const uint8_t* depth;      // frame f's depth image at depth + f * imgPitch (type ORBX_DEPTH_U16 / _F32), or nullptr
+  long long rowPitch, imgPitch;
+  int w, h, type, scale;     // scale: Tracking::GrabImageRGBD's convertTo runs (rgbd_scales)
+  float depthScale, bf;
+  float K[4];
+  float k[12];
+  int undist;                // mDistCoef(0) != 0: x_un through undistort_point, else x_un = x (src/Frame.cc:854-857)
+  float* uR;                 // [f][cap] mvuRight / mvDepth (with depth)
+  float* dep;
+  orbx_keypoint* kpsUn;      // [f][cap] mvKeysUn, or nullptr
+};
+hipError_t launch_rgbd_depth(const RgbdArgs& a, int nframes, hipStream_t s);
+
 // Pre-processing: gray conversion and a generic (any size, 1/3/4 channels) bilinear resize; pitches in bytes.
 // ---- bag of words ---------------------------------------------------------------------------------------
 // DBoW2 vocabulary tree on the device: children of node i = children[childStart[i] .. childStart[i + 1]) in file order.
