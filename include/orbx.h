@@ -787,6 +787,43 @@ int orbx_search_by_projection_frame_fisheye_batch(orbx_extractor* ex, int first_
                                                   int check_orientation, const uint8_t* occupied_in, uint8_t* occupied,
                                                   int32_t* match, int32_t* n_matches);
 
+/* ---- pose optimisation: Optimizer::PoseOptimization (src/Optimizer.cc:781-1107) -------------------------------------------------
+ * The last stage of the tracking step (callers src/Tracking.cc:2687, 2844, 2898, 2902, 3620, 3635, 3650), for pinhole / rectified
+ * frames (pFrame->mpCamera2 == NULL): one mono edge (Huber delta (float)sqrt(5.991)) per keypoint with a map point and
+ * mvuRight < 0, one stereo edge (u, v, uR; delta (float)sqrt(7.815)) otherwise, information I * mvInvLevelSigma2[octave]; four
+ * rounds of at most 10 g2o Levenberg iterations (tau 1e-5, 10 trials), each round restarting from the frame's pose, only the
+ * edges classified as inliers by the previous round active, the robust kernel dropped after round 2 and the loop left after a
+ * round when fewer than 10 edges exist; classification by float(chi2) > 5.991f / 7.815f, outlier edges re-evaluated at the
+ * round's estimate, inlier edges keeping the error of the optimizer's last (possibly rejected) trial.  DESIGN.md lists every rule.
+ * Tolerance parity: doubles where the reference computes in double (the stereo error's invz in float, as there); the reduction
+ * order over the edges, the 6x6 LDLT (here without pivoting; a pivot <= 0 or not finite is a failed factorisation) and the
+ * device's sin / cos / sqrt differ from Eigen / glibc in the last bits, so poses agree with a float64 restatement to 2e-6 rad and
+ * 1e-5 relative translation (the tests' bound), and a classification may differ where chi2 lies within rounding of its threshold.  A point at exactly z = 0 under an evaluated
+ * pose is outside the contract (the reference divides by it).  Results are run-to-run identical (fixed reduction tree), and a
+ * frame of the batch entry gives the same bits as the one-shot entry on the same data.
+ * Pose as Sophus stores Tcw (quaternion x y z w, translation; in/out: the optimised pose on return, normalised as
+ * Sophus::SO3f does) plus the Pinhole parameters and mbf.  48 bytes. */
+typedef struct orbx_pose_opt_frame {
+  float q[4], t[3], fx, fy, cx, cy, bf;
+} orbx_pose_opt_frame;
+/* One frame from host arrays: kps_un = mvKeysUn (n), u_right = mvuRight (NULL: every edge mono), world_pos [n][3] =
+ * mvpMapPoints[i]->GetWorldPos() where has_point[i] != 0, inv_level_sigma2 = mvInvLevelSigma2 (nlevels).  outlier[i] (in/out) =
+ * mvbOutlier: entries with a point receive the classification, the others keep the caller's value.  Returns nGood =
+ * nInitialCorrespondences - nBad (0 with the pose untouched for fewer than 3 edges), or a negative error.  Arguments are validated
+ * before any device is touched (n <= 15000, octaves in [0, nlevels), finite world positions, pose and camera). */
+int orbx_pose_optimization(int device, const orbx_keypoint* kps_un, const float* u_right, const float* world_pos,
+                           const uint8_t* has_point, int n, const float* inv_level_sigma2, int nlevels,
+                           orbx_pose_opt_frame* frame, uint8_t* outlier);
+/* The same for n_frames frames in ONE kernel launch (one workgroup per frame): frame f = image first_image + f of ex's last batch,
+ * keypoints taken as mvKeysUn (like the other batched entries), mvInvLevelSigma2 = the handle's; stereo_pair0 >= 0 reads mvuRight
+ * from pair stereo_pair0 + f of the handle's stereo results (orbx_stereo_match_batch or orbx_rgbd_depth_batch), -1 = monocular.
+ * world_pos [n_frames][cap][3], has_point / outlier [n_frames][cap] (cap = orbx_batch_results_device's; rows past a frame's
+ * keypoint count are not read or written), frames / n_good [n_frames]; n_trials (may be NULL) [n_frames] receives the number of
+ * Levenberg trials (linear solves) the frame ran.  Returns ORBX_OK or a negative error. */
+int orbx_pose_optimization_batch(orbx_extractor* ex, int first_image, int n_frames, int stereo_pair0, const float* world_pos,
+                                 const uint8_t* has_point, orbx_pose_opt_frame* frames, uint8_t* outlier, int32_t* n_good,
+                                 int32_t* n_trials);
+
 
 /* ---- measurement ------------------------------------------------------------------------------------ */
 

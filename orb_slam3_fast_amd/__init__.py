@@ -38,6 +38,9 @@ assert TRI_RIG_DTYPE.itemsize == 324
 MPR_DTYPE = np.dtype([("proj_yr", "<f4"), ("view_cos_r", "<f4"), ("predicted_level_r", "<i4"), ("in_view_r", "u1"),
                       ("pad_", "u1", (3,))])   # orbx_map_point_right
 assert MPR_DTYPE.itemsize == 16
+POSE_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                       ("bf", "<f4")])   # orbx_pose_opt_frame
+assert POSE_DTYPE.itemsize == 48
 
 
 class OrbxError(RuntimeError):
@@ -94,6 +97,8 @@ def lib():
         L.orbx_stereo_results_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.orbx_stereo_download.argtypes = [vp, i, vp, vp, i]
         L.orbx_rgbd_depth_batch.argtypes = [vp, i, i, vp, i, C.c_ssize_t, C.c_ssize_t, f, f, vp, vp, i, vp]
+        L.orbx_pose_optimization.argtypes = [i, vp, vp, vp, vp, i, vp, i, vp, vp]
+        L.orbx_pose_optimization_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
                                         C.POINTER(i), vp, vp, vp]
         L.orbx_bf_knn2.argtypes = [i, vp, i, vp, i, vp, vp, vp]
@@ -702,6 +707,55 @@ def rgbd_depth_async(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, de
                      n_frames=1, d_kps_un_ptr=None):
     _rgbd_enqueue(ex, d_depth_ptr, depth_type, row_pitch, image_pitch, bf, depth_scale, K, dist, first_image, n_frames,
                   d_kps_un_ptr)
+
+
+def _pose_frames(q, t, cam, n_frames):
+    fr = np.zeros(n_frames, POSE_DTYPE)
+    fr["q"] = np.asarray(q, np.float32).reshape(n_frames, 4)
+    fr["t"] = np.asarray(t, np.float32).reshape(n_frames, 3)
+    cam = np.asarray(cam, np.float32).reshape(-1, 5)
+    for j, name in enumerate(("fx", "fy", "cx", "cy", "bf")):
+        fr[name] = cam[:, j]
+    return fr
+
+
+def PoseOptimization(kpsUn, uRight, worldPos, hasPoint, invLevelSigma2, q, t, cam, outlier=None, device=0):
+    """Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:781-1107) for a pinhole / rectified frame on the GPU
+    (orbx_pose_optimization).  kpsUn = mvKeysUn (KP_DTYPE), uRight = mvuRight (None: every edge mono), worldPos [n][3] and
+    hasPoint [n] = the frame's map points, invLevelSigma2 = mvInvLevelSigma2, (q, t) = Tcw as Sophus stores it (x y z w),
+    cam = (fx, fy, cx, cy, mbf), outlier = mvbOutlier (entries without a point keep their value; default all False).
+    Returns (nGood, q, t, outlier)."""
+    k = np.ascontiguousarray(kpsUn, KP_DTYPE)
+    n = len(k)
+    ur = None if uRight is None else np.ascontiguousarray(uRight, np.float32).reshape(n)
+    wp = np.ascontiguousarray(worldPos, np.float32).reshape(n, 3)
+    hp = np.ascontiguousarray(hasPoint, np.uint8).reshape(n)
+    sig = np.ascontiguousarray(invLevelSigma2, np.float32)
+    fr = _pose_frames(q, t, cam, 1)
+    out = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(n)
+    ng = _check(lib().orbx_pose_optimization(int(device), _p(k), None if ur is None else _p(ur), _p(wp), _p(hp), n, _p(sig),
+                                             len(sig), _p(fr), _p(out)))
+    return ng, fr["q"][0].copy(), fr["t"][0].copy(), out.astype(bool)
+
+
+def PoseOptimizationBatch(ex, first_image, n_frames, worldPos, hasPoint, q, t, cam, stereo_pair0=-1, outlier=None,
+                          want_trials=False):
+    """PoseOptimization of the frames of ex's last extraction batch in ONE kernel launch (orbx_pose_optimization_batch):
+    frame f = image first_image + f, keypoints = mvKeysUn, mvInvLevelSigma2 = the handle's, mvuRight from stereo pair
+    stereo_pair0 + f (-1: monocular).  worldPos [n_frames][cap][3], hasPoint / outlier [n_frames][cap], q [n_frames][4],
+    t [n_frames][3], cam [n_frames][5] (or one row for all).  Returns (nGood, q, t, outlier[, trials])."""
+    cap = ex.capacity
+    wp = np.ascontiguousarray(worldPos, np.float32).reshape(n_frames, cap, 3)
+    hp = np.ascontiguousarray(hasPoint, np.uint8).reshape(n_frames, cap)
+    cam = np.broadcast_to(np.asarray(cam, np.float32).reshape(-1, 5), (n_frames, 5))
+    fr = _pose_frames(q, t, cam, n_frames)
+    out = np.zeros((n_frames, cap), np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(n_frames, cap)
+    ng = np.zeros(n_frames, np.int32)
+    tr = np.zeros(n_frames, np.int32)
+    _check(lib().orbx_pose_optimization_batch(ex._h, int(first_image), int(n_frames), int(stereo_pair0), _p(wp), _p(hp), _p(fr),
+                                              _p(out), _p(ng), _p(tr)))
+    res = (ng, fr["q"].copy(), fr["t"].copy(), out.astype(bool))
+    return res + (tr,) if want_trials else res
 
 
 def debug_sincos(angles, fused=True, device=0):
