@@ -824,6 +824,42 @@ int orbx_pose_optimization_batch(orbx_extractor* ex, int first_image, int n_fram
                                  const uint8_t* has_point, orbx_pose_opt_frame* frames, uint8_t* outlier, int32_t* n_good,
                                  int32_t* n_trials);
 
+/* PoseOptimization for KannalaBrandt8 frames: monocular KB8 (mpCamera2 == NULL) and stereo-fisheye rigs (mpCamera2 != NULL,
+ * Optimizer.cc:903-984).  Keypoint i < n_left gets an EdgeSE3ProjectXYZOnlyPose on the left camera, observation mvKeys[i] (for
+ * monocular KB8 mvKeysUn, equal to mvKeys since Settings zeroes mDistCoef); i >= n_left an EdgeSE3ProjectXYZOnlyPoseToBody on the
+ * right camera, observation mvKeysRight[i - n_left], mTrl = SE3Quat(Trl) (normalised).  Every edge: Huber delta (float)sqrt(5.991),
+ * information I * mvInvLevelSigma2[octave], classification by float(chi2) > 5.991f; right edges count in nBad like left ones and
+ * in the `edges < 10` rule; mvuRight is not read.  The rounds, Levenberg rules and classification are those of
+ * orbx_pose_optimization.  KannalaBrandt8::project(Vector3d) narrows to float for theta = atan2f(sqrtf(x^2 + y^2), z) and
+ * psi = atan2f(y, x) (here: sqrtf correctly rounded, atan2f = the double atan2 rounded once to float, within 1 ulp of glibc's);
+ * the polynomial, cos / sin and projectJac run in double.  The to-body error maps Xw through (mTrl * T) (composed, then
+ * normalised), its Jacobian through mTrl.map(T.map(Xw)) and mTrl's rotation matrix, as the reference does.  KB8 does not divide by
+ * z: points behind a camera (theta > pi/2) keep finite errors and stay in the solve.  A point at exactly x = y = 0 in a camera
+ * under an evaluated pose is outside the contract (projectJac divides by sqrt(x^2 + y^2)).  Tolerance parity as DESIGN.md states.
+ * Frame: Tcw as Sophus stores it (q x y z w, t; in/out as orbx_pose_opt_frame), the eight KB8 parameters (fx fy cx cy k0..k3) of
+ * the left and the right camera, and Trl = GetRelativePoseTrl() as Sophus stores it (q x y z w, t).  The right camera and Trl are
+ * validated and used only when the frame has right keypoints.  120 bytes. */
+typedef struct orbx_pose_opt_frame_kb8 {
+  float q[4], t[3], kb8_left[8], kb8_right[8], trl_q[4], trl_t[3];
+} orbx_pose_opt_frame_kb8;
+/* One frame from host arrays: kps holds N = n_left + n_right keypoints, the left camera's raw keypoints then the right camera's
+ * (n_right = 0: monocular KB8); world_pos [N][3], has_point / outlier [N] as orbx_pose_optimization.  Returns nGood or a negative
+ * error; arguments are validated before any device is touched (N <= 15000, octaves in [0, nlevels), finite world positions,
+ * pose, KB8 parameters and Trl, no zero quaternion). */
+int orbx_pose_optimization_kb8(int device, const orbx_keypoint* kps, int n_left, int n_right, const float* world_pos,
+                               const uint8_t* has_point, const float* inv_level_sigma2, int nlevels,
+                               orbx_pose_opt_frame_kb8* frame, uint8_t* outlier);
+/* The same for n_frames frames of ex's last extraction batch in ONE launch: frame f = left image first_left + f and right image
+ * first_right + f (first_right = -1: monocular KB8), keypoints as extracted (the raw keypoints the fisheye matchers read).
+ * world_pos [n_frames][2 cap][3], has_point / outlier [n_frames][2 cap]: the row layout of orbx_search_by_projection_fisheye_batch's
+ * occupied / match (left keypoint i at i, right keypoint j at n_left(f) + j, cap = orbx_batch_results_device's), so the matcher's
+ * match >= 0 is has_point as it stands; entries past a frame's n_left + n_right are not read or written.  frames / n_good /
+ * n_trials (may be NULL) [n_frames].  A frame gives the bits of the one-shot entry on the same data.  Returns ORBX_OK or a
+ * negative error. */
+int orbx_pose_optimization_fisheye_batch(orbx_extractor* ex, int first_left, int first_right, int n_frames, const float* world_pos,
+                                         const uint8_t* has_point, orbx_pose_opt_frame_kb8* frames, uint8_t* outlier,
+                                         int32_t* n_good, int32_t* n_trials);
+
 
 /* ---- measurement ------------------------------------------------------------------------------------ */
 

@@ -41,6 +41,9 @@ assert MPR_DTYPE.itemsize == 16
 POSE_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
                        ("bf", "<f4")])   # orbx_pose_opt_frame
 assert POSE_DTYPE.itemsize == 48
+POSE_KB8_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("kb8_left", "<f4", 8), ("kb8_right", "<f4", 8), ("trl_q", "<f4", 4),
+                           ("trl_t", "<f4", 3)])   # orbx_pose_opt_frame_kb8
+assert POSE_KB8_DTYPE.itemsize == 120
 
 
 class OrbxError(RuntimeError):
@@ -99,6 +102,8 @@ def lib():
         L.orbx_rgbd_depth_batch.argtypes = [vp, i, i, vp, i, C.c_ssize_t, C.c_ssize_t, f, f, vp, vp, i, vp]
         L.orbx_pose_optimization.argtypes = [i, vp, vp, vp, vp, i, vp, i, vp, vp]
         L.orbx_pose_optimization_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        L.orbx_pose_optimization_kb8.argtypes = [i, vp, i, i, vp, vp, vp, i, vp, vp]
+        L.orbx_pose_optimization_fisheye_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
                                         C.POINTER(i), vp, vp, vp]
         L.orbx_bf_knn2.argtypes = [i, vp, i, vp, i, vp, vp, vp]
@@ -754,6 +759,57 @@ def PoseOptimizationBatch(ex, first_image, n_frames, worldPos, hasPoint, q, t, c
     tr = np.zeros(n_frames, np.int32)
     _check(lib().orbx_pose_optimization_batch(ex._h, int(first_image), int(n_frames), int(stereo_pair0), _p(wp), _p(hp), _p(fr),
                                               _p(out), _p(ng), _p(tr)))
+    res = (ng, fr["q"].copy(), fr["t"].copy(), out.astype(bool))
+    return res + (tr,) if want_trials else res
+
+
+def _pose_frames_kb8(q, t, cam_left, cam_right, trl_q, trl_t, n_frames):
+    fr = np.zeros(n_frames, POSE_KB8_DTYPE)
+    fr["q"] = np.asarray(q, np.float32).reshape(n_frames, 4)
+    fr["t"] = np.asarray(t, np.float32).reshape(n_frames, 3)
+    fr["kb8_left"] = np.asarray(cam_left, np.float32).reshape(-1, 8)
+    if cam_right is not None:
+        fr["kb8_right"] = np.asarray(cam_right, np.float32).reshape(-1, 8)
+    fr["trl_q"] = [0, 0, 0, 1] if trl_q is None else np.asarray(trl_q, np.float32).reshape(-1, 4)
+    if trl_t is not None:
+        fr["trl_t"] = np.asarray(trl_t, np.float32).reshape(-1, 3)
+    return fr
+
+
+def PoseOptimizationKB8(kps, nLeft, worldPos, hasPoint, invLevelSigma2, q, t, camLeft, camRight=None, TrlQ=None, TrlT=None,
+                        outlier=None, device=0):
+    """Optimizer::PoseOptimization(Frame*) for a KannalaBrandt8 frame on the GPU (orbx_pose_optimization_kb8).  kps = mvKeys then
+    mvKeysRight (KP_DTYPE, N = Nleft + Nright; N == nLeft: monocular KB8), camLeft / camRight = the 8 KB8 parameters, (TrlQ, TrlT) =
+    GetRelativePoseTrl() as Sophus stores it (x y z w, t), other arguments as PoseOptimization.  Returns (nGood, q, t, outlier)."""
+    k = np.ascontiguousarray(kps, KP_DTYPE)
+    n = len(k)
+    nLeft = int(nLeft)
+    wp = np.ascontiguousarray(worldPos, np.float32).reshape(n, 3)
+    hp = np.ascontiguousarray(hasPoint, np.uint8).reshape(n)
+    sig = np.ascontiguousarray(invLevelSigma2, np.float32)
+    fr = _pose_frames_kb8(q, t, camLeft, camRight, TrlQ, TrlT, 1)
+    out = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(n)
+    ng = _check(lib().orbx_pose_optimization_kb8(int(device), _p(k), nLeft, n - nLeft, _p(wp), _p(hp), _p(sig), len(sig), _p(fr),
+                                                 _p(out)))
+    return ng, fr["q"][0].copy(), fr["t"][0].copy(), out.astype(bool)
+
+
+def PoseOptimizationFisheyeBatch(ex, first_left, first_right, n_frames, worldPos, hasPoint, q, t, camLeft, camRight=None, TrlQ=None,
+                                 TrlT=None, outlier=None, want_trials=False):
+    """PoseOptimizationKB8 of the frames of ex's last extraction batch in ONE kernel launch (orbx_pose_optimization_fisheye_batch):
+    frame f = left image first_left + f, right image first_right + f (-1: monocular KB8).  worldPos [n_frames][2 cap][3],
+    hasPoint / outlier [n_frames][2 cap] in the row layout of SearchByProjectionFisheyeBatch's match (left keypoints, then the
+    right ones), q [n_frames][4], t [n_frames][3], cameras / Trl one row for all frames or one per frame.
+    Returns (nGood, q, t, outlier[, trials])."""
+    n2 = 2 * ex.capacity
+    wp = np.ascontiguousarray(worldPos, np.float32).reshape(n_frames, n2, 3)
+    hp = np.ascontiguousarray(hasPoint, np.uint8).reshape(n_frames, n2)
+    fr = _pose_frames_kb8(q, t, camLeft, camRight, TrlQ, TrlT, n_frames)
+    out = np.zeros((n_frames, n2), np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(n_frames, n2)
+    ng = np.zeros(n_frames, np.int32)
+    tr = np.zeros(n_frames, np.int32)
+    _check(lib().orbx_pose_optimization_fisheye_batch(ex._h, int(first_left), int(first_right), int(n_frames), _p(wp), _p(hp),
+                                                      _p(fr), _p(out), _p(ng), _p(tr)))
     res = (ng, fr["q"].copy(), fr["t"].copy(), out.astype(bool))
     return res + (tr,) if want_trials else res
 

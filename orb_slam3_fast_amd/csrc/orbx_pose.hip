@@ -5,160 +5,11 @@
 // already holds the next iteration's system (g2o's next solve() recomputes exactly those errors at the same estimate).  Sums are
 // reduced per wave by a fixed xor butterfly and across waves in wave order: no atomics, run-to-run identical.  Thread 0 does
 // the 6x6 LDLT, the lambda logic, SE3Quat::exp and the composition and hands the next pose to evaluate over LDS.
-#include "orbx_host.h"
-#include <cfloat>
+// The KannalaBrandt8 kernel (orbx_pose_kb8.hip) shares that machinery (orbx_pose.h); the host side of both entries is here.
+#include "orbx_pose.h"
+#include <type_traits>
 
 namespace {
-
-#ifndef ORBX_POSE_BS
-#define ORBX_POSE_BS 256
-#endif
-constexpr int kBS = ORBX_POSE_BS;           // workgroup size (see DESIGN.md for the measurement behind it)
-constexpr int kNW = kBS / 64;
-constexpr int kMaxEdges = 15000;
-constexpr int kLdsEdges = 4096;             // edges staged in LDS (2 x float4 each: 128 KiB); larger frames stage in HBM
-constexpr int kNSum = 28;                   // H upper triangle (21), b (6), robust chi2
-static_assert(kBS * 64 >= kMaxEdges, "one 64-bit outlier mask per thread must cover a frame's edges");
-
-struct PoseArgs {
-  const orbx_keypoint* kps;        // mvKeysUn, by keypoint index
-  const float* uR;                 // mvuRight by keypoint index, nullptr = every edge mono
-  const float* wpos;               // [nE][3] world positions, by edge
-  const int* eidx;                 // edge -> keypoint index (ascending)
-  const orbx_pose_opt_frame* in;
-  float4* stage;                   // 2 * nE float4 when nE > kLdsEdges
-  float* poseOut;                  // q[4], t[3]
-  int* result;                     // nGood, trials
-  uint8_t* eout;                   // outlier flag by edge
-  int nE;
-};
-
-struct Pose { double q[4], t[3]; };   // Eigen order: x y z w
-
-// ---- SE3Quat (Thirdparty/g2o/g2o/types/se3quat.h) with Eigen's quaternion formulas
-__device__ __forceinline__ void qmul(const double* a, const double* b, double* r) {
-  r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-  r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-  r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-  r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ void cross(const double* a, const double* b, double* r) {
-  r[0] = a[1] * b[2] - a[2] * b[1];
-  r[1] = a[2] * b[0] - a[0] * b[2];
-  r[2] = a[0] * b[1] - a[1] * b[0];
-}
-// q * v = v + w * uv + vec x uv, uv = 2 (vec x v)
-__device__ __forceinline__ void qrot(const double* q, const double* v, double* r) {
-  double uv[3], c[3];
-  cross(q, v, uv);
-  uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-  cross(q, uv, c);
-  for (int i = 0; i < 3; i++) r[i] = v[i] + q[3] * uv[i] + c[i];
-}
-__device__ __forceinline__ void normalize_rotation(double* q) {   // SE3Quat::normalizeRotation: w >= 0, unit norm
-  if (q[3] < 0) for (int i = 0; i < 4; i++) q[i] = -q[i];
-  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  for (int i = 0; i < 4; i++) q[i] /= n;
-}
-template <int i>
-__device__ __forceinline__ void quat_from_R_diag(const double R[3][3], double* q) {   // the branch led by diagonal entry i
-  constexpr int j = (i + 1) % 3, k = (j + 1) % 3;
-  double t = sqrt(R[i][i] - R[j][j] - R[k][k] + 1.0);
-  q[i] = 0.5 * t;
-  t = 0.5 / t;
-  q[3] = (R[k][j] - R[j][k]) * t;
-  q[j] = (R[j][i] + R[i][j]) * t;
-  q[k] = (R[k][i] + R[i][k]) * t;
-}
-__device__ __forceinline__ void quat_from_R(const double R[3][3], double* q) {   // Eigen's Quaternion(const Matrix3&)
-  double t = R[0][0] + R[1][1] + R[2][2];
-  if (t > 0) {
-    t = sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (R[2][1] - R[1][2]) * t;
-    q[1] = (R[0][2] - R[2][0]) * t;
-    q[2] = (R[1][0] - R[0][1]) * t;
-  } else {
-    const bool i1 = R[1][1] > R[0][0];   // i = argmax of the diagonal, first index on ties
-    if (R[2][2] > (i1 ? R[1][1] : R[0][0])) quat_from_R_diag<2>(R, q);
-    else if (i1) quat_from_R_diag<1>(R, q);
-    else quat_from_R_diag<0>(R, q);
-  }
-}
-// SE3Quat::exp(update) * P (VertexSE3Expmap::oplusImpl): rotation first in the update vector, small-angle branch R = I + W + W^2
-__device__ __forceinline__ void oplus(const double* x, const Pose& P, Pose& out) {
-  const double w[3] = {x[0], x[1], x[2]}, u[3] = {x[3], x[4], x[5]};
-  const double theta = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  const double W[3][3] = {{0, -w[2], w[1]}, {w[2], 0, -w[0]}, {-w[1], w[0], 0}};
-  double W2[3][3], R[3][3], V[3][3];
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) W2[r][c] = W[r][0] * W[0][c] + W[r][1] * W[1][c] + W[r][2] * W[2][c];
-  if (theta < 0.00001) {
-    for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 3; c++) R[r][c] = V[r][c] = (r == c ? 1.0 : 0.0) + W[r][c] + W2[r][c];
-  } else {
-    const double s = sin(theta), co = cos(theta), th2 = theta * theta;
-    const double a = s / theta, b = (1 - co) / th2, c3 = (theta - s) / (th2 * theta);
-    for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 3; c++) {
-        const double I = r == c ? 1.0 : 0.0;
-        R[r][c] = I + a * W[r][c] + b * W2[r][c];
-        V[r][c] = I + b * W[r][c] + c3 * W2[r][c];
-      }
-  }
-  double qe[4], te[3], rt[3];
-  quat_from_R(R, qe);
-  normalize_rotation(qe);                       // SE3Quat(q, t) constructor
-  for (int r = 0; r < 3; r++) te[r] = V[r][0] * u[0] + V[r][1] * u[1] + V[r][2] * u[2];
-  qrot(qe, P.t, rt);                            // operator*: t = t_e + q_e * t_P, q = q_e * q_P, normalizeRotation
-  for (int r = 0; r < 3; r++) out.t[r] = te[r] + rt[r];
-  qmul(qe, P.q, out.q);
-  normalize_rotation(out.q);
-}
-
-// (H + lambda I) x = b by LDLT (linear_solver_dense.h:107-118); false = failed factorisation, x untouched
-__device__ __forceinline__ bool ldlt_solve(const double* H, const double* b, double lambda, double* x) {
-  double A[6][6], L[6][6], D[6], y[6];
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-  #pragma unroll
-  for (int c = r; c < 6; c++) { A[r][c] = A[c][r] = H[k++]; }
-#pragma unroll
-  for (int r = 0; r < 6; r++) A[r][r] += lambda;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = A[j][j];
-  #pragma unroll
-  for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
-    if (!(d > 0) || !isfinite(d)) return false;
-    D[j] = d;
-    L[j][j] = 1.0;
-  #pragma unroll
-  for (int i = j + 1; i < 6; i++) {
-      double s = A[i][j];
-    #pragma unroll
-  for (int m = 0; m < j; m++) s -= L[i][m] * L[j][m] * D[m];
-      L[i][j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double s = b[i];
-  #pragma unroll
-  for (int m = 0; m < i; m++) s -= L[i][m] * y[m];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double s = y[i] / D[i];
-  #pragma unroll
-  for (int m = i + 1; m < 6; m++) s -= L[m][i] * x[m];
-    x[i] = s;
-  }
-  return true;
-}
 
 // One edge at pose P: error, chi2 and (want_j) the 2x6 / 3x6 Jacobian.  Mono: Pinhole::project / projectJac with float
 // parameters times double (src/CameraModels/Pinhole.cpp:38-44,75-85; src/OptimizableTypes.cpp:49-62).  Stereo: the error with a
@@ -237,99 +88,6 @@ __device__ __forceinline__ bool edge_bad(const Pose& P, const Cam& K, const floa
   double e[M], chi2;
   edge_eval<M, false>(P, K, A, B, e, chi2, nullptr);
   return (float)chi2 > (M == 2 ? 5.991f : 7.815f);
-}
-
-enum : int { kEval = 0, kClassify = 1, kDone = 2 };
-
-struct Ctl {   // thread 0's optimiser state, in LDS
-  Pose P0, P, T, L;                  // initial, current estimate, pose to evaluate / last trial, last evaluated trial
-  double H[21], b[6], x[6];
-  double lambda, ni, curChi, iniChi;
-  int phase, stage, iter, qmax, nbadR, round, robust, nActive, trials, ok2;
-};
-
-__device__ __forceinline__ void ctl_trial(Ctl& c) {   // push, H + lambda I, solve, update
-  double x[6];
-  for (int i = 0; i < 6; i++) x[i] = c.x[i];
-  c.ok2 = ldlt_solve(c.H, c.b, c.lambda, x);
-  for (int i = 0; i < 6; i++) c.x[i] = x[i];   // a failed solve leaves g2o's x as it was
-  oplus(x, c.P, c.T);
-  c.phase = kEval;
-  c.stage = 1;
-}
-
-__device__ __forceinline__ void ctl_start_round(Ctl& c) {
-  c.P = c.P0;
-  c.L = c.P0;
-  if (c.nActive == 0) {   // initializeOptimization(0) drops the vertex, optimize() returns -1: the estimate stays
-    c.phase = kClassify;
-    return;
-  }
-  c.T = c.P;
-  c.stage = 0;
-  c.iter = 0;
-  c.phase = kEval;
-}
-
-// after an evaluation pass: sums = H (21), b (6), robust chi2 at c.T
-__device__ __forceinline__ void ctl_after_eval(Ctl& c, const double* sums) {
-  if (c.stage == 0) {   // solve(iteration 0): computeActiveErrors, buildSystem, lambda init
-    c.curChi = sums[27];
-    for (int i = 0; i < 21; i++) c.H[i] = sums[i];
-    for (int i = 0; i < 6; i++) c.b[i] = sums[21 + i];
-    c.iniChi = c.curChi;
-    double maxDiag = 0;
-    for (int j = 0, k = 0; j < 6; k += 6 - j, j++) maxDiag = fmax(fabs(c.H[k]), maxDiag);
-    c.lambda = 1e-5 * maxDiag;
-    c.ni = 2;
-    c.nbadR = 0;
-    c.qmax = 0;
-    for (int i = 0; i < 6; i++) c.x[i] = 0;
-    ctl_trial(c);
-    return;
-  }
-  c.trials++;
-  c.L = c.T;
-  double tempChi = sums[27];
-  if (!c.ok2) tempChi = DBL_MAX;
-  double rho = c.curChi - tempChi, scale = 0;
-  for (int j = 0; j < 6; j++) scale += c.x[j] * (c.lambda * c.x[j] + c.b[j]);
-  scale += 1e-3;
-  rho /= scale;
-  if (rho > 0 && isfinite(tempChi)) {
-    double alpha = 1. - pow(2 * rho - 1, 3);
-    alpha = fmin(alpha, 2. / 3.);
-    c.lambda *= fmax(1. / 3., alpha);
-    c.ni = 2;
-    c.curChi = tempChi;
-    c.P = c.T;
-    for (int i = 0; i < 21; i++) c.H[i] = sums[i];
-    for (int i = 0; i < 6; i++) c.b[i] = sums[21 + i];
-  } else {
-    c.lambda *= c.ni;
-    c.ni *= 2;
-  }
-  c.qmax++;
-  if (rho < 0 && c.qmax < 10) { ctl_trial(c); return; }
-  bool term = c.qmax == 10 || rho == 0;
-  if (!term) {   // Raul's stop criterion
-    if ((c.iniChi - c.curChi) * 1e3 < c.iniChi) c.nbadR++; else c.nbadR = 0;
-    term = c.nbadR >= 3;
-  }
-  c.iter++;
-  if (!term && c.iter < 10) {   // next solve(): errors and system at the estimate are the ones held
-    c.iniChi = c.curChi;
-    c.qmax = 0;
-    ctl_trial(c);
-    return;
-  }
-  c.phase = kClassify;
-}
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 __global__ __launch_bounds__(kBS) void k_pose_opt(const PoseArgs* __restrict__ frames, const float* __restrict__ invSigma2,
@@ -435,14 +193,19 @@ __global__ __launch_bounds__(kBS) void k_pose_opt(const PoseArgs* __restrict__ f
   for (int k = tid, j = 0; k < nE; k += kBS, j++) A.eout[k] = (outMask >> j) & 1;
 }
 
-int launch_pose_opt(const PoseArgs* d_frames, int nFrames, int maxE, const float* d_invSigma2, int nlevels) {
+template <class Args>
+int launch_pose_opt(const Args* d_frames, int nFrames, int maxE, const float* d_invSigma2, int nlevels) {
   const size_t lds = (size_t)std::min(std::max(maxE, 1), kLdsEdges) * 2 * sizeof(float4);
-  if (lds > 48 * 1024) {
-    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_opt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if constexpr (std::is_same<Args, PoseArgsKb8>::value) {
+    HIPC(launch_pose_opt_kb8(d_frames, nFrames, lds, d_invSigma2, nlevels));
+  } else {
+    if (lds > 48 * 1024) {
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pose_opt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    const double deltaMono = (float)std::sqrt(5.991), deltaStereo = (float)std::sqrt(7.815);
+    hipLaunchKernelGGL(k_pose_opt, dim3(nFrames), dim3(kBS), lds, nullptr, d_frames, d_invSigma2, nlevels, deltaMono, deltaStereo);
+    HIPC(hipGetLastError());
   }
-  const double deltaMono = (float)std::sqrt(5.991), deltaStereo = (float)std::sqrt(7.815);
-  hipLaunchKernelGGL(k_pose_opt, dim3(nFrames), dim3(kBS), lds, nullptr, d_frames, d_invSigma2, nlevels, deltaMono, deltaStereo);
-  HIPC(hipGetLastError());
   return ORBX_OK;
 }
 
@@ -461,13 +224,30 @@ struct FrameEdges {
   std::vector<float> pos;
 };
 
+bool finite_kb8_frame(const orbx_pose_opt_frame_kb8& f, bool rig) {
+  for (int i = 0; i < 4; i++)
+    if (!std::isfinite(f.q[i]) || (rig && !std::isfinite(f.trl_q[i]))) return false;
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(f.t[i]) || (rig && !std::isfinite(f.trl_t[i]))) return false;
+  for (int i = 0; i < 8; i++)
+    if (!std::isfinite(f.kb8_left[i]) || (rig && !std::isfinite(f.kb8_right[i]))) return false;
+  const auto nonzero = [](const float* q) { return q[0] != 0 || q[1] != 0 || q[2] != 0 || q[3] != 0; };
+  return nonzero(f.q) && (!rig || nonzero(f.trl_q));
+}
+
+template <class Frame> struct ArgsOf { using type = PoseArgs; };
+template <> struct ArgsOf<orbx_pose_opt_frame_kb8> { using type = PoseArgsKb8; };
+
 // One pack for every frame: inputs (args, tables, edges), then the outputs (poses, results, flags) in one contiguous area.
-int run_frames(const std::vector<PoseArgs>& proto, const std::vector<FrameEdges>& fe, const orbx_pose_opt_frame* frames,
+// Frame = orbx_pose_opt_frame (pinhole, k_pose_opt) or orbx_pose_opt_frame_kb8 (k_pose_opt_kb8).
+template <class Frame>
+int run_frames(const std::vector<typename ArgsOf<Frame>::type>& proto, const std::vector<FrameEdges>& fe, const Frame* frames,
                const float* invSigma2, int nlevels, const orbx_keypoint* hostKps, const float* hostUR, int hostN,
                std::vector<float>& poses, std::vector<int>& results, std::vector<uint8_t>& flags, std::vector<size_t>& flagOff) {
   const int F = (int)proto.size();
   Pack pk;
-  std::vector<PoseArgs> args = proto;
+  using Args = typename ArgsOf<Frame>::type;
+  std::vector<Args> args = proto;
   std::vector<size_t> oIdx(F), oPos(F), oStage(F, 0);
   size_t totalE = 0;
   int maxE = 0;
@@ -482,9 +262,10 @@ int run_frames(const std::vector<PoseArgs>& proto, const std::vector<FrameEdges>
   // one-shot frame: its keypoints and uR travel in the pack
   const size_t oKps = hostKps ? pk.add(hostKps, std::max<size_t>(hostN, 1) * sizeof(orbx_keypoint), (size_t)hostN * sizeof(orbx_keypoint)) : 0;
   const size_t oUR = hostUR ? pk.add(hostUR, std::max<size_t>(hostN, 1) * sizeof(float), (size_t)hostN * sizeof(float)) : 0;
-  const size_t oIn = pk.add(frames, (size_t)F * sizeof(orbx_pose_opt_frame));
+  constexpr bool kb8 = std::is_same<Frame, orbx_pose_opt_frame_kb8>::value;
+  const size_t oIn = pk.add(frames, (size_t)F * sizeof(Frame));
   const size_t oSig = pk.add(invSigma2, (size_t)nlevels * sizeof(float));
-  const size_t oArgs = pk.add(args.data(), (size_t)F * sizeof(PoseArgs));
+  const size_t oArgs = pk.add(args.data(), (size_t)F * sizeof(Args));
   const size_t oPose = pk.add(nullptr, (size_t)F * 8 * sizeof(float));
   const size_t oRes = pk.add(nullptr, (size_t)F * 2 * sizeof(int));
   const size_t oFlags = pk.add(nullptr, std::max<size_t>(totalE, 1));
@@ -494,10 +275,11 @@ int run_frames(const std::vector<PoseArgs>& proto, const std::vector<FrameEdges>
   hipError_t e = pk.reserve();
   if (e != hipSuccess) { pk.release(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
   for (int f = 0; f < F; f++) {
-    PoseArgs& a = args[f];
+    Args& a = args[f];
     a.eidx = pk.ptr<int>(oIdx[f]);
     a.wpos = pk.ptr<float>(oPos[f]);
-    a.in = pk.ptr<orbx_pose_opt_frame>(oIn) + f;
+    if constexpr (kb8) a.inK = pk.ptr<orbx_pose_opt_frame_kb8>(oIn) + f;
+    else a.in = pk.ptr<orbx_pose_opt_frame>(oIn) + f;
     a.stage = oStage[f] ? pk.ptr<float4>(oStage[f]) : nullptr;
     a.poseOut = pk.ptr<float>(oPose) + 8 * f;
     a.result = pk.ptr<int>(oRes) + 2 * f;
@@ -506,12 +288,13 @@ int run_frames(const std::vector<PoseArgs>& proto, const std::vector<FrameEdges>
     if (hostKps) {
       a.kps = pk.ptr<orbx_keypoint>(oKps);
       a.uR = hostUR ? pk.ptr<float>(oUR) : nullptr;
+      if constexpr (kb8) a.kpsR = a.kps + a.nLeft;   // one array: the left camera's keypoints, then the right camera's
     }
   }
   e = pk.commit();
   int rc = ORBX_OK;
   if (e == hipSuccess) {
-    rc = launch_pose_opt(pk.ptr<PoseArgs>(oArgs), F, maxE, pk.ptr<float>(oSig), nlevels);
+    rc = launch_pose_opt(pk.ptr<Args>(oArgs), F, maxE, pk.ptr<float>(oSig), nlevels);
     if (rc == ORBX_OK) {
       const uint8_t* h = pk.fetch(oPose, outBytes, &e);
       if (e == hipSuccess) {
@@ -530,7 +313,8 @@ int run_frames(const std::vector<PoseArgs>& proto, const std::vector<FrameEdges>
   return ORBX_OK;
 }
 
-void write_pose(orbx_pose_opt_frame& f, const float* p) {
+template <class Frame>
+void write_pose(Frame& f, const float* p) {
   for (int i = 0; i < 4; i++) f.q[i] = p[i];
   for (int i = 0; i < 3; i++) f.t[i] = p[4 + i];
 }
@@ -614,6 +398,91 @@ int orbx_pose_optimization_batch(orbx_extractor* ex, int first_image, int n_fram
     n_good[f] = results[2 * f];
     if (n_trials) n_trials[f] = results[2 * f + 1];
     for (size_t k = 0; k < fe[f].idx.size(); k++) outlier[(size_t)f * cap + fe[f].idx[k]] = flags[flagOff[f] + k];
+  }
+  return ORBX_OK;
+}
+
+int orbx_pose_optimization_kb8(int device, const orbx_keypoint* kps, int n_left, int n_right, const float* world_pos,
+                               const uint8_t* has_point, const float* inv_level_sigma2, int nlevels,
+                               orbx_pose_opt_frame_kb8* frame, uint8_t* outlier) {
+  if (n_left < 0 || n_right < 0 || !frame || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || !inv_level_sigma2)
+    return fail(ORBX_E_BADARG, "bad argument");
+  if ((long long)n_left + n_right > kMaxEdges) return fail(ORBX_E_BADARG, "more than 15000 keypoints");
+  const int n = n_left + n_right;
+  if (n && (!kps || !world_pos || !has_point || !outlier)) return fail(ORBX_E_BADARG, "bad argument");
+  if (!finite_kb8_frame(*frame, n_right > 0))
+    return fail(ORBX_E_BADARG, "pose, KB8 parameters or Trl not finite (or a zero quaternion)");
+  FrameEdges fe;
+  for (int i = 0; i < n; i++) {
+    if (!has_point[i]) continue;
+    if (kps[i].octave < 0 || kps[i].octave >= nlevels) return fail(ORBX_E_BADARG, "keypoint octave outside [0, nlevels)");
+    if (!finite3(world_pos + 3 * (size_t)i)) return fail(ORBX_E_BADARG, "world position not finite");
+    fe.idx.push_back(i);
+    fe.pos.insert(fe.pos.end(), world_pos + 3 * (size_t)i, world_pos + 3 * (size_t)i + 3);
+  }
+  int rc = set_device(device);
+  if (rc != ORBX_OK) return rc;
+  std::vector<PoseArgsKb8> proto(1);
+  proto[0].nLeft = n_left;
+  std::vector<size_t> flagOff(1);
+  std::vector<float> poses;
+  std::vector<int> results;
+  std::vector<uint8_t> flags;
+  rc = run_frames(proto, {fe}, frame, inv_level_sigma2, nlevels, kps, nullptr, n, poses, results, flags, flagOff);
+  if (rc != ORBX_OK) return rc;
+  write_pose(*frame, poses.data());
+  for (size_t k = 0; k < fe.idx.size(); k++) outlier[fe.idx[k]] = flags[k];
+  return results[0];
+}
+
+int orbx_pose_optimization_fisheye_batch(orbx_extractor* ex, int first_left, int first_right, int n_frames, const float* world_pos,
+                                         const uint8_t* has_point, orbx_pose_opt_frame_kb8* frames, uint8_t* outlier,
+                                         int32_t* n_good, int32_t* n_trials) {
+  if (!ex || n_frames < 0 || first_left < 0 || first_right < -1 ||
+      (n_frames && (!world_pos || !has_point || !frames || !outlier || !n_good)))
+    return fail(ORBX_E_BADARG, "bad argument");
+  if (n_frames == 0) return ORBX_OK;
+  const bool rig = first_right >= 0;
+  if (ex->lastN <= 0 || first_left + n_frames > ex->lastN || (rig && first_right + n_frames > ex->lastN))
+    return fail(ORBX_E_BADARG, "frames outside the handle's last batch");
+  const int cap = ex->gmax.outCap, F = n_frames;
+  const size_t row = 2 * (size_t)cap;
+  for (int f = 0; f < F; f++)
+    if (!finite_kb8_frame(frames[f], rig)) return fail(ORBX_E_BADARG, "pose, KB8 parameters or Trl not finite (or a zero quaternion)");
+  int rc = set_device(ex->device);
+  if (rc != ORBX_OK) return rc;
+  std::vector<int> nL(F), nR(F, 0);
+  HIPC(hipStreamSynchronize(ex->stream));
+  HIPC(hipMemcpy(nL.data(), ex->d_nOut.p + first_left, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  if (rig) HIPC(hipMemcpy(nR.data(), ex->d_nOut.p + first_right, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<FrameEdges> fe(F);
+  std::vector<PoseArgsKb8> proto(F);
+  for (int f = 0; f < F; f++) {
+    nL[f] = std::min(std::max(nL[f], 0), cap);
+    nR[f] = std::min(std::max(nR[f], 0), cap);
+    for (int i = 0; i < nL[f] + nR[f]; i++) {   // row = [left keypoints | right keypoints], as the fisheye matchers write it
+      const size_t r = f * row + i;
+      if (!has_point[r]) continue;
+      if (!finite3(world_pos + 3 * r)) return fail(ORBX_E_BADARG, "world position not finite");
+      fe[f].idx.push_back(i);
+      fe[f].pos.insert(fe[f].pos.end(), world_pos + 3 * r, world_pos + 3 * r + 3);
+    }
+    if ((int)fe[f].idx.size() > kMaxEdges) return fail(ORBX_E_BADARG, "more than 15000 edges in a frame");
+    proto[f].kps = ex->d_kps.p + (size_t)(first_left + f) * cap;
+    proto[f].kpsR = rig ? ex->d_kps.p + (size_t)(first_right + f) * cap : nullptr;
+    proto[f].nLeft = nL[f];
+  }
+  std::vector<size_t> flagOff(F);
+  std::vector<float> poses;
+  std::vector<int> results;
+  std::vector<uint8_t> flags;
+  rc = run_frames(proto, fe, frames, ex->invsig2.data(), ex->prm.nlevels, nullptr, nullptr, 0, poses, results, flags, flagOff);
+  if (rc != ORBX_OK) return rc;
+  for (int f = 0; f < F; f++) {
+    write_pose(frames[f], poses.data() + 8 * f);
+    n_good[f] = results[2 * f];
+    if (n_trials) n_trials[f] = results[2 * f + 1];
+    for (size_t k = 0; k < fe[f].idx.size(); k++) outlier[f * row + fe[f].idx[k]] = flags[flagOff[f] + k];
   }
   return ORBX_OK;
 }
