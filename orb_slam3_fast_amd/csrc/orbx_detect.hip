@@ -13,9 +13,9 @@ namespace orbx {
 // (the loader funnel-shifts the unaligned global row).  Stage 1: a lane owns a "quad" of 4 detectable pixels and reads
 // the three rows that hold ring pixels 0 / 4 / 8 / 12 of the quad (7 dwords, kept in registers) for the compass pre-test
 // on two packed pixel pairs (compass_pair); survivors go to an LDS list.
-// Stage 2: dense lanes, two survivors per lane in packed f16: the exact contrast M from the 16 ring pixels (8-windows of
-// minima / maxima shared by the two arcs that contain them, 36 packed operations per polarity); corner iff M > t, score
-// M - 1.  Then list-based 3x3 NMS.
+// Stage 2: dense lanes, one survivor per lane and packed f16 network, bright polarity in the low half and dark in the high half:
+// the exact contrast M from the 16 ring pixels (8-windows of minima shared by the two arcs that contain them, 36 packed
+// operations for both polarities); corner iff M > t, score M - 1.  Then list-based 3x3 NMS.
 constexpr int kRingDX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
 constexpr int kRingDY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
 #ifndef ORBX_ROW_ROUNDS
@@ -45,12 +45,10 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) { retur
 // = max( max_s min(arc_s) - c , c - min_s max(arc_s) ).  Sliding 9-windows are built from 3-windows: 16 + 16 + 8
 // three-input operations per polarity.  The pixel is a corner at threshold t iff M > t, and its cornerScore is M - 1
 //  -- one pass gives both the decision and the score.
-// Two pixels per lane in packed half precision.  A pixel value v (0..255) is used
-// as the f16 BIT PATTERN v, i.e. the subnormal v * 2^-24 (kernels run with f16 denormals preserved,
-// .amdhsa_float_denorm_mode_16_64 3): order preserving, and sums / differences of such values (|d| <= 255) are exact
-// multiples of 2^-24, so v_pk_minimum3_f16 / v_pk_maximum3_f16 / v_pk_add_f16 give bit-exact integer results for two
-// pixels at the cost of one, and the two bytes are packed by a single v_perm (no bias to OR in).  Returns M for
-// pixel A in .x and pixel B in .y, each as the bit pattern of |M| with the f16 sign bit for M < 0.
+// Packed half precision.  A pixel value v (0..255) is used as the f16 BIT PATTERN v, i.e. the subnormal v * 2^-24 (kernels run
+// with f16 denormals preserved, .amdhsa_float_denorm_mode_16_64 3): order preserving, and sums / differences of such values
+// (|d| <= 255) are exact multiples of 2^-24, so v_pk_minimum3_f16 / v_pk_maximum3_f16 / v_pk_add_f16 give bit-exact integer
+// results for two values at the cost of one (two pixels in stage 1, two polarities of one pixel in stage 2).
 typedef _Float16 orbx_h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ orbx_h2 pk_min3(orbx_h2 a, orbx_h2 b, orbx_h2 c) {
   return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c);
@@ -80,154 +78,39 @@ __device__ __forceinline__ void compass_pair(const uint32_t (&r)[7][3], orbx_h2 
   m1 = __ballot(M.y > th2.y);
 }
 
-// EXPERIMENT (round 5, -DORBX_EVEN_FILTER=1; measured and rejected): a second necessary test on the dense survivor
-// list, in front of the 16-pixel contrast pass.  A 9-arc covers at least four CONSECUTIVE even ring positions (0, 2, .., 14), so
-// a corner has four cyclically consecutive even-ring pixels all > c + t or all < c - t: with e[q] = ring pixel 2q,
-// hi = max_q min(e[q], e[q+1], e[q+2], e[q+3]), lo = min_q max(...), the pixel can only be a corner if max(hi - c, c - lo) > t.
-// Two survivors per lane in packed f16 like the contrast pass: 9 byte reads + 9 v_perm per pair, 8 + 8 + 3 packed operations per
-// polarity, 3 + 2 to decide.
-#ifndef ORBX_D16_PAIRS
-#define ORBX_D16_PAIRS 0   // measured: bit-exact, 17 v_perm -> 17 v_or per pass, and NO faster (216.5 vs 218.4 us: one wait for all 34 loads loses the overlap the compiler's staged waits had); profiles/r5_d16_pairs_ab.txt
-#endif
-#ifndef ORBX_EVEN_FILTER
-#define ORBX_EVEN_FILTER 0
-#endif
-// TIMING-ONLY ablations (wrong results; tools/build_variant.sh): 1 no tile load, 2 no stage 1 (no survivors), 4 no stage 2 (survivors
-// dropped), 8 no NMS / emit, 16 return behind the scalar front
-#ifndef DET_ABLATE
-#define DET_ABLATE 0
-#endif
-__device__ __forceinline__ orbx_h2 even_ring_contrast2_lds(const uint8_t* a8, const uint8_t* b8, int TP) {
-  orbx_h2 e[8];
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    const int off = (kRingDY[2 * q] + 3) * TP + kRingDX[2 * q] + 3;
-    orbx_us2 v;
-    v.x = a8[off];
-    v.y = b8[off];
-    e[q] = __builtin_bit_cast(orbx_h2, v);
-  }
-  orbx_h2 hi, lo;
-  {
-    orbx_h2 p2[8], w[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) p2[q] = __builtin_elementwise_minimum(e[q], e[(q + 1) & 7]);
-#pragma unroll
-    for (int q = 0; q < 8; q++) w[q] = __builtin_elementwise_minimum(p2[q], p2[(q + 2) & 7]);
-    hi = pk_max3(w[0], w[1], w[2]);
-    hi = pk_max3(hi, w[3], w[4]);
-    hi = pk_max3(hi, w[5], w[6]);
-    hi = __builtin_elementwise_maximum(hi, w[7]);
-  }
-  {
-    orbx_h2 p2[8], w[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) p2[q] = __builtin_elementwise_maximum(e[q], e[(q + 1) & 7]);
-#pragma unroll
-    for (int q = 0; q < 8; q++) w[q] = __builtin_elementwise_maximum(p2[q], p2[(q + 2) & 7]);
-    lo = pk_min3(w[0], w[1], w[2]);
-    lo = pk_min3(lo, w[3], w[4]);
-    lo = pk_min3(lo, w[5], w[6]);
-    lo = __builtin_elementwise_minimum(lo, w[7]);
-  }
-  orbx_us2 cv;
-  cv.x = a8[3 * TP + 3];
-  cv.y = b8[3 * TP + 3];
-  const orbx_h2 c = __builtin_bit_cast(orbx_h2, cv);
-  return __builtin_elementwise_maximum(hi - c, c - lo);
-}
-
-// a8 / b8 point at the TOP-LEFT corner of each pixel's 7x7 window, so every ring offset is a non-negative ds_read immediate.
-typedef unsigned short orbx_us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ orbx_h2 fast_contrast_network(const orbx_h2 (&r)[16], orbx_h2 c) {
-  // max over the 16 arcs of the arc's minimum, 36 packed operations per polarity instead of 40 (round 4): for even k the arcs
-  // starting at k and k + 1 share the 8-window W = r[k+1 .. k+8], and max(min(W, r[k]), min(W, r[k+9])) = min(W, max(r[k], r[k+9])):
-  // pair minima p (8), 4-windows w4 (8), e = max of the two end points (8), f = min3(w4[j], w4[j+2], e[j]) (8), max over f (4).
-  // One polarity after the other (the scheduling barrier keeps them apart): the kernel's register peak is here.
-  orbx_h2 maxmin, minmax;
-  {
-    orbx_h2 pr[8], w4[8], f[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) pr[q] = __builtin_elementwise_minimum(r[(2 * q + 1) & 15], r[(2 * q + 2) & 15]);
-#pragma unroll
-    for (int q = 0; q < 8; q++) w4[q] = __builtin_elementwise_minimum(pr[q], pr[(q + 1) & 7]);
-#pragma unroll
-    for (int q = 0; q < 8; q++)
-      f[q] = pk_min3(w4[q], w4[(q + 2) & 7], __builtin_elementwise_maximum(r[2 * q], r[(2 * q + 9) & 15]));
-    maxmin = pk_max3(f[0], f[1], f[2]);
-    maxmin = pk_max3(maxmin, f[3], f[4]);
-    maxmin = pk_max3(maxmin, f[5], f[6]);
-    maxmin = __builtin_elementwise_maximum(maxmin, f[7]);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  {
-    orbx_h2 pr[8], w4[8], f[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) pr[q] = __builtin_elementwise_maximum(r[(2 * q + 1) & 15], r[(2 * q + 2) & 15]);
-#pragma unroll
-    for (int q = 0; q < 8; q++) w4[q] = __builtin_elementwise_maximum(pr[q], pr[(q + 1) & 7]);
-#pragma unroll
-    for (int q = 0; q < 8; q++)
-      f[q] = pk_max3(w4[q], w4[(q + 2) & 7], __builtin_elementwise_minimum(r[2 * q], r[(2 * q + 9) & 15]));
-    minmax = pk_min3(f[0], f[1], f[2]);
-    minmax = pk_min3(minmax, f[3], f[4]);
-    minmax = pk_min3(minmax, f[5], f[6]);
-    minmax = __builtin_elementwise_minimum(minmax, f[7]);
-  }
-  return __builtin_elementwise_maximum(maxmin - c, c - minmax);
-}
-
-__device__ __forceinline__ orbx_h2 fast_contrast2_lds(const uint8_t* a8, const uint8_t* b8, int TP) {
+// FAST contrast of ONE pixel per lane with both polarities in the two halves of one packed network (round 7).  Every ring pixel
+// v enters as (v, -v): the f16 sign bit negates a subnormal pattern exactly, and min / max of negated values are the negated max /
+// min, so the half that computes the bright term max_s min(arc_s) on (v) computes -min_s max(arc_s) on (-v) -- the dark term --
+// with the same instructions.  The compiler folds (v, -v) into op_sel_hi / neg_hi modifiers of the first layer: no packing
+// instruction at all (rounds 1-6 paired two survivors per lane, which needs a v_perm per ring pixel and one 36-operation network
+// per polarity; this is one network per survivor, i.e. the same network count without the 17 v_perm per pair).  Returns
+// M = max(M_bright, M_dark) as a plain f16 (the bit pattern of |M|, sign bit for M < 0).
+// The network: max over the 16 arcs of the arc's minimum, 36 packed operations instead of 40 (round 4): for even k the arcs
+// starting at k and k + 1 share the 8-window W = r[k+1 .. k+8], and max(min(W, r[k]), min(W, r[k+9])) = min(W, max(r[k], r[k+9])):
+// pair minima p (8), 4-windows w4 (8), e = max of the two end points (8), f = min3(w4[j], w4[j+2], e[j]) (8), max over f (4).
+// a8 points at the TOP-LEFT corner of the pixel's 7x7 window, so every ring offset is a non-negative ds_read immediate.
+__device__ __forceinline__ _Float16 fast_contrast_lds(const uint8_t* a8, int TP) {
   orbx_h2 r[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
-    const int off = (kRingDY[k] + 3) * TP + kRingDX[k] + 3;
-    orbx_us2 v;
-    v.x = a8[off];
-    v.y = b8[off];  // ds_read_u8_d16_hi: the pair is packed by the loads
-    r[k] = __builtin_bit_cast(orbx_h2, v);
+    const _Float16 v = __builtin_bit_cast(_Float16, (unsigned short)a8[(kRingDY[k] + 3) * TP + kRingDX[k] + 3]);
+    r[k] = orbx_h2{v, -v};
   }
-  orbx_us2 cv;
-  cv.x = a8[3 * TP + 3];
-  cv.y = b8[3 * TP + 3];
-  return fast_contrast_network(r, __builtin_bit_cast(orbx_h2, cv));
-}
-
-// The same contrast for a pair of DIFFERENT survivors with the byte pairs packed by the LOADS (round 5).  On gfx950 a d16 load
-// zeroes the other half of its destination (tools/ubench/d16_probe.hip: ds_read_u8_d16 -> 0x000000bb, ds_read_u8_d16_hi ->
-// 0x00bb0000), which is why the compiler will not merge two of them into one register -- but it also means that the pair is
-// lo | hi: a 2-cycle v_or_b32 instead of the 4-cycle v_perm_b32 the compiler's ds_read_u8 pairs need (17 per pass; VALU issue is
-// this kernel's limit).  The loads are inline asm (the compiler never selects the d16 forms on an SRAM-ECC target):
-// it does not count them, so all 34 are issued, ONE s_waitcnt follows, and the registers only become visible to later code
-// through the "+v" ties behind it.  Compile-time pitch only (the offsets are ds_read immediates).
-template <int OFF>
-__device__ __forceinline__ void lds_byte_pair_d16(uint32_t aA, uint32_t aB, uint32_t& lo, uint32_t& hi) {
-  asm volatile("ds_read_u8_d16 %0, %2 offset:%4\n\tds_read_u8_d16_hi %1, %3 offset:%4" : "=&v"(lo), "=&v"(hi) : "v"(aA), "v"(aB), "n"(OFF));
-}
-template <int TP, int K>
-__device__ __forceinline__ void ring_pairs_d16(uint32_t aA, uint32_t aB, uint32_t (&lo)[17], uint32_t (&hi)[17]) {
-  if constexpr (K < 16) {
-    lds_byte_pair_d16<(kRingDY[K] + 3) * TP + kRingDX[K] + 3>(aA, aB, lo[K], hi[K]);
-    ring_pairs_d16<TP, K + 1>(aA, aB, lo, hi);
-  } else {
-    lds_byte_pair_d16<3 * TP + 3>(aA, aB, lo[16], hi[16]);   // the centre
-  }
-}
-template <int TP>
-__device__ __forceinline__ orbx_h2 fast_contrast2_lds_d16(const uint8_t* a8, const uint8_t* b8) {
-  uint32_t lo[17], hi[17];
-  ring_pairs_d16<TP, 0>((uint32_t)(uintptr_t)a8, (uint32_t)(uintptr_t)b8, lo, hi);
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "+v"(lo[4]), "+v"(lo[5]), "+v"(lo[6]), "+v"(lo[7]), "+v"(lo[8]),
-                 "+v"(lo[9]), "+v"(lo[10]), "+v"(lo[11]), "+v"(lo[12]), "+v"(lo[13]), "+v"(lo[14]));
-  asm volatile("" : "+v"(lo[15]), "+v"(lo[16]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(hi[4]), "+v"(hi[5]),
-                     "+v"(hi[6]), "+v"(hi[7]), "+v"(hi[8]), "+v"(hi[9]), "+v"(hi[10]), "+v"(hi[11]), "+v"(hi[12]));
-  asm volatile("" : "+v"(hi[13]), "+v"(hi[14]), "+v"(hi[15]), "+v"(hi[16]));
-  orbx_h2 r[16];
+  const _Float16 cv = __builtin_bit_cast(_Float16, (unsigned short)a8[3 * TP + 3]);
+  orbx_h2 pr[8], w4[8], f[8];
 #pragma unroll
-  for (int k = 0; k < 16; k++) r[k] = __builtin_bit_cast(orbx_h2, lo[k] | hi[k]);
-  const orbx_h2 c = __builtin_bit_cast(orbx_h2, lo[16] | hi[16]);
-  return fast_contrast_network(r, c);
+  for (int q = 0; q < 8; q++) pr[q] = __builtin_elementwise_minimum(r[(2 * q + 1) & 15], r[(2 * q + 2) & 15]);
+#pragma unroll
+  for (int q = 0; q < 8; q++) w4[q] = __builtin_elementwise_minimum(pr[q], pr[(q + 1) & 7]);
+#pragma unroll
+  for (int q = 0; q < 8; q++)
+    f[q] = pk_min3(w4[q], w4[(q + 2) & 7], __builtin_elementwise_maximum(r[2 * q], r[(2 * q + 9) & 15]));
+  orbx_h2 maxmin = pk_max3(f[0], f[1], f[2]);
+  maxmin = pk_max3(maxmin, f[3], f[4]);
+  maxmin = pk_max3(maxmin, f[5], f[6]);
+  maxmin = __builtin_elementwise_maximum(maxmin, f[7]);
+  const orbx_h2 d = maxmin - orbx_h2{cv, -cv};   // (max min(arc) - c, c - min max(arc)): exact, |d| <= 255
+  return __builtin_elementwise_maximum(d.x, d.y);
 }
 
 // wave mask of the lanes below n (n <= 0: none, n >= 64: all) -- scalar ALU only
@@ -323,8 +206,7 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
 
   int pitch;
   const uint8_t* im = level_ptr(g, p, img, l, pitch);
-  if ((DET_ABLATE & 16) && dw != 4095) { if (lane == 0) *myCount = 0; return; }
-  bool tileDone = (DET_ABLATE & 1) && dw != 4095;
+  bool tileDone = false;
   if (TPC != 0 && kDetectWideLoad) {
     // Fast loader for the compile-time tile pitches: a row is TPC / P pieces of P = 16, 8 or 4 bytes (the largest power of two that
     // divides the pitch: 48 -> 3 x 16, 56 -> 7 x 8, 44 / 52 -> 11 / 13 x 4); lane = (row, piece), one UNALIGNED global load
@@ -421,7 +303,7 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     __syncthreads();
     if (pass == 0) DET_MK();
     // dense corner test, 4 pixels per lane; corners are compacted into an LDS list and scored with dense
-    // lanes (the score needs ~110 min/max ops: running it under per-lane divergence would dominate).
+    // lanes (the score needs ~40 min/max ops: running it under per-lane divergence would dominate).
     // Stage 1 (4 pixels per lane, registers): compass pre-test -> survivor list.
     // Stage 2 (dense lanes over survivors): contrast M from the 16 ring pixels; corner iff M > t, score M - 1
     //          goes to the u8 score tile and the corner to the corner list (for the list-based NMS).
@@ -431,55 +313,36 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     bool overflowed = false;  // more corners than the list holds: the NMS falls back to scanning the score tile
     auto flush_survivors = [&]() {
       __syncthreads();
-      const orbx_h2 th2 = __builtin_bit_cast(orbx_h2, (uint32_t)t * 0x00010001u);  // t in the same subnormal encoding
+      const _Float16 th = __builtin_bit_cast(_Float16, (unsigned short)t);  // t in the same subnormal encoding
       const int s0 = nList;
-      int nSurv = sEnd - s0;
-#if ORBX_EVEN_FILTER
-      {  // compaction of the survivor list in place by the even-ring test (entry k is read before entry k' <= k is written:
-         // one wave, LDS operations complete in order)
-        int wpos = 0;
-        for (int base = 0; base < nSurv; base += 128) {
-          const int rem = nSurv - base;
-          const uint64_t vA = low_lanes(rem), vB = low_lanes(rem - 64);
-          const int oA = list[s0 + min(base + lane, nSurv - 1)], oB = list[s0 + min(base + 64 + lane, nSurv - 1)];
-          const orbx_h2 M = even_ring_contrast2_lds(tile8 + oA, tile8 + oB, TP);
-          const uint64_t mA = __ballot(M.x > th2.x) & vA, mB = __ballot(M.y > th2.y) & vB;
-          if (__builtin_amdgcn_inverse_ballot_w64(mA)) (list + s0 + wpos)[prefix_count(mA)] = (uint16_t)oA;
-          wpos += __popcll(mA);
-          if (__builtin_amdgcn_inverse_ballot_w64(mB)) (list + s0 + wpos)[prefix_count(mB)] = (uint16_t)oB;
-          wpos += __popcll(mB);
-        }
-        nSurv = wpos;
-        __syncthreads();
-      }
-#endif
-      if ((DET_ABLATE & 4) && dw != 4095) nSurv = 0;
-      for (int base = 0; base < nSurv; base += 128) {  // two survivors per lane (packed f16 contrast)
+      const int nSurv = sEnd - s0;
+      for (int base = 0; base < nSurv; base += 128) {  // two survivors per lane, one after the other
         const int rem = nSurv - base;
         const uint64_t vA = low_lanes(rem), vB = low_lanes(rem - 64);
         // a list entry IS the tile byte offset y * TP + x of the pixel's 7x7 window corner (image and score tile share the
         // pitch): no unpacking of (y, x) and no multiply per survivor / corner; (x, y) is only recovered when a corner is emitted
         const int oA = list[s0 + min(base + lane, nSurv - 1)], oB = list[s0 + min(base + 64 + lane, nSurv - 1)];
-        // a last pass of <= 64 survivors gathers one pixel per lane only (17 instead of 34 byte reads: the LDS pipe is this
-        // kernel's busiest); the packed network then carries the same pixel in both halves
-        orbx_h2 M;
-        if (rem <= 64) M = fast_contrast2_lds(tile8 + oA, tile8 + oA, TP);
-        else if constexpr (TPC != 0 && ORBX_D16_PAIRS) M = fast_contrast2_lds_d16<TPC>(tile8 + oA, tile8 + oB);
-        else M = fast_contrast2_lds(tile8 + oA, tile8 + oB, TP);
-        const uint32_t Mbits = __builtin_bit_cast(uint32_t, M);  // a corner has M > t >= 0: the pattern is the integer
-        const uint64_t mA = __ballot(M.x > th2.x) & vA, mB = __ballot(M.y > th2.y) & vB;
+        // one survivor per lane and network, both polarities in its halves (fast_contrast_lds); a last pass of <= 64 survivors
+        // runs one network only
+        const _Float16 MA = fast_contrast_lds(tile8 + oA, TP);
+        const uint64_t mA = __ballot(MA > th) & vA;
         if (__builtin_amdgcn_inverse_ballot_w64(mA)) {
-          score8[oA + SPB + 4] = (uint8_t)((Mbits & 0xFFFFu) - 1);  // (y + 1) * pitch + x + 4: same pitch as the image tile
+          // a corner has M > t >= 0: the pattern is the integer.  (y + 1) * pitch + x + 4: same pitch as the image tile
+          score8[oA + SPB + 4] = (uint8_t)(__builtin_bit_cast(unsigned short, MA) - 1);
           const int k = prefix_count(mA);  // nList + k <= the position of the survivor it replaces
           if (k < cornerCap - nList) (list + nList)[k] = (uint16_t)oA;
         }
         nList += __popcll(mA);
-        if (__builtin_amdgcn_inverse_ballot_w64(mB)) {
-          score8[oB + SPB + 4] = (uint8_t)((Mbits >> 16) - 1);
-          const int k = prefix_count(mB);
-          if (k < cornerCap - nList) (list + nList)[k] = (uint16_t)oB;
+        if (rem > 64) {
+          const _Float16 MB = fast_contrast_lds(tile8 + oB, TP);
+          const uint64_t mB = __ballot(MB > th) & vB;
+          if (__builtin_amdgcn_inverse_ballot_w64(mB)) {
+            score8[oB + SPB + 4] = (uint8_t)(__builtin_bit_cast(unsigned short, MB) - 1);
+            const int k = prefix_count(mB);
+            if (k < cornerCap - nList) (list + nList)[k] = (uint16_t)oB;
+          }
+          nList += __popcll(mB);
         }
-        nList += __popcll(mB);
       }
       if (nList > cornerCap) {
         overflowed = true;
@@ -497,7 +360,7 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     const uint64_t notLastR = ~__ballot(j0 == qpr - 1);
     // ceil(dh / dq) = floor((dh - 0.5) / dq) + 1; as a quad count, so that one loop serves both schemes
     const int nRounds = kRowRounds ? ((int)(((float)dh - 0.5f) * __builtin_amdgcn_rcpf((float)dq)) + 1) * 64 : nq;
-    for (int qb = 0; qb < ((DET_ABLATE & 2) && dw != 4095 ? 0 : nRounds); qb += 64) {
+    for (int qb = 0; qb < nRounds; qb += 64) {
       uint64_t actM;
       int q0;
       if (kRowRounds) {
@@ -560,8 +423,7 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     if (pass == 0) DET_MK();
     flush_survivors();
     if (pass == 0) DET_MK();
-    const int nCorners = ((DET_ABLATE & 8) && dw != 4095) ? 0 : nList;
-    if ((DET_ABLATE & 8) && dw != 4095) kept = 1;
+    const int nCorners = nList;
     // 3x3 non-max suppression (strict '>') inside the cell + emission
     if (TAP && pass == 0) {  // test tap (orbx_debug_score_map): the cell's FAST scores at iniThFAST, 0 = no corner
       uint8_t* dm = dbgScore + (long long)img * g.pyrImg + L.off;
