@@ -747,20 +747,10 @@ void orbx_extractor_destroy(orbx_extractor* ex) {
   if (ex->streamPyr) (void)hipStreamDestroy(ex->streamPyr);
   if (ex->h_lap) (void)hipHostFree(ex->h_lap);
   ex->h_lap = nullptr;
-  ex->d_dbgScore.free(); ex->d_pyr.free(); ex->d_blur.free(); ex->d_stage.free(); ex->d_desc.free(); ex->d_cand.free(); ex->d_cellCand.free(); ex->d_cellCount.free(); ex->d_cellPrefix.free();
-  ex->d_sel.free(); ex->d_knode.free(); ex->d_candCount.free(); ex->d_selCount.free(); ex->d_slot.free();
-  ex->d_nOut.free(); ex->d_mono.free(); ex->d_lap.free(); ex->d_fl2r.free(); ex->d_fr2l.free(); ex->d_fcnt.free(); ex->d_fcand.free(); ex->d_bowWord.free(); ex->d_bowNode.free(); ex->d_bowStart.free();
-  ex->d_bowCounts.free(); ex->d_bowWeight.free(); ex->d_bowValues.free(); ex->d_bowWords.free(); ex->d_bowNodes.free(); ex->d_bowFeats.free(); ex->d_fdepth.free(); ex->d_fp3d.free(); ex->d_xtab.free(); ex->d_tailBands.free(); ex->d_yofs.free(); ex->d_yrow.free(); ex->d_packCtr.free();
-  ex->d_mapPos.free(); ex->d_mapNormal.free(); ex->d_mapMinD.free(); ex->d_mapMaxD.free(); ex->d_mapDesc.free(); ex->d_mapFlags.free();
-  ex->d_mapSkip.free(); ex->d_poses.free(); ex->d_views.free();
-  ex->d_lfPos.free(); ex->d_lfAngle.free(); ex->d_lfOct.free(); ex->d_lfN.free(); ex->d_lfDesc.free(); ex->d_lfFlags.free();
-  ex->d_posesQ.free(); ex->d_pviews.free(); ex->d_scaleF.free(); ex->d_posesK.free(); ex->d_fviewsL.free(); ex->d_fviewsR.free();
-  ex->d_latBands.free();
-  ex->d_yab.free(); ex->d_kps.free(); ex->d_uR.free(); ex->d_depth.free(); ex->d_sad.free(); ex->d_rowStart.free(); ex->d_srec.free(); ex->d_sdesc.free();
   for (hipEvent_t e : ex->evPool) (void)hipEventDestroy(e);
   if (ex->done) (void)hipEventDestroy(ex->done);
   if (ex->stream) (void)hipStreamDestroy(ex->stream);
-  delete ex;
+  delete ex;   // (the device buffers free themselves, with the device still current)
 }
 
 int orbx_get_tables(const orbx_extractor* ex, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
@@ -1749,7 +1739,6 @@ int orbx_debug_introsort_device(int device, uint64_t* v, int n) {
   if (e == hipSuccess) e = launch_debug_sort(d.p, n, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(v, d.p, (size_t)n * 8, hipMemcpyDeviceToHost);
-  d.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -1790,7 +1779,6 @@ int orbx_debug_sincos(int device, const float* angles, int n, int fused, float* 
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(sin_out, d.p + n, (size_t)n * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(cos_out, d.p + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost);
-  d.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }

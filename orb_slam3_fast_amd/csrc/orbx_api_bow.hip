@@ -15,7 +15,6 @@ struct orbx_vocabulary {
     v.L = L; v.nNodes = nNodes; v.scoring = scoring; v.weighting = weighting;
     return v;
   }
-  ~orbx_vocabulary() { childStart.free(); children.free(); wordId.free(); desc.free(); weight.free(); }
 };
 
 int orbx_vocabulary_create(int device, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
@@ -156,7 +155,6 @@ int orbx_bow_transform(const orbx_vocabulary* voc, const uint8_t* desc, int n, i
       if (cnt[2] && feature_idx) std::memcpy(feature_idx, h + rFeats, (size_t)cnt[2] * 4);
     }
   }
-  pk.release();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   *n_words = cnt[0];
   *n_nodes = cnt[1];

@@ -2,6 +2,166 @@
 // the SearchByProjection family, SearchByBoW.  One-shot calls: host arrays in, host results out, inputs through one packed upload.
 #include "orbx_host.h"
 
+namespace {
+
+// The matchers' knobs, read once per process.  ORBX_PROJ_CAND_CAP: the candidate-list capacity of a first attempt (> 0; the
+// tests force the exact-size retry with it).  ORBX_PROJ_BLIND: the fixed-point rounds the batched forms enqueue without
+// reading a flag, [1, 48], default 16.  ORBX_PROJ_SERIAL=1: the serial walk instead of the parallel rounds (a cross-check).
+struct Knobs {
+  int candCap, blind;
+  bool serial;
+};
+const Knobs& knobs() {
+  static const Knobs k = [] {
+    const char* cap = getenv("ORBX_PROJ_CAND_CAP");
+    const char* blind = getenv("ORBX_PROJ_BLIND");
+    const char* serial = getenv("ORBX_PROJ_SERIAL");
+    return Knobs{cap ? atoi(cap) : 0, blind ? std::min(48, std::max(1, atoi(blind))) : 16, serial && atoi(serial) != 0};
+  }();
+  return k;
+}
+// first guess of a candidate-list capacity: perItem candidates for each of `items` (at least one) queries
+int first_cand_cap(int items, int perItem) { return knobs().candCap > 0 ? knobs().candCap : std::max(items, 1) * perItem; }
+
+// Runs attempt(cap, &needed) and, when the candidate lists did not fit, once more with the exact size (cap becomes it).
+template <class Attempt>
+int with_exact_capacity(int& cap, Attempt attempt) {
+  int needed = 0;
+  int rc = attempt(cap, &needed);
+  if (rc >= 0 && needed > cap) {
+    cap = needed;
+    rc = attempt(cap, &needed);
+  }
+  return rc;
+}
+
+constexpr int kFlagInts = 40 + 48;   // a resolve's flag words: [1] list overflow, [40 + r] round r changed something
+
+// The stepped resolve of the one-shot searches: rounds(r) enqueues rounds r .. r + 3, then the flags are read (synchronises);
+// at most 48 rounds.  True when a group's last round changed nothing (*lastRound: that round); false on a claimer / writer
+// list overflow, when the rounds ran out, or on an error (e) -- the caller then takes the serial walk.
+template <class Rounds>
+bool stepped_rounds(const int* flags, hipError_t& e, int* lastRound, Rounds rounds) {
+  for (int r = 0; r < 48 && e == hipSuccess; r += 4) {
+    e = rounds(r);
+    int st[kFlagInts];
+    st[1] = 0;
+    st[40 + r + 3] = 1;
+    if (e == hipSuccess) e = hipMemcpy(st, flags, sizeof(st), hipMemcpyDeviceToHost);
+    if (st[1]) return false;
+    *lastRound = r + 3;
+    if (st[40 + r + 3] == 0) return true;
+  }
+  return false;
+}
+
+// The frame grid of a search (mGrid, src/Frame.cc): bounds, the keypoints it holds and its device scratch.  candCap: no
+// candidate lists of the grid's own (the init searches set theirs).
+InitArgs grid_block(float min_x, float min_y, float max_x, float max_y, const orbx_keypoint* k2, int n2, int* cellStart,
+                    int* cellItems, int* matchedDist, int* matches21, int* matches12, int* result, int* candOff) {
+  InitArgs g{};
+  g.k2 = k2; g.n2 = n2;
+  g.minX = min_x; g.minY = min_y;
+  g.invW = 64.f / (max_x - min_x);  // mfGridElementWidthInv, src/Frame.cc:243
+  g.invH = 48.f / (max_y - min_y);
+  g.cellStart = cellStart; g.cellItems = cellItems; g.matchedDist = matchedDist; g.matches21 = matches21;
+  g.matches12 = matches12; g.result = result; g.candOff = candOff; g.candCap = 1 << 30;
+  return g;
+}
+
+// One key frame (or frame) of a BoW search: its FeatureVector in CSR form -- node ids, offsets into the feature list, feature
+// indices -- and its keypoints, descriptors and per-keypoint flags (valid / has a map point).
+struct BowSide {
+  const uint32_t* ids; const int32_t* start; const uint32_t* feat; int nNodes;
+  const orbx_keypoint* kps; const uint8_t* desc; const uint8_t* flags; int n;
+  int list() const { return nNodes ? start[nNodes] : 0; }
+};
+// A FeatureVector is a std::map: ascending node ids, and the CSR offsets must be monotone (the kernels trust them).  The
+// callers check both sides' nodes before either side's feature indices.
+int check_nodes(const BowSide& s, const char* what) {
+  for (int j = 0; j < s.nNodes; j++)
+    if (s.start[j] < 0 || s.start[j] > s.start[j + 1] || (j && s.ids[j] <= s.ids[j - 1]))
+      return fail(ORBX_E_BADARG, std::string(what) + ": node ids must ascend and offsets must be monotone");
+  return ORBX_OK;
+}
+int check_features(const BowSide& s, const char* what) {
+  for (int i = 0; i < s.list(); i++)
+    if (s.feat[i] >= (uint32_t)s.n) return fail(ORBX_E_BADARG, std::string(what) + " out of range");
+  return ORBX_OK;
+}
+
+// The two-key-frame searches (triangulation, SearchByBoW(KeyFrame, KeyFrame)): a side's arrays in the call's upload, and the
+// TriArgs pointers to both sides once the pack is committed.
+struct SideAreas { size_t ids, start, feat, desc, flags, kps; };
+SideAreas add_side(Pack& pk, const BowSide& s) {
+  SideAreas o;
+  o.ids = pk.add(s.ids, (size_t)s.nNodes * 4);
+  o.start = pk.add(s.start, ((size_t)s.nNodes + 1) * 4);
+  o.feat = pk.add(s.feat, (size_t)s.list() * 4);
+  o.desc = pk.add(s.desc, (size_t)s.n * 32);
+  o.flags = pk.add(s.flags, s.n);
+  o.kps = pk.add(s.kps, (size_t)s.n * sizeof(orbx_keypoint));
+  return o;
+}
+TriArgs tri_args(const Pack& pk, const BowSide& s1, const SideAreas& o1, const BowSide& s2, const SideAreas& o2) {
+  TriArgs a{};
+  a.nodes1 = pk.ptr<uint32_t>(o1.ids); a.start1 = pk.ptr<int>(o1.start); a.feat1 = pk.ptr<uint32_t>(o1.feat);
+  a.nNodes1 = s1.nNodes; a.nList1 = s1.list();
+  a.nodes2 = pk.ptr<uint32_t>(o2.ids); a.start2 = pk.ptr<int>(o2.start); a.feat2 = pk.ptr<uint32_t>(o2.feat); a.nNodes2 = s2.nNodes;
+  a.k1 = pk.ptr<orbx_keypoint>(o1.kps); a.k2 = pk.ptr<orbx_keypoint>(o2.kps);
+  a.d1 = pk.ptr<uint32_t>(o1.desc); a.d2 = pk.ptr<uint32_t>(o2.desc); a.mp1 = pk.ptr<uint8_t>(o1.flags); a.mp2 = pk.ptr<uint8_t>(o2.flags);
+  a.n1 = s1.n; a.n2 = s2.n;
+  return a;
+}
+
+// The tail of the single-launch searches: the result word, then n matches, come back in one copy.
+hipError_t fetch_result(Pack& pk, size_t off, int n, int32_t* matches, int* result) {
+  hipError_t e;
+  const uint8_t* h = pk.fetch(off, ((size_t)n + 1) * 4, &e);
+  if (e == hipSuccess) {
+    std::memcpy(result, h, 4);
+    std::memcpy(matches, h + 4, (size_t)n * 4);
+  }
+  return e;
+}
+
+// A batched search's redo path: host copy of the n keypoints and descriptors of image img of the handle's last batch, to
+// hand to the one-shot call.
+int download_frame(orbx_extractor* ex, int img, int n, orbx_keypoint* k, uint8_t* d) {
+  const size_t cap = ex->gmax.outCap;
+  HIPC(hipMemcpy(k, ex->d_kps.p + (size_t)img * cap, (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(d, ex->d_desc.p + (size_t)img * cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
+  return ORBX_OK;
+}
+
+// The stereo-fisheye views as the matcher takes them, for frames [0, F) of stride st: the left camera's, and the right
+// camera's as a second list of views -- (mTrackProjXR, mTrackProjYR), mTrackViewCosR, mnTrackScaleLevelR (:141-144).
+// `if (!mbTrackInView && !mbTrackInViewR) continue` (:54) is implied: both lists stay empty.
+int kb8_view_lists(const orbx_map_point_view* mps, const orbx_map_point_right* mpr, const int32_t* n, int F, int st, int nlevels,
+                   std::vector<orbx_map_point_view>& left, std::vector<orbx_map_point_view>& right) {
+  left.assign((size_t)F * st, orbx_map_point_view{});
+  right.assign((size_t)F * st, orbx_map_point_view{});
+  for (int f = 0; f < F; f++)
+    for (int i = 0; i < n[f]; i++) {
+      const size_t o = (size_t)f * st + i;
+      const orbx_map_point_view& m = mps[o];
+      const orbx_map_point_right& r = mpr[o];
+      if ((m.in_view && (m.predicted_level < 0 || m.predicted_level >= nlevels)) ||
+          (r.in_view_r && (r.predicted_level_r < -1 || r.predicted_level_r >= nlevels)))
+        return fail(ORBX_E_BADARG, "map point with a predicted level outside [0, nlevels)");
+      left[o] = right[o] = m;
+      if (!m.in_view) left[o].predicted_level = 0;
+      right[o].proj_x = m.proj_xr;
+      right[o].proj_y = r.proj_yr;
+      right[o].view_cos = r.view_cos_r;
+      right[o].predicted_level = r.predicted_level_r < 0 ? 0 : r.predicted_level_r;
+      right[o].in_view = (r.in_view_r && r.predicted_level_r != -1) ? 1 : 0;
+    }
+  return ORBX_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int orbx_bf_knn2(int device, const uint8_t* descQ, int nQ, const uint8_t* descT, int nT, int32_t* idx2,
@@ -28,7 +188,6 @@ int orbx_bf_knn2(int device, const uint8_t* descQ, int nQ, const uint8_t* descT,
       std::memcpy(ratio_ok, h + Q * 16, Q);
     }
   }
-  pk.release();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -51,13 +210,10 @@ int orbx_fisheye_stereo_match(int device, const orbx_keypoint* kps_left, const u
   for (int i = 0; i < n_right; i++) right_to_left[i] = -1;
   if (n_desc_matches) *n_desc_matches = 0;
   const int nQ = n_left - mono_left, nT = n_right - mono_right;
-  // knnMatch(k = 2) yields pairs only when the train set has two rows (`(*it).size() >= 2`, src/Frame.cc:1302)
-  if (nQ == 0 || nT < 2) {
-    int rc0 = set_device(device);  // still a device routine: no GPU is an error, never a silent host path
-    return rc0 != ORBX_OK ? rc0 : 0;
-  }
+  // knnMatch(k = 2) yields pairs only when the train set has two rows (`(*it).size() >= 2`, src/Frame.cc:1302); with nothing
+  // to match this is still a device routine: no GPU is an error, never a silent host path
   int rc = set_device(device);
-  if (rc != ORBX_OK) return rc;
+  if (rc != ORBX_OK || nQ == 0 || nT < 2) return rc;
   // one packed upload (the -1 / 0 fills of the outputs travel with it); the outputs are contiguous: one copy back
   std::vector<float> zeros((size_t)n_left * 3 + 2, 0.0f);  // points3d fill + the two counters
   Pack pk;
@@ -94,7 +250,6 @@ int orbx_fisheye_stereo_match(int device, const orbx_keypoint* kps_left, const u
       std::memcpy(counts, h + (oCnt - oL2r), sizeof(counts));
     }
   }
-  pk.release();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   if (n_desc_matches) *n_desc_matches = counts[1];
   return counts[0];
@@ -109,20 +264,15 @@ int orbx_search_by_bow(int device, const uint32_t* kf_node_ids, const int32_t* k
       (n_kf_nodes && (!kf_node_ids || !kf_node_start || !kf_feature_idx || !kf_kps || !kf_desc || !kf_valid)) ||
       (n_f_nodes && (!f_node_ids || !f_node_start || !f_feature_idx || !f_kps || !f_desc)))
     return fail(ORBX_E_BADARG, "bad argument");
-  const int nkl = n_kf_nodes ? kf_node_start[n_kf_nodes] : 0, nfl = n_f_nodes ? f_node_start[n_f_nodes] : 0;
+  const BowSide kf{kf_node_ids, kf_node_start, kf_feature_idx, n_kf_nodes, kf_kps, kf_desc, kf_valid, n_kf};
+  const BowSide fr{f_node_ids, f_node_start, f_feature_idx, n_f_nodes, f_kps, f_desc, nullptr, n_f};
+  const int nkl = kf.list(), nfl = fr.list();
   if (nkl < 0 || nkl > n_kf || nfl < 0 || nfl > n_f) return fail(ORBX_E_BADARG, "feature vector larger than the frame");
-  // a FeatureVector is a std::map: ascending node ids, and the CSR offsets must be monotone (the kernels trust them)
-  for (int j = 0; j < n_kf_nodes; j++)
-    if (kf_node_start[j] < 0 || kf_node_start[j] > kf_node_start[j + 1] || (j && kf_node_ids[j] <= kf_node_ids[j - 1]))
-      return fail(ORBX_E_BADARG, "keyframe feature vector: node ids must ascend and offsets must be monotone");
-  for (int j = 0; j < n_f_nodes; j++)
-    if (f_node_start[j] < 0 || f_node_start[j] > f_node_start[j + 1] || (j && f_node_ids[j] <= f_node_ids[j - 1]))
-      return fail(ORBX_E_BADARG, "frame feature vector: node ids must ascend and offsets must be monotone");
-  for (int i = 0; i < nkl; i++)
-    if (kf_feature_idx[i] >= (uint32_t)n_kf) return fail(ORBX_E_BADARG, "keyframe feature index out of range");
-  for (int i = 0; i < nfl; i++)
-    if (f_feature_idx[i] >= (uint32_t)n_f) return fail(ORBX_E_BADARG, "frame feature index out of range");
-  int rc = set_device(device);
+  int rc;
+  if ((rc = check_nodes(kf, "keyframe feature vector")) || (rc = check_nodes(fr, "frame feature vector")) ||
+      (rc = check_features(kf, "keyframe feature index")) || (rc = check_features(fr, "frame feature index")))
+    return rc;
+  rc = set_device(device);
   if (rc != ORBX_OK) return rc;
   for (int i = 0; i < n_f; i++) matches[i] = -1;
   if (n_kf_nodes == 0 || n_f_nodes == 0 || n_f == 0) return 0;
@@ -145,14 +295,7 @@ int orbx_search_by_bow(int device, const uint32_t* kf_node_ids, const int32_t* k
   a.result = pk.ptr<int>(oOut); a.match = pk.ptr<int>(oOut) + 1; a.bin = pk.ptr<int>(oBin); a.flags = pk.ptr<int>(oFlags);
   if (e == hipSuccess) e = launch_bow_match(a, nullptr);
   int n = 0;
-  if (e == hipSuccess) {
-    const uint8_t* h = pk.fetch(oOut, ((size_t)n_f + 1) * 4, &e);
-    if (e == hipSuccess) {
-      std::memcpy(&n, h, 4);
-      std::memcpy(matches, h + 4, (size_t)n_f * 4);
-    }
-  }
-  pk.release();
+  if (e == hipSuccess) e = fetch_result(pk, oOut, n_f, matches, &n);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   if (n < 0) return fail(ORBX_E_UNSUPPORTED, "a vocabulary node holds more than 4096 frame features");
   return n;
@@ -184,29 +327,21 @@ int orbx_search_by_bow_batch(orbx_extractor* ex, int first_image, int n_frames, 
   }
   if (maxNodes && (!kf_node_ids || !kf_node_start || !kf_feature_idx || !kf_kps || !kf_desc || !kf_valid))
     return fail(ORBX_E_BADARG, "null key-frame array");
+  int rc;
   for (int f = 0; f < F; f++) {   // the same trust boundary as the one-shot call
-    const uint32_t* ids = kf_node_ids + (size_t)f * ns;
-    const int32_t* stt = kf_node_start + (size_t)f * (ns + 1);
-    const int nn = n_kf_nodes[f], nkl = nn ? stt[nn] : 0;
+    const BowSide kf{kf_node_ids + (size_t)f * ns, kf_node_start + (size_t)f * (ns + 1), kf_feature_idx + (size_t)f * ks,
+                     n_kf_nodes[f], nullptr, nullptr, nullptr, n_kf[f]};
+    const int nkl = kf.list();
     if (nkl < 0 || nkl > n_kf[f]) return fail(ORBX_E_BADARG, "feature vector larger than the key frame");
-    for (int j = 0; j < nn; j++)
-      if (stt[j] < 0 || stt[j] > stt[j + 1] || (j && ids[j] <= ids[j - 1]))
-        return fail(ORBX_E_BADARG, "keyframe feature vector: node ids must ascend and offsets must be monotone");
-    for (int i = 0; i < nkl; i++)
-      if (kf_feature_idx[(size_t)f * ks + i] >= (uint32_t)n_kf[f]) return fail(ORBX_E_BADARG, "keyframe feature index out of range");
+    if ((rc = check_nodes(kf, "keyframe feature vector")) || (rc = check_features(kf, "keyframe feature index"))) return rc;
   }
-  int rc = set_device(ex->device);
+  rc = set_device(ex->device);
   if (rc != ORBX_OK) return rc;
   const int cap = ex->gmax.outCap;
-  std::vector<int> nF(F), cnt(3 * (size_t)F);
-  HIPC(hipStreamSynchronize(ex->stream));
-  HIPC(hipMemcpy(nF.data(), ex->d_nOut.p + first_image, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(cnt.data(), ex->d_bowCounts.p + 3 * (size_t)first_image, 3 * (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> nF, cnt(3 * (size_t)F);
   int maxNF = 0;
-  for (int f = 0; f < F; f++) {
-    nF[f] = std::min(std::max(nF[f], 0), cap);
-    maxNF = std::max(maxNF, nF[f]);
-  }
+  if ((rc = batch_counts(ex, first_image, F, nF, &maxNF)) != ORBX_OK) return rc;
+  HIPC(hipMemcpy(cnt.data(), ex->d_bowCounts.p + 3 * (size_t)first_image, 3 * (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
   Pack pk;
   std::vector<BowMatchArgs> frames(F);
   auto rows = [&](const int32_t* n, int stride) { return (size_t)(F - 1) * stride + (size_t)n[F - 1]; };  // (last pair's padding unread)
@@ -220,7 +355,7 @@ int orbx_search_by_bow_batch(orbx_extractor* ex, int first_image, int n_frames, 
   const size_t oOut = pk.add(nullptr, (size_t)F * ((size_t)cap + 1) * 4);   // per pair: result, then cap matches
   const size_t oBin = pk.add(nullptr, (size_t)F * cap * 4), oFlags = pk.add(nullptr, (size_t)F * 36 * 4);
   hipError_t e = pk.reserve();
-  if (e != hipSuccess) { pk.release(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f = 0; f < F; f++) {
     BowMatchArgs a{};
     const int img = first_image + f;
@@ -253,7 +388,6 @@ int orbx_search_by_bow_batch(orbx_extractor* ex, int first_image, int n_frames, 
         total += std::max(r[0], 0);
       }
   }
-  pk.release();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   if (tooLarge) return fail(ORBX_E_UNSUPPORTED, "a vocabulary node holds more than 4096 frame features");
   return total;
@@ -277,21 +411,12 @@ int search_for_initialization_try(const orbx_keypoint* kps1, const uint8_t* desc
   const size_t oM12 = pk.add(nullptr, (size_t)n1 * sizeof(int));
   const size_t outBytes = oM12 + (size_t)n1 * sizeof(int) - oPrev;
   chk(pk.commit());
-  struct { orbx_keypoint* p; } k1{pk.ptr<orbx_keypoint>(oK1)}, k2{pk.ptr<orbx_keypoint>(oK2)};
-  struct { uint8_t* p; } d1{pk.ptr<uint8_t>(oD1)}, d2{pk.ptr<uint8_t>(oD2)};
-  struct { float* p; } prev{pk.ptr<float>(oPrev)};
-  struct { int* p; } m12{pk.ptr<int>(oM12)}, result{pk.ptr<int>(oRes)};
   chk(cellStart.alloc(64 * 48 + 1)); chk(cellItems.alloc(std::max(n2, 1))); chk(candOff.alloc(n1 + 1));
   chk(mdist.alloc(std::max(n2, 1))); chk(m21.alloc(std::max(n2, 1)));
-  InitArgs a{};
-  a.k1 = k1.p; a.k2 = k2.p; a.d1 = d1.p; a.d2 = d2.p; a.n1 = n1; a.n2 = n2;
-  a.minX = min_x; a.minY = min_y;
-  a.invW = 64.f / (max_x - min_x);  // mfGridElementWidthInv, src/Frame.cc:243
-  a.invH = 48.f / (max_y - min_y);
-  a.prev = prev.p; a.matches12 = m12.p; a.window = window_size; a.nnratio = nnratio;
-  a.checkOri = check_orientation;
-  a.cellStart = cellStart.p; a.cellItems = cellItems.p; a.candOff = candOff.p;
-  a.matchedDist = mdist.p; a.matches21 = m21.p; a.result = result.p;
+  InitArgs a = grid_block(min_x, min_y, max_x, max_y, pk.ptr<orbx_keypoint>(oK2), n2, cellStart.p, cellItems.p, mdist.p, m21.p,
+                          pk.ptr<int>(oM12), pk.ptr<int>(oRes), candOff.p);
+  a.k1 = pk.ptr<orbx_keypoint>(oK1); a.d1 = pk.ptr<uint8_t>(oD1); a.d2 = pk.ptr<uint8_t>(oD2); a.n1 = n1;
+  a.prev = pk.ptr<float>(oPrev); a.window = window_size; a.nnratio = nnratio; a.checkOri = check_orientation;
   chk(candIdx.alloc((size_t)cand_cap));
   chk(candDist.alloc((size_t)cand_cap));
   a.candIdx = candIdx.p;
@@ -302,25 +427,15 @@ int search_for_initialization_try(const orbx_keypoint* kps1, const uint8_t* desc
   // resolve: parallel fixed-point rounds (k_init_round), serial walk as fallback / ORBX_PROJ_SERIAL=1 cross-check
   ScratchBuf<int2> cl0, cl1, cr0, cr1, cr2;
   ScratchBuf<int> nc0, nc1, nc2, fl;
-  static const bool forceSerial = getenv("ORBX_PROJ_SERIAL") && atoi(getenv("ORBX_PROJ_SERIAL")) != 0;
   bool done = false;
   int lastRound = 0;
   if (e == hipSuccess) chk(launch_search_init_cands_fill(a, nullptr));
-  if (!forceSerial && n2 > 0) {
+  if (!knobs().serial && n2 > 0) {
     chk(cl0.alloc(n1)); chk(cl1.alloc(n1)); chk(cr0.alloc((size_t)n2 * kFeWriters)); chk(cr1.alloc((size_t)n2 * kFeWriters));
-    chk(cr2.alloc((size_t)n2 * kFeWriters)); chk(nc0.alloc(n2)); chk(nc1.alloc(n2)); chk(nc2.alloc(n2)); chk(fl.alloc(40 + 48));
+    chk(cr2.alloc((size_t)n2 * kFeWriters)); chk(nc0.alloc(n2)); chk(nc1.alloc(n2)); chk(nc2.alloc(n2)); chk(fl.alloc(kFlagInts));
     a.claim[0] = cl0.p; a.claim[1] = cl1.p; a.claimers[0] = cr0.p; a.claimers[1] = cr1.p; a.claimers[2] = cr2.p;
     a.nclaimers[0] = nc0.p; a.nclaimers[1] = nc1.p; a.nclaimers[2] = nc2.p; a.flags = fl.p;
-    for (int r = 0; r < 48 && e == hipSuccess && !done; r += 4) {
-      chk(launch_search_init_rounds(a, r, 4, nullptr));
-      int st[40 + 48];
-      st[1] = 0;
-      st[40 + r + 3] = 1;
-      if (e == hipSuccess) chk(hipMemcpy(st, fl.p, sizeof(st), hipMemcpyDeviceToHost));  // synchronises
-      if (st[1]) break;  // an i2 collected more than kFeWriters claimers in one round
-      done = st[40 + r + 3] == 0;  // the last round of the group changed nothing
-      lastRound = r + 3;
-    }
+    done = stepped_rounds(fl.p, e, &lastRound, [&](int r) { return launch_search_init_rounds(a, r, 4, nullptr); });
   }
   if (e == hipSuccess) chk(done ? launch_search_init_finish(a, lastRound, nullptr) : launch_search_init_resolve_serial(a, nullptr));
   if (e == hipSuccess) {
@@ -335,9 +450,6 @@ int search_for_initialization_try(const orbx_keypoint* kps1, const uint8_t* desc
       }
     }
   }
-  cl0.free(); cl1.free(); cr0.free(); cr1.free(); cr2.free(); nc0.free(); nc1.free(); nc2.free(); fl.free();
-  pk.release(); cellStart.free(); cellItems.free();
-  candOff.free(); candIdx.free(); candDist.free(); mdist.free(); m21.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return res[0];
 }
@@ -354,14 +466,11 @@ int orbx_search_for_initialization(int device, const orbx_keypoint* kps1, const 
   if (rc != ORBX_OK) return rc;
   // first guess: 128 candidates per keypoint (a 100 px window over 1500 level-0 keypoints holds ~60); a denser frame repeats
   // the call once with the exact size (ORBX_PROJ_CAND_CAP forces that path in the tests)
-  static const int capEnv = getenv("ORBX_PROJ_CAND_CAP") ? atoi(getenv("ORBX_PROJ_CAND_CAP")) : 0;
-  int cap = capEnv > 0 ? capEnv : n1 * 128, needed = 0;
-  rc = search_for_initialization_try(kps1, desc1, n1, kps2, desc2, n2, min_x, min_y, max_x, max_y, prev_matched, matches12,
-                                     window_size, nnratio, check_orientation, cap, &needed);
-  if (rc >= 0 && needed > cap)
-    rc = search_for_initialization_try(kps1, desc1, n1, kps2, desc2, n2, min_x, min_y, max_x, max_y, prev_matched, matches12,
-                                       window_size, nnratio, check_orientation, needed, &needed);
-  return rc;
+  int cap = first_cand_cap(n1, 128);
+  return with_exact_capacity(cap, [&](int c, int* needed) {
+    return search_for_initialization_try(kps1, desc1, n1, kps2, desc2, n2, min_x, min_y, max_x, max_y, prev_matched, matches12,
+                                         window_size, nnratio, check_orientation, c, needed);
+  });
 }
 
 // SearchForInitialization on the frames of an extraction batch (round 5; the batched form of the call above, like
@@ -387,18 +496,11 @@ int orbx_search_for_initialization_batch(orbx_extractor* ex, int first_image, in
   int rc = set_device(ex->device);
   if (rc != ORBX_OK) return rc;
   const int cap = ex->gmax.outCap, F = n_frames, st = std::max(stride, 1);
-  std::vector<int> n2(F);
-  HIPC(hipStreamSynchronize(ex->stream));
-  HIPC(hipMemcpy(n2.data(), ex->d_nOut.p + first_image, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> n2;
   int maxN2 = 0;
-  for (int f = 0; f < F; f++) {
-    n2[f] = std::min(std::max(n2[f], 0), cap);
-    maxN2 = std::max(maxN2, n2[f]);
-  }
-  static const int capEnv = getenv("ORBX_PROJ_CAND_CAP") ? atoi(getenv("ORBX_PROJ_CAND_CAP")) : 0;
-  static const int kBlind = getenv("ORBX_PROJ_BLIND") ? std::min(48, std::max(1, atoi(getenv("ORBX_PROJ_BLIND")))) : 16;
-  const int nm = std::max(maxN1, 1), candCap = capEnv > 0 ? capEnv : nm * 128;
-  constexpr int kFlags = 40 + 48;
+  if ((rc = batch_counts(ex, first_image, F, n2, &maxN2)) != ORBX_OK) return rc;
+  const int kBlind = knobs().blind, kFlags = kFlagInts;
+  const int nm = std::max(maxN1, 1), candCap = first_cand_cap(nm, 128);
   Pack pk;
   std::vector<InitArgs> frames(F);
   const size_t rows = (size_t)(F - 1) * st + (size_t)n1[F - 1];   // (the last pair's padding is not read: see proj_batch_impl)
@@ -416,30 +518,21 @@ int orbx_search_for_initialization_batch(orbx_extractor* ex, int first_image, in
   const size_t oCr0 = per(2 * (size_t)cap * kFeWriters), oCr1 = per(2 * (size_t)cap * kFeWriters), oCr2 = per(2 * (size_t)cap * kFeWriters);
   const size_t oNc0 = per(cap), oNc1 = per(cap), oNc2 = per(cap);
   hipError_t e = pk.reserve();
-  if (e != hipSuccess) { pk.release(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f = 0; f < F; f++) {
-    InitArgs a{};
     const int img = first_image + f;
+    InitArgs a = grid_block(min_x, min_y, max_x, max_y, ex->d_kps.p + (size_t)img * cap, n2[f], pk.ptr<int>(oCs) + (size_t)f * cs,
+                            pk.ptr<int>(oCi) + (size_t)f * cap, pk.ptr<int>(oMd) + (size_t)f * cap, pk.ptr<int>(oM21) + (size_t)f * cap,
+                            pk.ptr<int>(oM12) + (size_t)f * st, pk.ptr<int>(oRes) + (size_t)f * 2, pk.ptr<int>(oCo) + (size_t)f * (nm + 4));
     a.k1 = pk.ptr<orbx_keypoint>(oK1) + (size_t)f * st;
     a.d1 = pk.ptr<uint8_t>(oD1) + (size_t)f * st * 32;
-    a.k2 = ex->d_kps.p + (size_t)img * cap;
     a.d2 = ex->d_desc.p + (size_t)img * cap * 32;
-    a.n1 = n1[f]; a.n2 = n2[f];
-    a.minX = min_x; a.minY = min_y;
-    a.invW = 64.f / (max_x - min_x);
-    a.invH = 48.f / (max_y - min_y);
+    a.n1 = n1[f];
     a.prev = pk.ptr<float>(oPrev) + (size_t)f * st * 2;
-    a.matches12 = pk.ptr<int>(oM12) + (size_t)f * st;
     a.window = window_size; a.nnratio = nnratio; a.checkOri = check_orientation;
-    a.cellStart = pk.ptr<int>(oCs) + (size_t)f * cs;
-    a.cellItems = pk.ptr<int>(oCi) + (size_t)f * cap;
-    a.candOff = pk.ptr<int>(oCo) + (size_t)f * (nm + 4);
     a.candIdx = pk.ptr<int>(oCx) + (size_t)f * candCap;
     a.candDist = pk.ptr<int>(oCd) + (size_t)f * candCap;
     a.candCap = candCap;
-    a.matchedDist = pk.ptr<int>(oMd) + (size_t)f * cap;
-    a.matches21 = pk.ptr<int>(oM21) + (size_t)f * cap;
-    a.result = pk.ptr<int>(oRes) + (size_t)f * 2;
     a.claim[0] = pk.ptr<int2>(oCl0) + (size_t)f * nm; a.claim[1] = pk.ptr<int2>(oCl1) + (size_t)f * nm;
     a.claimers[0] = pk.ptr<int2>(oCr0) + (size_t)f * cap * kFeWriters; a.claimers[1] = pk.ptr<int2>(oCr1) + (size_t)f * cap * kFeWriters;
     a.claimers[2] = pk.ptr<int2>(oCr2) + (size_t)f * cap * kFeWriters;
@@ -470,14 +563,13 @@ int orbx_search_for_initialization_batch(orbx_extractor* ex, int first_image, in
       }
     }
   }
-  pk.release();
+  pk.release();   // (its device block goes back to the pool before the redo calls)
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f : redo) {   // the one-shot call on a host copy of F2 (prev_matched / matches12 of this pair are still the caller's input)
-    const int img = first_image + f, n = n2[f];
+    const int n = n2[f];
     std::vector<orbx_keypoint> k(std::max(n, 1));
     std::vector<uint8_t> d((size_t)std::max(n, 1) * 32);
-    HIPC(hipMemcpy(k.data(), ex->d_kps.p + (size_t)img * cap, (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(d.data(), ex->d_desc.p + (size_t)img * cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
+    if ((rc = download_frame(ex, first_image + f, n, k.data(), d.data())) != ORBX_OK) return rc;
     rc = orbx_search_for_initialization(ex->device, kps1 + (size_t)f * st, desc1 + (size_t)f * st * 32, n1[f], k.data(), d.data(), n,
                                         min_x, min_y, max_x, max_y, prev_matched + (size_t)f * st * 2, matches12 + (size_t)f * st,
                                         window_size, nnratio, check_orientation);
@@ -506,13 +598,7 @@ int orbx_features_in_area(int device, const orbx_keypoint* kps, int n, float min
   chk(qOff.alloc(nq + 1)); chk(mdist.alloc(nn)); chk(m21.alloc(nn)); chk(m12.alloc(1)); chk(result.alloc(2));
   if (e == hipSuccess && n) chk(hipMemcpy(k.p, kps, (size_t)n * sizeof(orbx_keypoint), hipMemcpyHostToDevice));
   if (e == hipSuccess && n_queries) chk(hipMemcpy(q.p, queries, (size_t)n_queries * 5 * sizeof(float), hipMemcpyHostToDevice));
-  InitArgs a{};
-  a.k2 = k.p; a.n2 = n; a.n1 = 0;
-  a.minX = min_x; a.minY = min_y;
-  a.invW = 64.f / (max_x - min_x);
-  a.invH = 48.f / (max_y - min_y);
-  a.cellStart = cellStart.p; a.cellItems = cellItems.p; a.matchedDist = mdist.p; a.matches21 = m21.p;
-  a.matches12 = m12.p; a.result = result.p; a.candOff = qOff.p; a.candCap = 1 << 30;
+  InitArgs a = grid_block(min_x, min_y, max_x, max_y, k.p, n, cellStart.p, cellItems.p, mdist.p, m21.p, m12.p, result.p, qOff.p);
   int total = 0;
   if (e == hipSuccess) chk(launch_grid_build(a, nullptr));
   if (e == hipSuccess && n_queries) {
@@ -533,8 +619,6 @@ int orbx_features_in_area(int device, const orbx_keypoint* kps, int n, float min
   if (e == hipSuccess && grid_cell_start)
     chk(hipMemcpy(grid_cell_start, cellStart.p, (64 * 48 + 1) * sizeof(int), hipMemcpyDeviceToHost));
   if (e == hipSuccess && grid_items && n) chk(hipMemcpy(grid_items, cellItems.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-  k.free(); q.free(); cellStart.free(); cellItems.free(); qOff.free(); out.free(); mdist.free(); m21.free(); m12.free();
-  result.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   if (indices && total > indices_cap) return fail(ORBX_E_CAPACITY, "indices buffer too small");
   return total;
@@ -565,40 +649,32 @@ int search_by_projection_try(const orbx_keypoint* kps_un, const uint8_t* desc, c
   const size_t oMp = pk.add(mode == 0 && n_points ? map_points : nullptr, (size_t)nm * sizeof(orbx_map_point_view));
   const size_t oPp = pk.add(mode == 1 && n_points ? points : nullptr, (size_t)nm * sizeof(orbx_projected_point));
   const size_t oOcc = pk.add(occupied, n), oRes = pk.add(nullptr, 2 * sizeof(int));
-  const size_t oFlags = pk.add(nullptr, (40 + 48) * sizeof(int)), oMt = pk.add(nullptr, (size_t)n * sizeof(int));
+  const size_t oFlags = pk.add(nullptr, kFlagInts * sizeof(int)), oMt = pk.add(nullptr, (size_t)n * sizeof(int));
   const size_t outBytes = oMt + (size_t)n * sizeof(int) - oOcc;
   chk(pk.commit());
-  struct { orbx_keypoint* p; } k{pk.ptr<orbx_keypoint>(oK)};
-  struct { uint8_t* p; } d{pk.ptr<uint8_t>(oD)}, occ{pk.ptr<uint8_t>(oOcc)};
-  struct { float* p; } ur{pk.ptr<float>(oUr)}, sf{pk.ptr<float>(oSf)};
-  struct { orbx_map_point_view* p; } mp{pk.ptr<orbx_map_point_view>(oMp)};
-  struct { orbx_projected_point* p; } pp{pk.ptr<orbx_projected_point>(oPp)};
-  struct { int* p; } mt{pk.ptr<int>(oMt)}, result{pk.ptr<int>(oRes)}, flags{pk.ptr<int>(oFlags)};
   chk(taker0.alloc(n)); chk(taker1.alloc(n)); chk(taker2.alloc(n)); chk(choice.alloc(nm));
   chk(cellStart.alloc(64 * 48 + 1)); chk(cellItems.alloc(n));
   chk(candOff.alloc(nm + 1)); chk(mdist.alloc(n)); chk(m21.alloc(n)); chk(m12.alloc(1));
+  int* result = pk.ptr<int>(oRes);
   ProjArgs a{};
-  a.grid.k2 = k.p; a.grid.n2 = n; a.grid.n1 = 0;
-  a.grid.minX = min_x; a.grid.minY = min_y;
-  a.grid.invW = 64.f / (max_x - min_x);
-  a.grid.invH = 48.f / (max_y - min_y);
-  a.grid.cellStart = cellStart.p; a.grid.cellItems = cellItems.p; a.grid.matchedDist = mdist.p; a.grid.matches21 = m21.p;
-  a.grid.matches12 = m12.p; a.grid.result = result.p; a.grid.candOff = candOff.p; a.grid.candCap = 1 << 30;
-  a.desc = d.p; a.uRight = u_right ? ur.p : nullptr; a.scale = sf.p; a.mps = mp.p; a.pts = pp.p; a.nmp = n_points;
+  a.grid = grid_block(min_x, min_y, max_x, max_y, pk.ptr<orbx_keypoint>(oK), n, cellStart.p, cellItems.p, mdist.p, m21.p, m12.p,
+                      result, candOff.p);
+  a.desc = pk.ptr<uint8_t>(oD); a.uRight = u_right ? pk.ptr<float>(oUr) : nullptr; a.scale = pk.ptr<float>(oSf);
+  a.mps = pk.ptr<orbx_map_point_view>(oMp); a.pts = pk.ptr<orbx_projected_point>(oPp); a.nmp = n_points;
   a.mode = mode; a.checkOri = check_ori; a.maxDist = max_dist; a.claimAll = claim_all;
   a.th = th; a.thFar = th_far_points; a.nnratio = nnratio; a.far = far_points;
-  a.occupied = occ.p; a.match = mt.p; a.candOff = candOff.p; a.result = result.p;
+  a.occupied = pk.ptr<uint8_t>(oOcc); a.match = pk.ptr<int>(oMt); a.candOff = candOff.p; a.result = result;
   chk(candIdx.alloc((size_t)cand_cap));
   chk(candDist.alloc((size_t)cand_cap));
   a.candIdx = candIdx.p; a.candDist = candDist.p; a.candCap = cand_cap;
   int res[2] = {0, 0};
   if (e == hipSuccess) chk(launch_proj_count(a, nullptr));
-  a.taker[0] = taker0.p; a.taker[1] = taker1.p; a.taker[2] = taker2.p; a.choice = choice.p; a.flags = flags.p;
+  a.taker[0] = taker0.p; a.taker[1] = taker1.p; a.taker[2] = taker2.p; a.choice = choice.p; a.flags = pk.ptr<int>(oFlags);
   // Resolve: kProjBlindRounds (16; ORBX_PROJ_BLIND) rounds of the parallel fixed-point iteration (k_proj_round) are enqueued without looking --
   // rounds after the fixed point return at once -- followed by the finish kernels; whether the last round still changed
   // something comes back with the results.  Then (pathological claim chains) the caller repeats the attempt with the
   // one-wave serial walk, which ORBX_PROJ_SERIAL=1 also forces (tests).
-  static const int kProjBlindRounds = getenv("ORBX_PROJ_BLIND") ? std::min(48, std::max(1, atoi(getenv("ORBX_PROJ_BLIND")))) : 16;
+  const int kProjBlindRounds = knobs().blind;
   if (e == hipSuccess) chk(launch_proj_cands_fill(a, nullptr));
   const bool rounds = !serial && n_points > 0;
   if (e == hipSuccess && rounds) chk(launch_proj_rounds(a, 0, kProjBlindRounds, nullptr));
@@ -619,9 +695,6 @@ int search_by_projection_try(const orbx_keypoint* kps_un, const uint8_t* desc, c
       }
     }
   }
-  pk.release(); cellStart.free(); cellItems.free();
-  candOff.free(); candIdx.free(); candDist.free(); mdist.free(); m21.free(); m12.free();
-  taker0.free(); taker1.free(); taker2.free(); choice.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return res[0];
 }
@@ -636,22 +709,18 @@ int search_by_projection_impl(int device, const orbx_keypoint* kps_un, const uin
   if (rc != ORBX_OK) return rc;
   // room for 96 candidates per point on average (a search window holds 10-40); denser inputs repeat the call once with the
   // exact size.  ORBX_PROJ_CAND_CAP overrides the first guess (tests force the second attempt with it).
-  static const int capEnv = getenv("ORBX_PROJ_CAND_CAP") ? atoi(getenv("ORBX_PROJ_CAND_CAP")) : 0;
-  static const bool forceSerial = getenv("ORBX_PROJ_SERIAL") && atoi(getenv("ORBX_PROJ_SERIAL")) != 0;
-  int cap = capEnv > 0 ? capEnv : std::max(n_points, 1) * 96, needed = 0;
-  bool serial = forceSerial, converged = true;
-  for (int attempt = 0; attempt < 3; attempt++) {  // at most: capacity retry, then serial retry
-    rc = search_by_projection_try(kps_un, desc, u_right, n, min_x, min_y, max_x, max_y, scale_factors, nlevels, map_points, points,
-                                  n_points, th, far_points, th_far_points, nnratio, check_ori, occupied, match, cap, &needed,
-                                  serial, &converged, max_dist, claim_all);
-    if (rc < 0) break;
-    if (needed > cap) { cap = needed; continue; }
-    if (!converged) {
-      if (trace_slow_ms() > 0) std::fprintf(stderr, "ORBX_TRACE_SLOW SearchByProjection: no fixed point within the blind rounds, serial walk\n");
-      serial = true;
-      continue;
-    }
-    break;
+  int cap = first_cand_cap(n_points, 96);
+  bool serial = knobs().serial, converged = true;
+  const auto attempt = [&](int c, int* needed) {
+    return search_by_projection_try(kps_un, desc, u_right, n, min_x, min_y, max_x, max_y, scale_factors, nlevels, map_points, points,
+                                    n_points, th, far_points, th_far_points, nnratio, check_ori, occupied, match, c, needed, serial,
+                                    &converged, max_dist, claim_all);
+  };
+  rc = with_exact_capacity(cap, attempt);
+  if (rc >= 0 && !converged) {   // then the serial walk, at the capacity that fitted
+    if (trace_slow_ms() > 0) std::fprintf(stderr, "ORBX_TRACE_SLOW SearchByProjection: no fixed point within the blind rounds, serial walk\n");
+    serial = true;
+    rc = with_exact_capacity(cap, attempt);
   }
   return rc;
 }
@@ -736,20 +805,12 @@ int proj_batch_impl(orbx_extractor* ex, int first_image, int n_frames, float min
   int rc = set_device(ex->device);
   if (rc != ORBX_OK) return rc;
   const int cap = ex->gmax.outCap, F = n_frames;
-  // the frames' keypoint counts live on the device: one small copy behind the extraction
-  std::vector<int> n2(F);
-  HIPC(hipStreamSynchronize(ex->stream));
-  HIPC(hipMemcpy(n2.data(), ex->d_nOut.p + first_image, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> n2;
   int maxN2 = 0;
-  for (int f = 0; f < F; f++) {
-    n2[f] = std::min(std::max(n2[f], 0), cap);
-    maxN2 = std::max(maxN2, n2[f]);
-  }
-  static const int capEnv = getenv("ORBX_PROJ_CAND_CAP") ? atoi(getenv("ORBX_PROJ_CAND_CAP")) : 0;
-  static const int kBlind = getenv("ORBX_PROJ_BLIND") ? std::min(48, std::max(1, atoi(getenv("ORBX_PROJ_BLIND")))) : 16;
-  const int nm = std::max(maxPts, 1), candCap = capEnv > 0 ? capEnv : nm * 96;
+  if ((rc = batch_counts(ex, first_image, F, n2, &maxN2)) != ORBX_OK) return rc;
+  const int kBlind = knobs().blind, kFlags = kFlagInts;
+  const int nm = std::max(maxPts, 1), candCap = first_cand_cap(nm, 96);
   const size_t ptBytes = mode == 0 ? sizeof(orbx_map_point_view) : sizeof(orbx_projected_point);
-  constexpr int kFlags = 40 + 48;
   // ---- one device block: inputs | outputs (occupied, match, result, flags: one copy back) | scratch
   Pack pk;
   std::vector<ProjArgs> frames(F);
@@ -771,24 +832,13 @@ int proj_batch_impl(orbx_extractor* ex, int first_image, int n_frames, float min
   const size_t oCo = per((size_t)nm + 4), oCx = per(candCap), oCd = per(candCap);
   const size_t oT0 = per(cap), oT1 = per(cap), oT2 = per(cap), oCh = per(nm);
   hipError_t e = pk.reserve();
-  if (e != hipSuccess) { pk.release(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f = 0; f < F; f++) {
     ProjArgs a{};
     const int img = first_image + f;
-    a.grid.k2 = ex->d_kps.p + (size_t)img * cap;
-    a.grid.n2 = n2[f];
-    a.grid.n1 = 0;
-    a.grid.minX = min_x; a.grid.minY = min_y;
-    a.grid.invW = 64.f / (max_x - min_x);
-    a.grid.invH = 48.f / (max_y - min_y);
-    a.grid.cellStart = pk.ptr<int>(oCs) + (size_t)f * cs;
-    a.grid.cellItems = pk.ptr<int>(oCi) + (size_t)f * cap;
-    a.grid.matchedDist = pk.ptr<int>(oMd) + (size_t)f * cap;
-    a.grid.matches21 = pk.ptr<int>(oM21) + (size_t)f * cap;
-    a.grid.matches12 = pk.ptr<int>(oM12) + (size_t)f * 4;
-    a.grid.result = pk.ptr<int>(oRes) + (size_t)f * 2;
-    a.grid.candOff = pk.ptr<int>(oCo) + (size_t)f * (nm + 4);
-    a.grid.candCap = 1 << 30;
+    a.grid = grid_block(min_x, min_y, max_x, max_y, ex->d_kps.p + (size_t)img * cap, n2[f], pk.ptr<int>(oCs) + (size_t)f * cs,
+                        pk.ptr<int>(oCi) + (size_t)f * cap, pk.ptr<int>(oMd) + (size_t)f * cap, pk.ptr<int>(oM21) + (size_t)f * cap,
+                        pk.ptr<int>(oM12) + (size_t)f * 4, pk.ptr<int>(oRes) + (size_t)f * 2, pk.ptr<int>(oCo) + (size_t)f * (nm + 4));
     a.desc = ex->d_desc.p + (size_t)img * cap * 32;
     a.uRight = stereo_pair0 >= 0 ? ex->d_uR.p + (size_t)(stereo_pair0 + f) * cap : nullptr;
     a.scale = pk.ptr<float>(oSf);
@@ -831,16 +881,15 @@ int proj_batch_impl(orbx_extractor* ex, int first_image, int n_frames, float min
       }
     }
   }
-  pk.release();
+  pk.release();   // (its device block goes back to the pool before the redo calls)
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   // ---- the rare frames the blind batch could not finish: the one-shot path on a host copy of the frame
   for (int f : redo) {
-    const int img = first_image + f, n = n2[f];
+    const int n = n2[f];
     std::vector<orbx_keypoint> k(std::max(n, 1));
     std::vector<uint8_t> d((size_t)std::max(n, 1) * 32);
     std::vector<float> ur(std::max(n, 1));
-    HIPC(hipMemcpy(k.data(), ex->d_kps.p + (size_t)img * cap, (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(d.data(), ex->d_desc.p + (size_t)img * cap * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
+    if ((rc = download_frame(ex, first_image + f, n, k.data(), d.data())) != ORBX_OK) return rc;
     if (stereo_pair0 >= 0)
       HIPC(hipMemcpy(ur.data(), ex->d_uR.p + (size_t)(stereo_pair0 + f) * cap, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     uint8_t* occ = occupied + (size_t)f * cap;
@@ -1075,58 +1124,38 @@ int orbx_search_for_triangulation_rig(int device, const uint32_t* node_ids1, con
       (n2 && (!kps2 || !desc2 || !has_map_point2)) || (n_nodes1 && (!node_ids1 || !node_start1 || !feature_idx1)) ||
       (n_nodes2 && (!node_ids2 || !node_start2 || !feature_idx2)))
     return fail(ORBX_E_BADARG, "bad argument");
-  const int nl1 = n_nodes1 ? node_start1[n_nodes1] : 0, nl2 = n_nodes2 ? node_start2[n_nodes2] : 0;
+  const BowSide s1{node_ids1, node_start1, feature_idx1, n_nodes1, kps1, desc1, has_map_point1, n1};
+  const BowSide s2{node_ids2, node_start2, feature_idx2, n_nodes2, kps2, desc2, has_map_point2, n2};
+  const int nl1 = s1.list(), nl2 = s2.list();
   if (nl1 < 0 || nl1 > n1 || nl2 < 0 || nl2 > n2) return fail(ORBX_E_BADARG, "feature vector larger than the key frame");
   if (nl2 >= (1 << 24)) return fail(ORBX_E_CAPACITY, "more than 2^24 features");
-  for (int j = 0; j < n_nodes1; j++)
-    if (node_start1[j] < 0 || node_start1[j] > node_start1[j + 1] || (j && node_ids1[j] <= node_ids1[j - 1]))
-      return fail(ORBX_E_BADARG, "feature vector 1: node ids must ascend and offsets must be monotone");
-  for (int j = 0; j < n_nodes2; j++)
-    if (node_start2[j] < 0 || node_start2[j] > node_start2[j + 1] || (j && node_ids2[j] <= node_ids2[j - 1]))
-      return fail(ORBX_E_BADARG, "feature vector 2: node ids must ascend and offsets must be monotone");
-  for (int i = 0; i < nl1; i++)
-    if (feature_idx1[i] >= (uint32_t)n1) return fail(ORBX_E_BADARG, "feature index 1 out of range");
-  for (int i = 0; i < nl2; i++)
-    if (feature_idx2[i] >= (uint32_t)n2) return fail(ORBX_E_BADARG, "feature index 2 out of range");
+  int rc;
+  if ((rc = check_nodes(s1, "feature vector 1")) || (rc = check_nodes(s2, "feature vector 2")) ||
+      (rc = check_features(s1, "feature index 1")) || (rc = check_features(s2, "feature index 2")))
+    return rc;
   for (int i = 0; i < n1; i++)
     if (kps1[i].octave < 0 || kps1[i].octave >= nlevels) return fail(ORBX_E_BADARG, "keypoint octave outside [0, nlevels)");
   for (int i = 0; i < n2; i++)
     if (kps2[i].octave < 0 || kps2[i].octave >= nlevels) return fail(ORBX_E_BADARG, "keypoint octave outside [0, nlevels)");
-  int rc = set_device(device);
+  rc = set_device(device);
   if (rc != ORBX_OK) return rc;
   for (int i = 0; i < n1; i++) matches12[i] = -1;
   if (nl1 == 0 || nl2 == 0) return 0;
   Pack pk;
-  const size_t oN1 = pk.add(node_ids1, (size_t)n_nodes1 * 4), oS1 = pk.add(node_start1, ((size_t)n_nodes1 + 1) * 4);
-  const size_t oF1 = pk.add(feature_idx1, (size_t)nl1 * 4), oD1 = pk.add(desc1, (size_t)n1 * 32);
-  const size_t oM1 = pk.add(has_map_point1, n1), oK1 = pk.add(kps1, (size_t)n1 * sizeof(orbx_keypoint));
-  const size_t oN2 = pk.add(node_ids2, (size_t)n_nodes2 * 4), oS2 = pk.add(node_start2, ((size_t)n_nodes2 + 1) * 4);
-  const size_t oF2 = pk.add(feature_idx2, (size_t)nl2 * 4), oD2 = pk.add(desc2, (size_t)n2 * 32);
-  const size_t oM2 = pk.add(has_map_point2, n2), oK2 = pk.add(kps2, (size_t)n2 * sizeof(orbx_keypoint));
+  const SideAreas o1 = add_side(pk, s1), o2 = add_side(pk, s2);
   const size_t oG1 = pk.add(level_sigma2_1, (size_t)nlevels * 4), oG2 = pk.add(level_sigma2_2, (size_t)nlevels * 4);
   const size_t oRig = pk.add(rig, sizeof(orbx_tri_rig));
   const size_t oFlags = pk.add(nullptr, 33 * 4);
   const size_t oOut = pk.add(nullptr, ((size_t)n1 + 1) * 4);
   hipError_t e = pk.commit();
-  TriArgs a{};
-  a.nodes1 = pk.ptr<uint32_t>(oN1); a.start1 = pk.ptr<int>(oS1); a.feat1 = pk.ptr<uint32_t>(oF1); a.nNodes1 = n_nodes1; a.nList1 = nl1;
-  a.nodes2 = pk.ptr<uint32_t>(oN2); a.start2 = pk.ptr<int>(oS2); a.feat2 = pk.ptr<uint32_t>(oF2); a.nNodes2 = n_nodes2;
-  a.k1 = pk.ptr<orbx_keypoint>(oK1); a.k2 = pk.ptr<orbx_keypoint>(oK2);
-  a.d1 = pk.ptr<uint32_t>(oD1); a.d2 = pk.ptr<uint32_t>(oD2); a.mp1 = pk.ptr<uint8_t>(oM1); a.mp2 = pk.ptr<uint8_t>(oM2);
-  a.n1 = n1; a.n2 = n2; a.nLeft1 = n_left1; a.nLeft2 = n_left2;
+  TriArgs a = tri_args(pk, s1, o1, s2, o2);
+  a.nLeft1 = n_left1; a.nLeft2 = n_left2;
   a.sigma1 = pk.ptr<float>(oG1); a.sigma2 = pk.ptr<float>(oG2); a.rig = pk.ptr<orbx_tri_rig>(oRig);
   a.onlyStereo = only_stereo ? 1 : 0; a.coarse = coarse ? 1 : 0; a.checkOri = check_orientation ? 1 : 0;
   a.flags = pk.ptr<int>(oFlags); a.result = pk.ptr<int>(oOut); a.match = pk.ptr<int>(oOut) + 1;
   if (e == hipSuccess) e = launch_search_for_triangulation(a, nullptr);
   int n = 0;
-  if (e == hipSuccess) {
-    const uint8_t* h = pk.fetch(oOut, ((size_t)n1 + 1) * 4, &e);
-    if (e == hipSuccess) {
-      std::memcpy(&n, h, 4);
-      std::memcpy(matches12, h + 4, (size_t)n1 * 4);
-    }
-  }
-  pk.release();
+  if (e == hipSuccess) e = fetch_result(pk, oOut, n1, matches12, &n);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return n;
 }
@@ -1140,49 +1169,29 @@ int orbx_search_by_bow_keyframes(int device, const uint32_t* node_ids1, const in
       (n2 && (!kps2 || !desc2 || !valid2)) || (n_nodes1 && (!node_ids1 || !node_start1 || !feature_idx1)) ||
       (n_nodes2 && (!node_ids2 || !node_start2 || !feature_idx2)))
     return fail(ORBX_E_BADARG, "bad argument");
-  const int nl1 = n_nodes1 ? node_start1[n_nodes1] : 0, nl2 = n_nodes2 ? node_start2[n_nodes2] : 0;
+  const BowSide s1{node_ids1, node_start1, feature_idx1, n_nodes1, kps1, desc1, valid1, n1};
+  const BowSide s2{node_ids2, node_start2, feature_idx2, n_nodes2, kps2, desc2, valid2, n2};
+  const int nl1 = s1.list(), nl2 = s2.list();
   if (nl1 < 0 || nl1 > n1 || nl2 < 0 || nl2 > n2) return fail(ORBX_E_BADARG, "feature vector larger than the key frame");
-  for (int j = 0; j < n_nodes1; j++)
-    if (node_start1[j] < 0 || node_start1[j] > node_start1[j + 1] || (j && node_ids1[j] <= node_ids1[j - 1]))
-      return fail(ORBX_E_BADARG, "feature vector 1: node ids must ascend and offsets must be monotone");
-  for (int j = 0; j < n_nodes2; j++)
-    if (node_start2[j] < 0 || node_start2[j] > node_start2[j + 1] || (j && node_ids2[j] <= node_ids2[j - 1]))
-      return fail(ORBX_E_BADARG, "feature vector 2: node ids must ascend and offsets must be monotone");
-  for (int i = 0; i < nl1; i++)
-    if (feature_idx1[i] >= (uint32_t)n1) return fail(ORBX_E_BADARG, "feature index 1 out of range");
-  for (int i = 0; i < nl2; i++)
-    if (feature_idx2[i] >= (uint32_t)n2) return fail(ORBX_E_BADARG, "feature index 2 out of range");
-  int rc = set_device(device);
+  int rc;
+  if ((rc = check_nodes(s1, "feature vector 1")) || (rc = check_nodes(s2, "feature vector 2")) ||
+      (rc = check_features(s1, "feature index 1")) || (rc = check_features(s2, "feature index 2")))
+    return rc;
+  rc = set_device(device);
   if (rc != ORBX_OK) return rc;
   for (int i = 0; i < n1; i++) matches12[i] = -1;
   if (nl1 == 0 || nl2 == 0) return 0;
   Pack pk;
-  const size_t oN1 = pk.add(node_ids1, (size_t)n_nodes1 * 4), oS1 = pk.add(node_start1, ((size_t)n_nodes1 + 1) * 4);
-  const size_t oF1 = pk.add(feature_idx1, (size_t)nl1 * 4), oD1 = pk.add(desc1, (size_t)n1 * 32);
-  const size_t oV1 = pk.add(valid1, n1), oK1 = pk.add(kps1, (size_t)n1 * sizeof(orbx_keypoint));
-  const size_t oN2 = pk.add(node_ids2, (size_t)n_nodes2 * 4), oS2 = pk.add(node_start2, ((size_t)n_nodes2 + 1) * 4);
-  const size_t oF2 = pk.add(feature_idx2, (size_t)nl2 * 4), oD2 = pk.add(desc2, (size_t)n2 * 32);
-  const size_t oV2 = pk.add(valid2, n2), oK2 = pk.add(kps2, (size_t)n2 * sizeof(orbx_keypoint));
+  const SideAreas o1 = add_side(pk, s1), o2 = add_side(pk, s2);
   const size_t oFlags = pk.add(nullptr, 33 * 4);
   const size_t oOut = pk.add(nullptr, ((size_t)n1 + 1) * 4);  // result, then the matches: one copy back
   hipError_t e = pk.commit();
-  TriArgs a{};
-  a.nodes1 = pk.ptr<uint32_t>(oN1); a.start1 = pk.ptr<int>(oS1); a.feat1 = pk.ptr<uint32_t>(oF1); a.nNodes1 = n_nodes1; a.nList1 = nl1;
-  a.nodes2 = pk.ptr<uint32_t>(oN2); a.start2 = pk.ptr<int>(oS2); a.feat2 = pk.ptr<uint32_t>(oF2); a.nNodes2 = n_nodes2;
-  a.k1 = pk.ptr<orbx_keypoint>(oK1); a.k2 = pk.ptr<orbx_keypoint>(oK2);
-  a.d1 = pk.ptr<uint32_t>(oD1); a.d2 = pk.ptr<uint32_t>(oD2); a.mp1 = pk.ptr<uint8_t>(oV1); a.mp2 = pk.ptr<uint8_t>(oV2);
-  a.n1 = n1; a.n2 = n2; a.nnratio = nnratio; a.checkOri = check_orientation ? 1 : 0;
+  TriArgs a = tri_args(pk, s1, o1, s2, o2);
+  a.nnratio = nnratio; a.checkOri = check_orientation ? 1 : 0;
   a.flags = pk.ptr<int>(oFlags); a.result = pk.ptr<int>(oOut); a.match = pk.ptr<int>(oOut) + 1;
   if (e == hipSuccess) e = launch_search_by_bow_keyframes(a, nullptr);
   int n = 0;
-  if (e == hipSuccess) {
-    const uint8_t* h = pk.fetch(oOut, ((size_t)n1 + 1) * 4, &e);
-    if (e == hipSuccess) {
-      std::memcpy(&n, h, 4);
-      std::memcpy(matches12, h + 4, (size_t)n1 * 4);
-    }
-  }
-  pk.release();
+  if (e == hipSuccess) e = fetch_result(pk, oOut, n1, matches12, &n);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   if (n < 0) {
     for (int i = 0; i < n1; i++) matches12[i] = -1;
@@ -1221,12 +1230,8 @@ int orbx_fuse_search(int device, const orbx_keypoint* kps, const uint8_t* desc, 
   chk(pk.commit());
   chk(cellStart.alloc(64 * 48 + 1)); chk(cellItems.alloc(n)); chk(mdist.alloc(n)); chk(m21.alloc(n)); chk(m12.alloc(1));
   FuseArgs a{};
-  a.grid.k2 = pk.ptr<orbx_keypoint>(oK); a.grid.n2 = n; a.grid.n1 = 0;
-  a.grid.minX = min_x; a.grid.minY = min_y;
-  a.grid.invW = 64.f / (max_x - min_x);
-  a.grid.invH = 48.f / (max_y - min_y);
-  a.grid.cellStart = cellStart.p; a.grid.cellItems = cellItems.p; a.grid.matchedDist = mdist.p; a.grid.matches21 = m21.p;
-  a.grid.matches12 = m12.p; a.grid.result = pk.ptr<int>(oRes) + 2; a.grid.candCap = 1 << 30;
+  a.grid = grid_block(min_x, min_y, max_x, max_y, pk.ptr<orbx_keypoint>(oK), n, cellStart.p, cellItems.p, mdist.p, m21.p, m12.p,
+                      pk.ptr<int>(oRes) + 2, nullptr);
   a.desc = pk.ptr<uint32_t>(oD); a.uRight = u_right ? pk.ptr<float>(oU) : nullptr; a.invSigma2 = pk.ptr<float>(oS);
   a.pts = pk.ptr<orbx_fuse_point>(oP); a.npts = n_points; a.maxDist = max_dist;
   a.bestIdx = pk.ptr<int>(oBi); a.bestDist = pk.ptr<int>(oBd); a.result = pk.ptr<int>(oRes);
@@ -1240,7 +1245,6 @@ int orbx_fuse_search(int device, const orbx_keypoint* kps, const uint8_t* desc, 
       if (best_dist) std::memcpy(best_dist, h + (oBd - oRes), (size_t)n_points * 4);
     }
   }
-  pk.release(); cellStart.free(); cellItems.free(); mdist.free(); m21.free(); m12.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return nf;
 }
@@ -1256,59 +1260,40 @@ int orbx_search_for_triangulation(int device, const uint32_t* node_ids1, const i
       (!coarse && !F12) || (n1 && (!matches12 || !kps1 || !desc1 || !has_map_point1)) || (n2 && (!kps2 || !desc2 || !has_map_point2)) ||
       (n_nodes1 && (!node_ids1 || !node_start1 || !feature_idx1)) || (n_nodes2 && (!node_ids2 || !node_start2 || !feature_idx2)))
     return fail(ORBX_E_BADARG, "bad argument");
-  const int nl1 = n_nodes1 ? node_start1[n_nodes1] : 0, nl2 = n_nodes2 ? node_start2[n_nodes2] : 0;
+  const BowSide s1{node_ids1, node_start1, feature_idx1, n_nodes1, kps1, desc1, has_map_point1, n1};
+  const BowSide s2{node_ids2, node_start2, feature_idx2, n_nodes2, kps2, desc2, has_map_point2, n2};
+  const int nl1 = s1.list(), nl2 = s2.list();
   if (nl1 < 0 || nl1 > n1 || nl2 < 0 || nl2 > n2) return fail(ORBX_E_BADARG, "feature vector larger than the key frame");
   if (nl2 >= (1 << 24)) return fail(ORBX_E_CAPACITY, "more than 2^24 features");
-  for (int j = 0; j < n_nodes1; j++)
-    if (node_start1[j] < 0 || node_start1[j] > node_start1[j + 1] || (j && node_ids1[j] <= node_ids1[j - 1]))
-      return fail(ORBX_E_BADARG, "feature vector 1: node ids must ascend and offsets must be monotone");
-  for (int j = 0; j < n_nodes2; j++)
-    if (node_start2[j] < 0 || node_start2[j] > node_start2[j + 1] || (j && node_ids2[j] <= node_ids2[j - 1]))
-      return fail(ORBX_E_BADARG, "feature vector 2: node ids must ascend and offsets must be monotone");
-  for (int i = 0; i < nl1; i++)
-    if (feature_idx1[i] >= (uint32_t)n1) return fail(ORBX_E_BADARG, "feature index 1 out of range");
-  for (int i = 0; i < nl2; i++)
-    if (feature_idx2[i] >= (uint32_t)n2) return fail(ORBX_E_BADARG, "feature index 2 out of range");
+  int rc;
+  if ((rc = check_nodes(s1, "feature vector 1")) || (rc = check_nodes(s2, "feature vector 2")) ||
+      (rc = check_features(s1, "feature index 1")) || (rc = check_features(s2, "feature index 2")))
+    return rc;
   for (int i = 0; i < n2; i++)  // kp2.octave indexes mvScaleFactors / mvLevelSigma2 (:1001,1054)
     if (kps2[i].octave < 0 || kps2[i].octave >= nlevels2) return fail(ORBX_E_BADARG, "keypoint octave outside [0, nlevels2)");
-  int rc = set_device(device);
+  rc = set_device(device);
   if (rc != ORBX_OK) return rc;
   for (int i = 0; i < n1; i++) matches12[i] = -1;
   if (nl1 == 0 || nl2 == 0) return 0;
   Pack pk;
-  const size_t oN1 = pk.add(node_ids1, (size_t)n_nodes1 * 4), oS1 = pk.add(node_start1, ((size_t)n_nodes1 + 1) * 4);
-  const size_t oF1 = pk.add(feature_idx1, (size_t)nl1 * 4), oD1 = pk.add(desc1, (size_t)n1 * 32);
-  const size_t oM1 = pk.add(has_map_point1, n1), oK1 = pk.add(kps1, (size_t)n1 * sizeof(orbx_keypoint));
+  const SideAreas o1 = add_side(pk, s1);
   const size_t oU1 = pk.add(u_right1, (size_t)n1 * 4);
-  const size_t oN2 = pk.add(node_ids2, (size_t)n_nodes2 * 4), oS2 = pk.add(node_start2, ((size_t)n_nodes2 + 1) * 4);
-  const size_t oF2 = pk.add(feature_idx2, (size_t)nl2 * 4), oD2 = pk.add(desc2, (size_t)n2 * 32);
-  const size_t oM2 = pk.add(has_map_point2, n2), oK2 = pk.add(kps2, (size_t)n2 * sizeof(orbx_keypoint));
+  const SideAreas o2 = add_side(pk, s2);
   const size_t oU2 = pk.add(u_right2, (size_t)n2 * 4);
   const size_t oSf = pk.add(scale_factors2, (size_t)nlevels2 * 4), oSg = pk.add(level_sigma2_2, (size_t)nlevels2 * 4);
   const size_t oFlags = pk.add(nullptr, 33 * 4);
   const size_t oOut = pk.add(nullptr, ((size_t)n1 + 1) * 4);  // result, then vMatches12: one copy back
   hipError_t e = pk.commit();
-  TriArgs a{};
-  a.nodes1 = pk.ptr<uint32_t>(oN1); a.start1 = pk.ptr<int>(oS1); a.feat1 = pk.ptr<uint32_t>(oF1); a.nNodes1 = n_nodes1; a.nList1 = nl1;
-  a.nodes2 = pk.ptr<uint32_t>(oN2); a.start2 = pk.ptr<int>(oS2); a.feat2 = pk.ptr<uint32_t>(oF2); a.nNodes2 = n_nodes2;
-  a.k1 = pk.ptr<orbx_keypoint>(oK1); a.k2 = pk.ptr<orbx_keypoint>(oK2);
-  a.d1 = pk.ptr<uint32_t>(oD1); a.d2 = pk.ptr<uint32_t>(oD2); a.mp1 = pk.ptr<uint8_t>(oM1); a.mp2 = pk.ptr<uint8_t>(oM2);
+  TriArgs a = tri_args(pk, s1, o1, s2, o2);
   a.ur1 = u_right1 ? pk.ptr<float>(oU1) : nullptr; a.ur2 = u_right2 ? pk.ptr<float>(oU2) : nullptr;
-  a.n1 = n1; a.n2 = n2; a.scale2 = pk.ptr<float>(oSf); a.sigma2 = pk.ptr<float>(oSg);
+  a.scale2 = pk.ptr<float>(oSf); a.sigma2 = pk.ptr<float>(oSg);
   a.ep0 = ep[0]; a.ep1 = ep[1];
   for (int i = 0; i < 9; i++) a.F[i] = F12 ? F12[i] : 0.f;
   a.onlyStereo = only_stereo ? 1 : 0; a.coarse = coarse ? 1 : 0; a.checkOri = check_orientation ? 1 : 0;
   a.flags = pk.ptr<int>(oFlags); a.result = pk.ptr<int>(oOut); a.match = pk.ptr<int>(oOut) + 1;
   if (e == hipSuccess) e = launch_search_for_triangulation(a, nullptr);
   int n = 0;
-  if (e == hipSuccess) {
-    const uint8_t* h = pk.fetch(oOut, ((size_t)n1 + 1) * 4, &e);
-    if (e == hipSuccess) {
-      std::memcpy(&n, h, 4);
-      std::memcpy(matches12, h + 4, (size_t)n1 * 4);
-    }
-  }
-  pk.release();
+  if (e == hipSuccess) e = fetch_result(pk, oOut, n1, matches12, &n);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return n;
 }
@@ -1337,10 +1322,6 @@ struct ProjSide {
   orbx_map_point_view* mpp = nullptr;  // views of this camera inside the call's packed upload
   orbx_projected_point* ppp = nullptr;
   ProjArgs a{};
-  void release() {
-    cellStart.free(); cellItems.free(); candOff.free(); candIdx.free(); candDist.free(); mdist.free(); m21.free();
-    m12.free();
-  }
 };
 
 // One attempt with candidate arrays of cand_cap entries per camera; see search_by_projection_try.
@@ -1373,10 +1354,9 @@ int search_by_projection_fisheye_try(const orbx_keypoint* kps, const uint8_t* de
   const size_t oRes = pk.add(nullptr, 2 * sizeof(int)), oMt = pk.add(nullptr, (size_t)n * sizeof(int));
   const size_t outBytes = oMt + (size_t)n * sizeof(int) - oOcc;
   chk(pk.commit());
-  struct { orbx_keypoint* p; } k{pk.ptr<orbx_keypoint>(oK)};
-  struct { uint8_t* p; } d{pk.ptr<uint8_t>(oD)}, occ{pk.ptr<uint8_t>(oOcc)};
-  struct { float* p; } sf{pk.ptr<float>(oSf)};
-  struct { int* p; } a12{pk.ptr<int>(oA12)}, a21{pk.ptr<int>(oA21)}, mt{pk.ptr<int>(oMt)}, res{pk.ptr<int>(oRes)};
+  orbx_keypoint* k = pk.ptr<orbx_keypoint>(oK);
+  uint8_t* occ = pk.ptr<uint8_t>(oOcc);
+  int* mt = pk.ptr<int>(oMt);
   for (int side = 0; side < 2 && e == hipSuccess; side++) {
     ProjSide& P = S[side];
     const int ns = side ? n_right : n_left, first = side ? n_left : 0;
@@ -1387,18 +1367,14 @@ int search_by_projection_fisheye_try(const orbx_keypoint* kps, const uint8_t* de
     P.mpp = pk.ptr<orbx_map_point_view>(oMp[side]);
     P.ppp = pk.ptr<orbx_projected_point>(oPp[side]);
     ProjArgs& a = P.a;
-    a.grid.k2 = k.p + first; a.grid.n2 = ns; a.grid.n1 = 0;
-    a.grid.minX = min_x; a.grid.minY = min_y;
-    a.grid.invW = 64.f / (max_x - min_x);
-    a.grid.invH = 48.f / (max_y - min_y);
-    a.grid.cellStart = P.cellStart.p; a.grid.cellItems = P.cellItems.p; a.grid.matchedDist = P.mdist.p;
-    a.grid.matches21 = P.m21.p; a.grid.matches12 = P.m12.p; a.grid.result = sideRes; a.grid.candOff = P.candOff.p;
+    a.grid = grid_block(min_x, min_y, max_x, max_y, k + first, ns, P.cellStart.p, P.cellItems.p, P.mdist.p, P.m21.p, P.m12.p,
+                        sideRes, P.candOff.p);
     a.grid.candCap = cand_cap;
-    a.desc = d.p + (size_t)first * 32; a.uRight = nullptr;  // no mvuRight gate when F.Nleft != -1 (:90, :1667)
-    a.scale = sf.p; a.mps = P.mpp; a.pts = P.ppp; a.nmp = n_points; a.mode = mode; a.checkOri = check_ori;
+    a.desc = pk.ptr<uint8_t>(oD) + (size_t)first * 32; a.uRight = nullptr;  // no mvuRight gate when F.Nleft != -1 (:90, :1667)
+    a.scale = pk.ptr<float>(oSf); a.mps = P.mpp; a.pts = P.ppp; a.nmp = n_points; a.mode = mode; a.checkOri = check_ori;
     a.th = side ? 1.0f : th;  // the right-camera radius is not scaled by th (:144)
     a.thFar = th_far_points; a.nnratio = nnratio; a.far = far_points;
-    a.occupied = occ.p + first; a.match = mt.p + first; a.candOff = P.candOff.p; a.result = sideRes; a.candCap = cand_cap;
+    a.occupied = occ + first; a.match = mt + first; a.candOff = P.candOff.p; a.result = sideRes; a.candCap = cand_cap;
     a.candIdx = P.candIdx.p; a.candDist = P.candDist.p;
     if (e != hipSuccess) break;
     if (ns > 0) {
@@ -1412,31 +1388,21 @@ int search_by_projection_fisheye_try(const orbx_keypoint* kps, const uint8_t* de
   f.offL = S[0].candOff.p; f.idxL = S[0].candIdx.p; f.distL = S[0].candDist.p;
   f.offR = S[1].candOff.p; f.idxR = S[1].candIdx.p; f.distR = S[1].candDist.p;
   f.nLeft = n_left; f.n = n; f.nmp = n_points; f.mode = mode; f.checkOri = check_ori; f.nnratio = nnratio;
-  f.mps = S[0].mpp; f.pts = S[0].ppp; f.kps = k.p; f.l2r = a12.p; f.r2l = a21.p;
-  f.occupied = occ.p; f.match = mt.p; f.result = res.p;
+  f.mps = S[0].mpp; f.pts = S[0].ppp; f.kps = k; f.l2r = pk.ptr<int>(oA12); f.r2l = pk.ptr<int>(oA21);
+  f.occupied = occ; f.match = mt; f.result = pk.ptr<int>(oRes);
   int result[2] = {0, 0};
   // parallel fixed-point rounds (k_proj_round_fe); the serial walk is the fallback (writer-list overflow, no convergence
   // within 48 rounds) and the ORBX_PROJ_SERIAL=1 cross-check
   ScratchBuf<int4> wr0, wr1;
   ScratchBuf<int> wl0, wl1, wl2, wc0, wc1, wc2, fl;
-  static const bool forceSerial = getenv("ORBX_PROJ_SERIAL") && atoi(getenv("ORBX_PROJ_SERIAL")) != 0;
   bool done = false;
   int lastRound = 0;
-  if (!forceSerial && n_points > 0) {
+  if (!knobs().serial && n_points > 0) {
     chk(wr0.alloc(nm)); chk(wr1.alloc(nm)); chk(wl0.alloc((size_t)n * kFeWriters)); chk(wl1.alloc((size_t)n * kFeWriters));
-    chk(wl2.alloc((size_t)n * kFeWriters)); chk(wc0.alloc(n)); chk(wc1.alloc(n)); chk(wc2.alloc(n)); chk(fl.alloc(40 + 48));
+    chk(wl2.alloc((size_t)n * kFeWriters)); chk(wc0.alloc(n)); chk(wc1.alloc(n)); chk(wc2.alloc(n)); chk(fl.alloc(kFlagInts));
     f.writes[0] = wr0.p; f.writes[1] = wr1.p; f.writers[0] = wl0.p; f.writers[1] = wl1.p; f.writers[2] = wl2.p;
     f.nwriters[0] = wc0.p; f.nwriters[1] = wc1.p; f.nwriters[2] = wc2.p; f.flags = fl.p;
-    for (int r = 0; r < 48 && e == hipSuccess && !done; r += 4) {
-      chk(launch_proj_rounds_fisheye(f, r, 4, nullptr));
-      int st[40 + 48];
-      st[1] = 0;
-      st[40 + r + 3] = 1;
-      if (e == hipSuccess) chk(hipMemcpy(st, fl.p, sizeof(st), hipMemcpyDeviceToHost));  // synchronises
-      if (st[1]) break;  // a slot collected more than kFeWriters writers in one round
-      done = st[40 + r + 3] == 0;  // the last round of the group changed nothing
-      lastRound = r + 3;
-    }
+    done = stepped_rounds(fl.p, e, &lastRound, [&](int r) { return launch_proj_rounds_fisheye(f, r, 4, nullptr); });
   }
   if (e == hipSuccess) chk(done ? launch_proj_finish_fisheye(f, lastRound, nullptr) : launch_proj_resolve_fisheye(f, nullptr));
   if (e == hipSuccess) {
@@ -1453,9 +1419,6 @@ int search_by_projection_fisheye_try(const orbx_keypoint* kps, const uint8_t* de
       }
     }
   }
-  wr0.free(); wr1.free(); wl0.free(); wl1.free(); wl2.free(); wc0.free(); wc1.free(); wc2.free(); fl.free();
-  pk.release();
-  S[0].release(); S[1].release();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return result[0];
 }
@@ -1469,16 +1432,12 @@ int search_by_projection_fisheye_impl(int device, const orbx_keypoint* kps, cons
   if (n_left + n_right == 0) return 0;
   int rc = set_device(device);
   if (rc != ORBX_OK) return rc;
-  static const int capEnv = getenv("ORBX_PROJ_CAND_CAP") ? atoi(getenv("ORBX_PROJ_CAND_CAP")) : 0;
-  int cap = capEnv > 0 ? capEnv : std::max(n_points, 1) * 96, needed = 0;
-  rc = search_by_projection_fisheye_try(kps, desc, n_left, n_right, min_x, min_y, max_x, max_y, scale_factors, nlevels, viewsL,
-                                        viewsR, ptsL, ptsR, n_points, th, far_points, th_far_points, nnratio, check_ori, l2r, r2l,
-                                        occupied, match, cap, &needed);
-  if (rc >= 0 && needed > cap)
-    rc = search_by_projection_fisheye_try(kps, desc, n_left, n_right, min_x, min_y, max_x, max_y, scale_factors, nlevels, viewsL,
-                                          viewsR, ptsL, ptsR, n_points, th, far_points, th_far_points, nnratio, check_ori, l2r,
-                                          r2l, occupied, match, needed, &needed);
-  return rc;
+  int cap = first_cand_cap(n_points, 96);
+  return with_exact_capacity(cap, [&](int c, int* needed) {
+    return search_by_projection_fisheye_try(kps, desc, n_left, n_right, min_x, min_y, max_x, max_y, scale_factors, nlevels, viewsL,
+                                            viewsR, ptsL, ptsR, n_points, th, far_points, th_far_points, nnratio, check_ori, l2r, r2l,
+                                            occupied, match, c, needed);
+  });
 }
 }  // namespace
 
@@ -1497,25 +1456,11 @@ int orbx_search_by_projection_fisheye(int device, const orbx_keypoint* kps, cons
     if (left_to_right[i] < -1 || left_to_right[i] >= n_right) return fail(ORBX_E_BADARG, "left_to_right entry out of range");
   for (int i = 0; i < n_right; i++)
     if (right_to_left[i] < -1 || right_to_left[i] >= n_left) return fail(ORBX_E_BADARG, "right_to_left entry out of range");
-  // the right camera as a second list of views: (mTrackProjXR, mTrackProjYR), mTrackViewCosR, mnTrackScaleLevelR
-  std::vector<orbx_map_point_view> left(map_points, map_points + n_map_points), right(map_points, map_points + n_map_points);
-  for (int i = 0; i < n_map_points; i++) {
-    const orbx_map_point_right& r = map_points_right[i];
-    if ((left[i].in_view && (left[i].predicted_level < 0 || left[i].predicted_level >= nlevels)) ||
-        (r.in_view_r && (r.predicted_level_r < -1 || r.predicted_level_r >= nlevels)))
-      return fail(ORBX_E_BADARG, "map point with a predicted level outside [0, nlevels)");
-    if (!left[i].in_view) left[i].predicted_level = 0;
-    right[i].proj_x = map_points[i].proj_xr;
-    right[i].proj_y = r.proj_yr;
-    right[i].view_cos = r.view_cos_r;
-    right[i].predicted_level = r.predicted_level_r < 0 ? 0 : r.predicted_level_r;
-    right[i].in_view = (r.in_view_r && r.predicted_level_r != -1) ? 1 : 0;  // :141-143
-    // `if (!mbTrackInView && !mbTrackInViewR) continue` (:54) is implied: both lists stay empty
-  }
-  static const orbx_map_point_view dummy{};
+  std::vector<orbx_map_point_view> left, right;
+  const int rc = kb8_view_lists(map_points, map_points_right, &n_map_points, 1, std::max(n_map_points, 1), nlevels, left, right);
+  if (rc != ORBX_OK) return rc;
   return search_by_projection_fisheye_impl(device, kps, desc, n_left, n_right, min_x, min_y, max_x, max_y, scale_factors, nlevels,
-                                           n_map_points ? left.data() : &dummy, n_map_points ? right.data() : &dummy, nullptr,
-                                           nullptr, n_map_points, th, far_points, th_far_points, nnratio, 0, left_to_right,
+                                           left.data(), right.data(), nullptr, nullptr, n_map_points, th, far_points, th_far_points, nnratio, 0, left_to_right,
                                            right_to_left, occupied, match);
 }
 
@@ -1558,14 +1503,10 @@ int proj_fisheye_batch_impl(orbx_extractor* ex, int first_left, int first_right,
   std::vector<orbx_map_point_view> hvL, hvR;                             // (host copies for a frame that falls back to the one-shot path)
   int rc = set_device(ex->device);
   if (rc != ORBX_OK) return rc;
-  std::vector<int> nL(F), nR(F);
-  HIPC(hipStreamSynchronize(ex->stream));
-  HIPC(hipMemcpy(nL.data(), ex->d_nOut.p + first_left, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(nR.data(), ex->d_nOut.p + first_right, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> nL, nR;
+  if ((rc = batch_counts(ex, first_left, F, nL)) != ORBX_OK || (rc = batch_counts(ex, first_right, F, nR)) != ORBX_OK) return rc;
   int maxN = 0;
   for (int f = 0; f < F; f++) {
-    nL[f] = std::min(std::max(nL[f], 0), cap);
-    nR[f] = std::min(std::max(nR[f], 0), cap);
     maxN = std::max(maxN, nL[f] + nR[f]);
     if (mode == 0) {
       for (int i = 0; i < nL[f]; i++)
@@ -1574,11 +1515,9 @@ int proj_fisheye_batch_impl(orbx_extractor* ex, int first_left, int first_right,
         if (r2l[(size_t)f * cap + i] < -1 || r2l[(size_t)f * cap + i] >= nL[f]) return fail(ORBX_E_BADARG, "right_to_left entry out of range");
     }
   }
-  static const int capEnv = getenv("ORBX_PROJ_CAND_CAP") ? atoi(getenv("ORBX_PROJ_CAND_CAP")) : 0;
-  static const int kBlind = getenv("ORBX_PROJ_BLIND") ? std::min(48, std::max(1, atoi(getenv("ORBX_PROJ_BLIND")))) : 16;
-  const int nm = std::max(maxPts, 1), candCap = capEnv > 0 ? capEnv : nm * 96, n2c = 2 * cap;
+  const int kBlind = knobs().blind, kFlags = kFlagInts;
+  const int nm = std::max(maxPts, 1), candCap = first_cand_cap(nm, 96), n2c = 2 * cap;
   const size_t ptBytes = mode == 0 ? sizeof(orbx_map_point_view) : sizeof(orbx_projected_point);
-  constexpr int kFlags = 40 + 48;
   Pack pk;
   std::vector<ProjArgs> sides(2 * (size_t)F);
   std::vector<ProjFeArgs> frames(F);
@@ -1608,7 +1547,7 @@ int proj_fisheye_batch_impl(orbx_extractor* ex, int first_left, int first_right,
   const size_t oWl0 = per((size_t)n2c * kFeWriters), oWl1 = per((size_t)n2c * kFeWriters), oWl2 = per((size_t)n2c * kFeWriters);
   const size_t oWc0 = per(n2c), oWc1 = per(n2c), oWc2 = per(n2c);
   hipError_t e = pk.reserve();
-  if (e != hipSuccess) { pk.release(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f = 0; f < F; f++) {
     orbx_keypoint* kc = pk.ptr<orbx_keypoint>(oKc) + (size_t)f * n2c;
     uint8_t* dc = pk.ptr<uint8_t>(oDc) + (size_t)f * n2c * 32;
@@ -1618,14 +1557,10 @@ int proj_fisheye_batch_impl(orbx_extractor* ex, int first_left, int first_right,
       ProjArgs a{};
       const int ns = sd ? nR[f] : nL[f], first = sd ? nL[f] : 0;
       int* sideRes = pk.ptr<int>(oSideRes) + (size_t)f * 4 + 2 * sd;
-      a.grid.k2 = kc + first; a.grid.n2 = ns; a.grid.n1 = 0;
-      a.grid.minX = min_x; a.grid.minY = min_y;
-      a.grid.invW = 64.f / (max_x - min_x);
-      a.grid.invH = 48.f / (max_y - min_y);
-      a.grid.cellStart = pk.ptr<int>(oCs[sd]) + (size_t)f * cs; a.grid.cellItems = pk.ptr<int>(oCi[sd]) + (size_t)f * cap;
-      a.grid.matchedDist = pk.ptr<int>(oMd[sd]) + (size_t)f * cap; a.grid.matches21 = pk.ptr<int>(oM21[sd]) + (size_t)f * cap;
-      a.grid.matches12 = pk.ptr<int>(oM12[sd]) + (size_t)f * 4; a.grid.result = sideRes;
-      a.grid.candOff = pk.ptr<int>(oCo[sd]) + (size_t)f * (nm + 4); a.grid.candCap = 1 << 30;
+      a.grid = grid_block(min_x, min_y, max_x, max_y, kc + first, ns, pk.ptr<int>(oCs[sd]) + (size_t)f * cs,
+                          pk.ptr<int>(oCi[sd]) + (size_t)f * cap, pk.ptr<int>(oMd[sd]) + (size_t)f * cap,
+                          pk.ptr<int>(oM21[sd]) + (size_t)f * cap, pk.ptr<int>(oM12[sd]) + (size_t)f * 4, sideRes,
+                          pk.ptr<int>(oCo[sd]) + (size_t)f * (nm + 4));
       a.desc = dc + (size_t)first * 32; a.uRight = nullptr;   // no mvuRight gate when F.Nleft != -1 (:90, :1667)
       a.scale = pk.ptr<float>(oSf);
       const size_t oP = sd ? oPR : oPL;
@@ -1681,16 +1616,15 @@ int proj_fisheye_batch_impl(orbx_extractor* ex, int first_left, int first_right,
         n_matches[f] = (n_points[f] > 0 && n > 0) ? res[0] : 0;
       }
   }
-  pk.release();
+  pk.release();   // (its device block goes back to the pool before the redo calls)
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f : redo) {   // the one-shot path on a host copy of the frame's two cameras
     const int n = nL[f] + nR[f];
     std::vector<orbx_keypoint> k(std::max(n, 1));
     std::vector<uint8_t> d((size_t)std::max(n, 1) * 32);
-    HIPC(hipMemcpy(k.data(), ex->d_kps.p + (size_t)(first_left + f) * cap, (size_t)nL[f] * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(k.data() + nL[f], ex->d_kps.p + (size_t)(first_right + f) * cap, (size_t)nR[f] * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(d.data(), ex->d_desc.p + (size_t)(first_left + f) * cap * 32, (size_t)nL[f] * 32, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(d.data() + (size_t)nL[f] * 32, ex->d_desc.p + (size_t)(first_right + f) * cap * 32, (size_t)nR[f] * 32, hipMemcpyDeviceToHost));
+    if ((rc = download_frame(ex, first_left + f, nL[f], k.data(), d.data())) != ORBX_OK ||
+        (rc = download_frame(ex, first_right + f, nR[f], k.data() + nL[f], d.data() + (size_t)nL[f] * 32)) != ORBX_OK)
+      return rc;
     uint8_t* occ = occupied + (size_t)f * n2c;
     int32_t* mt = match + (size_t)f * n2c;
     if (occupied_in) std::memcpy(occ, occupied_in + (size_t)f * n2c, n2c); else std::memset(occ, 0, n2c);
@@ -1751,24 +1685,8 @@ int orbx_search_by_projection_fisheye_batch(orbx_extractor* ex, int first_left, 
                                    occupied_in, occupied, match, n_matches);
   }
   if (maxPts && (!map_points || !map_points_right)) return fail(ORBX_E_BADARG, "null map points");
-  // the right camera as a second list of views, exactly as the one-shot call builds it (:141-144)
-  std::vector<orbx_map_point_view> left((size_t)n_frames * st), right((size_t)n_frames * st);
-  for (int f = 0; f < n_frames; f++)
-    for (int i = 0; i < n_map_points[f]; i++) {
-      const size_t o = (size_t)f * st + i;
-      const orbx_map_point_right& r = map_points_right[o];
-      left[o] = map_points[o];
-      right[o] = map_points[o];
-      if ((left[o].in_view && (left[o].predicted_level < 0 || left[o].predicted_level >= nlevels)) ||
-          (r.in_view_r && (r.predicted_level_r < -1 || r.predicted_level_r >= nlevels)))
-        return fail(ORBX_E_BADARG, "map point with a predicted level outside [0, nlevels)");
-      if (!left[o].in_view) left[o].predicted_level = 0;
-      right[o].proj_x = map_points[o].proj_xr;
-      right[o].proj_y = r.proj_yr;
-      right[o].view_cos = r.view_cos_r;
-      right[o].predicted_level = r.predicted_level_r < 0 ? 0 : r.predicted_level_r;
-      right[o].in_view = (r.in_view_r && r.predicted_level_r != -1) ? 1 : 0;
-    }
+  std::vector<orbx_map_point_view> left, right;   // exactly as the one-shot call builds them
+  if ((rc = kb8_view_lists(map_points, map_points_right, n_map_points, n_frames, st, nlevels, left, right)) != ORBX_OK) return rc;
   return proj_fisheye_batch_impl(ex, first_left, first_right, n_frames, min_x, min_y, max_x, max_y, 0, left.data(), right.data(), nullptr,
                                  nullptr, n_map_points, points_stride, th, far_points, th_far_points, nnratio, 0, left_to_right,
                                  right_to_left, occupied_in, occupied, match, n_matches);

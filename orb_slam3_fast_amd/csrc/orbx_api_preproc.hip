@@ -19,7 +19,6 @@ int orbx_cvt_gray(int device, const uint8_t* src, int w, int h, ptrdiff_t src_st
   if (e == hipSuccess) e = launch_cvt_gray(ds.p, w, h, (long long)sp, 0, channels, rgb_order ? 1 : 0, dd.p, (long long)dp, 0, 1, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy2D(dst, (size_t)dst_stride, dd.p, dp, dp, h, hipMemcpyDeviceToHost);
-  ds.free(); dd.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -77,7 +76,6 @@ int orbx_resize_linear(int device, const uint8_t* src, int w, int h, ptrdiff_t s
                               dya.p, 1, nullptr));
   if (e == hipSuccess) chk(hipDeviceSynchronize());
   if (e == hipSuccess) chk(hipMemcpy2D(dst, (size_t)dst_stride, dd.p, dp, dp, dst_h, hipMemcpyDeviceToHost));
-  ds.free(); dd.free(); dxo.free(); dyo.free(); dxa.free(); dya.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -134,7 +132,6 @@ int orbx_remap_linear(int device, const uint8_t* src, int w, int h, ptrdiff_t sr
   if (e == hipSuccess) chk(launch_remap(a, 1, nullptr));
   if (e == hipSuccess) chk(hipDeviceSynchronize());
   if (e == hipSuccess) chk(hipMemcpy2D(dst, (size_t)dst_stride, dd.p, dp, (size_t)dst_w * channels, dst_h, hipMemcpyDeviceToHost));
-  ds.free(); dd.free(); mx.free(); my.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -161,7 +158,6 @@ int orbx_clahe(int device, const uint8_t* src, int w, int h, ptrdiff_t src_strid
   if (e == hipSuccess) chk(launch_clahe(a, 1, cells.p, nullptr));
   if (e == hipSuccess) chk(hipDeviceSynchronize());
   if (e == hipSuccess) chk(hipMemcpy2D(dst, (size_t)dst_stride, dd.p, p, (size_t)w, h, hipMemcpyDeviceToHost));
-  ds.free(); dd.free(); lut.free(); cells.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -188,10 +184,6 @@ struct orbx_preproc {
   int outW = 0, outH = 0;
   const uint8_t* out = nullptr;  // result of the last run (a stage buffer, or the caller's frames when nothing is enabled)
   long long outPitch = 0, outImgPitch = 0;
-  ~orbx_preproc() {
-    d_mapx.free(); d_mapy.free(); d_remapTab.free(); d_xofs.free(); d_yofs.free(); d_xab.free(); d_yab.free(); d_rxtab.free(); d_ryrow.free(); d_ryab.free();
-    d_clahe.free(); d_lut.free(); d_geo.free(); d_gray.free(); d_cells.free();
-  }
 };
 
 int orbx_preproc_create(const orbx_preproc_params* p, int max_batch, int device, orbx_preproc** out) {
@@ -391,7 +383,7 @@ int orbx_preproc_run(orbx_preproc* pp, const uint8_t* frame, ptrdiff_t stride, i
   hipError_t e = ds.alloc(sp * p.src_h * (slot + 1));
   if (e == hipSuccess)
     e = hipMemcpy2D(ds.p + sp * p.src_h * slot, sp, frame, (size_t)stride, (size_t)p.src_w * p.channels, p.src_h, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { ds.free(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   if (slot > 0) (void)hipMemset(ds.p, 0, sp * p.src_h * slot);
   rc = preproc_enqueue(pp, ds.p, slot + 1, (ptrdiff_t)sp, (ptrdiff_t)(sp * p.src_h), nullptr);
   if (rc == ORBX_OK) {
@@ -401,7 +393,6 @@ int orbx_preproc_run(orbx_preproc* pp, const uint8_t* frame, ptrdiff_t stride, i
                       hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(ORBX_E_HIP, hipGetErrorString(e));
   }
-  ds.free();
   return rc;
 }
 
@@ -457,7 +448,6 @@ int orbx_undistort_keypoints(int device, const orbx_keypoint* kps, int n, const 
   if (e == hipSuccess) e = launch_undistort(a, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(out, d.p, (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost);
-  d.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
 }
@@ -482,7 +472,6 @@ int orbx_compute_image_bounds(int device, int cols, int rows, const float K[4], 
   if (e == hipSuccess) e = launch_undistort(a, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(c, d.p, sizeof(c), hipMemcpyDeviceToHost);
-  d.free();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   bounds[0] = std::min(c[0], c[4]);  // mnMinX (:907)
   bounds[2] = std::max(c[2], c[6]);  // mnMaxX

@@ -61,15 +61,23 @@ inline short sat_short(float v) {
 }
 inline int align_up(long long v, int a) { return (int)((v + a - 1) / a * a); }
 
+// Device buffers own their memory: freed by the destructor (or free()), move-only.  None may have static or thread-local
+// storage -- a hipFree at process exit could run after the runtime is gone.
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
-  hipError_t alloc(size_t count) {
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { free(); }
+  hipError_t alloc(size_t count) {   // n records the size only once the allocation has succeeded
     free();
-    n = count;
     if (!count) return hipSuccess;
-    return hipMalloc((void**)&p, count * sizeof(T));
+    const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+    if (e == hipSuccess) n = count;
+    else p = nullptr;
+    return e;
   }
   hipError_t grow(size_t count) { return count <= n ? hipSuccess : alloc(count); }   // keeps a large enough buffer
   void free() {
@@ -131,12 +139,17 @@ template <class T>
 struct ScratchBuf {  // same face as DevBuf; the caller has made its device current (set_device)
   T* p = nullptr;
   size_t n = 0, cls = 0;
+  ScratchBuf() = default;
+  ScratchBuf(const ScratchBuf&) = delete;
+  ScratchBuf& operator=(const ScratchBuf&) = delete;
+  ~ScratchBuf() { free(); }
   hipError_t alloc(size_t count) {
     free();
-    n = count;
     if (!count) return hipSuccess;
     p = static_cast<T*>(ScratchPool::take(count * sizeof(T), &cls));
-    return p ? hipSuccess : hipErrorOutOfMemory;
+    if (!p) return hipErrorOutOfMemory;
+    n = count;
+    return hipSuccess;
   }
   void free() {
     if (p) ScratchPool::give(p, cls);
@@ -194,6 +207,10 @@ class Pack {
     if (*e == hipSuccess) pending_ = false;
     return h;
   }
+  Pack() = default;
+  Pack(const Pack&) = delete;
+  Pack& operator=(const Pack&) = delete;
+  ~Pack() { release(); }
   void release() {  // an error path may leave the upload in flight: the staging buffer is reused by the thread's next call
     if (pending_) (void)hipStreamSynchronize(nullptr);
     pending_ = false;
@@ -347,5 +364,20 @@ namespace orbx_host {
 // the whole extraction pipeline of n device-resident images on ex->stream (orbx_api.hip)
 int enqueue_extract(orbx_extractor* ex, const uint8_t* d_images, int n, int w, int h, ptrdiff_t row_pitch,
                     ptrdiff_t image_pitch, const int32_t* lap);
+
+// The preamble of the batched entries: the keypoint counts of images [first, first + F) of the handle's last batch live on
+// the device; waits for the handle's stream, copies them into n and clamps each to [0, outCap].  *maxN: the largest count.
+inline int batch_counts(orbx_extractor* ex, int first, int F, std::vector<int>& n, int* maxN = nullptr) {
+  n.resize(F);
+  HIPC(hipStreamSynchronize(ex->stream));
+  HIPC(hipMemcpy(n.data(), ex->d_nOut.p + first, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  int m = 0;
+  for (int& c : n) {
+    c = std::min(std::max(c, 0), ex->gmax.outCap);
+    m = std::max(m, c);
+  }
+  if (maxN) *maxN = m;
+  return ORBX_OK;
+}
 }  // namespace orbx_host
 #endif

@@ -273,7 +273,7 @@ int run_frames(const std::vector<typename ArgsOf<Frame>::type>& proto, const std
   for (int f = 0; f < F; f++)
     if ((int)fe[f].idx.size() > kLdsEdges) oStage[f] = pk.add(nullptr, fe[f].idx.size() * 2 * sizeof(float4));
   hipError_t e = pk.reserve();
-  if (e != hipSuccess) { pk.release(); return fail(ORBX_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   for (int f = 0; f < F; f++) {
     Args& a = args[f];
     a.eidx = pk.ptr<int>(oIdx[f]);
@@ -307,7 +307,6 @@ int run_frames(const std::vector<typename ArgsOf<Frame>::type>& proto, const std
       }
     }
   }
-  pk.release();
   if (rc != ORBX_OK) return rc;
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   return ORBX_OK;
@@ -370,14 +369,13 @@ int orbx_pose_optimization_batch(orbx_extractor* ex, int first_image, int n_fram
     if (has_point[r] && !finite3(world_pos + 3 * r)) return fail(ORBX_E_BADARG, "world position not finite");
   int rc = set_device(ex->device);
   if (rc != ORBX_OK) return rc;
-  std::vector<int> n2(F);
-  HIPC(hipStreamSynchronize(ex->stream));
-  HIPC(hipMemcpy(n2.data(), ex->d_nOut.p + first_image, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> n2;
+  rc = batch_counts(ex, first_image, F, n2);
+  if (rc != ORBX_OK) return rc;
   std::vector<FrameEdges> fe(F);
   std::vector<PoseArgs> proto(F);
   for (int f = 0; f < F; f++) {
-    const int n = std::min(std::max(n2[f], 0), cap);
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n2[f]; i++) {
       const size_t r = (size_t)f * cap + i;
       if (!has_point[r]) continue;
       fe[f].idx.push_back(i);
@@ -451,15 +449,13 @@ int orbx_pose_optimization_fisheye_batch(orbx_extractor* ex, int first_left, int
     if (!finite_kb8_frame(frames[f], rig)) return fail(ORBX_E_BADARG, "pose, KB8 parameters or Trl not finite (or a zero quaternion)");
   int rc = set_device(ex->device);
   if (rc != ORBX_OK) return rc;
-  std::vector<int> nL(F), nR(F, 0);
-  HIPC(hipStreamSynchronize(ex->stream));
-  HIPC(hipMemcpy(nL.data(), ex->d_nOut.p + first_left, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-  if (rig) HIPC(hipMemcpy(nR.data(), ex->d_nOut.p + first_right, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> nL, nR(F, 0);
+  rc = batch_counts(ex, first_left, F, nL);
+  if (rc == ORBX_OK && rig) rc = batch_counts(ex, first_right, F, nR);
+  if (rc != ORBX_OK) return rc;
   std::vector<FrameEdges> fe(F);
   std::vector<PoseArgsKb8> proto(F);
   for (int f = 0; f < F; f++) {
-    nL[f] = std::min(std::max(nL[f], 0), cap);
-    nR[f] = std::min(std::max(nR[f], 0), cap);
     for (int i = 0; i < nL[f] + nR[f]; i++) {   // row = [left keypoints | right keypoints], as the fisheye matchers write it
       const size_t r = f * row + i;
       if (!has_point[r]) continue;
