@@ -63,6 +63,8 @@ __device__ __forceinline__ orbx_h2 pk_max3(orbx_h2 a, orbx_h2 b, orbx_h2 c) {
 // the pair -- centre, ring 0 / 8 (rows 6 / 0, same columns), ring 4 / 12 (row 3, columns +3 / -3) -- are spread from the row
 // dwords by one v_perm each ([b, 0, b', 0] = two f16 subnormal patterns), then 6 packed min / max, two packed subtractions, one
 // packed max and two compares: 16 instructions per pair instead of 20.  M' = max(hiMin - c, c - loMax) > t, exact like stage 2.
+// th2 is per lane (round 8): a pixel outside the detectable window carries the pattern 0x7C00 | t (inf or NaN), so M' > th is false
+// and the ballots need no scalar masking for the row's last quad or the idle lanes.
 template <int P>
 __device__ __forceinline__ void compass_pair(const uint32_t (&r)[7][3], orbx_h2 th2, uint64_t& m0, uint64_t& m1) {
   auto spread = [&](int row, int b) {  // bytes b, b + 1 of the 12-byte row -> (f16 pattern, f16 pattern)
@@ -292,12 +294,24 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
   // a round of 64 quads advances a lane by dq rows and rq quads (no division per round)
   const int dq = __builtin_amdgcn_readfirstlane((int)(64.5f * inv_qpr)), rq = 64 - dq * qpr;
   const int vlast = dw - 4 * (qpr - 1);  // pixels of a row's last quad inside the detectable window (1..4)
-  const uint64_t keep1 = vlast > 1 ? ~0ull : 0ull, keep2 = vlast > 2 ? ~0ull : 0ull, keep3 = vlast > 3 ? ~0ull : 0ull;
   const int yd0 = (int)(((float)lane + 0.5f) * inv_qpr), j0 = lane - __mul24(yd0, qpr);
   const int nScore16 = (SPd * (dh + 2) + 3) >> 2;
+  // Stage-1 masks, all loop invariant (round 8).  Per lane: the compass threshold of a pixel outside the window is raised to inf / NaN
+  // (kill patterns ORed into t): the pixels of a row's last quad past vlast, and with kRowRounds the lanes past dq whole rows.  Per
+  // round: only the last round masks lanes (actLast, one SGPR pair), every other round takes the ballots as they are.
+  // ceil(dh / dq) = floor((dh - 0.5) / dq) + 1 rounds; as a quad count, so that one loop serves both schemes
+  const int nRounds = kRowRounds ? ((int)(((float)dh - 0.5f) * __builtin_amdgcn_rcpf((float)dq)) + 1) * 64 : nq;
+  const int lastQb = (nRounds - 1) & ~63;
+  const uint64_t actLast = low_lanes_pos(kRowRounds ? (dh - (lastQb >> 6) * dq) * qpr : nq - lastQb);
+  const uint32_t killLastA = (vlast > 1 ? 0u : 0x7C000000u), killLastB = (vlast > 2 ? 0u : 0x7C00u) | (vlast > 3 ? 0u : 0x7C000000u);
+  uint32_t killA = 0, killB = 0;   // kRowRounds: the lane's quad is the same in every round
+  if (kRowRounds) {
+    if (lane >= dq * qpr) killA = killB = 0x7C007C00u;
+    else if (j0 == qpr - 1) killA = killLastA, killB = killLastB;
+  }
   for (int pass = 0; pass < 2; pass++) {
     const int t = pass == 0 ? g.iniTh : g.minTh;
-    const orbx_h2 tc2 = __builtin_bit_cast(orbx_h2, (uint32_t)t * 0x00010001u);  // t as two f16 subnormal patterns
+    const uint32_t tc2 = (uint32_t)t * 0x00010001u;  // t as two f16 subnormal patterns
     // clear the score tile (16-byte stores; its zero ring is part of it).  The barrier also publishes the image tile.
     for (int i = lane; i < nScore16; i += 64) reinterpret_cast<uint4*>(score)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
@@ -316,32 +330,36 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
       const _Float16 th = __builtin_bit_cast(_Float16, (unsigned short)t);  // t in the same subnormal encoding
       const int s0 = nList;
       const int nSurv = sEnd - s0;
-      for (int base = 0; base < nSurv; base += 128) {  // two survivors per lane, one after the other
-        const int rem = nSurv - base;
-        const uint64_t vA = low_lanes(rem), vB = low_lanes(rem - 64);
+      // a corner's score and list entry.  A corner has M > t >= 0: the pattern is the integer; (y + 1) * pitch + x + 4: same pitch
+      // as the image tile.  Its entry goes to nList + k <= the position of the survivor it replaces; past cornerCap it is dropped
+      // (the NMS then scans the score tile).
+      auto emit = [&](uint64_t m, int o, _Float16 M) {
+        if (__builtin_amdgcn_inverse_ballot_w64(m)) {  // this lane's bit of the SGPR mask, without a 64-bit vector shift
+          score8[o + SPB + 4] = (uint8_t)(__builtin_bit_cast(unsigned short, M) - 1);
+          const int k = prefix_count(m);
+          if (k < cornerCap - nList) (list + nList)[k] = (uint16_t)o;
+        }
+        nList += __popcll(m);
+      };
+      // Two survivors per lane, one after the other.  The FIRST pass takes the odd ((nSurv - 1) mod 128) + 1 survivors, so that it is
+      // the only pass with idle lanes and its lane masks are set once per flush (round 8; the corners still come out in survivor
+      // order, each behind the survivors already read).
+      int n = ((nSurv - 1) & 127) + 1;
+      uint64_t vA = low_lanes(n), vB = low_lanes(n - 64);
+      for (int base = 0; base < nSurv; base += n, n = 128, vA = vB = ~0ull) {
         // a list entry IS the tile byte offset y * TP + x of the pixel's 7x7 window corner (image and score tile share the
         // pitch): no unpacking of (y, x) and no multiply per survivor / corner; (x, y) is only recovered when a corner is emitted
-        const int oA = list[s0 + min(base + lane, nSurv - 1)], oB = list[s0 + min(base + 64 + lane, nSurv - 1)];
-        // one survivor per lane and network, both polarities in its halves (fast_contrast_lds); a last pass of <= 64 survivors
+        // (indexed from the pass's first survivor, a scalar: one v_min and one address per network)
+        const uint16_t* sl = list + s0 + base;
+        const int lastI = nSurv - 1 - base;
+        const int oA = sl[min(lane, lastI)], oB = sl[min(lane + 64, lastI)];
+        // one survivor per lane and network, both polarities in its halves (fast_contrast_lds); a pass of <= 64 survivors
         // runs one network only
         const _Float16 MA = fast_contrast_lds(tile8 + oA, TP);
-        const uint64_t mA = __ballot(MA > th) & vA;
-        if (__builtin_amdgcn_inverse_ballot_w64(mA)) {
-          // a corner has M > t >= 0: the pattern is the integer.  (y + 1) * pitch + x + 4: same pitch as the image tile
-          score8[oA + SPB + 4] = (uint8_t)(__builtin_bit_cast(unsigned short, MA) - 1);
-          const int k = prefix_count(mA);  // nList + k <= the position of the survivor it replaces
-          if (k < cornerCap - nList) (list + nList)[k] = (uint16_t)oA;
-        }
-        nList += __popcll(mA);
-        if (rem > 64) {
+        emit(__ballot(MA > th) & vA, oA, MA);
+        if (n > 64) {
           const _Float16 MB = fast_contrast_lds(tile8 + oB, TP);
-          const uint64_t mB = __ballot(MB > th) & vB;
-          if (__builtin_amdgcn_inverse_ballot_w64(mB)) {
-            score8[oB + SPB + 4] = (uint8_t)(__builtin_bit_cast(unsigned short, MB) - 1);
-            const int k = prefix_count(mB);
-            if (k < cornerCap - nList) (list + nList)[k] = (uint16_t)oB;
-          }
-          nList += __popcll(mB);
+          emit(__ballot(MB > th) & vB, oB, MB);
         }
       }
       if (nList > cornerCap) {
@@ -356,23 +374,23 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     // clamp, the last-quad mask is loop invariant; 1 .. 4 lanes idle (9 / 10 / 12 quads per row: 63 / 60 / 60 lanes).  Otherwise
     // the quads are dealt to the lanes flat.  Lanes past the window read rows below the tile (still this block's LDS: masked).
     int yd = yd0, j = j0;
-    int q0r = __mul24(yd0, TPd) + j0;
-    const uint64_t notLastR = ~__ballot(j0 == qpr - 1);
-    // ceil(dh / dq) = floor((dh - 0.5) / dq) + 1; as a quad count, so that one loop serves both schemes
-    const int nRounds = kRowRounds ? ((int)(((float)dh - 0.5f) * __builtin_amdgcn_rcpf((float)dq)) + 1) * 64 : nq;
+    int yxr = (__mul24(yd0, TPd) + j0) << 2;   // kRowRounds: the lane's quad as a tile byte offset
+    const uint32_t thRA = tc2 | killA, thRB = tc2 | killB;   // kRowRounds: the per-lane thresholds of every round
+    const uint32_t thLA = tc2 | killLastA, thLB = tc2 | killLastB;
     for (int qb = 0; qb < nRounds; qb += 64) {
-      uint64_t actM;
-      int q0;
+      int yx;   // tile byte offset of the quad's first pixel window (a multiple of 4: | pI adds the pixel)
+      uint32_t thA, thB;
       if (kRowRounds) {
-        actM = low_lanes_pos(min(dq, dh - (qb >> 6) * dq) * qpr);
-        q0 = q0r;
-        q0r += dq * TPd;
+        yx = yxr;
+        yxr += dq * TP;
+        thA = thRA, thB = thRB;
       } else {
-        actM = low_lanes_pos(nq - qb);
         const int ydc = min(yd, dh - 1);  // idle lanes of the last round stay inside the tile (masked out below)
-        q0 = __mul24(ydc, TPd) + j;       // (24-bit multiplies are full rate, v_mul_lo_u32 a quarter)
+        yx = (__mul24(ydc, TPd) + j) << 2;  // (24-bit multiplies are full rate, v_mul_lo_u32 a quarter)
+        const bool lastQ = j == qpr - 1;  // a row's last quad may reach past the detectable window
+        thA = lastQ ? thLA : tc2, thB = lastQ ? thLB : tc2;
       }
-      const uint32_t* row0 = tile + q0;
+      const uint32_t* row0 = reinterpret_cast<const uint32_t*>(tile8 + yx);
       uint32_t r[7][3];
 #pragma unroll
       for (int i = 0; i < 7; i++) {
@@ -380,17 +398,17 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
         r[i][1] = row0[i * TPd + 1];
         r[i][2] = row0[i * TPd + 2];
       }
-      const uint64_t notLast = kRowRounds ? notLastR : ~__ballot(j == qpr - 1);  // a row's last quad may reach past the detectable window
       uint64_t sm[4];
-      compass_pair<0>(r, tc2, sm[0], sm[1]);
-      compass_pair<2>(r, tc2, sm[2], sm[3]);
-      sm[0] &= actM;
-      sm[1] &= actM & (notLast | keep1);
-      sm[2] &= actM & (notLast | keep2);
-      sm[3] &= actM & (notLast | keep3);
-      // flush first when this round's survivors (<= 256) would not fit: the list then only needs room for a typical cell
-      if (sEnd + (int)(__popcll(sm[0]) + __popcll(sm[1]) + __popcll(sm[2]) + __popcll(sm[3])) > listTotal) flush_survivors();
-      const int yx = q0 << 2;   // tile byte offset of the quad's first pixel window (a multiple of 4: | pI adds the pixel)
+      compass_pair<0>(r, __builtin_bit_cast(orbx_h2, thA), sm[0], sm[1]);
+      compass_pair<2>(r, __builtin_bit_cast(orbx_h2, thB), sm[2], sm[3]);
+      if (qb == lastQb) {
+#pragma unroll
+        for (int pI = 0; pI < 4; pI++) sm[pI] &= actLast;
+      }
+      // the round's survivor count, once: the flush test and the list end.  Flush first when this round's survivors (<= 256) would
+      // not fit: the list then only needs room for a typical cell
+      const int nRound = (int)(__popcll(sm[0]) + __popcll(sm[1]) + __popcll(sm[2]) + __popcll(sm[3]));
+      if (sEnd + nRound > listTotal) flush_survivors();
       // ROW-MAJOR list order (second half of round 4): a survivor goes behind the survivors of the lower lanes -- all four pixels of
       // their quads: one chain of four mbcnt pairs -- and behind the lane's own lower pixels (a pointer bumped under the pixel's
       // lane mask).  The per-pixel segments of rounds 1 - 4 (all pixel-0 survivors of the round's seven rows, then all pixel-1 ...)
@@ -404,13 +422,12 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
       uint16_t* wp = list + sEnd + below;
 #pragma unroll
       for (int pI = 0; pI < 4; pI++) {
-        const uint64_t m = sm[pI];
-        if (__builtin_amdgcn_inverse_ballot_w64(m)) {  // this lane's bit of the SGPR mask, without a 64-bit vector shift
+        if (__builtin_amdgcn_inverse_ballot_w64(sm[pI])) {  // this lane's bit of the SGPR mask, without a 64-bit vector shift
           *wp = (uint16_t)(yx | pI);
           wp++;
         }
-        sEnd += __popcll(m);
       }
+      sEnd += nRound;
       if (!kRowRounds) {
         j += rq;
         yd += dq;
