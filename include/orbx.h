@@ -861,6 +861,66 @@ int orbx_pose_optimization_fisheye_batch(orbx_extractor* ex, int first_left, int
                                          int32_t* n_good, int32_t* n_trials);
 
 
+/* ---- two-view reconstruction (monocular initialisation) ----------------------------------------------- */
+
+/* TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:42-136; Tracking::MonocularInitialization, src/Tracking.cc:
+ * 2451, through Pinhole::ReconstructWithTwoViews): `iterations` RANSAC hypotheses each for a homography and a fundamental
+ * matrix from the same 8-point sets, scored on every match (CheckHomography / CheckFundamental), model selection by
+ * RH = SH / (SH + SF), motion decomposition (ReconstructH: Faugeras' eight hypotheses; ReconstructF: DecomposeE's four) and
+ * CheckRT (linear triangulation, cheirality, reprojection and parallax gates) -- all on the device, five launches for any
+ * number of pairs.  Per-match arithmetic is float in the reference's expression order; the null vectors and the 3 x 3 SVDs are
+ * solved in double (one-sided Jacobi) and narrowed, so results agree with the reference to rounding, not bit for bit
+ * ("Two-view reconstruction").  Deterministic: fixed reduction trees, the same bits on every run, and pair f of
+ * the batch entry gives the bits of the one-shot entry on the same data.
+ *
+ * Deliberate differences from the reference:
+ *  - the 8-point index sets are an INPUT (`sets`, [iterations][8] indices into the match list = the (i, matches12[i]) with
+ *    matches12[i] >= 0 in ascending i).  The reference draws them with rand() seeded once per process, so they are no function
+ *    of the inputs; csrc/TwoViewReconstruction.h and the Python wrapper draw them the reference's way from the host's libc.
+ *  - ReconstructH never assigns vP3D on success in the reference (:774-780; the caller reads a stale mvIniP3D); here the
+ *    winning hypothesis' points are returned for both models and `model` reports which one won.
+ *  - the RH threshold is the parameter rh_threshold (reference: 0.50; its comment names 0.40 - 0.45).
+ *  - fewer than 8 matches (the reference indexes an empty vector): ok = 0 with n_matches set, p3d / triangulated zeroed,
+ *    `sets` not read.  Whenever ok = 0, p3d and triangulated are zeroed (the reference leaves them untouched).
+ *  - a set index outside [0, n_matches) or repeated within its set is ORBX_E_BADARG.
+ *  - keypoints are undistorted pinhole keypoints (mvKeysUn) and K a pinhole matrix: KannalaBrandt8::ReconstructWithTwoViews
+ *    (src/CameraModels/KannalaBrandt8.cpp:186-219) runs cv::fisheye::undistortPoints first, which stays with the caller. */
+typedef struct orbx_two_view_params {
+  float fx, fy, cx, cy;  /* mK */
+  float sigma;           /* mSigma (1.0 in the reference) */
+  float rh_threshold;    /* 0.50f in the reference */
+  int32_t iterations;    /* mMaxIterations (200), in [1, 4096] */
+} orbx_two_view_params;
+typedef struct orbx_two_view_result { /* one per pair */
+  int32_t ok;             /* Reconstruct's return value */
+  int32_t model;          /* 0 = homography, 1 = fundamental (valid when score_h + score_f != 0) */
+  int32_t best_h, best_f; /* winning hypothesis index per model, -1 when every score was 0 */
+  float score_h, score_f; /* SH, SF */
+  int32_t n_matches;      /* N */
+  int32_t n_inliers;      /* inliers of the chosen model's winning hypothesis */
+  int32_t n_good;         /* nGood of the chosen motion hypothesis */
+  float parallax;         /* its parallax, degrees */
+  float q[4], t[3];       /* T21 as Sophus stores it (x y z w, t), valid when ok */
+} orbx_two_view_result;
+/* One pair from host arrays.  kps1 / kps2: n1 / n2 undistorted keypoints, each count in [0, 15000]; matches12: n1 entries in
+ * [-1, n2); sets: [iterations][8]; p3d ([n1][3], frame-1 camera coordinates) and triangulated ([n1]) are indexed by frame-1
+ * keypoint like vP3D / vbTriangulated, entries of unmatched keypoints are 0; hyp_scores (may be NULL): [2][iterations], every
+ * hypothesis' score, homography then fundamental.  All arguments are validated before a device is touched; valid arguments
+ * without a device return ORBX_E_NODEVICE (there is no host path). */
+int orbx_reconstruct_two_views(int device, const orbx_keypoint* kps1, int n1, const orbx_keypoint* kps2, int n2,
+                               const int32_t* matches12, const int32_t* sets, const orbx_two_view_params* params,
+                               orbx_two_view_result* result, float* p3d, uint8_t* triangulated, float* hyp_scores);
+/* n_frames pairs in the layout orbx_search_for_initialization_batch produces: frame 2 of pair f = image first_image + f of the
+ * handle's last batch (its keypoints, taken as mvKeysUn, stay on the device), frame 1 = kps1[f * stride ...) with n1[f]
+ * keypoints, matches12 [n_frames][stride] as that call wrote it, sets [n_frames][iterations][8], results [n_frames],
+ * p3d [n_frames][stride][3], triangulated [n_frames][stride], hyp_scores (may be NULL) [n_frames][2][iterations].  One upload,
+ * one chain of five launches for all pairs, one download. */
+int orbx_reconstruct_two_views_batch(orbx_extractor* ex, int first_image, int n_frames, const orbx_keypoint* kps1,
+                                     const int32_t* n1, int stride, const int32_t* matches12, const int32_t* sets,
+                                     const orbx_two_view_params* params, orbx_two_view_result* results, float* p3d,
+                                     uint8_t* triangulated, float* hyp_scores);
+
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 
 /* Per-kernel timing with HIP events recorded on the handle's own stream around every kernel launch (the

@@ -104,6 +104,8 @@ def lib():
         L.orbx_pose_optimization_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
         L.orbx_pose_optimization_kb8.argtypes = [i, vp, i, i, vp, vp, vp, i, vp, vp]
         L.orbx_pose_optimization_fisheye_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        L.orbx_reconstruct_two_views.argtypes = [i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
+        L.orbx_reconstruct_two_views_batch.argtypes = [vp, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
                                         C.POINTER(i), vp, vp, vp]
         L.orbx_bf_knn2.argtypes = [i, vp, i, vp, i, vp, vp, vp]
@@ -761,6 +763,102 @@ def PoseOptimizationBatch(ex, first_image, n_frames, worldPos, hasPoint, q, t, c
                                               _p(out), _p(ng), _p(tr)))
     res = (ng, fr["q"].copy(), fr["t"].copy(), out.astype(bool))
     return res + (tr,) if want_trials else res
+
+
+TWO_VIEW_PARAMS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("sigma", "<f4"),
+                                  ("rh_threshold", "<f4"), ("iterations", "<i4")])
+TWO_VIEW_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("model", "<i4"), ("best_h", "<i4"), ("best_f", "<i4"), ("score_h", "<f4"),
+                                  ("score_f", "<f4"), ("n_matches", "<i4"), ("n_inliers", "<i4"), ("n_good", "<i4"),
+                                  ("parallax", "<f4"), ("q", "<f4", (4,)), ("t", "<f4", (3,))])
+assert TWO_VIEW_PARAMS_DTYPE.itemsize == 28 and TWO_VIEW_RESULT_DTYPE.itemsize == 68  # orbx_two_view_params / _result
+
+_libc = None
+
+
+def ransac_sets(n_matches, iterations=200, seed_once=True):
+    """The 8-point index sets of TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:69-96) drawn the reference's
+    way from the host's libc: DUtils::Random::SeedRandOnce(0) (srand(0) on the first call of the process only; seed_once=False
+    skips it), RandomInt(0, d - 1) = int(((double)rand() / ((double)RAND_MAX + 1.0)) * d), swap-with-back removal.
+    Returns [iterations][8] int32 indices into the match list; n_matches < 8 returns zeros (the library does not read them)."""
+    global _libc
+    if _libc is None:
+        _libc = C.CDLL(None)
+        _libc.rand.restype = C.c_int
+        _libc.srand.argtypes = [C.c_uint]
+        if seed_once:
+            _libc.srand(0)
+    sets = np.zeros((iterations, 8), np.int32)
+    if n_matches < 8:
+        return sets
+    rand_max = 2147483647  # glibc RAND_MAX
+    for it in range(iterations):
+        avail = list(range(n_matches))
+        for j in range(8):
+            d = len(avail)
+            randi = int((float(_libc.rand()) / (float(rand_max) + 1.0)) * d)
+            sets[it, j] = avail[randi]
+            avail[randi] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def _two_view_params(K, sigma, iterations, rh_threshold):
+    prm = np.zeros(1, TWO_VIEW_PARAMS_DTYPE)
+    K = np.asarray(K, np.float32)
+    prm["fx"], prm["fy"], prm["cx"], prm["cy"] = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.ndim == 2 else K[:4]
+    prm["sigma"], prm["rh_threshold"], prm["iterations"] = sigma, rh_threshold, iterations
+    return prm
+
+
+def ReconstructWithTwoViews(vKeys1, vKeys2, vMatches12, K, sets=None, sigma=1.0, iterations=200, rh_threshold=0.5,
+                            want_scores=False, device=0):
+    """Pinhole::ReconstructWithTwoViews = TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc) on the GPU
+    (orbx_reconstruct_two_views).  vKeys1 / vKeys2 = mvKeysUn of the initial and the current frame (KP_DTYPE), vMatches12 [n1]
+    (-1: unmatched), K = 3 x 3 pinhole matrix or (fx, fy, cx, cy), sets = [iterations][8] indices into the match list
+    (None: ransac_sets).  Returns (ok, q, t, vP3D [n1][3], vbTriangulated [n1], result record[, hyp_scores [2][iterations]])."""
+    k1, k2 = np.ascontiguousarray(vKeys1, KP_DTYPE), np.ascontiguousarray(vKeys2, KP_DTYPE)
+    m = np.ascontiguousarray(vMatches12, np.int32).reshape(len(k1))
+    if sets is None:
+        sets = ransac_sets(int((m >= 0).sum()), iterations)
+    st = np.ascontiguousarray(sets, np.int32).reshape(iterations, 8)
+    prm = _two_view_params(K, sigma, iterations, rh_threshold)
+    res = np.zeros(1, TWO_VIEW_RESULT_DTYPE)
+    p3d = np.zeros((len(k1), 3), np.float32)
+    tri = np.zeros(len(k1), np.uint8)
+    sc = np.zeros((2, iterations), np.float32)
+    _check(lib().orbx_reconstruct_two_views(int(device), _p(k1), len(k1), _p(k2), len(k2), _p(m), _p(st), _p(prm), _p(res), _p(p3d),
+                                            _p(tri), _p(sc) if want_scores else None))
+    r = res[0]
+    out = (bool(r["ok"]), r["q"].copy(), r["t"].copy(), p3d, tri.astype(bool), r)
+    return out + (sc,) if want_scores else out
+
+
+def ReconstructWithTwoViewsBatch(ex, first_image, vKeys1, vMatches12, K, sets=None, sigma=1.0, iterations=200, rh_threshold=0.5,
+                                 want_scores=False):
+    """ReconstructWithTwoViews for the frames of ex's last extraction batch in one call (orbx_reconstruct_two_views_batch), in
+    the layout of ORBmatcher.SearchForInitializationBatch: pair f = (vKeys1[f], image first_image + f), vMatches12[f] as that
+    call returned it, sets[f] [iterations][8] (None: ransac_sets per pair, in pair order).  Returns (results
+    [F] TWO_VIEW_RESULT_DTYPE, list of vP3D, list of vbTriangulated[, hyp_scores [F][2][iterations]])."""
+    F = len(vKeys1)
+    n1 = np.array([len(k) for k in vKeys1], np.int32)
+    stride = max(int(n1.max()) if F else 0, 1)
+    Kp = np.zeros((F, stride), KP_DTYPE)
+    M = np.full((F, stride), -1, np.int32)
+    for f in range(F):
+        Kp[f, :n1[f]] = vKeys1[f]
+        M[f, :n1[f]] = np.asarray(vMatches12[f], np.int32)
+    if sets is None:
+        sets = [ransac_sets(int((M[f] >= 0).sum()), iterations) for f in range(F)]
+    st = np.ascontiguousarray(np.asarray(sets, np.int32).reshape(F, iterations, 8))
+    prm = _two_view_params(K, sigma, iterations, rh_threshold)
+    res = np.zeros(F, TWO_VIEW_RESULT_DTYPE)
+    p3d = np.zeros((F, stride, 3), np.float32)
+    tri = np.zeros((F, stride), np.uint8)
+    sc = np.zeros((F, 2, iterations), np.float32)
+    _check(lib().orbx_reconstruct_two_views_batch(ex._h, int(first_image), F, _p(Kp), _p(n1), stride, _p(M), _p(st), _p(prm),
+                                                  _p(res), _p(p3d), _p(tri), _p(sc) if want_scores else None))
+    out = (res, [p3d[f, :n1[f]].copy() for f in range(F)], [tri[f, :n1[f]].astype(bool) for f in range(F)])
+    return out + (sc,) if want_scores else out
 
 
 def _pose_frames_kb8(q, t, cam_left, cam_right, trl_q, trl_t, n_frames):
