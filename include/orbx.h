@@ -735,7 +735,12 @@ typedef struct orbx_map_point_right {
  * + mOw) for the right one, computed by the caller in float -- plus that camera's eight KB8 parameters.  The views of both
  * cameras stay on the device for orbx_search_by_projection_fisheye_batch(map_points = NULL, map_points_right = NULL); views_out /
  * views_right_out (may be NULL) receive host copies in the matcher's input form ([n_frames][n] each).  Tolerance parity (device
- * atan2f / cosf / sinf / logf). */
+ * atan2f / cosf / sinf / logf).
+ * track_depth (mTrackDepth, the distance |Pc| in the LEFT camera) is written for points the left camera accepts and is 0 for every
+ * other point, also for one that only the right camera sees: the reference leaves mTrackDepth of such a point at whatever an
+ * earlier frame wrote (src/Frame.cc:1394-1400 set it in the left branch only), so its bFarPoints gate (src/ORBmatcher.cc:57) reads
+ * a stale value there; here the gate never culls a right-only point.  A caller that wants the host-fed behaviour passes its own
+ * mTrackDepth through orbx_search_by_projection_fisheye_batch's map_points.  tests/test_projection_device.py pins the 0. */
 typedef struct orbx_frame_pose_kb8 {
   float R[9], t[3], twc[3], kb8[8];
 } orbx_frame_pose_kb8;
@@ -991,6 +996,24 @@ void orbx_debug_set_clahe_cell_kernel(int on);
  * every 128 x 8 output tile staged through LDS (k_remap_lds) where the plan's maps allow it, 0 = the per-thread window
  * gathers (k_remap1) everywhere. */
 void orbx_debug_set_remap_lds(int on);
+/* The footprint table of k_remap_lds as orbx_preproc_create builds it for these maps (n_maps maps of out_h rows of map_stride
+ * floats each, one behind the other): per map and 128 x 8 output tile -- entry ((map * tiles_x) + tile_x) * tiles_y + tile_y --
+ * eight ints {x0a, y0, 16-byte pieces per row, rows, ceil(2^32 / pieces), 0, 0, 0}: the source rectangle
+ * [x0a, x0a + 16 * pieces) x [y0, y0 + rows) the workgroup stages.  Host only: touches no device and works without one.
+ * Returns 1 when a table was built (n_maps * tiles_x * tiles_y entries copied to table), 0 when the plan would keep k_remap1
+ * (a tile needs more than 256 pieces, src_w < 32 or src_w % 16 != 0; table untouched), ORBX_E_CAPACITY when cap (in ints) is
+ * too small (table untouched), ORBX_E_BADARG on bad arguments.  tiles_x / tiles_y (may be NULL) receive the tile grid. */
+int orbx_debug_remap_footprints(const float* map_x, const float* map_y, ptrdiff_t map_stride, int out_w, int out_h, int src_w,
+                                int src_h, int n_maps, int32_t* table, int cap, int32_t* tiles_x, int32_t* tiles_y);
+/* What a pre-processing plan decided at creation and what its LAST enqueue (orbx_preproc_run / _run_device,
+ * orbx_extract_batch_raw_device) launched, from the expressions that pick the launch:
+ *   info[0] k_remap_lds table built (0 / 1)          info[1] single-channel resize fast path prepared (0 / 1)
+ *   info[2] remap form: 2 = k_remap_lds, 1 = k_remap1, 0 = k_remap      info[3] resize form: 1 = plain (the pyramid's k_resize),
+ *   0 = generic          info[4] CLAHE read its source with dword loads (srcVec4, 0 / 1)
+ *   info[5] 16-pixel segments per row of the gray pass (0 = the per-pixel kernel only)
+ *   info[6] frames of the last enqueue (0 = none yet)                  info[7] 0
+ * info[2..5] are -1 for a stage that is not part of the plan or has not run. */
+int orbx_debug_preproc_plan(const orbx_preproc* pp, int32_t info[8]);
 /* Test hook of the pyramid's fused small-level launches (k_resize_tail: up to three consecutive levels of
  * ComputePyramid, src/ORBextractor.cc:1108-1145, per launch).  first_level: -1 = the library's policy, 0 = no fusion (every
  * level through k_resize), >= 2 = fuse from that level on; max_levels / band_rows: levels per launch and rows of the last

@@ -191,6 +191,8 @@ def lib():
         L.orbx_debug_upload_results.argtypes = [vp, i, vp, vp, i, i]
         L.orbx_debug_set_remap_lds.argtypes = [i]
         L.orbx_debug_set_remap_lds.restype = None
+        L.orbx_debug_remap_footprints.argtypes = [vp, vp, C.c_ssize_t, i, i, i, i, i, vp, i, C.POINTER(i), C.POINTER(i)]
+        L.orbx_debug_preproc_plan.argtypes = [vp, vp]
         L.orbx_debug_set_resize_tail.argtypes = [i, i, i]
         L.orbx_debug_set_resize_tail.restype = None
         L.orbx_debug_resize_plan.argtypes = [vp, vp, vp, vp, i]
@@ -1082,6 +1084,39 @@ class Preproc:
         _check(lib().orbx_preproc_run_device(self._h, C.c_void_p(d_frames_ptr), n_frames, row_pitch, image_pitch, C.byref(out),
                                              C.byref(w), C.byref(h), C.byref(rp), C.byref(ip)))
         return out.value, w.value, h.value, rp.value, ip.value
+
+    def plan(self):
+        """What the handle decided at creation and what its last enqueue launched (orbx_debug_preproc_plan); remap / resize /
+        clahe_vec4 / gray_segs are None for a stage that is not part of the plan or has not run."""
+        info = np.zeros(8, np.int32)
+        _check(lib().orbx_debug_preproc_plan(self._h, _p(info)))
+        opt = [None if v < 0 else int(v) for v in info[2:6]]
+        return {"lds_table": bool(info[0]), "resize_prepared": bool(info[1]), "remap": opt[0],
+                "resize": None if opt[1] is None else ("plain" if opt[1] else "generic"),
+                "clahe_vec4": None if opt[2] is None else bool(opt[2]), "gray_segs": opt[3], "frames": int(info[6])}
+
+
+REMAP_LDS, REMAP_WINDOWS, REMAP_GENERIC = 2, 1, 0   # Preproc.plan()["remap"]: k_remap_lds / k_remap1 / k_remap
+
+
+def remap_footprints(map_x, map_y, src_w, src_h):
+    """The k_remap_lds footprint table a plan would build for these maps (orbx_debug_remap_footprints; host only, no device):
+    an int32 array (n_maps, tiles_x, tiles_y, 8), or None when the plan keeps k_remap1."""
+    mx = np.ascontiguousarray(map_x, np.float32)
+    my = np.ascontiguousarray(map_y, np.float32)
+    if mx.ndim == 2:
+        mx, my = mx[None], my[None]
+    if mx.shape != my.shape or mx.ndim != 3:
+        raise ValueError("map_x and map_y must be float images of the same size")
+    nm, dh, dw = mx.shape
+    tx, ty = (dw + 127) // 128, (dh + 7) // 8
+    tab = np.zeros((nm, tx, ty, 8), np.int32)
+    gx, gy = C.c_int(), C.c_int()
+    rc = lib().orbx_debug_remap_footprints(_p(mx), _p(my), dw, dw, dh, src_w, src_h, nm, _p(tab), tab.size, C.byref(gx), C.byref(gy))
+    _check(rc)
+    if (gx.value, gy.value) != (tx, ty):
+        raise OrbxError("unexpected tile grid %d x %d" % (gx.value, gy.value))
+    return tab if rc == 1 else None
 
 
 class ORBVocabulary:

@@ -184,6 +184,8 @@ struct orbx_preproc {
   int outW = 0, outH = 0;
   const uint8_t* out = nullptr;  // result of the last run (a stage buffer, or the caller's frames when nothing is enabled)
   long long outPitch = 0, outImgPitch = 0;
+  // what the last enqueue launched (orbx_debug_preproc_plan): -1 = the stage is not part of the plan / nothing enqueued yet
+  int lastFrames = 0, lastRemapForm = -1, lastResizePlain = -1, lastClaheVec4 = -1, lastGraySegs = -1;
 };
 
 int orbx_preproc_create(const orbx_preproc_params* p, int max_batch, int device, orbx_preproc** out) {
@@ -317,6 +319,7 @@ static int preproc_enqueue(orbx_preproc* pp, const uint8_t* d_frames, int n, ptr
     a.lut = pp->d_lut.p;
     a.srcVec4 = !(((uintptr_t)cur | (uintptr_t)cp | (uintptr_t)cip) & 3);
     a.dstVec4 = 1;
+    pp->lastClaheVec4 = a.srcVec4;
     e = launch_clahe(a, n, pp->d_cells.p, s);
     cur = a.dst; cp = a.dstPitch; cip = a.dstImgPitch;
   }
@@ -330,10 +333,13 @@ static int preproc_enqueue(orbx_preproc* pp, const uint8_t* d_frames, int n, ptr
     if (pp->remapLds && !(((uintptr_t)cur | (uintptr_t)cp | (uintptr_t)cip) & 15)) {   // 16-byte staging pieces: aligned rows
       a.tileTab = pp->d_remapTab.p; a.tilesX = pp->remapTilesX; a.tilesY = pp->remapTilesY;
     }
+    pp->lastRemapForm = remap_form(a);
     e = launch_remap(a, n, s);
     cur = a.dst; cp = a.dstPitch; cip = a.dstImgPitch;
   } else if (e == hipSuccess && pp->doResize) {
-    if (pp->resizeFast && cp < (1ll << 31))
+    const bool plain = pp->resizeFast && cp < (1ll << 31);
+    pp->lastResizePlain = plain;
+    if (plain)
       e = launch_resize_plain(cur, p.src_w, p.src_h, cp, cip, pp->d_geo.p, pp->outW, pp->outH, pp->geoPitch, pp->geoPitch * pp->outH,
                               pp->d_rxtab.p, pp->d_ryrow.p, pp->d_ryab.p, n, s);
     else
@@ -342,13 +348,39 @@ static int preproc_enqueue(orbx_preproc* pp, const uint8_t* d_frames, int n, ptr
     cur = pp->d_geo.p; cp = pp->geoPitch; cip = pp->geoPitch * pp->outH;
   }
   if (e == hipSuccess && pp->doGray) {
+    pp->lastGraySegs = cvt_gray_segs(cur, pp->outW, cp, cip, cn, pp->d_gray.p, pp->grayPitch, pp->grayPitch * pp->outH);
     e = launch_cvt_gray(cur, pp->outW, pp->outH, cp, cip, cn, p.rgb_order ? 1 : 0, pp->d_gray.p, pp->grayPitch,
                         pp->grayPitch * pp->outH, n, s);
     cur = pp->d_gray.p; cp = pp->grayPitch; cip = pp->grayPitch * pp->outH;
   }
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   pp->out = cur; pp->outPitch = cp; pp->outImgPitch = cip;
+  pp->lastFrames = n;
   return ORBX_OK;
+}
+
+int orbx_debug_preproc_plan(const orbx_preproc* pp, int32_t info[8]) {
+  if (!pp || !info) return fail(ORBX_E_BADARG, "null argument");
+  info[0] = pp->remapLds; info[1] = pp->resizeFast;
+  info[2] = pp->lastRemapForm; info[3] = pp->lastResizePlain; info[4] = pp->lastClaheVec4; info[5] = pp->lastGraySegs;
+  info[6] = pp->lastFrames; info[7] = 0;
+  return ORBX_OK;
+}
+
+int orbx_debug_remap_footprints(const float* map_x, const float* map_y, ptrdiff_t map_stride, int out_w, int out_h, int src_w,
+                                int src_h, int n_maps, int32_t* table, int cap, int32_t* tiles_x, int32_t* tiles_y) {
+  if (!map_x || !map_y || out_w <= 0 || out_h <= 0 || src_w <= 0 || src_h <= 0 || src_w > 32767 || src_h > 32767 || n_maps <= 0 ||
+      map_stride < out_w || cap < 0 || (cap && !table))
+    return fail(ORBX_E_BADARG, "bad argument");
+  std::vector<int> tab;
+  int tx = 0, ty = 0;
+  const bool ok = remap_tile_table(map_x, map_y, (long long)map_stride, out_w, out_h, src_w, src_h, n_maps, tab, tx, ty);
+  if (tiles_x) *tiles_x = tx;
+  if (tiles_y) *tiles_y = ty;
+  if (!ok) return 0;
+  if (tab.size() > (size_t)cap) return fail(ORBX_E_CAPACITY, "table larger than cap");
+  std::memcpy(table, tab.data(), tab.size() * sizeof(int32_t));
+  return 1;
 }
 
 int orbx_preproc_run_device(orbx_preproc* pp, const uint8_t* d_frames, int n_frames, ptrdiff_t row_pitch,

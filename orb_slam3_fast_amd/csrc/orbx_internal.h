@@ -303,6 +303,7 @@ struct RemapArgs {
 bool remap_tile_table(const float* mapx, const float* mapy, long long mapStride, int dw, int dh, int sw, int sh, int nMaps,
                       std::vector<int>& tab, int& tilesX, int& tilesY);
 void debug_set_remap_lds(int on);
+int remap_form(const RemapArgs& a);   // the kernel launch_remap picks: 2 = k_remap_lds, 1 = k_remap1, 0 = k_remap
 hipError_t launch_remap(const RemapArgs& a, int nimg, hipStream_t s);
 // cv::CLAHE::apply (k_clahe_lut + k_clahe_apply)
 struct ClaheArgs {
@@ -315,6 +316,8 @@ struct ClaheArgs {
 // cells: clahe_cells_bytes() of scratch for the packed cell tables (nullptr: per-pixel lut gathers)
 size_t clahe_cells_bytes(const ClaheArgs& a, int nimg);
 hipError_t launch_clahe(const ClaheArgs& a, int nimg, uint32_t* cells, hipStream_t s);
+// 16-pixel segments per row that launch_cvt_gray gives to k_cvt_gray16 (0: the per-pixel kernel alone)
+int cvt_gray_segs(const uint8_t* src, int w, long long sp, long long sip, int cn, const uint8_t* dst, long long dp, long long dip);
 hipError_t launch_cvt_gray(const uint8_t* src, int w, int h, long long sp, long long sip, int cn, int rgb, uint8_t* dst,
                            long long dp, long long dip, int nimg, hipStream_t s);
 hipError_t launch_resize_generic(const uint8_t* src, int sw, int sh, long long sp, long long sip, int cn, uint8_t* dst, int dw,

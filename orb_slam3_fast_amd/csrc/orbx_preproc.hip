@@ -73,11 +73,14 @@ __global__ __launch_bounds__(256) void k_cvt_gray16(const uint8_t* __restrict__ 
   *reinterpret_cast<uint4*>(dst + blockIdx.y * dip + y * dp + (long long)sg * 16) = make_uint4(out[0], out[1], out[2], out[3]);
 }
 
-hipError_t launch_cvt_gray(const uint8_t* src, int w, int h, long long sp, long long sip, int cn, int rgb, uint8_t* dst,
-                           long long dp, long long dip, int nimg, hipStream_t s) {
+int cvt_gray_segs(const uint8_t* src, int w, long long sp, long long sip, int cn, const uint8_t* dst, long long dp, long long dip) {
   const bool aligned = !(((uintptr_t)src | (uintptr_t)dst | (uintptr_t)sp | (uintptr_t)sip | (uintptr_t)dp | (uintptr_t)dip) & 15);
   static const bool naive = getenv("ORBX_GRAY_NAIVE") && atoi(getenv("ORBX_GRAY_NAIVE")) != 0;   // A / B switch: the per-pixel kernel everywhere
-  const int segs = aligned && !naive && (cn == 3 || cn == 4) ? w / 16 : 0;
+  return aligned && !naive && (cn == 3 || cn == 4) ? w / 16 : 0;
+}
+hipError_t launch_cvt_gray(const uint8_t* src, int w, int h, long long sp, long long sip, int cn, int rgb, uint8_t* dst,
+                           long long dp, long long dip, int nimg, hipStream_t s) {
+  const int segs = cvt_gray_segs(src, w, sp, sip, cn, dst, dp, dip);
   if (segs > 0) {
     const dim3 grid((unsigned)(((long long)segs * h + 255) / 256), nimg);
     if (cn == 3) hipLaunchKernelGGL(k_cvt_gray16<3>, grid, dim3(256), 0, s, src, segs, h, sp, sip, rgb, dst, dp, dip);
@@ -531,10 +534,14 @@ __global__ __launch_bounds__(256) void k_remap_lds(RemapArgs a, int nimg, int nb
 }
 
 // Footprints of k_remap_lds (host, once per plan).  For map m and output tile (tx, ty) -- kRemapTileW x kRemapTileH pixels --
-// the taps of the tile's pixels are evaluated exactly as the kernel does (cvRound(32 x) >> 5, clamped into the source) and their
-// bounding box is widened to what the kernel reads: columns from (min sx) & ~15 to past the 12-byte window of the right-most
-// thread in 16-byte pieces, rows down to the third window row.  Entry = {x0a, y0, pieces per row, rows, ceil(2^32 / pieces per row), 0, 0, 0}.
+// the taps of the tile's THREADS are evaluated exactly as the kernel does (four consecutive pixels each, positions behind the right
+// edge repeating the edge's entry; cvRound(32 x) >> 5, clamped into the source), and the entry is the bounding box of what they may
+// read: the two tap columns on the two tap rows of every pixel (the byte path), and per thread the 12-byte window from bx & ~3 on rows
+// by .. min(by + 2, sh - 1) wherever that window ends inside the row (the fast path) -- columns in 16-byte pieces from (min) & ~15.
+// A footprint narrower than two pieces grows to the right, at the row end to the left: never in front of a row.
+// Entry = {x0a, y0, pieces per row, rows, ceil(2^32 / pieces per row), 0, 0, 0}.
 // Returns false when a tile needs more than kRemapLdsDwords (the plan keeps k_remap1) or the footprint would leave the rows.
+// tests/test_remap_footprints.py holds every entry against a restatement of the kernel's reads (orbx_debug_remap_footprints).
 bool remap_tile_table(const float* mapx, const float* mapy, long long mapStride, int dw, int dh, int sw, int sh, int nMaps,
                       std::vector<int>& tab, int& tilesX, int& tilesY) {
   tilesX = (dw + kRemapTileW - 1) / kRemapTileW;
@@ -545,25 +552,38 @@ bool remap_tile_table(const float* mapx, const float* mapy, long long mapStride,
   for (int m = 0; m < nMaps; m++)
     for (int tx = 0; tx < tilesX; tx++)
       for (int ty = 0; ty < tilesY; ty++) {
-        int minX = sw, maxX = 0, minY = sh, maxY = 0;
-        for (int y = ty * kRemapTileH; y < std::min(dh, (ty + 1) * kRemapTileH); y++) {
+        int minX = sw, lastX = 0, minY = sh, lastY = 0;   // first / last column and row read
+        for (int y = ty * kRemapTileH; y < std::min(dh, (ty + 1) * kRemapTileH); y++) {   // (rows behind the bottom edge repeat row dh - 1)
           const float* MX = mapx + ((long long)m * dh + y) * mapStride;
           const float* MY = mapy + ((long long)m * dh + y) * mapStride;
-          for (int x = tx * kRemapTileW; x < std::min(dw, (tx + 1) * kRemapTileW); x++) {
-            const int fsx = cvr(MX[x] * 32.f), fsy = cvr(MY[x] * 32.f);
-            const int sx = std::min(std::max(fsx >> 5, -32768), 32767), sy = std::min(std::max(fsy >> 5, -32768), 32767);
-            const int sxc = std::min(std::max(sx, 0), sw - 2);
-            const int y0c = std::min(std::max(sy, 0), sh - 1), y1c = std::min(std::max(sy + 1, 0), sh - 1);
-            minX = std::min(minX, sxc); maxX = std::max(maxX, sxc);
-            minY = std::min(minY, y0c); maxY = std::max(maxY, y1c);
+          for (int x0 = tx * kRemapTileW; x0 < (tx + 1) * kRemapTileW; x0 += 4) {
+            int bx = sw, by = sh;
+            for (int k = 0; k < 4; k++) {
+              const int x = std::min(x0 + k, dw - 1);
+              const int fsx = cvr(MX[x] * 32.f), fsy = cvr(MY[x] * 32.f);
+              const int sx = std::min(std::max(fsx >> 5, -32768), 32767), sy = std::min(std::max(fsy >> 5, -32768), 32767);
+              const int sxc = std::min(std::max(sx, 0), sw - 2);
+              const int y0c = std::min(std::max(sy, 0), sh - 1), y1c = std::min(std::max(sy + 1, 0), sh - 1);
+              bx = std::min(bx, sxc); by = std::min(by, y0c);
+              lastX = std::max(lastX, sxc + 1); lastY = std::max(lastY, y1c);
+            }
+            minX = std::min(minX, bx); minY = std::min(minY, by);
+            if ((bx & ~3) + 12 <= sw) {   // (a window that would cross the row end is not taken by the kernel's fast path)
+              lastX = std::max(lastX, (bx & ~3) + 11);
+              lastY = std::max(lastY, std::min(by + 2, sh - 1));
+            }
+            if (x0 >= dw) break;   // (the threads behind the right edge are all alike)
           }
         }
         int x0a = minX & ~15;
-        int endX = std::max(maxX + 2, (maxX & ~3) + 12);
-        endX = std::min((endX + 15) & ~15, sw);           // (a window that would cross the row end is not taken by the kernel's fast path)
-        if (endX - x0a < 32) x0a = endX - 32;             // (two pieces at least: the row / column split of a slot multiplies by 2^32 / pieces)
-        const int wD = (endX - x0a) / 16, rows = std::min(maxY + 2, sh) - minY;
-        if (wD <= 0 || rows <= 0 || (long long)wD * rows > kRemapLdsDwords / 4) return false;
+        int endX = (lastX + 16) & ~15;                    // (<= sw: lastX <= sw - 1, sw is a multiple of 16)
+        if (endX - x0a < 32) {                            // (two pieces at least: the row / column split of a slot multiplies by 2^32 / pieces)
+          if (x0a + 32 <= sw) endX = x0a + 32;            // widened to the right; to the left only at the row end (sw >= 32)
+          else x0a = endX - 32;
+        }
+        const int wD = (endX - x0a) / 16, rows = lastY - minY + 1;
+        if (x0a < 0 || endX > sw || minY < 0 || lastY >= sh || wD < 2 || rows <= 0 || (long long)wD * rows > kRemapLdsDwords / 4)
+          return false;
         int* e = &tab[(size_t)8 * (((size_t)m * tilesX + tx) * tilesY + ty)];
         e[0] = x0a; e[1] = minY; e[2] = wD; e[3] = rows;
         e[4] = (int)(unsigned)((0x100000000ull + (unsigned)wD - 1) / (unsigned)wD);
@@ -571,8 +591,13 @@ bool remap_tile_table(const float* mapx, const float* mapy, long long mapStride,
   return true;
 }
 
+int remap_form(const RemapArgs& a) {
+  if (a.cn == 1 && a.tileTab && g_remap_lds) return 2;
+  return a.cn == 1 && a.sw >= 8 ? 1 : 0;
+}
 hipError_t launch_remap(const RemapArgs& a, int nimg, hipStream_t s) {
-  if (a.cn == 1 && a.tileTab && g_remap_lds) {
+  const int form = remap_form(a);
+  if (form == 2) {
     // images per workgroup: the taps and weights of a tile are built once per group, so larger groups halve that share of the
     // vector work -- as long as the launch keeps a few workgroups per CU slot
     static const int gforce = [] { const char* e = getenv("ORBX_REMAP_GROUP"); return e ? atoi(e) : 0; }();
@@ -582,7 +607,7 @@ hipError_t launch_remap(const RemapArgs& a, int nimg, hipStream_t s) {
     if (gforce > 0) gsz = gforce;
     const int groups = (perMap + gsz - 1) / gsz, nblk = tiles * groups;
     hipLaunchKernelGGL(k_remap_lds, dim3(8 * ((nblk + 7) / 8)), dim3(256), 0, s, a, nimg, nblk, gsz);
-  } else if (a.cn == 1 && a.sw >= 8) {
+  } else if (form == 1) {
     const int perMap = (nimg + a.nMaps - 1) / a.nMaps, groups = (perMap + kRemapGroup - 1) / kRemapGroup;
     const int xb = (a.dw + 255) / 256, yb = (a.dh + 3) / 4, nblk = xb * yb * a.nMaps * groups;
     hipLaunchKernelGGL(k_remap1, dim3(8 * ((nblk + 7) / 8)), dim3(256), 0, s, a, nimg, xb, yb, nblk);

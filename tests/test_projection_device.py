@@ -276,7 +276,15 @@ def test_device_projection_for_fisheye_frames_and_matcher_against_the_oracle(ora
     (src/ORBmatcher.cc:41-221 with Nleft != -1).  Parity: per camera, gate decisions equal the oracle's restatement unless the oracle
     reports the decisive quantity within 1e-4 of its threshold (device atan2f / cosf / sinf), coordinates within 2e-4 relative,
     levels equal unless log(ratio) / logScaleFactor is within 1e-4 of an integer; the MATCHER is exact: the device-view call equals
-    the host-view batched entry fed with the downloaded views, which equals the oracle's matcher on them."""
+    the host-view batched entry fed with the downloaded views, which equals the oracle's matcher on them.
+
+    mTrackDepth: for points in the left view the device's track_depth equals the oracle's and the float64 |Pc| of the left camera
+    within the 2e-4 relative of the coordinates.  A point that only the right camera sees (the scene holds some on purpose: close
+    points at the right camera's left image border) carries track_depth 0 -- k_project_map_kb8 writes the left camera's distance
+    for points the left camera accepts and 0 otherwise, where the reference keeps the value of an earlier frame
+    (src/Frame.cc:1394-1400); include/orbx.h states it, this test pins it.  The bFarPoints gate (src/ORBmatcher.cc:57) is exercised
+    by a matcher pass whose thFarPoints = 12 lies well inside the scene's depths (|Pc| = 2 .. 30 m along the axis, more off it): on
+    the oracle's views the gate rejects some in-view points of every frame and not all of them."""
     from orb_slam3_fast_amd.hipmem import DeviceBuffer
     w, h, nf, F = 640, 480, 800, 3
     rng = np.random.default_rng(99)
@@ -342,6 +350,23 @@ def test_device_projection_for_fisheye_frames_and_matcher_against_the_oracle(ora
         mind.append(m / 3.5)
         desc.append(rng.integers(0, 256, 32, dtype=np.uint8))
         flags.append(2)
+    # points only the RIGHT camera sees: 0.5 .. 1 m away on rays through the first rows of the right image, left of its centre --
+    # in the left camera, 10 cm to the side, they fall 7 .. 14 px above the image (the image's left and right borders lie
+    # beyond 90 degrees from the axis, where the Z >= 0 gate decides for both cameras alike)
+    for f in range(F):
+        Rc, tc = Rrl @ Rs[f], Rrl @ ts[f] + trl
+        m_ = 30
+        rays = unproject(kb2.astype(np.float64), rng.uniform(180.0, 260.0, m_), rng.uniform(0.5, 3.0, m_))
+        for j in range(m_):
+            P = Rc.T @ (rays[j] / np.linalg.norm(rays[j]) * rng.uniform(0.5, 1.0) - tc)
+            pos.append(P)
+            v = P - (-Rs[f].T @ ts[f])
+            dist = np.linalg.norm(v)
+            nrm.append(v / dist)
+            maxd.append(dist * 1.1)
+            mind.append(maxd[-1] / 1.2 ** 7)
+            desc.append(rng.integers(0, 256, 32, dtype=np.uint8))
+            flags.append(2)
     pos, nrm = np.array(pos, np.float32), np.array(nrm, np.float32)
     mind, maxd = np.array(mind, np.float32), np.array(maxd, np.float32)
     desc, flags = np.array(desc, np.uint8), np.array(flags, np.uint8)
@@ -351,10 +376,23 @@ def test_device_projection_for_fisheye_frames_and_matcher_against_the_oracle(ora
     vl, vr = ex.project_map_points_fisheye(np.stack(posesL), np.stack(posesR), bounds, 0.5, None, want_views=True)
     logsf = np.float32(np.log(np.float32(1.2)))
     seen = [0, 0]
+    right_only, oracle_views = 0, []
     for f in range(F):
         ol, ml = oracle.is_in_frustum_kb8(posesL[f], pos, nrm, mind, maxd, bounds, 0.5, logsf, 8, flags, desc)
         orr, mr = oracle.is_in_frustum_kb8(posesR[f], pos, nrm, mind, maxd, bounds, 0.5, logsf, 8, flags, desc)
+        oracle_views.append((ol, orr))
         assert np.array_equal(vl[f]["desc"], ol["desc"]) and np.array_equal(vl[f]["bad"], ol["bad"])
+        # mTrackDepth: |Pc| of the left camera where the left camera accepts the point, 0 everywhere else
+        inl = (vl[f]["in_view"] != 0) & (ol["in_view"] != 0)
+        pc64 = pos.astype(np.float64) @ posesL[f][:9].astype(np.float64).reshape(3, 3).T + posesL[f][9:12].astype(np.float64)
+        for ref in (ol["track_depth"].astype(np.float64), np.linalg.norm(pc64, axis=1)):
+            a_ = vl[f]["track_depth"][inl].astype(np.float64)
+            assert (np.abs(a_ - ref[inl]) <= 2e-4 * np.maximum(1.0, np.abs(ref[inl]))).all(), f
+        assert (vl[f]["track_depth"][inl] > 0).all() and not vl[f]["track_depth"][vl[f]["in_view"] == 0].any()
+        ro = (vl[f]["in_view"] == 0) & (vr[f]["in_view_r"] != 0) & (ol["in_view"] == 0) & (orr["in_view"] != 0)
+        assert ro[-30 * (F - f):][:30].sum() >= 10, (f, int(ro.sum()))   # most of the frame's own points made for this
+        assert not vl[f]["track_depth"][ro].any()
+        right_only += int(ro.sum())
         for cam, (inv, px, py, vc, lv, ov, mg) in enumerate((
                 (vl[f]["in_view"], vl[f]["proj_x"], vl[f]["proj_y"], vl[f]["view_cos"], vl[f]["predicted_level"], ol, ml),
                 (vr[f]["in_view_r"], vl[f]["proj_xr"], vr[f]["proj_yr"], vr[f]["view_cos_r"], vr[f]["predicted_level_r"], orr, mr))):
@@ -369,6 +407,7 @@ def test_device_projection_for_fisheye_frames_and_matcher_against_the_oracle(ora
             assert (mg[ld, 1] < 1e-4).all()
         assert (vr[f]["predicted_level_r"][vr[f]["in_view_r"] == 0] == -1).all()
     assert seen[0] > 300 and seen[1] > 300, seen
+    assert right_only >= 10 * F, right_only
     # the matcher: device views == host-view batched entry on the downloaded views == the oracle on them
     l2r, r2l = np.full((F, cap), -1, np.int32), np.full((F, cap), -1, np.int32)
     for f in range(F):
@@ -380,9 +419,14 @@ def test_device_projection_for_fisheye_frames_and_matcher_against_the_oracle(ora
     occ = (rng.random((F, 2 * cap)) < 0.04).astype(np.uint8)
     m = orbx.ORBmatcher(0.8, True)
     total = 0
-    for th, far in ((3.0, True), (1.0, False)):
-        nm, match, oc = m.SearchByProjectionFisheyeBatchDevice(ex, 0, F, F, bounds, l2r, r2l, occ, th, far, 60.0)
-        nm2, match2, oc2 = m.SearchByProjectionFisheyeBatch(ex, 0, F, F, bounds, vl, vr, np.full(F, n, np.int32), l2r, r2l, occ, th, far, 60.0)
+    for th, far, th_far in ((3.0, True, 60.0), (1.0, False, 60.0), (3.0, True, 12.0)):
+        if th_far < 60.0:   # what the bFarPoints gate rejects, counted on the oracle's views: some in-view points, not all
+            for ol, orr in oracle_views:
+                cand = (ol["in_view"] != 0) | (orr["in_view"] != 0)
+                gated = int((cand & (ol["track_depth"] > np.float32(th_far))).sum())
+                assert 0 < gated < int(cand.sum()), (th_far, gated, int(cand.sum()))
+        nm, match, oc = m.SearchByProjectionFisheyeBatchDevice(ex, 0, F, F, bounds, l2r, r2l, occ, th, far, th_far)
+        nm2, match2, oc2 = m.SearchByProjectionFisheyeBatch(ex, 0, F, F, bounds, vl, vr, np.full(F, n, np.int32), l2r, r2l, occ, th, far, th_far)
         assert np.array_equal(nm, nm2) and np.array_equal(match, match2) and np.array_equal(oc, oc2)
         sf = ex.GetScaleFactors()
         for f in range(F):
@@ -391,7 +435,7 @@ def test_device_projection_for_fisheye_frames_and_matcher_against_the_oracle(ora
             nL, nn = len(kL), len(kL) + len(kR)
             occf = occ[f, :nn]                      # rows are [left keypoints | right keypoints] at Nleft, like the one-shot arrays
             exp = oracle.search_by_projection_fisheye(np.concatenate([kL, kR]), np.concatenate([dL, dR]), nL, bounds, sf,
-                                                      vl[f].view(oracle.MP_DTYPE), vr[f].view(oracle.MPR_DTYPE), th, far, 60.0, 0.8,
+                                                      vl[f].view(oracle.MP_DTYPE), vr[f].view(oracle.MPR_DTYPE), th, far, th_far, 0.8,
                                                       l2r[f, :nL], r2l[f, :len(kR)], occf)
             got_match, got_occ = match[f, :nn], oc[f, :nn]
             assert nm[f] == exp[0] and np.array_equal(got_match, exp[1]) and np.array_equal(got_occ, exp[2]), (f, th)

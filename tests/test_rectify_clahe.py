@@ -204,7 +204,15 @@ def test_hip_preproc_remap_forms_match_oracle(oracle):
     k_remap1) against the oracle: rectification maps of several sizes (tile edges: widths that are no multiple of 128, heights
     that are no multiple of 8), two maps, batches whose per-map image count is odd, even, below and above one group of eight;
     maps with seams and taps outside the source (the byte-read branch, zero weights); maps whose footprints do not fit (random,
-    a strong rotation: the plan keeps k_remap1 whatever the hook says) -- every result equal to the oracle's."""
+    a strong rotation: the plan keeps k_remap1 whatever the hook says) -- every result equal to the oracle's.
+
+    Which form ran is asserted through orbx_debug_preproc_plan, so that "both forms agree" never compares a kernel with itself:
+    the rectification cases and "seamfit" must build a footprint table and run k_remap_lds under hook 1, k_remap1 under hook 0.
+    "seam" does NOT reach k_remap_lds: its pair at the right edge sits in a tile of the left border (a footprint 512 bytes wide
+    x 10 rows > 256 pieces), as the 130 x 9 output of a 256 x 64 source does not (270 pieces); with the random and the rotated
+    maps they are the fallback cases and must report k_remap1 under both hook settings.  "seamfit" is the seam map whose tiles
+    fit (seam inside a thread's four pixels, shifted band, regions outside the source on every side, a pair across the right
+    and one across the top edge, each inside its own tile): it drives the byte-read branch and the zero weights of k_remap_lds."""
     import ctypes as C
     import orb_slam3_fast_amd as orbx
     from orb_slam3_fast_amd import hipmem
@@ -222,12 +230,26 @@ def test_hip_preproc_remap_forms_match_oracle(oracle):
         my[20:23, 10:20] = -0.75           # and the top edge
         return mx, my
 
-    cases = [((752, 480), (720, 460), "rectify", 2, (1, 2, 3, 4, 9, 17, 18)), ((1280, 720), (1280, 720), "rectify", 2, (2, 5)),
-             ((640, 480), (601, 353), "rectify", 1, (1, 8, 9)), ((512, 512), (512, 512), "seam", 2, (4, 7)),
-             ((256, 64), (130, 9), "rectify", 1, (3,)), ((640, 480), (600, 350), "random", 1, (2,)),
-             ((752, 480), (720, 460), "rotate", 2, (3,))]
+    def seam_maps_that_fit(dw, dh, sw, sh):   # a mild warp that leaves the source on every side, with the same disturbances
+        u, v = np.meshgrid(np.arange(dw, dtype=np.float32), np.arange(dh, dtype=np.float32))
+        mx = (u * (sw + 16) / dw - 8 + 1.5 * np.sin(v / 40)).astype(np.float32)
+        my = (v * (sh + 16) / dh - 8 + 1.5 * np.sin(u / 50)).astype(np.float32)
+        mx[:, 202:] += 9.25                     # the seam runs through the thread of columns 200 .. 203
+        my[dh // 3:dh // 3 + 5, :] += 3.5
+        mx[:7, :40] = -20.0
+        my[-6:, -50:] = sh + 30.0
+        mx[10:14, dw - 12:dw - 8] = sw - 1.25   # the pair straddles the right edge, in a tile that is there anyway
+        my[2:5, 10:20] = -0.75                  # and the top edge
+        return mx, my
+
+    # (source, output, maps, number of maps, batches, the plan is meant to run k_remap_lds)
+    cases = [((752, 480), (720, 460), "rectify", 2, (1, 2, 3, 4, 9, 17, 18), True), ((1280, 720), (1280, 720), "rectify", 2, (2, 5), True),
+             ((640, 480), (601, 353), "rectify", 1, (1, 8, 9), True), ((512, 512), (512, 512), "seam", 2, (4, 7), False),
+             ((512, 512), (512, 512), "seamfit", 2, (4, 7), True),
+             ((256, 64), (130, 9), "rectify", 1, (3,), False), ((640, 480), (600, 350), "random", 1, (2,), False),
+             ((752, 480), (720, 460), "rotate", 2, (3,), False)]
     try:
-        for (sw, sh), (dw, dh), kind, nmaps, batches in cases:
+        for (sw, sh), (dw, dh), kind, nmaps, batches, lds in cases:
             maps = []
             for m in range(nmaps):
                 if kind == "rectify":
@@ -235,12 +257,17 @@ def test_hip_preproc_remap_forms_match_oracle(oracle):
                 elif kind == "seam":
                     mx, my = seam_maps(dw, dh, sw, sh)
                     maps.append((mx + m, my))
+                elif kind == "seamfit":
+                    mx, my = seam_maps_that_fit(dw, dh, sw, sh)
+                    maps.append((mx + m, my))
                 elif kind == "rotate":
                     maps.append(synth.rectify_maps(dw, dh, sw, sh, seed=3, rot_deg=(2.0, -1.0, 25.0 + m)))
                 else:
                     maps.append(_maps(rng, dw, dh, sw, sh, "random"))
             mapsx, mapsy = np.stack([a for a, _ in maps]), np.stack([b for _, b in maps])
+            assert (orbx.remap_footprints(mapsx, mapsy, sw, sh) is not None) == lds, (kind, (sw, sh), (dw, dh))
             pp = orbx.Preproc(sw, sh, channels=1, maps=(mapsx, mapsy), max_batch=max(batches))
+            assert pp.plan()["lds_table"] == lds and pp.plan()["remap"] is None, (kind, (sw, sh), (dw, dh))
             for n in batches:
                 frames = np.stack([synth.mono_frame(sw, sh, 100 + i) if sw >= 512 else rng.integers(0, 256, (sh, sw), dtype=np.uint8)
                                    for i in range(min(n, 3))])
@@ -251,6 +278,8 @@ def test_hip_preproc_remap_forms_match_oracle(oracle):
                 for hook in (1, 0):
                     orbx.lib().orbx_debug_set_remap_lds(hook)
                     ptr, w, h, rp, ip = pp.run_device(raw.ptr.value, n, sw, sw * sh)
+                    assert pp.plan()["remap"] == (orbx.REMAP_LDS if lds and hook else orbx.REMAP_WINDOWS), (kind, (sw, sh), n, hook)
+                    assert pp.plan()["frames"] == n
                     got = np.zeros((n, ip), np.uint8)
                     hipmem._ck(hipmem.hip().hipMemcpy(got.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), got.nbytes, 2))
                     got = got[:, :h * rp].reshape(n, h, rp)[:, :, :w]
