@@ -926,6 +926,97 @@ int orbx_reconstruct_two_views_batch(orbx_extractor* ex, int first_image, int n_
                                      uint8_t* triangulated, float* hyp_scores);
 
 
+/* ---- relocalisation PnP (MLPnPsolver RANSAC) ----------------------------------------------------------- */
+
+/* MLPnPsolver (src/MLPnPsolver.cpp, include/MLPnPsolver.h; Tracking::Relocalization, src/Tracking.cc:3563-3594): the RANSAC of
+ * `iterate` (:107-223) over minimal sets of six correspondences -- computePose (:354-666: planar test, design matrix, the
+ * eigenvector of A^T A's smallest eigenvalue, the nearest rotation, scale, sign candidates, five Gauss-Newton steps),
+ * CheckInliers (:265-295), Refine (:297-351) and the fall-back to the best hypothesis -- on the device, three launches for any
+ * number of solvers: prepare (bearing vectors, null-space bases, mvMaxError), hypotheses (one wave per (solver, set): every set
+ * the call could reach is solved and scored), replay (one workgroup per solver walks the hypotheses in order and takes the
+ * decisions of the serial loop, running Refine where the loop would).  Solver arithmetic is double as in the reference;
+ * CheckInliers keeps the reference's mixed rule (camera coordinates = double sums narrowed to float, then
+ * GeometricCamera::project(cv::Point3f) in float, error2 < mvSigma2[i] * th2 in float).  The eigenvector and the 3 x 3 SVDs come
+ * from one-sided Jacobi sweeps, the 6 x 6 solve from an unpivoted LDLT, sums from a fixed reduction tree: hypothesis poses agree
+ * with a float64 restatement to rounding ("Relocalisation PnP"), not bit for bit.  Deterministic: the same bits on every
+ * run, and problem p of the batch entry gives the bits of the one-shot entry on the same data.
+ *
+ * Deliberate differences from the reference:
+ *  - the six-point index sets are an INPUT (`sets`, [n_sets][6] indices into the correspondence list = the keypoints i < n_left
+ *    with has_point[i] != 0, in ascending i).  The reference draws them with rand(); csrc/MLPnPsolver.h and the Python wrapper
+ *    draw them the reference's way from the host's libc.  Set j is the j-th pass of this call's loop; the call reads
+ *    max(max_iterations - state.iterations, call_iterations) sets and n_sets must be at least that.  An index outside the list or
+ *    repeated within its set is ORBX_E_BADARG; min_set other than 6 is ORBX_E_BADARG (the reference's `epsilon^3` and its
+ *    six-point sign test assume it).
+ *  - the solver's members that survive a call (mnIterations, mnBestInliers, mBestTcw, mvbBestInliers) are the in/out `state` and
+ *    `best_mask`; a zeroed state is a fresh solver, the returned one continues it.  state.best_inliers must equal the number of
+ *    correspondences flagged in best_mask (ORBX_E_BADARG otherwise).
+ *  - the null-space basis of a bearing vector is a fixed one (JacobiSVD picks a basis; A^T A, J^T J and J^T r do not depend on it).
+ *  - Eigen's pivoted LDLT is an unpivoted one; a pivot <= 0 or not finite leaves Gauss-Newton like the |dx| guard does.
+ *  - orbx_mlpnp_ransac_parameters with no correspondence (the reference divides by N): max_iterations_out = 1.
+ *  - the covariance branch of computePose is dead in the reference (covs(1)) and is not built.
+ *  - KannalaBrandt8::unproject's std::tan(float) is taken as the double tangent rounded once to float (what a correctly rounded
+ *    tanf returns; glibc's tanf is that from 2.41 on, within 1 ulp before), not the device's tanf: one float ulp in a bearing
+ *    vector moves a six-point pose by 1e-7, orders above what the solver's arithmetic leaves open.
+ * Out of contract: omega = 0 exactly inside Gauss-Newton (the reference's Jacobian divides by |omega|^2), a correspondence at
+ * z = 0 (pinhole) under an evaluated pose. */
+#define ORBX_CAMERA_PINHOLE 0
+#define ORBX_CAMERA_KB8 1
+typedef struct orbx_mlpnp_params {
+  int32_t model;           /* ORBX_CAMERA_PINHOLE | ORBX_CAMERA_KB8 */
+  float cam[8];            /* fx fy cx cy, then k0..k3 (KB8; not read for pinhole) */
+  float kb8_precision;     /* KannalaBrandt8::precision of unproject's Newton loop (1e-6 in the reference; KB8 only) */
+  float th2;               /* 5.991 at the call site */
+  int32_t min_set;         /* 6 */
+  int32_t min_inliers;     /* mRansacMinInliers as SetRansacParameters adjusted it (orbx_mlpnp_ransac_parameters), >= 6 */
+  int32_t max_iterations;  /* mRansacMaxIts as adjusted, in [1, 4096] */
+  int32_t call_iterations; /* iterate's nIterations (5 at the call site), in [0, 4096] */
+} orbx_mlpnp_params;       /* 60 bytes */
+typedef struct orbx_mlpnp_state {
+  int32_t iterations;      /* mnIterations */
+  int32_t best_inliers;    /* mnBestInliers */
+  float best_Tcw[12];      /* top three rows of mBestTcw, row-major */
+} orbx_mlpnp_state;        /* 56 bytes */
+typedef struct orbx_mlpnp_result {
+  int32_t ok;                /* iterate's return value */
+  int32_t no_more;           /* bNoMore */
+  int32_t n_inliers;         /* nInliers */
+  int32_t n_correspondences; /* N */
+  int32_t iterations_run;    /* passes of the loop in this call */
+  int32_t hypothesis;        /* index of the set at which Refine succeeded and the call returned, -1 otherwise */
+  int32_t refined;           /* 1 = Tcw is Refine's pose, 0 = the best hypothesis' own (fall-back, :209-220) or none */
+  float Tcw[12];             /* top three rows of Tout, row-major (double pose narrowed to float); identity when ok == 0 */
+} orbx_mlpnp_result;         /* 76 bytes */
+/* SetRansacParameters (:225-263) in its own arithmetic: nMinInliers = int(N * epsilon) through float, raised to min_inliers and
+ * min_set; epsilon raised to (float)minInliers / N; iterations = ceil(log(1 - p) / log(1 - pow(epsilon, 3))) (the cube is the
+ * reference's, whatever min_set), 1 when minInliers == N; max(1, min(iterations, max_iterations)).  Pure host code.  Outputs may
+ * be NULL.  Returns ORBX_OK, or ORBX_E_BADARG for a negative count. */
+int orbx_mlpnp_ransac_parameters(int n_correspondences, double probability, int min_inliers, int max_iterations, int min_set,
+                                 float epsilon, int32_t* min_inliers_out, int32_t* max_iterations_out, float* epsilon_out);
+/* One solver, one `iterate` call, from host arrays: kps_un = mvKeysUn (n <= 15000; only the first n_left are read, n_left = n
+ * unless the frame carries right-camera keypoints behind them), world_pos [n][3] / has_point [n] = vpMapPointMatches (non-NULL
+ * and not bad), level_sigma2 = mvLevelSigma2 (nlevels).  best_mask [n] (in/out) = mvbBestInliers by keypoint, inliers [n] =
+ * vbInliers, hyp_inliers (may be NULL) [n_sets] = mnInliersi of every pass the call ran, -1 for sets it did not reach.
+ * N < min_inliers: no_more = 1, nothing else runs, `sets` is not read.  All arguments are validated before a device is touched
+ * (finite inputs, octaves in [0, nlevels)); valid arguments without a device return ORBX_E_NODEVICE (there is no host solver). */
+int orbx_mlpnp_iterate(int device, const orbx_keypoint* kps_un, int n, int n_left, const float* world_pos,
+                       const uint8_t* has_point, const float* level_sigma2, int nlevels, const orbx_mlpnp_params* params,
+                       const int32_t* sets, int n_sets, orbx_mlpnp_state* state, uint8_t* best_mask, orbx_mlpnp_result* result,
+                       uint8_t* inliers, int32_t* hyp_inliers);
+/* n_problems solvers in one call: problem p uses the keypoints of image image[p] of the handle's last extraction batch (taken as
+ * mvKeysUn, resident on the device; several problems may name one image -- the candidate key frames of a relocalising frame),
+ * mvLevelSigma2 = the handle's.  world_pos [n_problems][cap][3], has_point / best_masks / inliers [n_problems][cap] (cap =
+ * orbx_batch_results_device's; the row layout orbx_search_by_bow_batch writes `matches` in, has_point = matches >= 0; entries
+ * past an image's keypoint count are not read or written), params / states / results [n_problems], sets [n_problems][n_sets][6],
+ * hyp_inliers (may be NULL) [n_problems][n_sets].  One upload, three launches, one download.  At most 65535 problems.
+ * Pointers, counts, image indices, params and states are validated before a device is touched; world_pos, best_masks and the sets
+ * depend on the images' keypoint counts, which live on the device, and are validated after those are read, before any launch. */
+int orbx_mlpnp_iterate_batch(orbx_extractor* ex, int n_problems, const int32_t* image, const float* world_pos,
+                             const uint8_t* has_point, const orbx_mlpnp_params* params, const int32_t* sets, int n_sets,
+                             orbx_mlpnp_state* states, uint8_t* best_masks, orbx_mlpnp_result* results, uint8_t* inliers,
+                             int32_t* hyp_inliers);
+
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 
 /* Per-kernel timing with HIP events recorded on the handle's own stream around every kernel launch (the

@@ -106,6 +106,9 @@ def lib():
         L.orbx_pose_optimization_fisheye_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
         L.orbx_reconstruct_two_views.argtypes = [i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_reconstruct_two_views_batch.argtypes = [vp, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
+        L.orbx_mlpnp_ransac_parameters.argtypes = [i, C.c_double, i, i, i, f, vp, vp, vp]
+        L.orbx_mlpnp_iterate.argtypes = [i, vp, i, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
+        L.orbx_mlpnp_iterate_batch.argtypes = [vp, i, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
                                         C.POINTER(i), vp, vp, vp]
         L.orbx_bf_knn2.argtypes = [i, vp, i, vp, i, vp, vp, vp]
@@ -861,6 +864,111 @@ def ReconstructWithTwoViewsBatch(ex, first_image, vKeys1, vMatches12, K, sets=No
                                                   _p(res), _p(p3d), _p(tri), _p(sc) if want_scores else None))
     out = (res, [p3d[f, :n1[f]].copy() for f in range(F)], [tri[f, :n1[f]].astype(bool) for f in range(F)])
     return out + (sc,) if want_scores else out
+
+
+MLPNP_PARAMS_DTYPE = np.dtype([("model", "<i4"), ("cam", "<f4", (8,)), ("kb8_precision", "<f4"), ("th2", "<f4"), ("min_set", "<i4"),
+                               ("min_inliers", "<i4"), ("max_iterations", "<i4"), ("call_iterations", "<i4")])
+MLPNP_STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("best_Tcw", "<f4", (12,))])
+MLPNP_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("no_more", "<i4"), ("n_inliers", "<i4"), ("n_correspondences", "<i4"),
+                               ("iterations_run", "<i4"), ("hypothesis", "<i4"), ("refined", "<i4"), ("Tcw", "<f4", (12,))])
+assert MLPNP_PARAMS_DTYPE.itemsize == 60 and MLPNP_STATE_DTYPE.itemsize == 56 and MLPNP_RESULT_DTYPE.itemsize == 76
+CAMERA_PINHOLE, CAMERA_KB8 = 0, 1
+
+
+def MLPnPRansacParameters(n_correspondences, probability=0.99, minInliers=8, maxIterations=300, minSet=6, epsilon=0.4):
+    """MLPnPsolver::SetRansacParameters (src/MLPnPsolver.cpp:225-263) in its own arithmetic (orbx_mlpnp_ransac_parameters; host
+    code, no device).  Defaults: include/MLPnPsolver.h; Tracking::Relocalization passes (0.99, 10, 300, 6, 0.5, 5.991).
+    Returns (mRansacMinInliers, mRansacMaxIts, mRansacEpsilon) as adjusted to the number of correspondences."""
+    mi, it, ep = C.c_int32(0), C.c_int32(0), C.c_float(0)
+    _check(lib().orbx_mlpnp_ransac_parameters(int(n_correspondences), float(probability), int(minInliers), int(maxIterations),
+                                              int(minSet), float(epsilon), C.addressof(mi), C.addressof(it), C.addressof(ep)))
+    return mi.value, it.value, ep.value
+
+
+def mlpnp_sets(n_correspondences, n_sets, seed=None):
+    """The six-point index sets of MLPnPsolver::iterate (src/MLPnPsolver.cpp:129-148) drawn the reference's way from the host's
+    libc: RandomInt(0, d - 1) = int(((double)rand() / ((double)RAND_MAX + 1.0)) * d), swap-with-back removal.  seed: srand(seed)
+    first (None: the process' rand() state as it stands).  Returns [n_sets][6] int32 indices into the correspondence list;
+    fewer than 6 correspondences return zeros (the library does not read them)."""
+    global _libc
+    if _libc is None:
+        _libc = C.CDLL(None)
+        _libc.rand.restype = C.c_int
+        _libc.srand.argtypes = [C.c_uint]
+    if seed is not None:
+        _libc.srand(int(seed))
+    sets = np.zeros((n_sets, 6), np.int32)
+    if n_correspondences < 6:
+        return sets
+    rand_max = 2147483647  # glibc RAND_MAX
+    for it in range(n_sets):
+        avail = list(range(n_correspondences))
+        for j in range(6):
+            d = len(avail)
+            randi = int((float(_libc.rand()) / (float(rand_max) + 1.0)) * d)
+            sets[it, j] = avail[randi]
+            avail[randi] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def mlpnp_params(camera, min_inliers, max_iterations, call_iterations=5, th2=5.991, kb8_precision=1e-6, n=1):
+    """orbx_mlpnp_params records: camera = (fx, fy, cx, cy) for a pinhole, (fx, fy, cx, cy, k0, k1, k2, k3) for KannalaBrandt8;
+    min_inliers / max_iterations as MLPnPRansacParameters adjusted them; call_iterations = iterate's nIterations."""
+    prm = np.zeros(n, MLPNP_PARAMS_DTYPE)
+    cam = np.asarray(camera, np.float32).reshape(-1)
+    prm["model"] = CAMERA_KB8 if len(cam) == 8 else CAMERA_PINHOLE
+    prm["cam"][:, :len(cam)] = cam
+    prm["kb8_precision"], prm["th2"], prm["min_set"] = kb8_precision, th2, 6
+    prm["min_inliers"], prm["max_iterations"], prm["call_iterations"] = min_inliers, max_iterations, call_iterations
+    return prm
+
+
+def MLPnPIterate(kpsUn, worldPos, hasPoint, levelSigma2, params, sets, state=None, best_mask=None, n_left=None,
+                 want_hyp=False, device=0):
+    """One MLPnPsolver::iterate call (src/MLPnPsolver.cpp:107-223) on the GPU (orbx_mlpnp_iterate).  kpsUn = mvKeysUn (KP_DTYPE),
+    worldPos [n][3] / hasPoint [n] = vpMapPointMatches, levelSigma2 = mvLevelSigma2, params = an mlpnp_params record, sets =
+    [n_sets][6] indices into the correspondence list (mlpnp_sets), state / best_mask = what an earlier call returned (None: a
+    fresh solver), n_left = the number of left-camera keypoints (None: all).  Returns (result record, vbInliers [n] bool, state,
+    best_mask[, hyp_inliers [n_sets]])."""
+    k = np.ascontiguousarray(kpsUn, KP_DTYPE)
+    n = len(k)
+    wp = np.ascontiguousarray(worldPos, np.float32).reshape(n, 3)
+    hp = np.ascontiguousarray(hasPoint, np.uint8).reshape(n)
+    sig = np.ascontiguousarray(levelSigma2, np.float32)
+    prm = np.ascontiguousarray(params, MLPNP_PARAMS_DTYPE).reshape(1)
+    st = np.ascontiguousarray(sets, np.int32).reshape(-1, 6)
+    state = np.zeros(1, MLPNP_STATE_DTYPE) if state is None else np.array(state, MLPNP_STATE_DTYPE).reshape(1)
+    bm = np.zeros(n, np.uint8) if best_mask is None else np.array(best_mask, np.uint8).reshape(n)
+    res = np.zeros(1, MLPNP_RESULT_DTYPE)
+    inl = np.zeros(n, np.uint8)
+    hyp = np.full(len(st), -1, np.int32)
+    _check(lib().orbx_mlpnp_iterate(int(device), _p(k), n, n if n_left is None else int(n_left), _p(wp), _p(hp), _p(sig), len(sig),
+                                    _p(prm), _p(st), len(st), _p(state), _p(bm), _p(res), _p(inl), _p(hyp) if want_hyp else None))
+    out = (res[0], inl.astype(bool), state, bm)
+    return out + (hyp,) if want_hyp else out
+
+
+def MLPnPIterateBatch(ex, image, worldPos, hasPoint, params, sets, states=None, best_masks=None, want_hyp=False):
+    """MLPnPIterate for n_problems solvers in one call (orbx_mlpnp_iterate_batch): problem p uses the keypoints of image image[p]
+    of ex's last extraction batch.  worldPos [P][cap][3], hasPoint [P][cap] (the row layout SearchByBoWBatch returns its matches
+    in: hasPoint = matches >= 0), params [P] records, sets [P][n_sets][6].  Returns (results [P], vbInliers [P][cap] bool,
+    states [P], best_masks [P][cap][, hyp_inliers [P][n_sets]])."""
+    img = np.ascontiguousarray(image, np.int32).reshape(-1)
+    P, cap = len(img), ex.capacity
+    wp = np.ascontiguousarray(worldPos, np.float32).reshape(P, cap, 3)
+    hp = np.ascontiguousarray(hasPoint, np.uint8).reshape(P, cap)
+    prm = np.ascontiguousarray(params, MLPNP_PARAMS_DTYPE).reshape(P)
+    st = np.ascontiguousarray(sets, np.int32).reshape(P, -1, 6)
+    states = np.zeros(P, MLPNP_STATE_DTYPE) if states is None else np.array(states, MLPNP_STATE_DTYPE).reshape(P)
+    bm = np.zeros((P, cap), np.uint8) if best_masks is None else np.array(best_masks, np.uint8).reshape(P, cap)
+    res = np.zeros(P, MLPNP_RESULT_DTYPE)
+    inl = np.zeros((P, cap), np.uint8)
+    hyp = np.full((P, st.shape[1]), -1, np.int32)
+    _check(lib().orbx_mlpnp_iterate_batch(ex._h, P, _p(img), _p(wp), _p(hp), _p(prm), _p(st), st.shape[1], _p(states), _p(bm),
+                                          _p(res), _p(inl), _p(hyp) if want_hyp else None))
+    out = (res, inl.astype(bool), states, bm)
+    return out + (hyp,) if want_hyp else out
 
 
 def _pose_frames_kb8(q, t, cam_left, cam_right, trl_q, trl_t, n_frames):

@@ -1,0 +1,54 @@
+// orbx_kb8.h — KannalaBrandt8::project / unproject (src/CameraModels/KannalaBrandt8.cpp) in float, in the reference's
+// expression order.  Shared by the fisheye association (orbx_stereo.hip) and the relocalisation PnP solver (orbx_mlpnp.hip);
+// include it from a translation unit compiled with -ffp-contract=off.
+#ifndef ORBX_KB8_H
+#define ORBX_KB8_H
+#include <hip/hip_runtime.h>
+
+namespace orbx {
+
+struct KB8Cam {
+  float p[8];
+  float precision;
+};
+
+__device__ __forceinline__ void kb8_project(const KB8Cam& c, const float X[3], float uv[2]) {  // :67-86
+  const float x2_plus_y2 = X[0] * X[0] + X[1] * X[1];
+  const float theta = atan2f(sqrtf(x2_plus_y2), X[2]);
+  const float psi = atan2f(X[1], X[0]);
+  const float theta2 = theta * theta;
+  const float theta3 = theta * theta2;
+  const float theta5 = theta3 * theta2;
+  const float theta7 = theta5 * theta2;
+  const float theta9 = theta7 * theta2;
+  const float r = theta + c.p[4] * theta3 + c.p[5] * theta5 + c.p[6] * theta7 + c.p[7] * theta9;
+  uv[0] = c.p[0] * r * cosf(psi) + c.p[2];
+  uv[1] = c.p[1] * r * sinf(psi) + c.p[3];
+}
+
+__device__ __forceinline__ void kb8_unproject(const KB8Cam& c, float u, float v, float ray[3]) {  // :116-147
+  const float pwx = (u - c.p[2]) / c.p[0], pwy = (v - c.p[3]) / c.p[1];
+  float scale = 1.f;
+  float theta_d = sqrtf(pwx * pwx + pwy * pwy);
+  const float halfPi = (float)(3.1415926535897932384626433832795 / 2.0);
+  theta_d = fminf(fmaxf(-halfPi, theta_d), halfPi);
+  if ((double)theta_d > 1e-8) {
+    float theta = theta_d;
+    for (int j = 0; j < 10; j++) {  // Newton on theta (1 + k0 theta^2 + ...) = theta_d
+      const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
+      const float k0_theta2 = c.p[4] * theta2, k1_theta4 = c.p[5] * theta4;
+      const float k2_theta6 = c.p[6] * theta6, k3_theta8 = c.p[7] * theta8;
+      const float theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
+                              (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
+      theta = theta - theta_fix;
+      if (fabsf(theta_fix) < c.precision) break;
+    }
+    scale = tanf(theta) / theta_d;
+  }
+  ray[0] = pwx * scale;
+  ray[1] = pwy * scale;
+  ray[2] = 1.f;
+}
+
+}  // namespace orbx
+#endif

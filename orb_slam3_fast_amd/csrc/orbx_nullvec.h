@@ -1,6 +1,6 @@
 // orbx_nullvec.h — the null vector of a 4 x 4 system (GeometricTools::Triangulate) and the double-precision reciprocal /
-// reciprocal square root it is built on.  Shared by the fisheye association (orbx_stereo.hip) and the two-view
-// reconstruction (orbx_twoview.hip).
+// reciprocal square root it is built on, and the one-sided Jacobi rotation and 3 x 3 SVD in double.  Shared by the fisheye
+// association (orbx_stereo.hip), the two-view reconstruction (orbx_twoview.hip) and the PnP solver (orbx_mlpnp.hip).
 #ifndef ORBX_NULLVEC_H
 #define ORBX_NULLVEC_H
 #include <hip/hip_runtime.h>
@@ -74,6 +74,84 @@ __device__ inline void null_vector4(const float A[16], float v[4]) {
   v[1] = (float)x1;
   v[2] = (float)x2;
   v[3] = (float)x3;
+}
+
+// One Jacobi rotation of a one-sided (Hestenes) SVD from the column moments alpha = |p|^2, beta = |q|^2, gamma = p.q.
+// false: the pair is already orthogonal to 1e-14 of its norms.
+__device__ __forceinline__ bool jacobi_cs(double alpha, double beta, double gamma, double& c, double& s) {
+  if (!(gamma * gamma > 1e-28 * (alpha * beta))) return false;
+  const double zeta = (beta - alpha) * 0.5 * rcp64(gamma), az = fabs(zeta);
+  double t;
+  if (az < 1e100) {
+    const double h = 1.0 + zeta * zeta;
+    t = rcp64(az + h * rsqrt64(h));
+  } else {
+    t = 0.5 * rcp64(az);
+  }
+  if (zeta < 0) t = -t;
+  c = rsqrt64(1.0 + t * t);
+  s = c * t;
+  return true;
+}
+
+// SVD of a row-major 3 x 3 in double: A = U diag(w) V^T, w descending (JacobiSVD's order).  The signs of the column pairs
+// (U_j, V_j) are whatever the sweeps leave: every use below is invariant to them.
+__device__ void svd3(const double* A, double* U, double* w, double* V) {
+  double b[9], v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+#pragma unroll
+  for (int i = 0; i < 9; i++) b[i] = A[i];
+  for (int sweep = 0; sweep < 40; sweep++) {
+    bool rotated = false;
+#pragma unroll
+    for (int p = 0; p < 2; p++)
+#pragma unroll
+      for (int q = p + 1; q < 3; q++) {
+        const double alpha = b[p] * b[p] + b[3 + p] * b[3 + p] + b[6 + p] * b[6 + p];
+        const double beta = b[q] * b[q] + b[3 + q] * b[3 + q] + b[6 + q] * b[6 + q];
+        const double gamma = b[p] * b[q] + b[3 + p] * b[3 + q] + b[6 + p] * b[6 + q];
+        double c, s;
+        if (!jacobi_cs(alpha, beta, gamma, c, s)) continue;
+        rotated = true;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+          const double bp = b[3 * r + p], bq = b[3 * r + q], vp = v[3 * r + p], vq = v[3 * r + q];
+          b[3 * r + p] = c * bp - s * bq;
+          b[3 * r + q] = s * bp + c * bq;
+          v[3 * r + p] = c * vp - s * vq;
+          v[3 * r + q] = s * vp + c * vq;
+        }
+      }
+    if (!rotated) break;
+  }
+  double n[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) n[j] = b[j] * b[j] + b[3 + j] * b[3 + j] + b[6 + j] * b[6 + j];
+#define ORBX_TV_SORT(a, c)                                                                       \
+  if (n[a] < n[c]) {                                                                             \
+    double x = n[a]; n[a] = n[c]; n[c] = x;                                                      \
+    for (int r = 0; r < 3; r++) {                                                                \
+      x = b[3 * r + a]; b[3 * r + a] = b[3 * r + c]; b[3 * r + c] = x;                           \
+      x = v[3 * r + a]; v[3 * r + a] = v[3 * r + c]; v[3 * r + c] = x;                           \
+    }                                                                                            \
+  }
+  ORBX_TV_SORT(0, 1)
+  ORBX_TV_SORT(1, 2)
+  ORBX_TV_SORT(0, 1)
+#undef ORBX_TV_SORT
+#pragma unroll
+  for (int j = 0; j < 3; j++) w[j] = sqrt(n[j]);
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const double inv = w[j] > 0 ? 1.0 / w[j] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) U[3 * r + j] = b[3 * r + j] * inv;
+  }
+  // third left vector: U0 x U1, oriented along A V2 (which fixes it whenever w2 is not zero)
+  double u2[3] = {U[3] * U[7] - U[6] * U[4], U[6] * U[1] - U[0] * U[7], U[0] * U[4] - U[3] * U[1]};
+  if (u2[0] * b[2] + u2[1] * b[5] + u2[2] * b[8] < 0) { u2[0] = -u2[0]; u2[1] = -u2[1]; u2[2] = -u2[2]; }
+  U[2] = u2[0]; U[5] = u2[1]; U[8] = u2[2];
+#pragma unroll
+  for (int i = 0; i < 9; i++) V[i] = v[i];
 }
 
 }  // namespace orbx
