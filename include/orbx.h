@@ -1016,6 +1016,112 @@ int orbx_mlpnp_iterate_batch(orbx_extractor* ex, int n_problems, const int32_t* 
                              orbx_mlpnp_state* states, uint8_t* best_masks, orbx_mlpnp_result* results, uint8_t* inliers,
                              int32_t* hyp_inliers);
 
+/* ---- new map points (local mapping) ------------------------------------------------------------------- */
+
+/* The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), which consumes the match list of
+ * ORBmatcher::SearchForTriangulation: ray parallax and stereo parallax (:579-601), the choice between
+ * GeometricTools::Triangulate (src/GeometricTools.cc:48-73) and KeyFrame::UnprojectStereo (src/KeyFrame.cc:756-773) (:607-624),
+ * the depth signs (:631-635), the two chi-square reprojection gates (:638-685), the zero-distance, far-point and
+ * scale-consistency gates (:688-707).  One kernel, one candidate per lane, float arithmetic in the reference's expression order
+ * (doubles where the reference promotes: the 0.9996 / 0.9998 parallax thresholds, invz = 1.0 / z, 5.991 * sigma2, 7.8 * sigma2).
+ *
+ * Deliberate differences from the reference:
+ *  - Triangulate's null vector of the float 4 x 4 comes from null_vector4 (double arithmetic on the float matrix, shared with the
+ *    fisheye association and orbx_search_for_triangulation_rig) instead of Eigen::JacobiSVD<Matrix4f>: points agree to float
+ *    rounding, accept / reject decisions unless a gated quantity lies within rounding noise of its threshold.
+ *  - `if (i > 0 && CheckNewKeyFrames()) return` (:459) stays with the caller, who chooses how many neighbours a call gets.
+ *  - MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth (:720-722) stay on the host.
+ *
+ * One camera of a key frame: its model, parameters (fx fy cx cy, then k0..k3 for KB8), pose Tcw (top three rows, row-major) and
+ * centre Ow (GetPose / GetCameraCenter, or GetRightPose / GetRightCameraCenter). */
+typedef struct orbx_np_camera {
+  int32_t model;        /* ORBX_CAMERA_PINHOLE | ORBX_CAMERA_KB8 */
+  float p[8];
+  float kb8_precision;  /* KannalaBrandt8::precision (KB8 only) */
+  float Tcw[12];
+  float Ow[3];
+} orbx_np_camera;       /* 100 bytes */
+/* What CreateNewMapPoints reads of a key frame.  Single camera (n_cameras = 1, n_left = -1): kps = mvKeysUn, kps_raw = mvKeys
+ * (read by UnprojectStereo only; NULL = kps), u_right / depth = mvuRight / mvDepth (both NULL: monocular).  Two cameras
+ * (n_cameras = 2): kps = mvKeys | mvKeysRight, n_left = NLeft, cam[1] = the right camera; u_right / depth are not read (bStereo is
+ * false for every feature, :516,526).  scale_factors / level_sigma2 = mvScaleFactors / mvLevelSigma2 (nlevels entries). */
+typedef struct orbx_np_keyframe {
+  orbx_np_camera cam[2];
+  int32_t n_cameras;
+  int32_t n_left;
+  int32_t n;            /* features */
+  int32_t nlevels;
+  float mb;
+  int32_t reserved;
+  const orbx_keypoint* kps;
+  const orbx_keypoint* kps_raw;
+  const float* u_right;
+  const float* depth;
+  const float* scale_factors;
+  const float* level_sigma2;
+} orbx_np_keyframe;     /* 272 bytes */
+typedef struct orbx_np_params {
+  float mbf;              /* mpCurrentKeyFrame->mbf: used for BOTH key frames' stereo residual (:654,677) */
+  int32_t inertial;       /* mbInertial: parallax threshold 0.9996 instead of 0.9998 */
+  int32_t far_points;     /* mbFarPoints */
+  float th_far;           /* mThFarPoints */
+  float ratio_factor;     /* 1.5f * mpCurrentKeyFrame->mfScaleFactor (:451) */
+  int32_t monocular;      /* mbMonocular: which baseline test skips a neighbour (orbx_create_new_map_points only) */
+  int32_t only_stereo, coarse, check_orientation;  /* SearchForTriangulation's (orbx_create_new_map_points only; the call site
+                                                      passes false, bCoarse, false) */
+} orbx_np_params;         /* 36 bytes */
+/* Status of one feature of key frame 1, in the reference's order of exits. */
+#define ORBX_NP_CREATED 0
+#define ORBX_NP_LOW_PARALLAX 1   /* :622-624 no stereo and very low parallax */
+#define ORBX_NP_TRIANGULATE 2    /* Triangulate returned false (w == 0) */
+#define ORBX_NP_UNPROJECT 3      /* UnprojectStereo returned false (z <= 0) */
+#define ORBX_NP_Z1 4
+#define ORBX_NP_Z2 5
+#define ORBX_NP_REPROJ1 6
+#define ORBX_NP_REPROJ2 7
+#define ORBX_NP_ZERO_DIST 8
+#define ORBX_NP_FAR 9
+#define ORBX_NP_SCALE 10
+#define ORBX_NP_NO_MATCH 255
+/* One pair of key frames and a caller-supplied match list matches12[kf1->n] (idx2 or -1, as the searches return it; one feature
+ * of key frame 2 may appear several times).  Outputs per idx1: status (above), x3d [n][3] (the point wherever one was computed,
+ * i.e. status 0 or >= 4; zeros otherwise), point_stereo = bPointStereo.  The two key frames are both single-camera or both
+ * two-camera.  Validated before a device is touched: octaves inside [0, nlevels), match indices inside [-1, n2), finite poses
+ * and camera parameters.  Returns the number of points created (status 0) or a negative error. */
+int orbx_triangulate_matches(int device, const orbx_np_keyframe* kf1, const orbx_np_keyframe* kf2, const int32_t* matches12,
+                             const orbx_np_params* params, uint8_t* status, float* x3d, uint8_t* point_stereo);
+/* The SearchForTriangulation arguments of a key frame that orbx_np_keyframe does not hold: mFeatVec as CSR, mDescriptors,
+ * has_map_point (see orbx_search_for_triangulation). */
+typedef struct orbx_np_bow {
+  const uint32_t* node_ids;
+  const int32_t* node_start;
+  const uint32_t* feature_idx;
+  const uint8_t* desc;
+  const uint8_t* has_map_point;
+  int32_t n_nodes;
+  int32_t reserved;
+} orbx_np_bow;            /* 48 bytes */
+typedef struct orbx_np_neighbour {
+  orbx_np_keyframe kf;
+  orbx_np_bow bow;
+  float ep[2], F12[9];    /* as orbx_search_for_triangulation takes them */
+  float median_depth;     /* pKF2->ComputeSceneMedianDepth(2) (read when params->monocular) */
+} orbx_np_neighbour;      /* 368 bytes */
+#define ORBX_NP_MAX_NEIGHBOURS 30
+/* The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:458-727) for single-camera key frames (monocular,
+ * rectified stereo, RGB-D): everything is uploaded once; per neighbour that passes the baseline test (:466-478, evaluated on the
+ * host in float: baseline < pKF2->mb, or baseline / median_depth < 0.01 when monocular) the kernels of
+ * orbx_search_for_triangulation and then the geometry above run on one stream.  A point created with neighbour i sets
+ * has_map_point1[idx1] on the device (AddMapPoint, :717), which the search of neighbour i + 1 reads (:953): neighbour i of the
+ * chain gives the bits of orbx_search_for_triangulation + orbx_triangulate_matches called with the flags updated on the host.
+ * One download at the end: n_matches [K] (nmatches, -1 for a skipped neighbour), n_created [K], and rows of kf1->n entries per
+ * neighbour -- matches12 [K][n], status [K][n], x3d [K][n][3], point_stereo [K][n] -- and has_map_point1_out [n], the final flags.
+ * pKF2->AddMapPoint (:718) is the caller's: each neighbour's has_map_point is read only.  Returns the total number of points
+ * created or a negative error. */
+int orbx_create_new_map_points(int device, const orbx_np_keyframe* kf1, const orbx_np_bow* bow1, const orbx_np_neighbour* neighbours,
+                               int n_neighbours, const orbx_np_params* params, int32_t* n_matches, int32_t* n_created,
+                               int32_t* matches12, uint8_t* status, float* x3d, uint8_t* point_stereo, uint8_t* has_map_point1_out);
+
 
 /* ---- measurement ------------------------------------------------------------------------------------ */
 

@@ -109,6 +109,8 @@ def lib():
         L.orbx_mlpnp_ransac_parameters.argtypes = [i, C.c_double, i, i, i, f, vp, vp, vp]
         L.orbx_mlpnp_iterate.argtypes = [i, vp, i, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_mlpnp_iterate_batch.argtypes = [vp, i, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
+        L.orbx_triangulate_matches.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
+        L.orbx_create_new_map_points.argtypes = [i, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
                                         C.POINTER(i), vp, vp, vp]
         L.orbx_bf_knn2.argtypes = [i, vp, i, vp, i, vp, vp, vp]
@@ -969,6 +971,131 @@ def MLPnPIterateBatch(ex, image, worldPos, hasPoint, params, sets, states=None, 
                                           _p(res), _p(inl), _p(hyp) if want_hyp else None))
     out = (res, inl.astype(bool), states, bm)
     return out + (hyp,) if want_hyp else out
+
+
+class _NpCamera(C.Structure):      # orbx_np_camera
+    _fields_ = [("model", C.c_int32), ("p", C.c_float * 8), ("kb8_precision", C.c_float), ("Tcw", C.c_float * 12),
+                ("Ow", C.c_float * 3)]
+
+
+class _NpKeyFrame(C.Structure):    # orbx_np_keyframe
+    _fields_ = [("cam", _NpCamera * 2), ("n_cameras", C.c_int32), ("n_left", C.c_int32), ("n", C.c_int32), ("nlevels", C.c_int32),
+                ("mb", C.c_float), ("reserved", C.c_int32), ("kps", C.c_void_p), ("kps_raw", C.c_void_p), ("u_right", C.c_void_p),
+                ("depth", C.c_void_p), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p)]
+
+
+class _NpParams(C.Structure):      # orbx_np_params
+    _fields_ = [("mbf", C.c_float), ("inertial", C.c_int32), ("far_points", C.c_int32), ("th_far", C.c_float),
+                ("ratio_factor", C.c_float), ("monocular", C.c_int32), ("only_stereo", C.c_int32), ("coarse", C.c_int32),
+                ("check_orientation", C.c_int32)]
+
+
+class _NpBow(C.Structure):         # orbx_np_bow
+    _fields_ = [("node_ids", C.c_void_p), ("node_start", C.c_void_p), ("feature_idx", C.c_void_p), ("desc", C.c_void_p),
+                ("has_map_point", C.c_void_p), ("n_nodes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _NpNeighbour(C.Structure):   # orbx_np_neighbour
+    _fields_ = [("kf", _NpKeyFrame), ("bow", _NpBow), ("ep", C.c_float * 2), ("F12", C.c_float * 9), ("median_depth", C.c_float)]
+
+
+NP_CREATED, NP_LOW_PARALLAX, NP_TRIANGULATE, NP_UNPROJECT, NP_Z1, NP_Z2, NP_REPROJ1, NP_REPROJ2, NP_ZERO_DIST, NP_FAR, NP_SCALE = range(11)
+NP_NO_MATCH = 255
+
+
+def np_camera(params, Tcw, Ow=None, kb8_precision=1e-6):
+    """One camera of a key frame for TriangulateMatches / CreateNewMapPoints: params = (fx, fy, cx, cy) for a pinhole or (fx, fy, cx,
+    cy, k0..k3) for KannalaBrandt8, Tcw = the 3 x 4 (or 4 x 4) pose, Ow = the camera centre (None: -Rcw^T tcw in float32)."""
+    prm = np.asarray(params, np.float32).reshape(-1)
+    T = np.asarray(Tcw, np.float32).reshape(-1, 4)[:3]
+    if Ow is None:
+        Ow = -(T[:, :3].T @ T[:, 3])
+    c = _NpCamera()
+    c.model = CAMERA_KB8 if len(prm) == 8 else CAMERA_PINHOLE
+    c.p[:len(prm)] = prm.tolist()
+    c.kb8_precision = kb8_precision
+    c.Tcw[:] = T.reshape(12).tolist()
+    c.Ow[:] = np.asarray(Ow, np.float32).reshape(3).tolist()
+    return c
+
+
+class NpKeyFrame:
+    """What LocalMapping::CreateNewMapPoints reads of a key frame (orbx_np_keyframe).  cameras = one np_camera or (left, right);
+    kps = mvKeysUn (single camera) or mvKeys | mvKeysRight with n_left = NLeft (two cameras); uRight / depth = mvuRight / mvDepth
+    (None: monocular); kpsRaw = mvKeys where it differs from mvKeysUn (read by UnprojectStereo)."""
+
+    def __init__(self, cameras, kps, scaleFactors, levelSigma2, uRight=None, depth=None, mb=0.0, n_left=-1, kpsRaw=None):
+        cams = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras]
+        self.kps = np.ascontiguousarray(kps, KP_DTYPE)
+        self.raw = None if kpsRaw is None else np.ascontiguousarray(kpsRaw, KP_DTYPE)
+        self.ur = None if uRight is None else np.ascontiguousarray(uRight, np.float32)
+        self.depth = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        self.sf, self.sg = np.ascontiguousarray(scaleFactors, np.float32), np.ascontiguousarray(levelSigma2, np.float32)
+        s = self.c = _NpKeyFrame()
+        for j, c in enumerate(cams):
+            s.cam[j] = c
+        s.n_cameras, s.n_left, s.n, s.nlevels, s.mb = len(cams), int(n_left), len(self.kps), len(self.sf), float(mb)
+        s.kps, s.scale_factors, s.level_sigma2 = _p(self.kps), _p(self.sf), _p(self.sg)
+        s.kps_raw = None if self.raw is None else _p(self.raw)
+        s.u_right = None if self.ur is None else _p(self.ur)
+        s.depth = None if self.depth is None else _p(self.depth)
+
+
+def _np_params(mbf, inertial, far_points, th_far, ratio_factor, monocular=False, only_stereo=False, coarse=False, check_ori=False):
+    return _NpParams(float(mbf), int(inertial), int(far_points), float(th_far), float(ratio_factor), int(monocular),
+                     int(only_stereo), int(coarse), int(check_ori))
+
+
+def TriangulateMatches(kf1, kf2, matches12, ratio_factor, mbf=0.0, inertial=False, far_points=False, th_far=0.0, device=0):
+    """The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707) for one pair of NpKeyFrame and a
+    match list matches12[n1] (idx2 or -1) on the GPU (orbx_triangulate_matches).  ratio_factor = 1.5f * mfScaleFactor, mbf = the
+    current key frame's.  Returns (n_created, status [n1] NP_*, x3d [n1][3], point_stereo [n1] bool)."""
+    m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+    n1 = kf1.c.n
+    if len(m) != n1:
+        raise ValueError("one match entry per feature of key frame 1")
+    prm = _np_params(mbf, inertial, far_points, th_far, ratio_factor)
+    status, x3d, ps = np.full(n1, NP_NO_MATCH, np.uint8), np.zeros((n1, 3), np.float32), np.zeros(n1, np.uint8)
+    n = _check(lib().orbx_triangulate_matches(int(device), C.addressof(kf1.c), C.addressof(kf2.c), _p(m), C.addressof(prm),
+                                              _p(status), _p(x3d), _p(ps)))
+    return n, status, x3d, ps.astype(bool)
+
+
+def _np_bow(fv, desc, has_map_point, keep):
+    ids, start, feats = (np.ascontiguousarray(fv[0], np.uint32), np.ascontiguousarray(fv[1], np.int32),
+                         np.ascontiguousarray(fv[2], np.uint32))
+    d, h = np.ascontiguousarray(desc, np.uint8), np.ascontiguousarray(has_map_point, np.uint8)
+    keep.extend([ids, start, feats, d, h])
+    return _NpBow(_p(ids), _p(start), _p(feats), _p(d), _p(h), len(ids), 0)
+
+
+def CreateNewMapPoints(kf1, fv1, desc1, hasMapPoint1, neighbours, ratio_factor, mbf=0.0, monocular=False, inertial=False,
+                       far_points=False, th_far=0.0, bCoarse=False, bOnlyStereo=False, check_ori=False, device=0):
+    """The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:458-727) in one call (orbx_create_new_map_points),
+    single-camera key frames.  kf1 = NpKeyFrame of the current key frame, fv1 / desc1 / hasMapPoint1 as SearchForTriangulation takes
+    them; neighbours = up to 30 dicts with kf (NpKeyFrame), fv, desc, hasMapPoint, ep, F12 and median_depth (monocular only).
+    Returns a dict: n_matches [K] (-1 = skipped by the baseline test), n_created [K], matches12 [K][n1], status [K][n1], x3d
+    [K][n1][3], point_stereo [K][n1], has_map_point1 [n1] (the final flags), total."""
+    K, n1 = len(neighbours), kf1.c.n
+    keep = []
+    b1 = _np_bow(fv1, desc1, hasMapPoint1, keep)
+    nbs = (_NpNeighbour * max(K, 1))()
+    for k, nb in enumerate(neighbours):
+        nbs[k].kf = nb["kf"].c
+        nbs[k].bow = _np_bow(nb["fv"], nb["desc"], nb["hasMapPoint"], keep)
+        nbs[k].ep[:] = np.asarray(nb["ep"], np.float32).reshape(2).tolist()
+        if nb.get("F12") is not None:
+            nbs[k].F12[:] = np.asarray(nb["F12"], np.float32).reshape(9).tolist()
+        nbs[k].median_depth = float(nb.get("median_depth", 0.0))
+    prm = _np_params(mbf, inertial, far_points, th_far, ratio_factor, monocular, bOnlyStereo, bCoarse, check_ori)
+    nm, nc = np.zeros(K, np.int32), np.zeros(K, np.int32)
+    m = np.full((K, n1), -1, np.int32)
+    status, x3d, ps = np.full((K, n1), NP_NO_MATCH, np.uint8), np.zeros((K, n1, 3), np.float32), np.zeros((K, n1), np.uint8)
+    flags = np.zeros(n1, np.uint8)
+    total = _check(lib().orbx_create_new_map_points(int(device), C.addressof(kf1.c), C.addressof(b1), C.addressof(nbs), K,
+                                                    C.addressof(prm), _p(nm), _p(nc), _p(m), _p(status), _p(x3d), _p(ps), _p(flags)))
+    return dict(n_matches=nm, n_created=nc, matches12=m, status=status, x3d=x3d, point_stereo=ps.astype(bool),
+                has_map_point1=flags, total=total)
 
 
 def _pose_frames_kb8(q, t, cam_left, cam_right, trl_q, trl_t, n_frames):

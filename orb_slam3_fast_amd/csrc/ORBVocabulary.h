@@ -157,6 +157,16 @@ struct KeyFrameView {
   const std::vector<float>* mvuRight = nullptr;
   const std::vector<float>* mvScaleFactors = nullptr;
   const std::vector<float>* mvLevelSigma2 = nullptr;
+  // What LocalMapping::CreateNewMapPoints reads beyond the search (csrc/LocalMapping.h): GetPose() as the top three rows of Tcw
+  // (row-major) and GetCameraCenter(), the pinhole (fx, fy, cx, cy), mb, mvDepth (empty: monocular), mvKeys for
+  // KeyFrame::UnprojectStereo (nullptr: the same as mvKeysUn), ComputeSceneMedianDepth(2) (read for a monocular map).
+  float Tcw[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  float Ow[3] = {0, 0, 0};
+  float K[4] = {1, 1, 0, 0};
+  float mb = 0.f;
+  const std::vector<float>* mvDepth = nullptr;
+  const std::vector<ocv::KeyPoint>* mvKeys = nullptr;
+  float medianDepth = 0.f;
 };
 
 // ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, vector<pair<size_t, size_t>>& vMatchedPairs, bOnlyStereo,

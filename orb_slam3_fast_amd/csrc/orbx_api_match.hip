@@ -69,51 +69,6 @@ InitArgs grid_block(float min_x, float min_y, float max_x, float max_y, const or
   return g;
 }
 
-// One key frame (or frame) of a BoW search: its FeatureVector in CSR form -- node ids, offsets into the feature list, feature
-// indices -- and its keypoints, descriptors and per-keypoint flags (valid / has a map point).
-struct BowSide {
-  const uint32_t* ids; const int32_t* start; const uint32_t* feat; int nNodes;
-  const orbx_keypoint* kps; const uint8_t* desc; const uint8_t* flags; int n;
-  int list() const { return nNodes ? start[nNodes] : 0; }
-};
-// A FeatureVector is a std::map: ascending node ids, and the CSR offsets must be monotone (the kernels trust them).  The
-// callers check both sides' nodes before either side's feature indices.
-int check_nodes(const BowSide& s, const char* what) {
-  for (int j = 0; j < s.nNodes; j++)
-    if (s.start[j] < 0 || s.start[j] > s.start[j + 1] || (j && s.ids[j] <= s.ids[j - 1]))
-      return fail(ORBX_E_BADARG, std::string(what) + ": node ids must ascend and offsets must be monotone");
-  return ORBX_OK;
-}
-int check_features(const BowSide& s, const char* what) {
-  for (int i = 0; i < s.list(); i++)
-    if (s.feat[i] >= (uint32_t)s.n) return fail(ORBX_E_BADARG, std::string(what) + " out of range");
-  return ORBX_OK;
-}
-
-// The two-key-frame searches (triangulation, SearchByBoW(KeyFrame, KeyFrame)): a side's arrays in the call's upload, and the
-// TriArgs pointers to both sides once the pack is committed.
-struct SideAreas { size_t ids, start, feat, desc, flags, kps; };
-SideAreas add_side(Pack& pk, const BowSide& s) {
-  SideAreas o;
-  o.ids = pk.add(s.ids, (size_t)s.nNodes * 4);
-  o.start = pk.add(s.start, ((size_t)s.nNodes + 1) * 4);
-  o.feat = pk.add(s.feat, (size_t)s.list() * 4);
-  o.desc = pk.add(s.desc, (size_t)s.n * 32);
-  o.flags = pk.add(s.flags, s.n);
-  o.kps = pk.add(s.kps, (size_t)s.n * sizeof(orbx_keypoint));
-  return o;
-}
-TriArgs tri_args(const Pack& pk, const BowSide& s1, const SideAreas& o1, const BowSide& s2, const SideAreas& o2) {
-  TriArgs a{};
-  a.nodes1 = pk.ptr<uint32_t>(o1.ids); a.start1 = pk.ptr<int>(o1.start); a.feat1 = pk.ptr<uint32_t>(o1.feat);
-  a.nNodes1 = s1.nNodes; a.nList1 = s1.list();
-  a.nodes2 = pk.ptr<uint32_t>(o2.ids); a.start2 = pk.ptr<int>(o2.start); a.feat2 = pk.ptr<uint32_t>(o2.feat); a.nNodes2 = s2.nNodes;
-  a.k1 = pk.ptr<orbx_keypoint>(o1.kps); a.k2 = pk.ptr<orbx_keypoint>(o2.kps);
-  a.d1 = pk.ptr<uint32_t>(o1.desc); a.d2 = pk.ptr<uint32_t>(o2.desc); a.mp1 = pk.ptr<uint8_t>(o1.flags); a.mp2 = pk.ptr<uint8_t>(o2.flags);
-  a.n1 = s1.n; a.n2 = s2.n;
-  return a;
-}
-
 // The tail of the single-launch searches: the result word, then n matches, come back in one copy.
 hipError_t fetch_result(Pack& pk, size_t off, int n, int32_t* matches, int* result) {
   hipError_t e;

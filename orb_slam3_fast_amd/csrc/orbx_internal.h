@@ -291,6 +291,27 @@ hipError_t launch_tri_match_rig(const TriArgs& a, hipStream_t s);  // orbx_stere
 // mp1 / mp2 = "holds a good map point" flags, match = the feature of pKF2 whose map point vpMatches12[idx1] receives
 hipError_t launch_search_by_bow_keyframes(const TriArgs& a, hipStream_t s);
 
+// The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), k_new_points (orbx_newpoints.hip).
+// A key frame as the kernel reads it: orbx_np_keyframe with device pointers (kraw = mvKeys for UnprojectStereo, never null).
+struct NpKf {
+  orbx_np_camera cam[2];
+  int twoCam, nLeft, n;
+  float mb;
+  const orbx_keypoint* k; const orbx_keypoint* kraw;
+  const float* ur; const float* depth;        // both null: no stereo observations
+  const float* scale; const float* sigma2;    // mvScaleFactors, mvLevelSigma2
+};
+struct NewPointsArgs {
+  NpKf kf1, kf2;
+  const int* match;        // [kf1.n] idx2 or -1, as k_tri_cull leaves it
+  float mbf; int inertial, farPoints; float thFar, ratioFactor;
+  float* x3d;              // [kf1.n][3]
+  uint8_t* status;         // [kf1.n] ORBX_NP_*
+  uint8_t* pointStereo;    // [kf1.n] bPointStereo
+  uint8_t* mp1;            // chained form: has_map_point1, set for a created point (AddMapPoint, :717); null otherwise
+};
+hipError_t launch_new_points(const NewPointsArgs& a, hipStream_t s);
+
 // cv::remap INTER_LINEAR with float maps (k_remap): batch of nimg images, image i uses map i % nMaps.
 struct RemapArgs {
   const uint8_t* src; int sw, sh, cn; long long srcPitch, srcImgPitch;
