@@ -1202,6 +1202,21 @@ void orbx_debug_set_remap_lds(int on);
  * too small (table untouched), ORBX_E_BADARG on bad arguments.  tiles_x / tiles_y (may be NULL) receive the tile grid. */
 int orbx_debug_remap_footprints(const float* map_x, const float* map_y, ptrdiff_t map_stride, int out_w, int out_h, int src_w,
                                 int src_h, int n_maps, int32_t* table, int cap, int32_t* tiles_x, int32_t* tiles_y);
+/* The tables that replace the fronts of k_detect and k_resize, as orbx_extractor_configure builds them for a width x height
+ * frame and these parameters.  Host only: touches no device and works without one.
+ *   cells: one record of 16 dwords per FAST cell, in the order (level, cell row, cell column):
+ *     {iniX | iniY << 16, rw | rh << 16, flags | level << 8 | level width << 16, level pitch, byte offset of the ROI in an image's
+ *      pyramid block, entry offset of the cell's candidate slots, slots, qpr | dq << 8 | rq << 16, 64 * whole-row rounds, 16-byte
+ *      pieces of the score tile, lanes of the last round (2 dwords), threshold patterns of a row's last quad (2 dwords), 1 / qpr as
+ *      a float, 0};  flags: 1 = rejected cell (every other field but level and width is 0), 2 = wide tile loader, 4 = level 0.
+ *   tiles: per level >= 1, eight dwords per 256 x 16 destination tile (row-major) -- {first x-table entry, x0 | rows << 16,
+ *     rb | nrows << 16, cb | ndw << 16, flags (1 = straight-line loader, 2 = every footprint dword inside its source row), byte
+ *     offset of the tile's first row in the level, tile row, 0} --, then per tile row and wave 4 x {b0 | b1 << 16, byte offsets of the
+ *     row's two source rows in the horizontal pass's output (512 bytes per footprint row, relative to rb), 0}.
+ * info: {cell records, dwords of the tile table, LDS tile pitch of k_detect, its rows}.  cells / tiles may be NULL (sizes only);
+ * ORBX_E_CAPACITY when a cap (in dwords) is too small. */
+int orbx_debug_front_tables(const orbx_params* p, int width, int height, uint32_t* cells, int cells_cap, uint32_t* tiles,
+                            int tiles_cap, int32_t info[4]);
 /* What a pre-processing plan decided at creation and what its LAST enqueue (orbx_preproc_run / _run_device,
  * orbx_extract_batch_raw_device) launched, from the expressions that pick the launch:
  *   info[0] k_remap_lds table built (0 / 1)          info[1] single-channel resize fast path prepared (0 / 1)

@@ -198,6 +198,8 @@ def lib():
         L.orbx_debug_set_remap_lds.restype = None
         L.orbx_debug_remap_footprints.argtypes = [vp, vp, C.c_ssize_t, i, i, i, i, i, vp, i, C.POINTER(i), C.POINTER(i)]
         L.orbx_debug_preproc_plan.argtypes = [vp, vp]
+        if hasattr(L, "orbx_debug_front_tables"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
+            L.orbx_debug_front_tables.argtypes = [vp, i, i, vp, i, vp, i, vp]
         L.orbx_debug_set_resize_tail.argtypes = [i, i, i]
         L.orbx_debug_set_resize_tail.restype = None
         L.orbx_debug_resize_plan.argtypes = [vp, vp, vp, vp, i]
@@ -1352,6 +1354,20 @@ def remap_footprints(map_x, map_y, src_w, src_h):
     if (gx.value, gy.value) != (tx, ty):
         raise OrbxError("unexpected tile grid %d x %d" % (gx.value, gy.value))
     return tab if rc == 1 else None
+
+
+def front_tables(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height):
+    """The tables that stand in for the fronts of k_detect and k_resize at this frame size (orbx_debug_front_tables; host only,
+    no device): (cells, tiles, tile_pitch, tile_rows) -- cells a uint32 array (FAST cells, 16), tiles the flat uint32 table of
+    the resize levels (include/orbx.h describes both)."""
+    prm = _Params(int(nfeatures), float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
+    info = np.zeros(4, np.int32)
+    _check(lib().orbx_debug_front_tables(C.byref(prm), width, height, None, 0, None, 0, _p(info)))
+    cells = np.zeros((int(info[0]), 16), np.uint32)
+    tiles = np.zeros(int(info[1]), np.uint32)
+    _check(lib().orbx_debug_front_tables(C.byref(prm), width, height, _p(cells), cells.size, _p(tiles) if tiles.size else None,
+                                         tiles.size, _p(info)))
+    return cells, tiles, int(info[2]), int(info[3])
 
 
 class ORBVocabulary:

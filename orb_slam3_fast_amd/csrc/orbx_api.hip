@@ -90,7 +90,6 @@ void build_tables(orbx_extractor* ex) {
 int build_geom(const orbx_extractor* ex, int w, int h, Geom& g, std::string& why) {
   std::memset(&g, 0, sizeof(g));
   const int L = ex->prm.nlevels;
-  for (int l = 0; l < ORBX_MAX_LEVELS; l++) g.levelCell[l] = INT_MAX;
   g.nlevels = L;
   g.iniTh = ex->prm.ini_th_fast;
   g.minTh = ex->prm.min_th_fast;
@@ -117,7 +116,6 @@ int build_geom(const orbx_extractor* ex, int w, int h, Geom& g, std::string& why
     v.wCell = (int)std::ceil(width / v.nCols);
     v.hCell = (int)std::ceil(height / v.nRows);
     v.cellStart = cells;
-    g.levelCell[l] = cells;
     cells += v.nCols * v.nRows;
     v.quota = ex->nfeat[l];
     const int nIni = (int)std::round(width / height);
@@ -171,6 +169,110 @@ int build_geom(const orbx_extractor* ex, int w, int h, Geom& g, std::string& why
     return ORBX_E_UNSUPPORTED;
   }
   return ORBX_OK;
+}
+
+// k_resize's row table: the two source rows of every destination row, clamped to the source level, as u16 halves
+void build_yrow(const Geom& g, const std::vector<int>& yofs, std::vector<uint32_t>& yrow) {
+  yrow.assign(yofs.size(), 0);
+  for (int l = 1; l < g.nlevels; l++) {
+    const int Sh = g.lv[l - 1].h;
+    for (int dy = 0; dy < g.lv[l].h; dy++) {
+      const int sy = yofs[g.lv[l].ycoef + dy];
+      const int a = std::min(std::max(sy, 0), Sh - 1), b = std::min(std::max(sy + 1, 0), Sh - 1);
+      yrow[g.lv[l].ycoef + dy] = (uint32_t)a | ((uint32_t)b << 16);
+    }
+  }
+}
+
+// ---- k_resize's front as tables (layout: resize_records_layout).  Per 256 x 16 destination tile of a level, eight dwords:
+//   {first entry of the tile in xtab, x0 | dst rows << 16, rb | nrows << 16, cb | ndw << 16, kTile* flags, byte offset of the tile's
+//    first row in the level, tile row, 0}  -- the source footprint is rows [rb, rb + nrows) x dwords [cb / 4, cb / 4 + ndw).
+// Per tile row and wave w (rows w, w + 4, w + 8, w + 12 of the tile; past the level's last row: that row again), four dwords a row:
+//   {b0 | b1 << 16, byte offset of the upper source row in the horizontal pass's output (256 u16 per footprint row), of the lower, 0}
+void build_resize_records(const Geom& g, const std::vector<uint4>& xtab, const std::vector<uint32_t>& yrow, const std::vector<short>& yab,
+                          std::vector<uint32_t>& tab) {
+  int tileOff, rowOff;
+  tab.assign((size_t)resize_records_layout(g, g.nlevels, tileOff, rowOff), 0u);
+  for (int l = 1; l < g.nlevels; l++) {
+    const LevelDev &D = g.lv[l], &S = g.lv[l - 1];
+    resize_records_layout(g, l, tileOff, rowOff);
+    const int nbx = (D.w + 255) / 256, nby = (D.h + 15) / 16;
+    for (int tby = 0; tby < nby; tby++) {
+      const int y0 = tby * 16, y1 = std::min(y0 + 16, D.h) - 1;
+      const int rb = (int)(yrow[D.ycoef + y0] & 0xFFFFu), re = (int)(yrow[D.ycoef + y1] >> 16);
+      const int nrows = re - rb + 1;
+      for (int tbx = 0; tbx < nbx; tbx++) {
+        const int x0 = tbx * 256, x1 = std::min(x0 + 256, D.w) - 1;
+        const int cb = (int)xtab[D.xcoef + x0].y;
+        const int ce = std::min((int)xtab[D.xcoef + x1].x + 1, S.w - 1);
+        const int ndw = ((ce - cb) >> 2) + 1;
+        const bool whole = l > 1 || cb + 4 * ndw <= S.w;   // only level 0 (the caller's buffer) may end with its last pixel
+        const bool fast = whole && ndw > 64 && ndw <= 85 && nrows <= 24 && rb + 28 <= S.h;   // k_resize's straight-line loader
+        uint32_t* t = &tab[(size_t)tileOff + 8 * (size_t)(tby * nbx + tbx)];
+        t[0] = (uint32_t)(D.xcoef + x0);
+        t[1] = (uint32_t)x0 | ((uint32_t)(y1 - y0 + 1) << 16);
+        t[2] = (uint32_t)rb | ((uint32_t)nrows << 16);
+        t[3] = (uint32_t)cb | ((uint32_t)ndw << 16);
+        t[4] = (fast ? kTileFast : 0u) | (whole ? kTileWhole : 0u);
+        t[5] = (uint32_t)((long long)y0 * D.pitch);
+        t[6] = (uint32_t)tby;
+      }
+      for (int w = 0; w < 4; w++)
+        for (int k = 0; k < 4; k++) {
+          const int dy = std::min(y0 + w + 4 * k, D.h - 1);
+          const uint32_t sy = yrow[D.ycoef + dy];
+          uint32_t* r = &tab[(size_t)rowOff + 16 * (size_t)(4 * tby + w) + 4 * k];
+          r[0] = (uint32_t)(uint16_t)yab[2 * (D.ycoef + dy)] | ((uint32_t)(uint16_t)yab[2 * (D.ycoef + dy) + 1] << 16);
+          r[1] = (uint32_t)(((int)(sy & 0xFFFFu) - rb) * 512);
+          r[2] = (uint32_t)(((int)(sy >> 16) - rb) * 512);
+        }
+    }
+  }
+}
+
+// ---- k_detect's per-cell records: the cell loop's bounds (src/ORBextractor.cc:892-919) and the constants of the stage-1 rounds
+// for every FAST cell of the size, in the order of the cell numbers (level, cell row, cell column).
+void build_cell_records(const Geom& g, std::vector<CellRec>& recs) {
+  recs.assign((size_t)g.totalCells, CellRec{});
+  const int TPd = g.tileP >> 2;
+  for (int l = 0; l < g.nlevels; l++) {
+    const LevelDev& L = g.lv[l];
+    const int maxBX = L.w - kBorder, maxBY = L.h - kBorder;
+    for (int ci = 0; ci < L.nRows; ci++)
+      for (int cj = 0; cj < L.nCols; cj++) {
+        const int cell = ci * L.nCols + cj;
+        CellRec& r = recs[(size_t)L.cellStart + cell];
+        const int iniY = kBorder + ci * L.hCell, iniX = kBorder + cj * L.wCell;
+        const int maxY = std::min(iniY + L.hCell + 6, maxBY), maxX = std::min(iniX + L.wCell + 6, maxBX);
+        const int rw = maxX - iniX, rh = maxY - iniY;
+        const int dw = rw - 6, dh = rh - 6;  // detectable window of the cell (FAST needs a 3 px ring)
+        r.flags = ((uint32_t)l << 8) | ((uint32_t)L.w << 16) | (l == 0 ? kCellL0 : 0u);
+        if (iniY >= maxBY - 3 || iniX >= maxBX - 6 || dw <= 0 || dh <= 0) {  // :913,919
+          r.flags |= kCellReject;
+          continue;
+        }
+        if (iniX + g.tileP <= L.w) r.flags |= kCellWide;
+        r.xy = (uint32_t)iniX | ((uint32_t)iniY << 16);
+        r.roi = (uint32_t)rw | ((uint32_t)rh << 16);
+        r.pitch = (uint32_t)L.pitch;
+        r.baseOff = (uint32_t)(L.off + (long long)iniY * L.pitch + iniX);
+        r.outOff = (uint32_t)(L.cellOff + (long long)cell * L.cellCap);
+        r.cellCap = (uint32_t)L.cellCap;
+        const int qpr = (dw + 3) >> 2, dq = 64 / qpr, rq = 64 - dq * qpr;   // (qpr <= 63: build_geom limits a cell to 250 px)
+        r.rounds = (uint32_t)qpr | ((uint32_t)dq << 8) | ((uint32_t)rq << 16);
+        const int rounds = (dh + dq - 1) / dq;
+        r.nRounds = (uint32_t)rounds * 64u;
+        r.nScore16 = (uint32_t)((TPd * (dh + 2) + 3) >> 2);
+        const int actN = std::min((dh - (rounds - 1) * dq) * qpr, 64);
+        const uint64_t act = ~0ull >> (64 - actN);
+        r.actLastLo = (uint32_t)act;
+        r.actLastHi = (uint32_t)(act >> 32);
+        const int vlast = dw - 4 * (qpr - 1);  // pixels of a row's last quad inside the detectable window (1..4)
+        r.killLastA = vlast > 1 ? 0u : 0x7C000000u;
+        r.killLastB = (vlast > 2 ? 0u : 0x7C00u) | (vlast > 3 ? 0u : 0x7C000000u);
+        r.invQpr = 1.0f / (float)qpr;
+      }
+  }
 }
 
 // ---- resize coefficient tables, cv::resize INTER_LINEAR 8U -------------------------------
@@ -396,19 +498,20 @@ int configure(orbx_extractor* ex, int w, int h) {
   HIPC(hipStreamSynchronize(ex->stream));
   HIPC(hipMemcpy(ex->d_xtab.p, xtab.data(), xtab.size() * sizeof(uint4), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(ex->d_yofs.p, yofs.data(), yofs.size() * sizeof(int), hipMemcpyHostToDevice));
-  {  // k_resize's row table: the two source rows of every destination row, clamped to the source level, as u16 halves
-    std::vector<uint32_t> yrow(yofs.size(), 0);
-    for (int l = 1; l < g.nlevels; l++) {
-      const int Sh = g.lv[l - 1].h;
-      for (int dy = 0; dy < g.lv[l].h; dy++) {
-        const int sy = yofs[g.lv[l].ycoef + dy];
-        const int a = std::min(std::max(sy, 0), Sh - 1), b = std::min(std::max(sy + 1, 0), Sh - 1);
-        yrow[g.lv[l].ycoef + dy] = (uint32_t)a | ((uint32_t)b << 16);
-      }
-    }
+  {
+    std::vector<uint32_t> yrow, rec;
+    build_yrow(g, yofs, yrow);
     HIPC(hipMemcpy(ex->d_yrow.p, yrow.data(), yrow.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    build_resize_records(g, xtab, yrow, yab, rec);
+    if (ex->d_rsRec.n < rec.size()) HIPC(ex->d_rsRec.alloc(rec.size()));
+    if (!rec.empty()) HIPC(hipMemcpy(ex->d_rsRec.p, rec.data(), rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   HIPC(hipMemcpy(ex->d_yab.p, yab.data(), yab.size() * sizeof(short), hipMemcpyHostToDevice));
+  {
+    std::vector<CellRec> recs;
+    build_cell_records(g, recs);
+    HIPC(hipMemcpy(ex->d_cellRec.p, recs.data(), recs.size() * sizeof(CellRec), hipMemcpyHostToDevice));
+  }
   HIPC(prepare_kernels(g));
   std::vector<TailPlan> plans;
   std::vector<TailBand> bands;
@@ -535,7 +638,7 @@ static int enqueue_pyramid(orbx_extractor* ex, hipStream_t s, int img0, int n) {
       HIPC(launch_resize_tail(g, ex->pyr, tp, ex->d_tailBands.p + tp.bandOff, 0, n, ex->d_xtab.p, ex->d_yofs.p, ex->d_yab.p, s));
       l += tp.nT;
     } else {
-      HIPC(launch_resize(g, ex->pyr, n, l, ex->d_xtab.p, ex->d_yrow.p, ex->d_yab.p, s));
+      HIPC(launch_resize(g, ex->pyr, n, l, ex->d_xtab.p, ex->d_yrow.p, ex->d_yab.p, ex->d_rsRec.p, s));
       l++;
     }
   }
@@ -611,14 +714,14 @@ int record_pipeline(orbx_extractor* ex, int n, bool lapTrivial, bool capturing, 
     ex->lastEvValid = false;
     {
       StageTimer t(ex, s, ORBX_STAGE_DETECT);
-      HIPC(launch_detect(g, ex->pyr, n, ex->d_cellCand.p, ex->d_cellCount.p, 0, g.nlevels, ex->d_dbgScore.p, s));
+      HIPC(launch_detect(g, ex->pyr, ex->d_cellRec.p, n, ex->d_cellCand.p, ex->d_cellCount.p, 0, g.nlevels, ex->d_dbgScore.p, s));
     }
     HIPC(hipEventRecord(tok->ev, s));
     tok->valid = true;
     tok->last = ex;
   } else {
     StageTimer t(ex, s, ORBX_STAGE_DETECT);
-    HIPC(launch_detect(g, ex->pyr, n, ex->d_cellCand.p, ex->d_cellCount.p, 0, g.nlevels, ex->d_dbgScore.p, s));
+    HIPC(launch_detect(g, ex->pyr, ex->d_cellRec.p, n, ex->d_cellCand.p, ex->d_cellCount.p, 0, g.nlevels, ex->d_dbgScore.p, s));
   }
   {
     StageTimer t(ex, s, ORBX_STAGE_OCTREE);
@@ -712,6 +815,15 @@ int orbx_extractor_create(const orbx_params* p, int max_width, int max_height, i
   ok(ex->d_lap.alloc(B * 2));
   ok(hipHostMalloc(reinterpret_cast<void**>(&ex->h_lap), (size_t)B * 2 * sizeof(int), hipHostMallocDefault));
   ok(ex->d_xtab.alloc(nx + 64));
+  ok(ex->d_cellRec.alloc(m.totalCells));
+  {  // tile records: every level of a smaller size has at most as many tiles (+ one row / column of rounding) as the largest one
+    int tiles = 0, trows = 0;
+    for (int l = 1; l < m.nlevels; l++) {
+      tiles += ((m.lv[l].w + 255) / 256 + 1) * ((m.lv[l].h + 15) / 16 + 1);
+      trows += (m.lv[l].h + 15) / 16 + 1;
+    }
+    ok(ex->d_rsRec.alloc((size_t)8 * tiles + 64 * trows + 64));
+  }
   ok(ex->d_yofs.alloc(ny + 64));
   ok(ex->d_yrow.alloc(ny + 64));
   ok(ex->d_packCtr.alloc(4));
@@ -1403,6 +1515,39 @@ int orbx_debug_candidates(orbx_extractor* ex, int image, int level, int32_t* xys
       xys[3 * n + 2] = key_r(k);
     }
   return n;
+}
+
+int orbx_debug_front_tables(const orbx_params* p, int width, int height, uint32_t* cells, int cells_cap, uint32_t* tiles,
+                            int tiles_cap, int32_t info[4]) {
+  if (!p || !info || width < 1 || height < 1 || cells_cap < 0 || tiles_cap < 0 || (cells_cap && !cells) || (tiles_cap && !tiles) ||
+      p->nlevels < 1 || p->nlevels > ORBX_MAX_LEVELS || p->nfeatures < 1 || !(p->scale_factor > 1.0f))
+    return fail(ORBX_E_BADARG, "bad argument");
+  std::unique_ptr<orbx_extractor> ex(new orbx_extractor());   // parameters and tables only: no device, no buffers
+  ex->prm = *p;
+  build_tables(ex.get());
+  Geom g;
+  std::string why;
+  const int rc = build_geom(ex.get(), width, height, g, why);
+  if (rc != ORBX_OK) return fail(rc, why);
+  std::vector<uint4> xtab;
+  std::vector<int> yofs;
+  std::vector<short> yab;
+  std::vector<uint32_t> yrow, rec;
+  std::vector<CellRec> cr;
+  build_coefs(g, xtab, yofs, yab);
+  build_yrow(g, yofs, yrow);
+  build_resize_records(g, xtab, yrow, yab, rec);
+  build_cell_records(g, cr);
+  info[0] = (int32_t)cr.size(); info[1] = (int32_t)rec.size(); info[2] = g.tileP; info[3] = g.tileH;
+  if (cells) {
+    if (cr.size() * 16 > (size_t)cells_cap) return fail(ORBX_E_CAPACITY, "cell records larger than cells_cap");
+    std::memcpy(cells, cr.data(), cr.size() * sizeof(CellRec));
+  }
+  if (tiles) {
+    if (rec.size() > (size_t)tiles_cap) return fail(ORBX_E_CAPACITY, "tile records larger than tiles_cap");
+    std::memcpy(tiles, rec.data(), rec.size() * sizeof(uint32_t));
+  }
+  return ORBX_OK;
 }
 
 int orbx_hamming256(const void* a, const void* b) {

@@ -135,8 +135,8 @@ __device__ __forceinline__ uint64_t low_lanes_pos(int n) {  // n >= 1
 // ds_read immediate offsets instead of costing one v_add each.  The pitch must stay the tight one of the geometry:
 // padding it to 64 made the kernel 6 % SLOWER.  Instantiated for the pitches of the usual cell widths (33..48 px).
 template <bool TAP, int TPC>
-__global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restrict__ cellCand,
-                                               int* __restrict__ cellCount, int listCap, int cellBegin,
+__global__ __launch_bounds__(64) void k_detect(DetectArgs g, Pyr p, const CellRec* __restrict__ cellRec,
+                                               uint32_t* __restrict__ cellCand, int* __restrict__ cellCount,
                                                uint8_t* __restrict__ dbgScore) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x;
@@ -163,26 +163,23 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
   DET_MK();
   // Runs of xcdRun horizontally consecutive cells share an XCD and therefore the L2 lines of their common halo
   // columns (HBM-side fetch 410 -> 151 MB per 64-image launch; same duration, the kernel is VALU-bound).
-  int cell = cellBegin + xcd_run_remap<kDetectXcdRun>(blockIdx.x, gridDim.x, blockIdx.y);
-  int l = 0;  // the scalar ALU is nearly as busy as the vector ALU in this kernel: no search loop, no integer divisions
-#pragma unroll
-  for (int q = 1; q < ORBX_MAX_LEVELS; q++) l -= (g.levelCell[q] - 1 - cell) >> 31;   // += (cell >= levelCell[q]), on the scalar ALU
-  // (written as a select the compiler went through v_cndmask + v_readfirstlane for every level)
-  const LevelDev L = g.lv[l];
+  const int cell = g.cellBegin + xcd_run_remap<kDetectXcdRun>(blockIdx.x, gridDim.x, blockIdx.y);
+  // The scalar ALU is nearly as busy as the vector ALU in this kernel, and everything the front used to derive -- the level of
+  // the cell, its row and column, the ROI with its clamps (src/ORBextractor.cc:901-919), the constants of the stage-1 rounds --
+  // depends only on the configured size: it comes as one record, one 64-byte scalar load (round 9; build_cell_records).
+  typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+  u32x16 recv;   // ONE load (left to the compiler the record came field by field: seven loads, the flags first and the rest behind it)
+  asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(recv) : "s"(cellRec + cell) : "memory");
+  const CellRec rec = __builtin_bit_cast(CellRec, recv);
   int* myCount = cellCount + (long long)img * g.totalCells + cell;
-  cell -= L.cellStart;
-  // cell / nCols by a 1-ulp reciprocal: (cell + 0.5) / nCols stays 0.5 / nCols away from the next integer
-  const int ci = __builtin_amdgcn_readfirstlane((int)(((float)cell + 0.5f) * __builtin_amdgcn_rcpf((float)L.nCols))),
-            cj = cell - ci * L.nCols;
-  const int maxBX = L.w - kBorder, maxBY = L.h - kBorder;
-  const int iniY = kBorder + ci * L.hCell, iniX = kBorder + cj * L.wCell;
-  const int maxY = min(iniY + L.hCell + 6, maxBY), maxX = min(iniX + L.wCell + 6, maxBX);
-  const int rw = maxX - iniX, rh = maxY - iniY;
-  const int dw = rw - 6, dh = rh - 6;  // detectable window of the cell (FAST needs a 3 px ring)
-  if (iniY >= maxBY - 3 || iniX >= maxBX - 6 || dw <= 0 || dh <= 0) {  // src/ORBextractor.cc:913,919
+  if (rec.flags & kCellReject) {  // src/ORBextractor.cc:913,919
     if (lane == 0) *myCount = 0;
     return;
   }
+  const int iniX = (int)(rec.xy & 0xFFFFu), iniY = (int)(rec.xy >> 16);
+  const int rw = (int)(rec.roi & 0xFFFFu), rh = (int)(rec.roi >> 16);
+  const int dw = rw - 6, dh = rh - 6;  // detectable window of the cell (FAST needs a 3 px ring)
+  const int levelW = (int)(rec.flags >> 16), cellCap = (int)rec.cellCap;
 
   const int TP = TPC ? TPC : g.tileP, SPB = TP;  // pitch of the image tile and of the score tile, bytes (tileP == scoreP)
   constexpr bool kRowRounds = ORBX_ROW_ROUNDS && (TPC == 44 || TPC == 48 || TPC == 56);
@@ -197,17 +194,20 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
   // survivors, hence the corner limit of total - 256.  Measured: 480 entries (32 cells per CU instead of 29) 270 us, 704
   // entries 245 us, 832 entries 246 us, 1024 entries (26 cells) 261 us.
   uint16_t* list = reinterpret_cast<uint16_t*>(score + SPd * g.scoreH);
-  const int listTotal = min(listCap, kListTotal), cornerCap = listTotal - 256;
+  const int listTotal = min(g.listCap, kListTotal), cornerCap = listTotal - 256;
   const uint8_t* tile8 = reinterpret_cast<const uint8_t*>(tile);
-  const int qpr = (dw + 3) >> 2;  // quads per detect row
+  const int qpr = (int)(rec.rounds & 0xFFu);  // quads per detect row
   const int nq = qpr * dh;
-  // 1-ulp reciprocals suffice: (lane + 0.5) / qpr and 64.5 / qpr stay 0.5 / qpr away from the next integer (an IEEE division is 12
-  // instructions, an integer division ~ 30)
-  const float inv_qpr = __builtin_amdgcn_rcpf((float)qpr);
-  const float inv_tp = __builtin_amdgcn_rcpf((float)TP);
+  // reciprocals good to 1 ulp suffice: (lane + 0.5) / qpr and (oc + 0.5) / TP stay 0.5 / qpr, 0.5 / TP away from the next integer
+  // (an IEEE division is 12 instructions, an integer division ~ 30)
+  const float inv_qpr = rec.invQpr;
+  const float inv_tp = g.invTileP;
 
-  int pitch;
-  const uint8_t* im = level_ptr(g, p, img, l, pitch);
+  // the ROI's first byte: level 0 lies in the caller's frames, with their pitches
+  const bool level0 = (rec.flags & kCellL0) != 0;
+  const int pitch = level0 ? (int)p.l0Row : (int)rec.pitch;
+  const uint8_t* roi0 = (level0 ? p.l0 : p.pyr) + (long long)img * (level0 ? p.l0Img : g.pyrImg) +
+                        (level0 ? (long long)iniY * pitch + iniX : (long long)rec.baseOff);   // (selects: one 64-bit product)
   bool tileDone = false;
   if (TPC != 0 && kDetectWideLoad) {
     // Fast loader for the compile-time tile pitches: a row is TPC / P pieces of P = 16, 8 or 4 bytes (the largest power of two that
@@ -218,8 +218,8 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     constexpr int P = (TPC % 16 == 0) ? 16 : (TPC % 8 == 0) ? 8 : 4, PPR = TPC ? TPC / P : 1;
     constexpr uint32_t kInv = (65536u + PPR - 1) / PPR;   // it / PPR == (it * kInv) >> 16 for it < 4096 (checked below)
     static_assert(PPR * ((4095u * kInv) >> 16) <= 4095u && (4095u / PPR) == ((4095u * kInv) >> 16), "reciprocal division");
-    if (iniX + TPC <= L.w) {
-      const uint8_t* rowBase = im + (long long)iniY * pitch + iniX;   // wave-uniform
+    if (rec.flags & kCellWide) {   // iniX + TPC <= the level's width
+      const uint8_t* rowBase = roi0;   // wave-uniform
       const int nItems = rh * PPR;                                    // <= 78 rows x 13 pieces
       constexpr int kB = 3;   // loads in flight per lane and batch
       for (int base = 0; base < nItems; base += 64 * kB) {
@@ -253,12 +253,12 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     const int mis = iniX & 3, xa = iniX - mis;
     const int dpr = (rw + 3) >> 2;
     const int r0 = lane >> 4;
-    const uint8_t* rowBase = im + (long long)iniY * pitch + xa;  // wave-uniform: the loads take it as their scalar base
+    const uint8_t* rowBase = roi0 - mis;  // wave-uniform: the loads take it as their scalar base
     const uint32_t pitch4 = 4u * (uint32_t)pitch;
     for (int cc = lane & 15; cc < dpr; cc += 16) {  // one trip unless the cell is wider than 58 px (tiny levels)
       const int gx = xa + 4 * cc;
       const uint8_t* src0 = rowBase + 4 * cc;
-      if (gx + 8 <= L.w) {
+      if (gx + 8 <= levelW) {
         // rows past the ROI are clamped to its last row on both sides (load and store): the same bytes land on the
         // same LDS dword again, and the loop body needs no predicate
         const uint32_t offLast = (uint32_t)__mul24(rh - 1, pitch) + 4u * (uint32_t)cc;
@@ -282,28 +282,27 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
           const uint8_t* src = src0 + __mul24(r, pitch);
           uint64_t v = 0;
           for (int k = 0; k < 8; k++)
-            if (gx + k < L.w) v |= (uint64_t)src[k] << (8 * k);
+            if (gx + k < levelW) v |= (uint64_t)src[k] << (8 * k);
           tile[__mul24(r, TPd) + cc] = __builtin_amdgcn_alignbyte((uint32_t)(v >> 32), (uint32_t)v, mis);
         }
       }
     }
   }
   DET_MK();
-  uint32_t* out = cellCand + (long long)img * g.cellImg + L.cellOff + (long long)cell * L.cellCap;
+  uint32_t* out = cellCand + (long long)img * g.cellImg + rec.outOff;
   int kept = 0;
   // a round of 64 quads advances a lane by dq rows and rq quads (no division per round)
-  const int dq = __builtin_amdgcn_readfirstlane((int)(64.5f * inv_qpr)), rq = 64 - dq * qpr;
-  const int vlast = dw - 4 * (qpr - 1);  // pixels of a row's last quad inside the detectable window (1..4)
+  const int dq = (int)((rec.rounds >> 8) & 0xFFu), rq = (int)(rec.rounds >> 16);
   const int yd0 = (int)(((float)lane + 0.5f) * inv_qpr), j0 = lane - __mul24(yd0, qpr);
-  const int nScore16 = (SPd * (dh + 2) + 3) >> 2;
+  const int nScore16 = (int)rec.nScore16;
   // Stage-1 masks, all loop invariant (round 8).  Per lane: the compass threshold of a pixel outside the window is raised to inf / NaN
   // (kill patterns ORed into t): the pixels of a row's last quad past vlast, and with kRowRounds the lanes past dq whole rows.  Per
   // round: only the last round masks lanes (actLast, one SGPR pair), every other round takes the ballots as they are.
-  // ceil(dh / dq) = floor((dh - 0.5) / dq) + 1 rounds; as a quad count, so that one loop serves both schemes
-  const int nRounds = kRowRounds ? ((int)(((float)dh - 0.5f) * __builtin_amdgcn_rcpf((float)dq)) + 1) * 64 : nq;
+  // ceil(dh / dq) whole-row rounds (from the record); as a quad count, so that one loop serves both schemes
+  const int nRounds = kRowRounds ? (int)rec.nRounds : nq;
   const int lastQb = (nRounds - 1) & ~63;
-  const uint64_t actLast = low_lanes_pos(kRowRounds ? (dh - (lastQb >> 6) * dq) * qpr : nq - lastQb);
-  const uint32_t killLastA = (vlast > 1 ? 0u : 0x7C000000u), killLastB = (vlast > 2 ? 0u : 0x7C00u) | (vlast > 3 ? 0u : 0x7C000000u);
+  const uint64_t actLast = kRowRounds ? ((uint64_t)rec.actLastHi << 32) | rec.actLastLo : low_lanes_pos(nq - lastQb);
+  const uint32_t killLastA = rec.killLastA, killLastB = rec.killLastB;
   uint32_t killA = 0, killB = 0;   // kRowRounds: the lane's quad is the same in every round
   if (kRowRounds) {
     if (lane >= dq * qpr) killA = killB = 0x7C007C00u;
@@ -443,10 +442,10 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     const int nCorners = nList;
     // 3x3 non-max suppression (strict '>') inside the cell + emission
     if (TAP && pass == 0) {  // test tap (orbx_debug_score_map): the cell's FAST scores at iniThFAST, 0 = no corner
-      uint8_t* dm = dbgScore + (long long)img * g.pyrImg + L.off;
+      uint8_t* dm = dbgScore + (long long)img * g.pyrImg + rec.baseOff;
       for (int i = lane; i < dw * dh; i += 64) {
         const int y = i / dw, x = i - y * dw;
-        dm[(long long)(iniY + 3 + y) * L.pitch + iniX + 3 + x] = score8[(y + 1) * SPB + x + 4];
+        dm[(long long)(3 + y) * rec.pitch + 3 + x] = score8[(y + 1) * SPB + x + 4];
       }
     }
     if (!overflowed) {
@@ -464,7 +463,7 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
           const int o = kept + prefix_count(m);
           // (x, y) from the offset: oc / TP by a 1-ulp reciprocal ((oc + 0.5) / TP stays 0.5 / TP away from the next integer)
           const int y = (int)(((float)oc + 0.5f) * inv_tp), x = oc - __mul24(y, SP);
-          if (o < L.cellCap) out[o] = pack_key(iniX + 3 + x - kBorder, iniY + 3 + y - kBorder, sc);
+          if (o < cellCap) out[o] = pack_key(iniX + 3 + x - kBorder, iniY + 3 + y - kBorder, sc);
         }
         kept += __popcll(m);
       }
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
           if ((keepmask >> pI) & 1u) {
             const int o = pos + lanebefore;
             lanebefore++;
-            if (o < L.cellCap)
+            if (o < cellCap)
               out[o] = pack_key(iniX + 3 + 4 * j + pI - kBorder, iniY + 3 + yd - kBorder, (sw >> (8 * pI)) & 0xFF);
           }
         }
@@ -519,13 +518,13 @@ __global__ __launch_bounds__(64) void k_detect(Geom g, Pyr p, uint32_t* __restri
     if (kept > 0) break;
     __syncthreads();
   }
-  if (lane == 0) *myCount = min(kept, L.cellCap);
+  if (lane == 0) *myCount = min(kept, cellCap);
 #ifdef DET_PROF
   DET_MK();
-  if (lane == 0 && (blockIdx.x % 16) == 3) printf("detw %d %d %lld %lld\n", l, kept, dq_[0] % 100000000, dq_[ndq_ - 1] % 100000000);
+  if (lane == 0 && (blockIdx.x % 16) == 3) printf("detw %d %d %lld %lld\n", (int)((rec.flags >> 8) & 15u), kept, dq_[0] % 100000000, dq_[ndq_ - 1] % 100000000);
   if (lane == 0 && ((blockIdx.x % 293) == 7 || blockIdx.x + 1 == gridDim.x || blockIdx.x == 0) && ndq_ >= 6)
     printf("det img %d blk %4d level %d start %6lld: issue tile loads %d | tile in LDS + clear %d | stage 1 %d | flush (stage 2) %d | "
-           "NMS + emit%s %d | total %d  kept %d\n", img, (int)blockIdx.x, l, dq_[0] % 1000000, (int)(dq_[1] - dq_[0]), (int)(dq_[2] - dq_[1]),
+           "NMS + emit%s %d | total %d  kept %d\n", img, (int)blockIdx.x, (int)((rec.flags >> 8) & 15u), dq_[0] % 1000000, (int)(dq_[1] - dq_[0]), (int)(dq_[2] - dq_[1]),
            (int)(dq_[3] - dq_[2]), (int)(dq_[4] - dq_[3]), ndq_ > 6 ? " + pass 2" : "", (int)(dq_[ndq_ - 1] - dq_[4]), (int)(dq_[ndq_ - 1] - dq_[0]), kept);
 #endif
 }
@@ -541,16 +540,20 @@ static size_t cell_lds_bytes(const Geom& g) {
 // (Round 4 also built k_detect_stack -- a wave owning a vertical stack of 2 .. 3 cells with pooled quads / survivors, scores kept
 // in place of the image tile and a direct-mode fallback; bit-exact, 7 % fewer instructions per cell, and SLOWER: 6.9 KB of LDS per
 // wave leave 23 instead of 29 waves per CU, 276 vs 241 us.  Commit a461b2d holds it; DESIGN.md 4 has the numbers.)
-hipError_t launch_detect(const Geom& g, const Pyr& p, int nimg, uint32_t* cellCand, int* cellCount, int level0,
-                         int level1, uint8_t* dbgScore, hipStream_t s) {
+hipError_t launch_detect(const Geom& g, const Pyr& p, const CellRec* cellRec, int nimg, uint32_t* cellCand, int* cellCount,
+                         int level0, int level1, uint8_t* dbgScore, hipStream_t s) {
   const size_t lds = cell_lds_bytes(g);
   const int cellBegin = g.lv[level0].cellStart;
   const int cellEnd = level1 < g.nlevels ? g.lv[level1].cellStart : g.totalCells;
   if (cellEnd <= cellBegin) return hipSuccess;
   dim3 grid(cellEnd - cellBegin, nimg);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, g, p, cellCand, cellCount, g_detect_list_cap, cellBegin, dbgScore);
-  };
+  DetectArgs a;
+  a.totalCells = g.totalCells; a.iniTh = g.iniTh; a.minTh = g.minTh;
+  a.tileP = g.tileP; a.tileH = g.tileH; a.scoreH = g.scoreH;
+  a.invTileP = 1.0f / (float)g.tileP;
+  a.listCap = g_detect_list_cap; a.cellBegin = cellBegin;
+  a.pyrImg = g.pyrImg; a.cellImg = g.cellImg;
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a, p, cellRec, cellCand, cellCount, dbgScore); };
   const int tp = (!dbgScore && g.scoreP == g.tileP) ? g.tileP : 0;
   switch (tp) {
     case 44: go(k_detect<false, 44>); break;

@@ -28,6 +28,10 @@ namespace orbx_host {
 
 extern thread_local std::string g_err;  // defined in orbx_api.hip
 void build_coefs(const Geom& g, std::vector<uint4>& xtab, std::vector<int>& yofs, std::vector<short>& yab);   // orbx_api.hip: k_resize's tables
+void build_cell_records(const Geom& g, std::vector<CellRec>& recs);   // orbx_api.hip: k_detect's per-cell records
+void build_yrow(const Geom& g, const std::vector<int>& yofs, std::vector<uint32_t>& yrow);   // k_resize's clamped source row pairs
+void build_resize_records(const Geom& g, const std::vector<uint4>& xtab, const std::vector<uint32_t>& yrow, const std::vector<short>& yab,
+                          std::vector<uint32_t>& tab);   // orbx_api.hip: k_resize's per-tile and per-tile-row records
 inline int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
@@ -321,6 +325,8 @@ struct orbx_extractor {
   DevBuf<int> d_rowStart, d_cellCount, d_cellPrefix, d_candCount, d_selCount, d_slot, d_nOut, d_mono, d_lap, d_yofs, d_sad;
   DevBuf<short> d_yab;
   DevBuf<uint4> d_xtab;  // k_resize's per-column table (build_coefs)
+  DevBuf<uint32_t> d_rsRec;  // k_resize's tile records and tile-row blocks of the configured size (build_resize_records)
+  DevBuf<orbx::CellRec> d_cellRec;  // k_detect's per-cell records of the configured size (build_cell_records)
   DevBuf<int> d_packCtr;    // arrival counter of the single-frame gather workgroups (launch_stereo_match)
   uint32_t packSeq = 0;     // sequence number of the last single stereo frame (hostResults + hr_flag())
   bool packCtrDirty = false; // a fused single-frame launch is (or may be, after a failure) in flight: d_packCtr is cleared before the next one

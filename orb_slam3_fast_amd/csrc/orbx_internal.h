@@ -42,8 +42,40 @@ struct Geom {
   long long pyrImg;              // bytes per image of the internal pyramid block
   long long candImg;             // dense candidate entries per image
   long long cellImg;             // per-cell slot entries per image
-  int levelCell[ORBX_MAX_LEVELS];  // lv[l].cellStart again, contiguous (INT_MAX past the last level): k_detect's level lookup
   LevelDev lv[ORBX_MAX_LEVELS];
+};
+
+// k_detect's front as a table: one record per FAST cell of a configured size, indexed by the cell number over all levels
+// (build_cell_records in orbx_api.hip; a wave fetches its record with one 64-byte scalar load).  Everything here depends only on
+// the image size and the extractor's parameters; the caller's level-0 base and pitches stay kernel arguments.
+constexpr uint32_t kCellReject = 1u;  // the cell holds no detectable pixel (src/ORBextractor.cc:913,919): its count is 0
+constexpr uint32_t kCellWide = 2u;    // all tileP bytes of every ROI row lie inside the level's row: the wide tile loader may run
+constexpr uint32_t kCellL0 = 4u;      // level 0: base and row pitch come from the caller's frames
+struct alignas(64) CellRec {
+  uint32_t xy;          // iniX | iniY << 16: origin of the ROI (cell + 3 px FAST ring each side) in level coordinates
+  uint32_t roi;         // rw | rh << 16: its size; the detectable window is (rw - 6) x (rh - 6)
+  uint32_t flags;       // kCell* | level << 8 | level width << 16
+  uint32_t pitch;       // row pitch of the level in the internal pyramid block
+  uint32_t baseOff;     // byte offset of the ROI's first pixel inside one image's pyramid block (levels >= 1; level 0: of the
+                        // same pixel in the pyramid layout, which the score tap writes)
+  uint32_t outOff;      // entry offset of the cell's slots inside one image's per-cell candidate store
+  uint32_t cellCap;     // slots of the cell
+  uint32_t rounds;      // qpr | dq << 8 | rq << 16: quads per detect row; rows and left-over quads a round of 64 quads advances
+  uint32_t nRounds;     // whole-row rounds: 64 * ceil(dh / dq)
+  uint32_t nScore16;    // 16-byte pieces of the score tile to clear
+  uint32_t actLastLo, actLastHi;   // lanes of the last whole-row round that hold a quad of the window
+  uint32_t killLastA, killLastB;   // threshold patterns of a row's last quad (pixels 0 | 1 and 2 | 3): 0x7C00 past the window
+  float invQpr;         // 1 / qpr
+  uint32_t pad_;
+};
+static_assert(sizeof(CellRec) == 64, "one scalar load");
+// k_detect's per-launch constants (what it used to read from Geom)
+struct DetectArgs {
+  int totalCells, iniTh, minTh;
+  int tileP, tileH, scoreH;      // LDS image / score tile pitch (the same) and rows
+  float invTileP;                // 1 / tileP
+  int listCap, cellBegin;
+  long long pyrImg, cellImg;
 };
 
 // Where the pyramid of the current batch lives.  Level 0 aliases the caller's images.
@@ -98,10 +130,13 @@ hipError_t prepare_resize_plain(int sw, int sh, int dw, int dh);
 hipError_t launch_resize_plain(const uint8_t* src, int sw, int sh, long long sp, long long sip, uint8_t* dst, int dw, int dh,
                                long long dp, long long dip, const uint4* xtab, const uint32_t* yrow, const short* yab, int nimg,
                                hipStream_t s);
+// records: the handle's tile / tile-row table (build_resize_records); nullptr = the kernel derives its bounds itself
 hipError_t launch_resize(const Geom& g, const Pyr& p, int nimg, int level, const uint4* xtab, const uint32_t* yofs /* clamped row pairs */,
-                         const short* yab, hipStream_t s);
-hipError_t launch_detect(const Geom& g, const Pyr& p, int nimg, uint32_t* cellCand, int* cellCount, int level0,
-                         int level1, uint8_t* dbgScore, hipStream_t s);
+                         const short* yab, const uint32_t* records, hipStream_t s);
+int resize_records_layout(const Geom& g, int level, int& tileOff, int& rowOff);
+constexpr uint32_t kTileFast = 1u, kTileWhole = 2u;   // flags of a tile record (k_resize, orbx_kernels.hip)
+hipError_t launch_detect(const Geom& g, const Pyr& p, const CellRec* cellRec, int nimg, uint32_t* cellCand, int* cellCount,
+                         int level0, int level1, uint8_t* dbgScore, hipStream_t s);
 hipError_t launch_octree(const Geom& g, int nimg, const uint32_t* cellCand, const int* cellCount, int* cellPrefix,
                          uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, int level0,
                          int level1, hipStream_t s);

@@ -47,10 +47,13 @@ struct ResizeLv {
   struct { int w, h, pitch, xcoef, ycoef; } D;
   struct { int w, h; } S;
   int sp, l;                      // source row pitch; destination level (1 = the source is the caller's level 0)
-  int nbx, xcdRun;                // tiles per row of tiles; run length of the XCD-aware tile order (<= 1: plain order)
+  int nbx;                        // tiles per row of tiles
   const uint8_t* src; long long srcImg;   // level l-1 of image 0, bytes between images
   uint8_t* dst; long long dstImg;         // level l of image 0
+  const uint32_t* tiles;          // TAB: the level's tile records and tile-row blocks (build_resize_records, orbx_api.hip)
+  const uint32_t* rows;
 };
+constexpr int kResizeXcdRun = 8;  // tiles per XCD run of k_resize's block order (1 = plain order fetched 1.74 x the bytes, round 4)
 // Vertical blend of cv::resize for four pixels: (((b0 * u0) >> 16) + ((b1 * u1) >> 16) + 2) >> 2 with u0 / u1 = the u16 halves of
 // t0 / t1 (horizontal results >> 4, < 2^15) and bb = b0 | b1 << 16 (wave-uniform, an SGPR).  Hand-assembled (the compiler spent
 // 24 instructions per four pixels on it: unpacking shifts, per-pixel shift-and-insert with materialised constants): the products
@@ -75,7 +78,10 @@ __device__ __forceinline__ uint32_t vblend4(uint2 t0, uint2 t1, uint32_t bb, uin
   asm("v_pk_lshrrev_b16 %0, 2, %1 op_sel_hi:[0,1]" : "=v"(w23) : "v"(w23));
   return __builtin_amdgcn_perm(w23, w01, 0x06040200u);
 }
-template <int NDW>
+// TAB: the block's bounds and its rows' constants come from the handle's tables -- one record per destination tile, one block
+// per tile row and wave (round 9: 224 -> 127 scalar instructions per wave; the scalar unit was this kernel's busiest pipe).  The
+// pre-processing plans' single launches (launch_resize_plain) keep the computed front.
+template <int NDW, bool TAB>
 __global__ __launch_bounds__(256) void k_resize(ResizeLv rl, const uint4* __restrict__ xtab,
                                                 const uint32_t* __restrict__ yrow, const short* __restrict__ yab,
                                                 int srcRowsMax, int srcDwMaxRt) {
@@ -90,11 +96,7 @@ __global__ __launch_bounds__(256) void k_resize(ResizeLv rl, const uint4* __rest
   // an XCD, i.e. an L2: the 307-byte source-row segments of x-adjacent blocks meet inside 128-byte lines, and in the plain
   // (x, y, z) grid order those neighbours sat on different XCDs and each fetched the shared line from HBM (k_resize fetched
   // 1.74 x its algorithmic read bytes, profiles/r4e_pmc_traffic.json; k_detect has had the same remap since round 2).
-  const int tIdx = xcd_run_remap_rt((int)blockIdx.x, (int)gridDim.x, (int)blockIdx.z, rl.xcdRun);
-  const int tby = __builtin_amdgcn_readfirstlane((int)(((float)tIdx + 0.5f) * __builtin_amdgcn_rcpf((float)rl.nbx)));
-  const int tbx = tIdx - tby * rl.nbx;
-  const int x0 = tbx * RS_DW, y0 = tby * RS_DR;
-  const int x1 = min(x0 + RS_DW, D.w) - 1, y1 = min(y0 + RS_DR, D.h) - 1;  // last dst column / row of the block
+  const int tIdx = xcd_run_remap<kResizeXcdRun>((int)blockIdx.x, (int)gridDim.x, (int)blockIdx.z);
   const int sp = rl.sp;
   const uint8_t* src = rl.src + (long long)img * rl.srcImg;
   uint32_t* st = reinterpret_cast<uint32_t*>(smem);                        // [srcRowsMax][SDW] dwords
@@ -102,44 +104,74 @@ __global__ __launch_bounds__(256) void k_resize(ResizeLv rl, const uint4* __rest
 #ifdef RS_PROF
   long long tq0 = wall_clock64();
 #endif
-  // yrow[dy] = the two source rows of destination row dy, already clamped to the level (low / high half; built on the host):
-  // no s_max / s_min chains per row on the scalar ALU, this kernel's busiest pipe (round 5)
-  const int rb = (int)(yrow[D.ycoef + y0] & 0xFFFFu);                           // first source row needed
-  const int re = (int)(yrow[D.ycoef + y1] >> 16);                               // last source row needed
-  const int nrows = re - rb + 1;
-  const int cb = (int)xtab[D.xcoef + x0].y;                                     // first source byte (dword aligned)
-  const int ce = min((int)xtab[D.xcoef + x1].x + 1, S.w - 1);
-  const int ndw = ((ce - cb) >> 2) + 1;
+  const int qc = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int x0, rowsHere;        // first dst column of the block; dst rows it holds (RS_DR, fewer in the level's last tile row)
+  int rb, nrows, cb, ndw;  // footprint: first source row, rows, first source byte (dword aligned), dwords per row
+  bool whole, fastGeom;    // every footprint dword lies inside its source row; the footprint suits the fast loader (below)
+  const uint4* xt;         // the block's 256 entries of the x table
+  uint8_t* dstTile;        // the block's first dst row
+  uint32_t vbb[RS_DR / 4]; // rows w, w + 4, ... of the block belong to this wave: coefficient pair of the row and the byte offsets
+  int vr0[RS_DR / 4], vr1[RS_DR / 4];  // of its two source rows in the horizontal pass's output (wave-uniform: scalar loads)
+  constexpr int kFastTrips = 8;
+  if (TAB) {
+    const uint32_t* tr = rl.tiles + 8 * tIdx;
+    xt = xtab + tr[0];
+    x0 = (int)(tr[1] & 0xFFFFu), rowsHere = (int)(tr[1] >> 16);
+    rb = (int)(tr[2] & 0xFFFFu), nrows = (int)(tr[2] >> 16);
+    cb = (int)(tr[3] & 0xFFFFu), ndw = (int)(tr[3] >> 16);
+    whole = (tr[4] & kTileWhole) != 0, fastGeom = (tr[4] & kTileFast) != 0;
+    dstTile = rl.dst + (long long)img * rl.dstImg + tr[5];
+    const uint4* rw4 = reinterpret_cast<const uint4*>(rl.rows) + (4 * (int)tr[6] + w) * (RS_DR / 4);
+#pragma unroll
+    for (int k = 0; k < RS_DR / 4; k++) {
+      const uint4 e = rw4[k];
+      vbb[k] = e.x, vr0[k] = (int)e.y, vr1[k] = (int)e.z;
+    }
+  } else {
+    const int tby = __builtin_amdgcn_readfirstlane((int)(((float)tIdx + 0.5f) * __builtin_amdgcn_rcpf((float)rl.nbx)));
+    const int tbx = tIdx - tby * rl.nbx;
+    const int y0 = tby * RS_DR;
+    x0 = tbx * RS_DW;
+    const int x1 = min(x0 + RS_DW, D.w) - 1, y1 = min(y0 + RS_DR, D.h) - 1;  // last dst column / row of the block
+    rowsHere = y1 - y0 + 1;
+    // yrow[dy] = the two source rows of destination row dy, already clamped to the level (low / high half; built on the host):
+    // no s_max / s_min chains per row on the scalar ALU (round 5)
+    rb = (int)(yrow[D.ycoef + y0] & 0xFFFFu);                            // first source row needed
+    nrows = (int)(yrow[D.ycoef + y1] >> 16) - rb + 1;                    // ... up to the last one
+    cb = (int)xtab[D.xcoef + x0].y;
+    const int ce = min((int)xtab[D.xcoef + x1].x + 1, S.w - 1);
+    ndw = ((ce - cb) >> 2) + 1;
+    // Only a level-0 source (the caller's buffer) may end with its last pixel: then the last dword is read byte-wise.
+    whole = l > 1 || cb + 4 * ndw <= S.w;
+    fastGeom = whole && ndw > 64 && ndw <= 85 && nrows <= 3 * kFastTrips && rb + 3 * kFastTrips + 4 <= S.h;
+    xt = xtab + D.xcoef + x0;
+    dstTile = rl.dst + (long long)img * rl.dstImg + (long long)y0 * D.pitch;
+#pragma unroll
+    for (int k = 0; k < RS_DR / 4; k++) {
+      const int dy = min(y0 + w + 4 * k, D.h - 1);
+      const uint32_t sy = yrow[D.ycoef + dy];
+      vbb[k] = reinterpret_cast<const uint32_t*>(yab)[D.ycoef + dy];
+      vr0[k] = ((int)(sy & 0xFFFFu) - rb) * (RS_DW * 2), vr1[k] = ((int)(sy >> 16) - rb) * (RS_DW * 2);
+    }
+  }
   // Every coefficient the two passes need is fetched HERE, together with the footprint: a block is a chain of dependent
   // memory latencies (tile bounds -> footprint -> column coefficients -> row coefficients), and the kernel's time is that
   // chain times the number of block generations, not bandwidth or issue slots.
-  const int qc = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint32_t sel[4], coef[4];
   int ba[4];  // byte offset, inside a footprint row, of the aligned dword pair that holds S[sx], S[sx + 1]
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    const uint4 e = xtab[D.xcoef + x0 + 4 * qc + j];  // S[sx + 1] is only weighted by a1 != 0 when it exists (build_coefs)
+    const uint4 e = xt[4 * qc + j];  // S[sx + 1] is only weighted by a1 != 0 when it exists (build_coefs)
     ba[j] = (int)e.y - cb;
     sel[j] = e.z;
     coef[j] = e.w;
-  }
-  uint32_t vsy[RS_DR / 4];
-  uint32_t vbb[RS_DR / 4];
-#pragma unroll
-  for (int k = 0; k < RS_DR / 4; k++) {  // rows w, w + 4, ... of the block belong to this wave (wave-uniform: scalar loads)
-    const int dy = min(y0 + w + 4 * k, D.h - 1);
-    vsy[k] = yrow[D.ycoef + dy];
-    vbb[k] = reinterpret_cast<const uint32_t*>(yab)[D.ycoef + dy];
   }
   {
     // Footprint -> LDS.  Thread = (row phase r0, dword column c): rpp = 256 / ndw source rows per pass, so a trip is an
     // offset increment and a load (no per-item index division); all of a thread's global loads are issued before its
     // first LDS store (a plain copy loop serialised one HBM latency per trip).  Rows past the footprint are clamped to its
     // last row on both sides (the same bytes land on the same LDS dword again): no predicates in the loop.
-    // Only a level-0 source (the caller's buffer) may end with its last pixel: then the last dword is read byte-wise.
-    const bool whole = l > 1 || cb + 4 * ndw <= S.w;
-    constexpr int kFastTrips = 8;
-    if (NDW != 0 && whole && ndw > 64 && ndw <= 85 && nrows <= 3 * kFastTrips && rb + 3 * kFastTrips + 4 <= S.h) {
+    if (NDW != 0 && fastGeom) {   // whole, 64 < ndw <= 85, nrows <= 3 * kFastTrips, rb + 3 * kFastTrips + 4 <= S.h
       // The usual block (1.2 pyramid; not the level's last rows or a narrow last column block): 65 .. 85 dwords per footprint row,
       // i.e. three rows per trip of the 256 threads, so the trips are SCALAR base increments of the loads and immediate offsets of
       // the LDS stores -- no per-trip address arithmetic, no clamps, and straight-line code (inside the general loops below the
@@ -275,16 +307,14 @@ __global__ __launch_bounds__(256) void k_resize(ResizeLv rl, const uint4* __rest
     if (dx < D.w) {                            // lane-invariant over the rows: tested once, the row loop only has uniform exits
       const uint8_t* htq = ht8 + 8 * qx;
       // wave-uniform: the stores take row base + 32-bit lane offset; the row base advances by four rows per trip
-      uint8_t* dstRow = rl.dst + (long long)img * rl.dstImg + (long long)(y0 + w) * D.pitch;
+      uint8_t* dstRow = dstTile + (long long)w * D.pitch;
       const long long dstStep = 4ll * D.pitch;
 #pragma unroll
       for (int k = 0; k < RS_DR / 4; k++) {
-        const int dy = y0 + w + 4 * k;
-        if (dy >= D.h) break;
+        if (w + 4 * k >= rowsHere) break;
         const uint32_t bb = vbb[k];
-        const int r0 = (int)(vsy[k] & 0xFFFFu) - rb, r1 = (int)(vsy[k] >> 16) - rb;
-        const uint2 t0 = *reinterpret_cast<const uint2*>(htq + r0 * (RS_DW * 2));
-        const uint2 t1 = *reinterpret_cast<const uint2*>(htq + r1 * (RS_DW * 2));
+        const uint2 t0 = *reinterpret_cast<const uint2*>(htq + vr0[k]);
+        const uint2 t1 = *reinterpret_cast<const uint2*>(htq + vr1[k]);
         const uint32_t outw = vblend4(t0, t1, bb, kRound);
         // scalar base + 32-bit lane offset (left to itself the compiler folds dx into the pointer and multiplies dy * pitch
         // per lane in 64 bits)
@@ -294,8 +324,8 @@ __global__ __launch_bounds__(256) void k_resize(ResizeLv rl, const uint4* __rest
     }
   }
 #ifdef RS_PROF
-  if (tid == 0 && blockIdx.z == 7 && tbx == 1 && (tby % 9) == 3)
-    printf("L%d by %d: load %d wait %d horiz %d wait %d vert %d (x10ns)\n", l, tby, (int)(tq1 - tq0), (int)(tq2 - tq1),
+  if (tid == 0 && blockIdx.z == 7 && x0 == RS_DW && ((tIdx / rl.nbx) % 9) == 3)
+    printf("L%d by %d: load %d wait %d horiz %d wait %d vert %d (x10ns)\n", l, tIdx / rl.nbx, (int)(tq1 - tq0), (int)(tq2 - tq1),
            (int)(tq3 - tq2), (int)(tq4 - tq3), (int)(wall_clock64() - tq4));
 #endif
 }
@@ -320,8 +350,22 @@ size_t resize_lds_bytes(const Geom& g) {
 }
 
 constexpr int kResizeNdw = 80;  // footprint pitch of the compile-time instantiation (every level of a 1.2 pyramid)
+// dword offsets of a level's tile records (8 dwords per tile) and tile-row blocks (4 waves x 4 rows x 4 dwords per tile row) in the
+// handle's table; returns the table's size with level = nlevels
+int resize_records_layout(const Geom& g, int level, int& tileOff, int& rowOff) {
+  int n = 0;
+  tileOff = rowOff = 0;
+  for (int l = 1; l < g.nlevels && l <= level; l++) {
+    const int nbx = (g.lv[l].w + RS_DW - 1) / RS_DW, nby = (g.lv[l].h + RS_DR - 1) / RS_DR;
+    tileOff = n;
+    rowOff = n + 8 * nbx * nby;
+    n = rowOff + 4 * RS_DR * nby;
+  }
+  return n;
+}
+
 hipError_t launch_resize(const Geom& g, const Pyr& p, int nimg, int level, const uint4* xtab, const uint32_t* yofs,
-                         const short* yab, hipStream_t s) {
+                         const short* yab, const uint32_t* records, hipStream_t s) {
   const LevelDev& D = g.lv[level];
   int srcRowsMax, srcDwMax;
   size_t lds;
@@ -329,10 +373,15 @@ hipError_t launch_resize(const Geom& g, const Pyr& p, int nimg, int level, const
   const int nbx = (D.w + RS_DW - 1) / RS_DW, nby = (D.h + RS_DR - 1) / RS_DR;
   dim3 grid(nbx * nby, 1, nimg);
   const LevelDev& S = g.lv[level - 1];
-  static const int xcdRun = getenv("ORBX_RESIZE_XCD_RUN") ? atoi(getenv("ORBX_RESIZE_XCD_RUN")) : 8;   // A/B aid (1 = plain order)
   ResizeLv rl;
   rl.nbx = nbx;
-  rl.xcdRun = xcdRun;
+  rl.tiles = rl.rows = nullptr;
+  if (records) {
+    int tileOff, rowOff;
+    resize_records_layout(g, level, tileOff, rowOff);
+    rl.tiles = records + tileOff;
+    rl.rows = records + rowOff;
+  }
   rl.D.w = D.w; rl.D.h = D.h; rl.D.pitch = D.pitch; rl.D.xcoef = D.xcoef; rl.D.ycoef = D.ycoef;
   rl.S.w = S.w; rl.S.h = S.h;
   rl.l = level;
@@ -342,10 +391,12 @@ hipError_t launch_resize(const Geom& g, const Pyr& p, int nimg, int level, const
     rl.sp = S.pitch; rl.src = p.pyr + S.off; rl.srcImg = g.pyrImg;
   }
   rl.dst = p.pyr + D.off; rl.dstImg = g.pyrImg;
-  if (srcDwMax == kResizeNdw)
-    hipLaunchKernelGGL(k_resize<kResizeNdw>, grid, dim3(256), lds, s, rl, xtab, yofs, yab, srcRowsMax, srcDwMax);
-  else
-    hipLaunchKernelGGL(k_resize<0>, grid, dim3(256), lds, s, rl, xtab, yofs, yab, srcRowsMax, srcDwMax);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, rl, xtab, yofs, yab, srcRowsMax, srcDwMax); };
+  if (srcDwMax == kResizeNdw) {
+    if (records) go(k_resize<kResizeNdw, true>); else go(k_resize<kResizeNdw, false>);
+  } else {
+    if (records) go(k_resize<0, true>); else go(k_resize<0, false>);
+  }
   return hipGetLastError();
 }
 
@@ -367,8 +418,8 @@ static Geom resize_plain_geom(int sw, int sh, int dw, int dh, long long dp, long
 size_t resize_plain_lds(int sw, int sh, int dw, int dh) { return resize_lds_bytes(resize_plain_geom(sw, sh, dw, dh, 0, 0)); }
 hipError_t prepare_resize_plain(int sw, int sh, int dw, int dh) {
   const size_t lds = std::max<size_t>(resize_plain_lds(sw, sh, dw, dh), 1024);
-  hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<0>), lds);
-  if (e == hipSuccess) e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<kResizeNdw>), lds);
+  hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<0, false>), lds);
+  if (e == hipSuccess) e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<kResizeNdw, false>), lds);
   return e;
 }
 hipError_t launch_resize_plain(const uint8_t* src, int sw, int sh, long long sp, long long sip, uint8_t* dst, int dw, int dh,
@@ -377,7 +428,7 @@ hipError_t launch_resize_plain(const uint8_t* src, int sw, int sh, long long sp,
   const Geom g = resize_plain_geom(sw, sh, dw, dh, dp, dip);
   Pyr p{};
   p.l0 = src; p.l0Row = sp; p.l0Img = sip; p.pyr = dst;
-  return launch_resize(g, p, nimg, 1, xtab, yrow, yab, s);
+  return launch_resize(g, p, nimg, 1, xtab, yrow, yab, nullptr, s);
 }
 
 // ================================================================================================ octree
@@ -2679,9 +2730,9 @@ hipError_t prepare_kernels(const Geom& g) {
   hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_octree), octree_lds_bytes(g));
   if (e != hipSuccess) return e;
   if (g.nlevels > 1) {
-    e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<0>), std::max<size_t>(resize_lds_bytes(g), 1024));
+    e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<0, true>), std::max<size_t>(resize_lds_bytes(g), 1024));
     if (e != hipSuccess) return e;
-    e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<kResizeNdw>), std::max<size_t>(resize_lds_bytes(g), 1024));
+    e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<kResizeNdw, true>), std::max<size_t>(resize_lds_bytes(g), 1024));
     if (e != hipSuccess) return e;
   }
   return prepare_detect(g);
