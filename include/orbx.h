@@ -1123,6 +1123,75 @@ int orbx_create_new_map_points(int device, const orbx_np_keyframe* kf1, const or
                                int32_t* matches12, uint8_t* status, float* x3d, uint8_t* point_stereo, uint8_t* has_map_point1_out);
 
 
+/* ---- key-frame database (place recognition) -------------------------------------------------------------------------------
+ * ORB_SLAM3::KeyFrameDatabase (src/KeyFrameDatabase.cc) resident on the device: add / erase / clear / clearMap (:37-97),
+ * DetectRelocalizationCandidates (:742-856) and DetectNBestCandidates (:612-740).  The BoW vector of every key frame lies in a
+ * slot of a forward store (no inverted file); a query scores all slots at once.  Candidate lists, common-word counts, scores
+ * and accumulated scores are those of the reference bit for bit:
+ *  - the order of lKFsSharingWords is the order of (smallest word id shared with the query, sequence number of the add);
+ *  - the score is DBoW2::L1Scoring::score(query, key frame), the sequential double sum in ascending word id, narrowed to float;
+ *  - the covisibility accumulation adds the score a neighbour HOLDS: this query's if the neighbour passed the 0.8 word gate,
+ *    otherwise what the last query of the same flavour that scored it left (0 after add), as the reference's mRelocScore /
+ *    mPlaceRecognitionScore members do.  The two flavours keep separate scores.
+ * What stays with the caller: key frames are ints (mnId) and maps are ints (Map::mnId); the ten best covisible key frames of a
+ * key frame (GetBestCovisibilityKeyFrames(10)) are handed over with orbx_kfdb_set_covisibles whenever UpdateConnections changes
+ * them, and belong to the database entry (erase drops them); bad key frames are erased (KeyFrame::SetBadFlag does); bad maps and
+ * the query's connected key frames are per-call lists.  Calls on one database must not overlap. */
+typedef struct orbx_kfdb orbx_kfdb;
+/* Optional per-query records of a detect call, in the order of the reference's lScoreAndMatch (every key frame that passed
+ * the word gate).  Arrays hold `cap` entries per query ([n_frames][cap] for the batched entry), n_scored / max_common_words one
+ * per query; any pointer may be NULL.  n_scored may exceed cap: only the first cap records are written then. */
+typedef struct orbx_kfdb_details {
+  int32_t cap;
+  int32_t* n_scored;
+  int32_t* max_common_words;
+  int32_t* kf_id;          /* the scored key frame */
+  int32_t* common_words;   /* mnRelocWords / mnPlaceRecognitionWords */
+  float* score;            /* si */
+  float* acc_score;        /* accScore */
+  int32_t* best_kf_id;     /* pBestKF */
+} orbx_kfdb_details;
+/* A database for up to max_keyframes key frames of up to max_words_per_keyframe words each (12 bytes of device memory per
+ * word) on the vocabulary's device.  ORBX_E_UNSUPPORTED for a vocabulary whose scoring is not L1_NORM (0).  _create_sized takes
+ * the two facts the database needs from a vocabulary: its number of words and its scoring type. */
+int orbx_kfdb_create(const orbx_vocabulary* voc, int max_keyframes, int max_words_per_keyframe, orbx_kfdb** out);
+int orbx_kfdb_create_sized(int device, int n_vocabulary_words, int scoring, int max_keyframes, int max_words_per_keyframe,
+                           orbx_kfdb** out);
+void orbx_kfdb_destroy(orbx_kfdb* db);
+int orbx_kfdb_size(const orbx_kfdb* db);   /* key frames in the database, or a negative error */
+/* Measurement aid (tools/bench_kfdb.py): on > 0 brackets the device work of every following detect call -- stage 1, the tails
+ * and the copy back -- with two events on the database's stream, on = 0 stops, on < 0 leaves the setting.  last_ms (may be NULL)
+ * receives the elapsed time of the last bracketed call, -1 before the first. */
+int orbx_kfdb_profile(orbx_kfdb* db, int on, float* last_ms);
+/* KeyFrameDatabase::add with pKF->mBowVec as host arrays: strictly ascending word ids below the vocabulary's word count
+ * (ORBX_E_BADARG otherwise, and for kf_id < 0 or already present); ORBX_E_CAPACITY when the database is full or n_words exceeds
+ * max_words_per_keyframe.  The key frame's stored scores start at 0 and its covisible list is empty. */
+int orbx_kfdb_add(orbx_kfdb* db, int kf_id, int map_id, const uint32_t* word_ids, const double* word_values, int n_words);
+/* The same with the BoW vector of image `image` of the handle's last orbx_bow_transform_batch, copied device to device. */
+int orbx_kfdb_add_from_batch(orbx_kfdb* db, orbx_extractor* ex, int image, int kf_id, int map_id);
+int orbx_kfdb_erase(orbx_kfdb* db, int kf_id);      /* ORBX_E_BADARG when absent */
+int orbx_kfdb_clear(orbx_kfdb* db);
+int orbx_kfdb_clear_map(orbx_kfdb* db, int map_id); /* returns the number of key frames removed */
+/* best10 [n][10], -1 padded: GetBestCovisibilityKeyFrames(10) of key frames kf_ids[0..n) (all in the database, else
+ * ORBX_E_BADARG and nothing changes).  Listed ids that are not in the database are ignored by the queries until they are. */
+int orbx_kfdb_set_covisibles(orbx_kfdb* db, int n, const int32_t* kf_ids, const int32_t* best10);
+/* DetectRelocalizationCandidates(F, pMap): the query's BoW vector (host arrays, ascending, at most 8192 words) and map.
+ * candidates[0 .. min(*n, cap)) = vpRelocCandidates; *n is the full count, ORBX_E_CAPACITY when it exceeds cap. */
+int orbx_kfdb_detect_relocalization_candidates(orbx_kfdb* db, const uint32_t* word_ids, const double* word_values, int n_words,
+                                               int map_id, int32_t* candidates, int cap, int32_t* n, const orbx_kfdb_details* details);
+/* The same for frames [first_image, first_image + n_frames) of the handle's last orbx_bow_transform_batch, read in place:
+ * candidates [n_frames][cap], n [n_frames].  The results are those of n_frames single calls made in frame order. */
+int orbx_kfdb_detect_relocalization_candidates_batch(orbx_kfdb* db, orbx_extractor* ex, int first_image, int n_frames,
+                                                     const int32_t* map_ids, int32_t* candidates, int cap, int32_t* n,
+                                                     const orbx_kfdb_details* details);
+/* DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates): connected_ids = pKF->GetConnectedKeyFrames() (ids not in
+ * the database are ignored), bad_map_ids = the maps whose IsBad() holds.  loop / merge hold n_candidates entries each. */
+int orbx_kfdb_detect_n_best_candidates(orbx_kfdb* db, const uint32_t* word_ids, const double* word_values, int n_words, int map_id,
+                                       const int32_t* connected_ids, int n_connected, const int32_t* bad_map_ids, int n_bad_maps,
+                                       int n_candidates, int32_t* loop, int32_t* n_loop, int32_t* merge, int32_t* n_merge,
+                                       const orbx_kfdb_details* details);
+
+
 /* ---- measurement ------------------------------------------------------------------------------------ */
 
 /* Per-kernel timing with HIP events recorded on the handle's own stream around every kernel launch (the

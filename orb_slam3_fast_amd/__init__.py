@@ -138,6 +138,21 @@ def lib():
         L.orbx_bow_transform_batch.argtypes = [vp, vp, i]
         L.orbx_bow_results_device.argtypes = [vp] + [C.POINTER(vp)] * 6 + [C.POINTER(i)]
         L.orbx_bow_download.argtypes = [vp, i, vp, vp, C.POINTER(i), vp, vp, vp, C.POINTER(i), i]
+        L.orbx_kfdb_create.argtypes = [vp, i, i, C.POINTER(vp)]
+        L.orbx_kfdb_create_sized.argtypes = [i, i, i, i, i, C.POINTER(vp)]
+        L.orbx_kfdb_destroy.argtypes = [vp]
+        L.orbx_kfdb_destroy.restype = None
+        L.orbx_kfdb_size.argtypes = [vp]
+        L.orbx_kfdb_profile.argtypes = [vp, i, C.POINTER(f)]
+        L.orbx_kfdb_add.argtypes = [vp, i, i, vp, vp, i]
+        L.orbx_kfdb_add_from_batch.argtypes = [vp, vp, i, i, i]
+        L.orbx_kfdb_erase.argtypes = [vp, i]
+        L.orbx_kfdb_clear.argtypes = [vp]
+        L.orbx_kfdb_clear_map.argtypes = [vp, i]
+        L.orbx_kfdb_set_covisibles.argtypes = [vp, i, vp, vp]
+        L.orbx_kfdb_detect_relocalization_candidates.argtypes = [vp, vp, vp, i, i, vp, i, C.POINTER(i), vp]
+        L.orbx_kfdb_detect_relocalization_candidates_batch.argtypes = [vp, vp, i, i, vp, vp, i, vp, vp]
+        L.orbx_kfdb_detect_n_best_candidates.argtypes = [vp, vp, vp, i, i, vp, i, vp, i, i, vp, C.POINTER(i), vp, C.POINTER(i), vp]
         L.orbx_search_by_bow.argtypes = [i, vp, vp, vp, i, vp, vp, vp, i, vp, vp, vp, i, vp, vp, i, i, f, i, vp]
         L.orbx_search_by_projection_fisheye_batch.argtypes = [vp, i, i, i, f, f, f, f, vp, vp, vp, i, f, i, f, f, vp, vp, vp, vp, vp, vp]
         L.orbx_search_by_projection_frame_fisheye_batch.argtypes = [vp, i, i, i, f, f, f, f, vp, vp, vp, i, i, vp, vp, vp, vp]
@@ -1420,6 +1435,130 @@ class ORBVocabulary:
         nf = _check(lib().orbx_bow_download(extractor._h, image, _p(words), _p(values), C.byref(nw), _p(nodes), _p(start), _p(feats),
                                             C.byref(nn), cap))
         return (words[:nw.value].copy(), values[:nw.value].copy()), (nodes[:nn.value].copy(), start[:nn.value + 1].copy(), feats[:nf].copy())
+
+
+class _KfdbDetails(C.Structure):   # orbx_kfdb_details
+    _fields_ = [("cap", C.c_int32), ("n_scored", C.c_void_p), ("max_common_words", C.c_void_p), ("kf_id", C.c_void_p),
+                ("common_words", C.c_void_p), ("score", C.c_void_p), ("acc_score", C.c_void_p), ("best_kf_id", C.c_void_p)]
+
+
+KFDB_DETAIL_DTYPE = np.dtype([("kf_id", "<i4"), ("common_words", "<i4"), ("score", "<f4"), ("acc_score", "<f4"), ("best_kf_id", "<i4")])
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM3::KeyFrameDatabase (src/KeyFrameDatabase.cc) on the device.  Key frames and maps are ints (mnId); a BoW vector is
+    the (word_ids, values) pair ORBVocabulary.transform returns.  The covisible lists (GetBestCovisibilityKeyFrames(10)), the
+    query's connected key frames and the bad maps stay with the caller and are handed over (set_covisibles, arguments)."""
+
+    def __init__(self, voc, max_keyframes, max_words):
+        self._h = None
+        h = C.c_void_p()
+        _check(lib().orbx_kfdb_create(voc._h if voc is not None else None, max_keyframes, max_words, C.byref(h)))
+        self._h = h
+        self.max_keyframes, self.max_words = max_keyframes, max_words
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orbx_kfdb_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __len__(self):
+        return _check(lib().orbx_kfdb_size(self._h))
+
+    @staticmethod
+    def _bow(bow):
+        w, v = np.ascontiguousarray(bow[0], np.uint32), np.ascontiguousarray(bow[1], np.float64)
+        if w.ndim != 1 or w.shape != v.shape:
+            raise ValueError("a BoW vector is (word_ids[n], values[n])")
+        return w, v
+
+    def profile(self, on=-1):
+        """Switches the device-event bracket of the detect calls (on = True / False) and returns the last call's milliseconds."""
+        ms = C.c_float()
+        _check(lib().orbx_kfdb_profile(self._h, int(on), C.byref(ms)))
+        return ms.value
+
+    def add(self, kf_id, map_id, bow):
+        w, v = self._bow(bow)
+        _check(lib().orbx_kfdb_add(self._h, kf_id, map_id, _p(w), _p(v), len(w)))
+
+    def add_from_batch(self, extractor, image, kf_id, map_id):
+        """add() with the BoW vector of `image` of the extractor's last ORBVocabulary.transform_batch (device to device)."""
+        _check(lib().orbx_kfdb_add_from_batch(self._h, extractor._h, image, kf_id, map_id))
+
+    def erase(self, kf_id):
+        _check(lib().orbx_kfdb_erase(self._h, kf_id))
+
+    def clear(self):
+        _check(lib().orbx_kfdb_clear(self._h))
+
+    def clearMap(self, map_id):
+        return _check(lib().orbx_kfdb_clear_map(self._h, map_id))
+
+    def set_covisibles(self, kf_ids, best10):
+        """best10[i] = up to ten key-frame ids, GetBestCovisibilityKeyFrames(10) of kf_ids[i]."""
+        ids = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        b = np.full((len(ids), 10), -1, np.int32)
+        for r, row in enumerate(best10):
+            row = np.asarray(row, np.int32).reshape(-1)[:10]
+            b[r, :len(row)] = row
+        _check(lib().orbx_kfdb_set_covisibles(self._h, len(ids), _p(ids), _p(b)))
+
+    def _details(self, nq, want):
+        if not want:
+            return None, None
+        cap = max(len(self), 1)
+        a = {"n": np.zeros(nq, np.int32), "max": np.zeros(nq, np.int32), "kf": np.zeros((nq, cap), np.int32),
+             "words": np.zeros((nq, cap), np.int32), "score": np.zeros((nq, cap), np.float32), "acc": np.zeros((nq, cap), np.float32),
+             "best": np.zeros((nq, cap), np.int32)}
+        d = _KfdbDetails(cap, *(a[k].ctypes.data for k in ("n", "max", "kf", "words", "score", "acc", "best")))
+        return a, d
+
+    @staticmethod
+    def _detail_records(a, q):
+        rec = np.zeros(int(a["n"][q]), KFDB_DETAIL_DTYPE)
+        for name, key in (("kf_id", "kf"), ("common_words", "words"), ("score", "score"), ("acc_score", "acc"), ("best_kf_id", "best")):
+            rec[name] = a[key][q, :len(rec)]
+        return {"max_common_words": int(a["max"][q]), "scored": rec}
+
+    def DetectRelocalizationCandidates(self, bow, map_id, details=False):
+        """-> vpRelocCandidates as a list of ids [, {"max_common_words", "scored": records in the order of lScoreAndMatch}]."""
+        w, v = self._bow(bow)
+        cap = max(len(self), 1)
+        cand, n = np.zeros(cap, np.int32), C.c_int()
+        a, d = self._details(1, details)
+        _check(lib().orbx_kfdb_detect_relocalization_candidates(self._h, _p(w), _p(v), len(w), map_id, _p(cand), cap, C.byref(n),
+                                                                C.byref(d) if d else None))
+        out = [int(x) for x in cand[:n.value]]
+        return (out, self._detail_records(a, 0)) if details else out
+
+    def DetectRelocalizationCandidatesBatch(self, extractor, first_image, map_ids, details=False):
+        """One DetectRelocalizationCandidates per frame of the extractor's last transform_batch, frames first_image .. +len(map_ids),
+        in frame order, with the queries read on the device."""
+        maps = np.ascontiguousarray(map_ids, np.int32).reshape(-1)
+        nq, cap = len(maps), max(len(self), 1)
+        cand, n = np.zeros((nq, cap), np.int32), np.zeros(nq, np.int32)
+        a, d = self._details(nq, details)
+        _check(lib().orbx_kfdb_detect_relocalization_candidates_batch(self._h, extractor._h, first_image, nq, _p(maps), _p(cand), cap,
+                                                                      _p(n), C.byref(d) if d else None))
+        out = [[int(x) for x in cand[q, :n[q]]] for q in range(nq)]
+        return (out, [self._detail_records(a, q) for q in range(nq)]) if details else out
+
+    def DetectNBestCandidates(self, bow, map_id, connected_ids, nNumCandidates, bad_map_ids=(), details=False):
+        """-> (vpLoopCand, vpMergeCand) [, details]."""
+        w, v = self._bow(bow)
+        conn = np.ascontiguousarray(list(connected_ids), np.int32).reshape(-1)
+        bad = np.ascontiguousarray(list(bad_map_ids), np.int32).reshape(-1)
+        k = max(int(nNumCandidates), 1)
+        loop, merge, nl, nm = np.zeros(k, np.int32), np.zeros(k, np.int32), C.c_int(), C.c_int()
+        a, d = self._details(1, details)
+        _check(lib().orbx_kfdb_detect_n_best_candidates(self._h, _p(w), _p(v), len(w), map_id, _p(conn), len(conn), _p(bad), len(bad),
+                                                        int(nNumCandidates), _p(loop), C.byref(nl), _p(merge), C.byref(nm),
+                                                        C.byref(d) if d else None))
+        out = ([int(x) for x in loop[:nl.value]], [int(x) for x in merge[:nm.value]])
+        return (out[0], out[1], self._detail_records(a, 0)) if details else out
 
 
 def SearchByBoW(kf_fv, kf_kps, kf_desc, kf_valid, f_fv, f_kps, f_desc, n_left_f=-1, nnratio=0.7, check_ori=True, device=0):

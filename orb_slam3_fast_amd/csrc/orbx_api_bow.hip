@@ -4,19 +4,7 @@
 extern "C" {
 
 // ---- bag of words -------------------------------------------------------------------------------------------
-struct orbx_vocabulary {
-  int device = 0, k = 0, L = 0, scoring = 0, weighting = 0, nNodes = 0, nWords = 0;
-  DevBuf<int> childStart, children, wordId;
-  DevBuf<uint32_t> desc;
-  DevBuf<double> weight;
-  BowVoc view() const {
-    BowVoc v{};
-    v.childStart = childStart.p; v.children = children.p; v.desc = desc.p; v.weight = weight.p; v.wordId = wordId.p;
-    v.L = L; v.nNodes = nNodes; v.scoring = scoring; v.weighting = weighting;
-    return v;
-  }
-};
-
+// (struct orbx_vocabulary: orbx_host.h -- the key-frame database reads its size and scoring)
 int orbx_vocabulary_create(int device, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
                            const uint8_t* is_leaf, const uint8_t* descriptors, const double* weights, orbx_vocabulary** out) {
   if (!out) return fail(ORBX_E_BADARG, "null argument");

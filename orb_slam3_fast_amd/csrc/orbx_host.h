@@ -411,6 +411,20 @@ struct orbx_extractor {
   }
 };
 
+// the vocabulary handle (orbx_api_bow.hip)
+struct orbx_vocabulary {
+  int device = 0, k = 0, L = 0, scoring = 0, weighting = 0, nNodes = 0, nWords = 0;
+  DevBuf<int> childStart, children, wordId;
+  DevBuf<uint32_t> desc;
+  DevBuf<double> weight;
+  BowVoc view() const {
+    BowVoc v{};
+    v.childStart = childStart.p; v.children = children.p; v.desc = desc.p; v.weight = weight.p; v.wordId = wordId.p;
+    v.L = L; v.nNodes = nNodes; v.scoring = scoring; v.weighting = weighting;
+    return v;
+  }
+};
+
 namespace orbx_host {
 // the whole extraction pipeline of n device-resident images on ex->stream (orbx_api.hip)
 int enqueue_extract(orbx_extractor* ex, const uint8_t* d_images, int n, int w, int h, ptrdiff_t row_pitch,

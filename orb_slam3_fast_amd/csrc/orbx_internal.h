@@ -281,6 +281,40 @@ struct BowMatchArgs {
 hipError_t launch_bow_match(const BowMatchArgs& a, hipStream_t s);
 hipError_t launch_bow_match_batch(const BowMatchArgs* d_frames, int nFrames, int maxKfNodes, int maxNF, int checkOri, hipStream_t s);
 
+// ---- key-frame database (KeyFrameDatabase.cc: place recognition) ------------------------------------------------------------
+// Forward store: slot s holds a key frame's ascending word ids / values at words + s * maxWords; seq 0 marks a free slot.
+struct KfdbSlot { int kfId, mapId; uint32_t seq; int nWords; };
+struct KfdbEntry { unsigned long long key; int slot, pad; };   // key = smallest shared word id << 32 | add sequence number
+constexpr int kKfdbNeigh = 10;          // GetBestCovisibilityKeyFrames(10)
+constexpr int kKfdbHdr = 8;             // per query: [0] maxCommonWords [1] scored key frames [2] candidates [3] merge candidates [4] append counter
+struct KfdbStore {
+  const uint32_t* words; const double* values; const KfdbSlot* slots; const int* neigh;   // neigh [slot][10]: slots or -1
+  int maxWords, hi;                     // slots [0, hi) are or were in use
+};
+// Stage 1, all queries of a call: query q = qCounts[q * qCountStride] words (clamped to qCap) at qWords / qValues + q * qPitch.
+// Rows [q][hi] of common-word counts, smallest shared word ids and L1 scores; zeroes hdr + q * hdrPitch.
+struct KfdbScoreArgs {
+  KfdbStore st;
+  const uint32_t* qWords; const double* qValues; const int* qCounts; long long qPitch; int qCountStride, qCap;
+  int shift;                            // (vocabulary words - 1) >> shift < 4096: the buckets of the query's search table
+  int* words; uint32_t* first; float* score;
+  int* hdr; long long hdrPitch;
+};
+hipError_t launch_kfdb_score(const KfdbScoreArgs& a, int nQueries, hipStream_t s);
+// Stage 2, one query: gate, commit into the flavour's persistent scores, covisibility accumulation, order, selection.
+struct KfdbTailArgs {
+  KfdbStore st;
+  const int* words; const uint32_t* first; const float* score;   // the query's stage-1 rows
+  float* persist;                       // mRelocScore / mPlaceRecognitionScore per slot
+  const int* conn; int nConn;           // ascending slots of the key frames connected to the query (N-best)
+  const int* badMaps; int nBad;
+  int queryMap, nbest, nCand, cap;
+  int* hdr; KfdbEntry* list; unsigned long long* order; int* firstIdx;
+  int* cand; int* merge;                // [cap] each
+  int* detKf; int* detWords; float* detScore; float* detAcc; int* detBest; int* bestSlot;   // [hi] each, list order
+};
+hipError_t launch_kfdb_tail(const KfdbTailArgs& a, hipStream_t s);
+
 // Results of up to two images gathered into the handle's PINNED host block by one kernel (the single-frame host entries
 // orbx_extract / orbx_extract_stereo): counts and mono indices, then the first n_i keypoint records / descriptor rows of every
 // image and the left image's uRight / depth -- count-trimmed, written straight over PCIe, instead of six D2H copies.
