@@ -1016,6 +1016,100 @@ int orbx_mlpnp_iterate_batch(orbx_extractor* ex, int n_problems, const int32_t* 
                              orbx_mlpnp_state* states, uint8_t* best_masks, orbx_mlpnp_result* results, uint8_t* inliers,
                              int32_t* hyp_inliers);
 
+/* ---- loop-closing Sim3 (Sim3Solver RANSAC) -------------------------------------------------------------- */
+
+/* Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h; LoopClosing::DetectCommonRegionsFromBoW, src/LoopClosing.cc:761-779): the
+ * RANSAC of `iterate` (:147-281) over triples of correspondences -- ComputeSim3 (:296-396: Horn's closed form) and CheckInliers
+ * (:398-418: both reprojections against the integer thresholds, no depth test) -- on the device, three launches for any number of
+ * solvers: prepare (the constructor, :34-118: the ordered correspondence list, X3Dc1 = Rcw1 Xw1 + tcw1 and X3Dc2 in float, their
+ * projections, mvnMaxError = 9.210 * mvLevelSigma2[octave] TRUNCATED to an integer as the reference's vector<size_t> does),
+ * hypotheses (one wave per (solver, triple): every triple the call could reach is solved and scored), replay (one workgroup per
+ * solver takes the decisions of the serial loop: `>=` replaces the best, so a later tie wins; `> min_inliers` converges).
+ * CheckInliers is float arithmetic in the reference's expression order.  Deterministic: the same bits on every run, and problem
+ * p of the batch entry gives the bits of the one-shot entry on the same data.
+ *
+ * The call site passes a non-empty vpKeyFrameMatchedMP, so pKFm is pKF2 for every correspondence; the caller resolves each map
+ * point's index in its key frame and hands over the octave of that key point.  matched[i1] != 0 <=> vpMatched12[i1] is set, key
+ * frame 1 has a map point at i1, neither point is bad and both indices are >= 0.
+ *
+ * Deliberate differences from the reference:
+ *  - the triples are an INPUT (`sets`, [n_sets][3] indices into the correspondence list = the i1 with matched[i1] != 0, ascending).
+ *    The reference draws them with rand(); csrc/Sim3Solver.h and the Python wrapper draw them the reference's way from the
+ *    host's libc.  Set j is the j-th pass of this call's loop; the call reads min(max_iterations - state.iterations,
+ *    call_iterations) sets and n_sets must be at least that.  An index outside the list or repeated within its set is
+ *    ORBX_E_BADARG.
+ *  - Horn's solve (centroids, M, the 4 x 4 N, its eigenvector by cyclic Jacobi rotations, the rotation, scale and translation) is
+ *    double arithmetic on the float points; R, t and s are then narrowed to float, and T12 = [s R | t], T21 = [(1 / s) R^T |
+ *    -(1 / s) R^T t] are formed in float from the narrowed values.  The reference solves in float with EigenSolver<Matrix4f>,
+ *    which moves a squared reprojection error by up to 3.5e-3 of itself; the double solve leaves 5.9e-5 of a threshold.
+ *  - the solver's members that survive a call (mnIterations, mnBestInliers, mBestRotation / Translation / Scale, mvbBestInliers)
+ *    are the in/out `state` and `best_mask`; a zeroed state is a fresh solver.  state.best_inliers must equal the number of
+ *    correspondences flagged in best_mask (ORBX_E_BADARG otherwise).
+ *  - a call that does not converge returns the best hypothesis the STATE knows (R12, t12, s12, T12), also when no hypothesis of
+ *    this call reached the carried best_inliers -- the bConverge overload of the reference returns an uninitialised matrix there,
+ *    the other overload the identity.  A solver that has never run a pass returns the identity.
+ *  - the first-wins merge of the covisibles' SearchByBoW lists (src/LoopClosing.cc:736-749) needs map-point identity and stays
+ *    with the caller.
+ * Out of contract: a triple whose two point sets are bitwise identical (|v| == 0 exactly: 0 / 0 in the reference too); the call
+ * returns, with results unspecified. */
+typedef struct orbx_sim3_params {
+  int32_t model1;          /* camera of key frame 1: ORBX_CAMERA_PINHOLE | ORBX_CAMERA_KB8 */
+  float cam1[8];           /* fx fy cx cy, then k0..k3 (KB8; not read for pinhole) */
+  int32_t model2;          /* camera of key frame 2 */
+  float cam2[8];
+  float kb8_precision;     /* KannalaBrandt8::precision (validated for KB8 cameras; project does not read it) */
+  int32_t fix_scale;       /* mbFixScale: s = 1 */
+  int32_t min_inliers;     /* mRansacMinInliers (15 at the call site), >= 3 */
+  int32_t max_iterations;  /* mRansacMaxIts as SetRansacParameters adjusted it (orbx_sim3_ransac_parameters), in [1, 4096] */
+  int32_t call_iterations; /* iterate's nIterations (20 at the call site), in [0, 4096] */
+} orbx_sim3_params;        /* 92 bytes */
+typedef struct orbx_sim3_state {
+  int32_t iterations;      /* mnIterations */
+  int32_t best_inliers;    /* mnBestInliers */
+  float best_R[9];         /* mBestRotation, row-major */
+  float best_t[3];         /* mBestTranslation */
+  float best_s;            /* mBestScale */
+} orbx_sim3_state;         /* 60 bytes */
+typedef struct orbx_sim3_result {
+  int32_t converged;         /* bConverge: a hypothesis with more than min_inliers inliers that also took the best */
+  int32_t no_more;           /* bNoMore */
+  int32_t n_inliers;         /* nInliers (0 unless converged) */
+  int32_t n_correspondences; /* N */
+  int32_t iterations_run;    /* passes of the loop in this call */
+  int32_t hypothesis;        /* index (within this call's sets) of the set that converged, -1 otherwise */
+  float R12[9], t12[3], s12; /* the converged hypothesis, else the best one the state knows (identity before any pass) */
+  float T12[12];             /* top three rows of [s12 R12 | t12], row-major */
+} orbx_sim3_result;          /* 124 bytes */
+/* SetRansacParameters (:120-145) in its own arithmetic: epsilon = (float)min_inliers / N, iterations = ceil(log(1 - p) /
+ * log(1 - pow(epsilon, 3))), 1 when min_inliers == N; max(1, min(iterations, max_iterations)).  No correspondence (the reference
+ * divides by N): 1.  Pure host code.  Returns ORBX_OK, or ORBX_E_BADARG for a negative count. */
+int orbx_sim3_ransac_parameters(int n_correspondences, double probability, int min_inliers, int max_iterations,
+                                int32_t* max_iterations_out);
+/* One solver, one `iterate` call, from host arrays over the n = vpMatched12.size() key points of key frame 1 (n <= 15000):
+ * Tcw1 / Tcw2 = the key frames' poses (top three rows, row-major), world_pos1 [n][3] = the world position of key frame 1's map
+ * point at i1, world_pos2 [n][3] = that of vpMatched12[i1], matched [n] (above), octave1 / octave2 [n] = the octaves of the two
+ * points' key points in their key frames, level_sigma2_1 / _2 = the key frames' mvLevelSigma2.  Entries with matched == 0 are not
+ * read.  best_mask [n] (in/out) = mvbBestInliers by i1, inliers [n] = vbInliers (zero unless converged), hyp_inliers (may be
+ * NULL) [n_sets] = mnInliersi of every pass the call ran, -1 for sets it did not reach.  N < min_inliers: no_more = 1, nothing
+ * else runs, `sets` is not read.  All arguments are validated before a device is touched (finite poses, positions, cameras and
+ * state; level_sigma2 in [0, 1e9]; octaves in [0, nlevels)); valid arguments without a device return ORBX_E_NODEVICE (there is
+ * no host solver). */
+int orbx_sim3_iterate(int device, int n, const float* Tcw1, const float* Tcw2, const float* world_pos1, const float* world_pos2,
+                      const uint8_t* matched, const int32_t* octave1, const int32_t* octave2, const float* level_sigma2_1,
+                      int nlevels1, const float* level_sigma2_2, int nlevels2, const orbx_sim3_params* params, const int32_t* sets,
+                      int n_sets, orbx_sim3_state* state, uint8_t* best_mask, orbx_sim3_result* result, uint8_t* inliers,
+                      int32_t* hyp_inliers);
+/* n_problems solvers in one call (the candidates of a key frame, loop and merge class): n [n_problems] key points per problem
+ * (<= cap <= 15000), Tcw1 / Tcw2 [n_problems][12], world_pos1 / world_pos2 [n_problems][cap][3], matched / octave1 / octave2 /
+ * best_masks / inliers [n_problems][cap] (entries past n[p] are not read or written), the two level_sigma2 tables shared by all
+ * problems, params / states / results [n_problems], sets [n_problems][n_sets][3], hyp_inliers (may be NULL)
+ * [n_problems][n_sets].  One upload, three launches, one download.  At most 65535 problems.  Validated like the one-shot entry. */
+int orbx_sim3_iterate_batch(int device, int n_problems, int cap, const int32_t* n, const float* Tcw1, const float* Tcw2,
+                            const float* world_pos1, const float* world_pos2, const uint8_t* matched, const int32_t* octave1,
+                            const int32_t* octave2, const float* level_sigma2_1, int nlevels1, const float* level_sigma2_2,
+                            int nlevels2, const orbx_sim3_params* params, const int32_t* sets, int n_sets, orbx_sim3_state* states,
+                            uint8_t* best_masks, orbx_sim3_result* results, uint8_t* inliers, int32_t* hyp_inliers);
+
 /* ---- new map points (local mapping) ------------------------------------------------------------------- */
 
 /* The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), which consumes the match list of

@@ -109,6 +109,9 @@ def lib():
         L.orbx_mlpnp_ransac_parameters.argtypes = [i, C.c_double, i, i, i, f, vp, vp, vp]
         L.orbx_mlpnp_iterate.argtypes = [i, vp, i, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_mlpnp_iterate_batch.argtypes = [vp, i, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
+        L.orbx_sim3_ransac_parameters.argtypes = [i, C.c_double, i, i, vp]
+        L.orbx_sim3_iterate.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
+        L.orbx_sim3_iterate_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_triangulate_matches.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_create_new_map_points.argtypes = [i, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
@@ -986,6 +989,129 @@ def MLPnPIterateBatch(ex, image, worldPos, hasPoint, params, sets, states=None, 
     hyp = np.full((P, st.shape[1]), -1, np.int32)
     _check(lib().orbx_mlpnp_iterate_batch(ex._h, P, _p(img), _p(wp), _p(hp), _p(prm), _p(st), st.shape[1], _p(states), _p(bm),
                                           _p(res), _p(inl), _p(hyp) if want_hyp else None))
+    out = (res, inl.astype(bool), states, bm)
+    return out + (hyp,) if want_hyp else out
+
+
+SIM3_PARAMS_DTYPE = np.dtype([("model1", "<i4"), ("cam1", "<f4", (8,)), ("model2", "<i4"), ("cam2", "<f4", (8,)),
+                              ("kb8_precision", "<f4"), ("fix_scale", "<i4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"),
+                              ("call_iterations", "<i4")])
+SIM3_STATE_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("best_R", "<f4", (9,)), ("best_t", "<f4", (3,)),
+                             ("best_s", "<f4")])
+SIM3_RESULT_DTYPE = np.dtype([("converged", "<i4"), ("no_more", "<i4"), ("n_inliers", "<i4"), ("n_correspondences", "<i4"),
+                              ("iterations_run", "<i4"), ("hypothesis", "<i4"), ("R12", "<f4", (9,)), ("t12", "<f4", (3,)),
+                              ("s12", "<f4"), ("T12", "<f4", (12,))])
+assert SIM3_PARAMS_DTYPE.itemsize == 92 and SIM3_STATE_DTYPE.itemsize == 60 and SIM3_RESULT_DTYPE.itemsize == 124
+
+
+def Sim3RansacParameters(n_correspondences, probability=0.99, minInliers=6, maxIterations=300):
+    """Sim3Solver::SetRansacParameters (src/Sim3Solver.cc:120-145) in its own arithmetic (orbx_sim3_ransac_parameters; host code,
+    no device).  Defaults: include/Sim3Solver.h; LoopClosing::DetectCommonRegionsFromBoW passes (0.99, 15, 300).  Returns
+    mRansacMaxIts as adjusted to the number of correspondences."""
+    it = C.c_int32(0)
+    _check(lib().orbx_sim3_ransac_parameters(int(n_correspondences), float(probability), int(minInliers), int(maxIterations),
+                                             C.addressof(it)))
+    return it.value
+
+
+def sim3_sets(n_correspondences, n_sets, seed=None):
+    """The triples of Sim3Solver::iterate (src/Sim3Solver.cc:170-183) drawn the reference's way from the host's libc, as
+    mlpnp_sets draws MLPnPsolver's six.  Returns [n_sets][3] int32 indices into the correspondence list; fewer than 3
+    correspondences return zeros (the library does not read them)."""
+    global _libc
+    if _libc is None:
+        _libc = C.CDLL(None)
+        _libc.rand.restype = C.c_int
+        _libc.srand.argtypes = [C.c_uint]
+    if seed is not None:
+        _libc.srand(int(seed))
+    sets = np.zeros((n_sets, 3), np.int32)
+    if n_correspondences < 3:
+        return sets
+    rand_max = 2147483647  # glibc RAND_MAX
+    for it in range(n_sets):
+        avail = list(range(n_correspondences))
+        for j in range(3):
+            d = len(avail)
+            randi = int((float(_libc.rand()) / (float(rand_max) + 1.0)) * d)
+            sets[it, j] = avail[randi]
+            avail[randi] = avail[-1]
+            avail.pop()
+    return sets
+
+
+def sim3_params(camera1, camera2, min_inliers, max_iterations, call_iterations=20, fix_scale=False, kb8_precision=1e-6, n=1):
+    """orbx_sim3_params records: camera1 / camera2 = (fx, fy, cx, cy) for a pinhole, (fx, fy, cx, cy, k0, k1, k2, k3) for
+    KannalaBrandt8; max_iterations as Sim3RansacParameters adjusted it; call_iterations = iterate's nIterations."""
+    prm = np.zeros(n, SIM3_PARAMS_DTYPE)
+    for k, camera in (("1", camera1), ("2", camera2)):
+        cam = np.asarray(camera, np.float32).reshape(-1)
+        prm["model" + k] = CAMERA_KB8 if len(cam) == 8 else CAMERA_PINHOLE
+        prm["cam" + k][:, :len(cam)] = cam
+    prm["kb8_precision"], prm["fix_scale"] = kb8_precision, int(bool(fix_scale))
+    prm["min_inliers"], prm["max_iterations"], prm["call_iterations"] = min_inliers, max_iterations, call_iterations
+    return prm
+
+
+def Sim3Iterate(Tcw1, Tcw2, worldPos1, worldPos2, matched, octave1, octave2, levelSigma2_1, levelSigma2_2, params, sets,
+                state=None, best_mask=None, want_hyp=False, device=0):
+    """One Sim3Solver::iterate call (src/Sim3Solver.cc:147-281) on the GPU (orbx_sim3_iterate).  Tcw1 / Tcw2 = the key frames'
+    poses (3 x 4 or 4 x 4), worldPos1 / worldPos2 [n][3] = the map point of key frame 1 at i1 and vpMatched12[i1], matched [n],
+    octave1 / octave2 [n], the two mvLevelSigma2 tables, params = a sim3_params record, sets = [n_sets][3] indices into the
+    correspondence list (sim3_sets), state / best_mask = what an earlier call returned (None: a fresh solver).  Returns (result
+    record, vbInliers [n] bool, state, best_mask[, hyp_inliers [n_sets]])."""
+    m = np.ascontiguousarray(matched, np.uint8).reshape(-1)
+    n = len(m)
+    T1 = np.ascontiguousarray(np.asarray(Tcw1, np.float32).reshape(-1)[:12])
+    T2 = np.ascontiguousarray(np.asarray(Tcw2, np.float32).reshape(-1)[:12])
+    w1 = np.ascontiguousarray(worldPos1, np.float32).reshape(n, 3)
+    w2 = np.ascontiguousarray(worldPos2, np.float32).reshape(n, 3)
+    o1 = np.ascontiguousarray(octave1, np.int32).reshape(n)
+    o2 = np.ascontiguousarray(octave2, np.int32).reshape(n)
+    s1 = np.ascontiguousarray(levelSigma2_1, np.float32)
+    s2 = np.ascontiguousarray(levelSigma2_2, np.float32)
+    prm = np.ascontiguousarray(params, SIM3_PARAMS_DTYPE).reshape(1)
+    st = np.ascontiguousarray(sets, np.int32).reshape(-1, 3)
+    state = np.zeros(1, SIM3_STATE_DTYPE) if state is None else np.array(state, SIM3_STATE_DTYPE).reshape(1)
+    bm = np.zeros(n, np.uint8) if best_mask is None else np.array(best_mask, np.uint8).reshape(n)
+    res = np.zeros(1, SIM3_RESULT_DTYPE)
+    inl = np.zeros(n, np.uint8)
+    hyp = np.full(len(st), -1, np.int32)
+    _check(lib().orbx_sim3_iterate(int(device), n, _p(T1), _p(T2), _p(w1), _p(w2), _p(m), _p(o1), _p(o2), _p(s1), len(s1), _p(s2),
+                                   len(s2), _p(prm), _p(st), len(st), _p(state), _p(bm), _p(res), _p(inl),
+                                   _p(hyp) if want_hyp else None))
+    out = (res[0], inl.astype(bool), state, bm)
+    return out + (hyp,) if want_hyp else out
+
+
+def Sim3IterateBatch(n, Tcw1, Tcw2, worldPos1, worldPos2, matched, octave1, octave2, levelSigma2_1, levelSigma2_2, params, sets,
+                     states=None, best_masks=None, want_hyp=False, device=0):
+    """Sim3Iterate for n_problems solvers in one call (orbx_sim3_iterate_batch): n [P] key points per problem, Tcw1 / Tcw2
+    [P][12], worldPos1 / worldPos2 [P][cap][3], matched / octave1 / octave2 [P][cap], the two mvLevelSigma2 tables (shared),
+    params [P] records, sets [P][n_sets][3].  Returns (results [P], vbInliers [P][cap] bool, states [P], best_masks [P][cap][,
+    hyp_inliers [P][n_sets]])."""
+    nn = np.ascontiguousarray(n, np.int32).reshape(-1)
+    P = len(nn)
+    m = np.ascontiguousarray(matched, np.uint8).reshape(P, -1)
+    cap = m.shape[1]
+    T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(P, 12)
+    T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(P, 12)
+    w1 = np.ascontiguousarray(worldPos1, np.float32).reshape(P, cap, 3)
+    w2 = np.ascontiguousarray(worldPos2, np.float32).reshape(P, cap, 3)
+    o1 = np.ascontiguousarray(octave1, np.int32).reshape(P, cap)
+    o2 = np.ascontiguousarray(octave2, np.int32).reshape(P, cap)
+    s1 = np.ascontiguousarray(levelSigma2_1, np.float32)
+    s2 = np.ascontiguousarray(levelSigma2_2, np.float32)
+    prm = np.ascontiguousarray(params, SIM3_PARAMS_DTYPE).reshape(P)
+    st = np.ascontiguousarray(sets, np.int32).reshape(P, -1, 3)
+    states = np.zeros(P, SIM3_STATE_DTYPE) if states is None else np.array(states, SIM3_STATE_DTYPE).reshape(P)
+    bm = np.zeros((P, cap), np.uint8) if best_masks is None else np.array(best_masks, np.uint8).reshape(P, cap)
+    res = np.zeros(P, SIM3_RESULT_DTYPE)
+    inl = np.zeros((P, cap), np.uint8)
+    hyp = np.full((P, st.shape[1]), -1, np.int32)
+    _check(lib().orbx_sim3_iterate_batch(int(device), P, cap, _p(nn), _p(T1), _p(T2), _p(w1), _p(w2), _p(m), _p(o1), _p(o2),
+                                         _p(s1), len(s1), _p(s2), len(s2), _p(prm), _p(st), st.shape[1], _p(states), _p(bm),
+                                         _p(res), _p(inl), _p(hyp) if want_hyp else None))
     out = (res, inl.astype(bool), states, bm)
     return out + (hyp,) if want_hyp else out
 
