@@ -60,6 +60,16 @@ __device__ __forceinline__ uint32_t wave_min_dpp(uint32_t v) {  // minimum over 
   v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xc, 0xf, false));
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
+// The __shfl_xor butterflies of the solvers: a fixed xor tree in `double`, for which the DPP helpers above have no form.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
 
 // XCD-aware block -> tile mapping.  Workgroups go to the 8 XCDs round-robin by flat workgroup id, so neighbouring
 // tiles land in 8 different L2s and every shared halo line is fetched from HBM once per XCD.  This permutation keeps

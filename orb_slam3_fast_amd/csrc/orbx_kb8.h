@@ -1,6 +1,7 @@
-// orbx_kb8.h — KannalaBrandt8::project / unproject (src/CameraModels/KannalaBrandt8.cpp) in float, in the reference's
-// expression order.  Shared by the fisheye association (orbx_stereo.hip) and the relocalisation PnP solver (orbx_mlpnp.hip);
-// include it from a translation unit compiled with -ffp-contract=off.
+// orbx_kb8.h — the float camera models: KannalaBrandt8::project / unproject (src/CameraModels/KannalaBrandt8.cpp) and the
+// "pinhole or KB8" project / unproject of GeometricCamera, in the reference's expression order.  Shared by the fisheye
+// association (orbx_stereo.hip), the relocalisation PnP solver (orbx_mlpnp.hip), the Sim3 solver (orbx_sim3.hip) and the new
+// map points (orbx_newpoints.hip); include it from a translation unit compiled with -ffp-contract=off.
 #ifndef ORBX_KB8_H
 #define ORBX_KB8_H
 #include <hip/hip_runtime.h>
@@ -11,6 +12,11 @@ struct KB8Cam {
   float p[8];
   float precision;
 };
+__device__ __forceinline__ void load_cam(const float* p, float precision, KB8Cam& c) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) c.p[i] = p[i];
+  c.precision = precision;
+}
 
 __device__ __forceinline__ void kb8_project(const KB8Cam& c, const float X[3], float uv[2]) {  // :67-86
   const float x2_plus_y2 = X[0] * X[0] + X[1] * X[1];
@@ -26,6 +32,10 @@ __device__ __forceinline__ void kb8_project(const KB8Cam& c, const float X[3], f
   uv[1] = c.p[1] * r * sinf(psi) + c.p[3];
 }
 
+// kRoundedTan: std::tan(float) as the double tangent rounded once to float -- what a correctly rounded tanf returns -- and not
+// the device's tanf.  The PnP solver asks for it: a bearing vector that is one float ulp off moves a six-point pose by 1e-7,
+// four orders above what the solver's own arithmetic leaves open.
+template <bool kRoundedTan = false>
 __device__ __forceinline__ void kb8_unproject(const KB8Cam& c, float u, float v, float ray[3]) {  // :116-147
   const float pwx = (u - c.p[2]) / c.p[0], pwy = (v - c.p[3]) / c.p[1];
   float scale = 1.f;
@@ -43,11 +53,32 @@ __device__ __forceinline__ void kb8_unproject(const KB8Cam& c, float u, float v,
       theta = theta - theta_fix;
       if (fabsf(theta_fix) < c.precision) break;
     }
-    scale = tanf(theta) / theta_d;
+    scale = (kRoundedTan ? (float)tan((double)theta) : tanf(theta)) / theta_d;
   }
   ray[0] = pwx * scale;
   ray[1] = pwy * scale;
   ray[2] = 1.f;
+}
+
+// GeometricCamera::project(cv::Point3f / Eigen::Vector3f) and unprojectEig of either model: Pinhole.cpp:33-36, :46-52, :63-67,
+// KannalaBrandt8.cpp:31-46, :68-86, :111-147
+__device__ __forceinline__ void cam_project(bool kb8, const KB8Cam& c, const float X[3], float uv[2]) {
+  if (kb8) {
+    kb8_project(c, X, uv);
+  } else {
+    uv[0] = c.p[0] * X[0] / X[2] + c.p[2];
+    uv[1] = c.p[1] * X[1] / X[2] + c.p[3];
+  }
+}
+template <bool kRoundedTan = false>
+__device__ __forceinline__ void cam_unproject(bool kb8, const KB8Cam& c, float u, float v, float ray[3]) {
+  if (kb8) {
+    kb8_unproject<kRoundedTan>(c, u, v, ray);
+  } else {
+    ray[0] = (u - c.p[2]) / c.p[0];
+    ray[1] = (v - c.p[3]) / c.p[1];
+    ray[2] = 1.f;
+  }
 }
 
 }  // namespace orbx

@@ -1,11 +1,31 @@
-// orbx_nullvec.h — the null vector of a 4 x 4 system (GeometricTools::Triangulate) and the double-precision reciprocal /
-// reciprocal square root it is built on, and the one-sided Jacobi rotation and 3 x 3 SVD in double.  Shared by the fisheye
-// association (orbx_stereo.hip), the two-view reconstruction (orbx_twoview.hip) and the PnP solver (orbx_mlpnp.hip).
-#ifndef ORBX_NULLVEC_H
-#define ORBX_NULLVEC_H
+// orbx_linalg.h — the small dense linear algebra of the geometric solvers, one copy of each: 3-vector and 3 x 3 helpers, the
+// 16-lane sum, the null vector of a 4 x 4 system (GeometricTools::Triangulate) and the double-precision reciprocal / reciprocal
+// square root it is built on, the one-sided Jacobi rotation with the 3 x 3 SVD and the wave-layout null vector in double, and the
+// 6 x 6 LDLT.  Shared by the fisheye association (orbx_stereo.hip), the two-view reconstruction (orbx_twoview.hip), the PnP
+// solver (orbx_mlpnp.hip), the new map points (orbx_newpoints.hip) and the pose optimisers (orbx_pose.h).
+#ifndef ORBX_LINALG_H
+#define ORBX_LINALG_H
 #include <hip/hip_runtime.h>
 
 namespace orbx {
+
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* r) {
+  r[0] = a[1] * b[2] - a[2] * b[1];
+  r[1] = a[2] * b[0] - a[0] * b[2];
+  r[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ __forceinline__ void matvec3(const double* R, const double* x, double* y) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) y[i] = R[3 * i] * x[0] + R[3 * i + 1] * x[1] + R[3 * i + 2] * x[2];
+}
+template <class T>
+__device__ __forceinline__ T det3(const T* m) {
+  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+}
+__device__ __forceinline__ double sum16(double v) {   // over each group of 16 lanes, by a fixed xor tree
+  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
 
 // 1 / x and 1 / sqrt(x) in double from the hardware seeds (v_rcp_f64 / v_rsq_f64) and two Newton steps each: relative error
 // ~1e-16 instead of correctly rounded, at a fifth of the IEEE division / square-root expansions (the Jacobi sweeps below are a
@@ -94,6 +114,43 @@ __device__ __forceinline__ bool jacobi_cs(double alpha, double beta, double gamm
   return true;
 }
 
+// Right singular vector of the smallest singular value of a (<= 16) x NC matrix, one wave.  Lane l holds row (l & 15) of the
+// matrix in x (zero rows pad it) and row (l & 15) of V in y (rows >= NC are zero): the four 16-lane groups run the same
+// arithmetic, so every decision is wave-uniform and no broadcast is needed.  Cyclic one-sided Jacobi on the matrix itself in
+// double (no Gram matrix: a float matrix's conditioning is not squared); the (p, q) order is unrolled so that x and y stay
+// in registers.  Returns the column of V whose rotated matrix column is shortest (all NC components in every lane).  Of a
+// symmetric positive semi-definite matrix that is the eigenvector of the smallest eigenvalue (= JacobiSVD(A^T A).matrixV()
+// .col(NC - 1)).
+template <int NC>
+__device__ void null_vector_sym(double (&x)[NC], double (&y)[NC], double (&out)[NC]) {
+  for (int sweep = 0; sweep < 40; sweep++) {
+    bool rotated = false;
+#pragma unroll
+    for (int p = 0; p < NC - 1; p++)
+#pragma unroll
+      for (int q = p + 1; q < NC; q++) {
+        const double alpha = sum16(x[p] * x[p]), beta = sum16(x[q] * x[q]), gamma = sum16(x[p] * x[q]);
+        double c, s;
+        if (!jacobi_cs(alpha, beta, gamma, c, s)) continue;
+        rotated = true;
+        const double xp = x[p], xq = x[q], yp = y[p], yq = y[q];
+        x[p] = c * xp - s * xq;
+        x[q] = s * xp + c * xq;
+        y[p] = c * yp - s * yq;
+        y[q] = s * yp + c * yq;
+      }
+    if (!rotated) break;
+  }
+  double best = sum16(x[0] * x[0]), sel = y[0];
+#pragma unroll
+  for (int j = 1; j < NC; j++) {
+    const double nj = sum16(x[j] * x[j]);
+    if (nj < best) { best = nj; sel = y[j]; }
+  }
+#pragma unroll
+  for (int i = 0; i < NC; i++) out[i] = __shfl(sel, i);
+}
+
 // SVD of a row-major 3 x 3 in double: A = U diag(w) V^T, w descending (JacobiSVD's order).  The signs of the column pairs
 // (U_j, V_j) are whatever the sweeps leave: every use below is invariant to them.
 __device__ void svd3(const double* A, double* U, double* w, double* V) {
@@ -152,6 +209,53 @@ __device__ void svd3(const double* A, double* U, double* w, double* V) {
   U[2] = u2[0]; U[5] = u2[1]; U[8] = u2[2];
 #pragma unroll
   for (int i = 0; i < 9; i++) V[i] = v[i];
+}
+
+// H x = b, or (H + lambda I) x = b when kDamped, by the unpivoted LDLT of a 6 x 6 normal matrix (upper triangle, row-major:
+// linear_solver_dense.h:107-118); false = a pivot <= 0 or not finite, x untouched
+template <bool kDamped = false>
+__device__ __forceinline__ bool ldlt6(const double* H, const double* b, double* x, double lambda = 0.0) {
+  double A[6][6], L[6][6], D[6], y[6];
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 6; r++)
+#pragma unroll
+    for (int c = r; c < 6; c++) { A[r][c] = A[c][r] = H[k++]; }
+  if (kDamped) {
+#pragma unroll
+    for (int r = 0; r < 6; r++) A[r][r] += lambda;
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    double d = A[j][j];
+#pragma unroll
+    for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
+    if (!(d > 0) || !isfinite(d)) return false;
+    D[j] = d;
+    L[j][j] = 1.0;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = A[i][j];
+#pragma unroll
+      for (int m = 0; m < j; m++) s -= L[i][m] * L[j][m] * D[m];
+      L[i][j] = s / d;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double s = b[i];
+#pragma unroll
+    for (int m = 0; m < i; m++) s -= L[i][m] * y[m];
+    y[i] = s;
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; i--) {
+    double s = y[i] / D[i];
+#pragma unroll
+    for (int m = i + 1; m < 6; m++) s -= L[m][i] * x[m];
+    x[i] = s;
+  }
+  return true;
 }
 
 }  // namespace orbx

@@ -10,7 +10,8 @@
 // atomics: run-to-run identical, and a problem's result does not depend on the other problems of the launch.  The kernels keep
 // every local array statically indexed (no scratch); the 60 moments of A^T A pass through LDS to be re-read by row.
 #include "orbx_mlpnp.h"
-#include "orbx_nullvec.h"
+#include "orbx_device.h"
+#include "orbx_linalg.h"
 #include "orbx_kb8.h"
 #include <cfloat>
 #include <cmath>
@@ -21,32 +22,6 @@ namespace {
 constexpr double kEps = 2.220446049250313e-16;   // std::numeric_limits<double>::epsilon()
 constexpr int kPrepBS = 256;
 
-template <class T>
-__device__ __forceinline__ T ml_wave_sum(T v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double ml_wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ double ml_sum16(double v) {
-  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ double det3d(const double* m) {
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-__device__ __forceinline__ void matvec3(const double* R, const double* x, double* y) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) y[i] = R[3 * i] * x[0] + R[3 * i + 1] * x[1] + R[3 * i + 2] * x[2];
-}
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* r) {
-  r[0] = a[1] * b[2] - a[2] * b[1];
-  r[1] = a[2] * b[0] - a[0] * b[2];
-  r[2] = a[0] * b[1] - a[1] * b[0];
-}
 // U V^T of the SVD of a row-major 3 x 3: the rotation (or reflection) nearest to it in the Frobenius sense
 __device__ __forceinline__ void nearest_orthogonal(const double* A, double* R) {
   double U[9], w[3], V[9];
@@ -129,40 +104,6 @@ __device__ int rank3_fullpiv(const double* M) {
   return rank;
 }
 
-// Eigenvector of the smallest eigenvalue of a symmetric positive semi-definite NC x NC matrix (= JacobiSVD(A^T A).matrixV()
-// .col(NC - 1)), one wave: lane l holds row (l & 15) of the matrix in x and of V in y (rows >= NC are zero), the four 16-lane
-// groups run the same arithmetic so every decision is wave-uniform (orbx_twoview.hip's null_vector9 for another width).  All
-// NC components are returned in every lane.
-template <int NC>
-__device__ void null_vector_sym(double (&x)[NC], double (&y)[NC], double (&out)[NC]) {
-  for (int sweep = 0; sweep < 40; sweep++) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < NC - 1; p++)
-#pragma unroll
-      for (int q = p + 1; q < NC; q++) {
-        const double alpha = ml_sum16(x[p] * x[p]), beta = ml_sum16(x[q] * x[q]), gamma = ml_sum16(x[p] * x[q]);
-        double c, s;
-        if (!jacobi_cs(alpha, beta, gamma, c, s)) continue;
-        rotated = true;
-        const double xp = x[p], xq = x[q], yp = y[p], yq = y[q];
-        x[p] = c * xp - s * xq;
-        x[q] = s * xp + c * xq;
-        y[p] = c * yp - s * yq;
-        y[q] = s * yp + c * yq;
-      }
-    if (!rotated) break;
-  }
-  double best = ml_sum16(x[0] * x[0]), sel = y[0];
-#pragma unroll
-  for (int j = 1; j < NC; j++) {
-    const double nj = ml_sum16(x[j] * x[j]);
-    if (nj < best) { best = nj; sel = y[j]; }
-  }
-#pragma unroll
-  for (int i = 0; i < NC; i++) out[i] = __shfl(sel, i);
-}
-
 // index of (a, c), a <= c, in the row-major upper triangle of an n x n symmetric matrix
 __device__ __forceinline__ int tri_index(int a, int c, int n) { return a * n - a * (a - 1) / 2 + (c - a); }
 __device__ __forceinline__ int sym_index(int a, int c, int n) { return a <= c ? tri_index(a, c, n) : tri_index(c, a, n); }
@@ -240,47 +181,6 @@ __device__ __forceinline__ void ml_rows(const double* R, const double* B, const 
   }
 }
 
-// unpivoted LDLT of the 6 x 6 normal matrix (upper triangle, row-major); false = a pivot <= 0 or not finite
-__device__ __forceinline__ bool ldlt6(const double* H, const double* b, double* x) {
-  double A[6][6], L[6][6], D[6], y[6];
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int c = r; c < 6; c++) { A[r][c] = A[c][r] = H[k++]; }
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = A[j][j];
-#pragma unroll
-    for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
-    if (!(d > 0) || !isfinite(d)) return false;
-    D[j] = d;
-    L[j][j] = 1.0;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double s = A[i][j];
-#pragma unroll
-      for (int m = 0; m < j; m++) s -= L[i][m] * L[j][m] * D[m];
-      L[i][j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double s = b[i];
-#pragma unroll
-    for (int m = 0; m < i; m++) s -= L[i][m] * y[m];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double s = y[i] / D[i];
-#pragma unroll
-    for (int m = i + 1; m < 6; m++) s -= L[m][i] * x[m];
-    x[i] = s;
-  }
-  return true;
-}
-
 // computePose (:354-666) by one wave.  set != nullptr: the six correspondences set[0..5] (lane p < 6 holds point p);
 // otherwise the correspondences flagged in `mask`, the lanes striding over all N.  sS (64 doubles) and s6 (8 ints) are LDS.
 // Every lane returns the pose.
@@ -320,7 +220,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
     m6[3] += k.X[1] * k.X[1]; m6[4] += k.X[1] * k.X[2]; m6[5] += k.X[2] * k.X[2];
   }
 #pragma unroll
-  for (int i = 0; i < 6; i++) m6[i] = ml_wave_sum(m6[i]);
+  for (int i = 0; i < 6; i++) m6[i] = wave_sum(m6[i]);
   const double M3[9] = {m6[0], m6[1], m6[2], m6[1], m6[3], m6[4], m6[2], m6[4], m6[5]};
   const bool planar = rank3_fullpiv(M3) == 2;
   double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // eigenRot: rows = eigenvectors, eigenvalues ascending
@@ -361,7 +261,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
       for (int b = 0; b < 10; b++) S[10 * a + b] += Q[a] * XX[b];
   }
 #pragma unroll
-  for (int i = 0; i < 60; i++) S[i] = ml_wave_sum(S[i]);
+  for (int i = 0; i < 60; i++) S[i] = wave_sum(S[i]);
   if (lane == 0) {
 #pragma unroll
     for (int i = 0; i < 60; i++) sS[i] = S[i];
@@ -387,7 +287,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
     const double scale = 1.0 / pow(fabs(n0 * n1 * n2), 1.0 / 3.0);
     double Rr[9], tl[3];
     nearest_orthogonal(tmp, Rr);
-    if (det3d(Rr) < 0) {
+    if (det3(Rr) < 0) {
 #pragma unroll
       for (int i = 0; i < 9; i++) Rr[i] *= -1.0;
     }
@@ -412,8 +312,8 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
       e0 = 1.0 - ((a[0] / na) * k.f[0] + (a[1] / na) * k.f[1] + (a[2] / na) * k.f[2]);
       e1 = 1.0 - ((b[0] / nb) * k.f[0] + (b[1] / nb) * k.f[1] + (b[2] / nb) * k.f[2]);
     }
-    e0 = ml_wave_sum(e0);
-    e1 = ml_wave_sum(e1);
+    e0 = wave_sum(e0);
+    e1 = wave_sum(e1);
 #pragma unroll
     for (int i = 0; i < 3; i++) t[i] = e0 < e1 ? -ti[i] : ti[i];
   } else {
@@ -436,7 +336,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
     const double scale = 1.0 / sqrt(fabs(nc1 * nc2));
     double R1[9], Q[9];
     nearest_orthogonal(tmp, R1);
-    if (det3d(R1) < 0) {
+    if (det3(R1) < 0) {
 #pragma unroll
       for (int i = 0; i < 9; i++) R1[i] *= -1.0;
     }
@@ -449,7 +349,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 0; j < 3; j++) R1[3 * i + j] = -Q[3 * j + i];
-    if (det3d(R1) < 0.0) { R1[2] *= -1; R1[5] *= -1; R1[8] *= -1; }
+    if (det3(R1) < 0.0) { R1[2] *= -1; R1[5] *= -1; R1[8] *= -1; }
     const double tp[3] = {scale * v[6], scale * v[7], scale * v[8]};
     double nv[4] = {0, 0, 0, 0};
     if (lane < kMlSet) {
@@ -468,7 +368,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
     double bestv = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      nv[i] = ml_wave_sum(nv[i]);
+      nv[i] = wave_sum(nv[i]);
       if (i == 0 || nv[i] < bestv) { bestv = nv[i]; idx = i; }   // std::min_element: the first minimum
     }
     const double sr = idx < 2 ? 1.0 : -1.0, st = (idx & 1) ? -1.0 : 1.0;
@@ -518,7 +418,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
       for (int a = 0; a < 6; a++) H[21 + a] += J0[a] * e0 + J1[a] * e1;
     }
 #pragma unroll
-    for (int i = 0; i < 27; i++) H[i] = ml_wave_sum(H[i]);
+    for (int i = 0; i < 27; i++) H[i] = wave_sum(H[i]);
     double dx[6] = {0, 0, 0, 0, 0, 0};
     if (!ldlt6(H, H + 21, dx)) break;
     double dmax = 0, dmin = fabs(dx[0]);
@@ -536,7 +436,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
       for (int a = 0; a < 6; a++) { a0 += J0[a] * dx[a]; a1 += J1[a] * dx[a]; }
       dl = fmax(dl, fmax(fabs(a0), fabs(a1)));
     }
-    dl = ml_wave_max(dl);
+    dl = wave_max(dl);
 #pragma unroll
     for (int i = 0; i < 6; i++) xv[i] -= dx[i];
     if (dl < 1e-5) break;
@@ -549,9 +449,7 @@ __device__ void ml_compute_pose(const MlArgs& A, const int* set, const unsigned 
 // narrowed to float, project(cv::Point3f) runs in float (Pinhole.cpp:33-36, KannalaBrandt8.cpp:31-46).
 __device__ int ml_check_inliers(const MlArgs& A, const double* R, const double* t, int lane, unsigned long long* flags) {
   KB8Cam cam;
-#pragma unroll
-  for (int i = 0; i < 8; i++) cam.p[i] = A.prm.cam[i];
-  cam.precision = A.prm.kb8_precision;
+  load_cam(A.prm.cam, A.prm.kb8_precision, cam);
   const bool kb8 = A.prm.model == ORBX_CAMERA_KB8;
   int count = 0;
   for (int base = 0; base < A.N; base += 64) {
@@ -581,46 +479,17 @@ __device__ int ml_check_inliers(const MlArgs& A, const double* R, const double* 
   return count;
 }
 
-// KannalaBrandt8::unproject (KannalaBrandt8.cpp:116-147) as orbx_kb8.h's kb8_unproject, except that std::tan(float) is the
-// double tangent rounded once to float -- what a correctly rounded tanf returns -- and not the device's tanf: a bearing vector
-// that is one float ulp off moves a six-point pose by 1e-7, four orders above what the solver's own arithmetic leaves open.
-__device__ __forceinline__ void kb8_unproject_cr(const KB8Cam& c, float u, float v, float ray[3]) {
-  const float pwx = (u - c.p[2]) / c.p[0], pwy = (v - c.p[3]) / c.p[1];
-  float scale = 1.f;
-  float theta_d = sqrtf(pwx * pwx + pwy * pwy);
-  const float halfPi = (float)(3.1415926535897932384626433832795 / 2.0);
-  theta_d = fminf(fmaxf(-halfPi, theta_d), halfPi);
-  if ((double)theta_d > 1e-8) {
-    float theta = theta_d;
-    for (int j = 0; j < 10; j++) {
-      const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
-      const float k0_theta2 = c.p[4] * theta2, k1_theta4 = c.p[5] * theta4;
-      const float k2_theta6 = c.p[6] * theta6, k3_theta8 = c.p[7] * theta8;
-      const float theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
-                              (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
-      theta = theta - theta_fix;
-      if (fabsf(theta_fix) < c.precision) break;
-    }
-    scale = (float)tan((double)theta) / theta_d;
-  }
-  ray[0] = pwx * scale;
-  ray[1] = pwy * scale;
-  ray[2] = 1.f;
-}
-
 // ================================================================================================ kernels
 
 __global__ __launch_bounds__(kPrepBS) void k_mlpnp_prepare(const MlArgs* __restrict__ args) {
   const MlArgs& A = args[blockIdx.x];
   KB8Cam cam;
-#pragma unroll
-  for (int i = 0; i < 8; i++) cam.p[i] = A.prm.cam[i];
-  cam.precision = A.prm.kb8_precision;
+  load_cam(A.prm.cam, A.prm.kb8_precision, cam);
   for (int c = threadIdx.x; c < A.N; c += kPrepBS) {
     const orbx_keypoint kp = A.kps[A.kidx[c]];
     float ray[3];
     if (A.prm.model == ORBX_CAMERA_KB8) {
-      kb8_unproject_cr(cam, kp.x, kp.y, ray);
+      kb8_unproject<true>(cam, kp.x, kp.y, ray);
     } else {
       ray[0] = (kp.x - cam.p[2]) / cam.p[0];
       ray[1] = (kp.y - cam.p[3]) / cam.p[1];

@@ -9,7 +9,7 @@
 // byte store; the next neighbour's k_tri_match reads it in stream order.
 #include "orbx_device.h"
 #include "orbx_kb8.h"
-#include "orbx_nullvec.h"
+#include "orbx_linalg.h"
 
 namespace orbx {
 
@@ -30,33 +30,16 @@ __device__ __forceinline__ orbx_np_camera np_pick_camera(const NpKf& f, bool rig
   return c;
 }
 
-// GeometricCamera::unprojectEig: Pinhole.cpp:63-67, KannalaBrandt8.cpp:111-147
+// GeometricCamera::unprojectEig / project(cv::Point3f) of a key frame's camera
 __device__ __forceinline__ void np_unproject(const orbx_np_camera& c, float u, float v, float r[3]) {
-  if (c.model == ORBX_CAMERA_KB8) {
-    KB8Cam k;
-#pragma unroll
-    for (int i = 0; i < 8; i++) k.p[i] = c.p[i];
-    k.precision = c.kb8_precision;
-    kb8_unproject(k, u, v, r);
-  } else {
-    r[0] = (u - c.p[2]) / c.p[0];
-    r[1] = (v - c.p[3]) / c.p[1];
-    r[2] = 1.f;
-  }
+  KB8Cam k;
+  load_cam(c.p, c.kb8_precision, k);
+  cam_unproject(c.model == ORBX_CAMERA_KB8, k, u, v, r);
 }
-
-// GeometricCamera::project(cv::Point3f): Pinhole.cpp:33-36, KannalaBrandt8.cpp:31-46
 __device__ __forceinline__ void np_project(const orbx_np_camera& c, const float X[3], float uv[2]) {
-  if (c.model == ORBX_CAMERA_KB8) {
-    KB8Cam k;
-#pragma unroll
-    for (int i = 0; i < 8; i++) k.p[i] = c.p[i];
-    k.precision = c.kb8_precision;
-    kb8_project(k, X, uv);
-  } else {
-    uv[0] = c.p[0] * X[0] / X[2] + c.p[2];
-    uv[1] = c.p[1] * X[1] / X[2] + c.p[3];
-  }
+  KB8Cam k;
+  load_cam(c.p, c.kb8_precision, k);
+  cam_project(c.model == ORBX_CAMERA_KB8, k, X, uv);
 }
 
 // Rwc * v with Rwc = Rcw^T read from the row-major 3 x 4 Tcw

@@ -1,12 +1,19 @@
 // orbx_pose.h — what the two pose-optimisation kernels share: k_pose_opt (pinhole / rectified, orbx_pose.hip) and k_pose_opt_kb8
-// (KannalaBrandt8, orbx_pose_kb8.hip).  SE3Quat, the 6x6 LDLT, thread 0's g2o Levenberg state machine and the wave reduction.
+// (KannalaBrandt8, orbx_pose_kb8.hip).  SE3Quat and thread 0's g2o Levenberg state machine (its 6 x 6 LDLT is orbx_linalg.h's, the wave
+// reduction orbx_device.h's).
 // The kernels live in separate translation units so that the pinhole kernel compiles to the code it had before KB8 existed.
 #ifndef ORBX_POSE_H
 #define ORBX_POSE_H
+#include "orbx_device.h"
 #include "orbx_host.h"
+#include "orbx_linalg.h"
 #include <cfloat>
 
 namespace {
+
+using orbx::cross3;
+using orbx::ldlt6;
+using orbx::wave_sum;
 
 #ifndef ORBX_POSE_BS
 #define ORBX_POSE_BS 256
@@ -45,17 +52,12 @@ __device__ __forceinline__ void qmul(const double* a, const double* b, double* r
   r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
   r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
 }
-__device__ __forceinline__ void cross(const double* a, const double* b, double* r) {
-  r[0] = a[1] * b[2] - a[2] * b[1];
-  r[1] = a[2] * b[0] - a[0] * b[2];
-  r[2] = a[0] * b[1] - a[1] * b[0];
-}
 // q * v = v + w * uv + vec x uv, uv = 2 (vec x v)
 __device__ __forceinline__ void qrot(const double* q, const double* v, double* r) {
   double uv[3], c[3];
-  cross(q, v, uv);
+  cross3(q, v, uv);
   uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-  cross(q, uv, c);
+  cross3(q, uv, c);
   for (int i = 0; i < 3; i++) r[i] = v[i] + q[3] * uv[i] + c[i];
 }
 __device__ __forceinline__ void normalize_rotation(double* q) {   // SE3Quat::normalizeRotation: w >= 0, unit norm
@@ -120,49 +122,6 @@ __device__ __forceinline__ void oplus(const double* x, const Pose& P, Pose& out)
   normalize_rotation(out.q);
 }
 
-// (H + lambda I) x = b by LDLT (linear_solver_dense.h:107-118); false = failed factorisation, x untouched
-__device__ __forceinline__ bool ldlt_solve(const double* H, const double* b, double lambda, double* x) {
-  double A[6][6], L[6][6], D[6], y[6];
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-  #pragma unroll
-  for (int c = r; c < 6; c++) { A[r][c] = A[c][r] = H[k++]; }
-#pragma unroll
-  for (int r = 0; r < 6; r++) A[r][r] += lambda;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = A[j][j];
-  #pragma unroll
-  for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
-    if (!(d > 0) || !isfinite(d)) return false;
-    D[j] = d;
-    L[j][j] = 1.0;
-  #pragma unroll
-  for (int i = j + 1; i < 6; i++) {
-      double s = A[i][j];
-    #pragma unroll
-  for (int m = 0; m < j; m++) s -= L[i][m] * L[j][m] * D[m];
-      L[i][j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double s = b[i];
-  #pragma unroll
-  for (int m = 0; m < i; m++) s -= L[i][m] * y[m];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double s = y[i] / D[i];
-  #pragma unroll
-  for (int m = i + 1; m < 6; m++) s -= L[m][i] * x[m];
-    x[i] = s;
-  }
-  return true;
-}
-
 enum : int { kEval = 0, kClassify = 1, kDone = 2 };
 
 struct Ctl {   // thread 0's optimiser state, in LDS
@@ -175,7 +134,7 @@ struct Ctl {   // thread 0's optimiser state, in LDS
 __device__ __forceinline__ void ctl_trial(Ctl& c) {   // push, H + lambda I, solve, update
   double x[6];
   for (int i = 0; i < 6; i++) x[i] = c.x[i];
-  c.ok2 = ldlt_solve(c.H, c.b, c.lambda, x);
+  c.ok2 = ldlt6<true>(c.H, c.b, x, c.lambda);
   for (int i = 0; i < 6; i++) c.x[i] = x[i];   // a failed solve leaves g2o's x as it was
   oplus(x, c.P, c.T);
   c.phase = kEval;
@@ -248,12 +207,6 @@ __device__ __forceinline__ void ctl_after_eval(Ctl& c, const double* sums) {
     return;
   }
   c.phase = kClassify;
-}
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 }  // namespace

@@ -19,22 +19,6 @@ namespace {
 
 constexpr int kPrepBS = 256;
 
-__device__ __forceinline__ void load_cam(const float* p, float prec, KB8Cam& c) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) c.p[i] = p[i];
-  c.precision = prec;
-}
-
-// GeometricCamera::project(Eigen::Vector3f) in float: Pinhole.cpp:46-52, KannalaBrandt8.cpp:68-86
-__device__ __forceinline__ void s3_project(bool kb8, const KB8Cam& cam, const float X[3], float uv[2]) {
-  if (kb8) {
-    kb8_project(cam, X, uv);
-  } else {
-    uv[0] = cam.p[0] * X[0] / X[2] + cam.p[2];
-    uv[1] = cam.p[1] * X[1] / X[2] + cam.p[3];
-  }
-}
-
 // R x + t of a row-major 3 x 4 in float, the product summed left to right
 __device__ __forceinline__ void s3_transform(const float* T, float x, float y, float z, float out[3]) {
 #pragma unroll
@@ -219,8 +203,8 @@ __global__ __launch_bounds__(kPrepBS) void k_sim3_prepare(const S3Args* __restri
         float X1[3], X2[3], p1[2], p2[2];
         s3_transform(A.Tcw1, w1[0], w1[1], w1[2], X1);
         s3_transform(A.Tcw2, w2[0], w2[1], w2[2], X2);
-        s3_project(kb1, cam1, X1, p1);
-        s3_project(kb2, cam2, X2, p2);
+        cam_project(kb1, cam1, X1, p1);
+        cam_project(kb2, cam2, X2, p2);
         // 9.210 * sigma2 is a double truncated into a size_t (Sim3Solver.h:92-93) and compared as a float (:412)
         const float e1 = (float)(unsigned long long)(9.210 * (double)A.sigma2_1[A.oct1[i]]);
         const float e2 = (float)(unsigned long long)(9.210 * (double)A.sigma2_2[A.oct2[i]]);
@@ -271,9 +255,9 @@ __global__ __launch_bounds__(64) void k_sim3_hypotheses(const S3Args* __restrict
       const float4 a = A.c1[c], b = A.c2[c], p = A.im[c];
       float X[3], uv1[2], uv2[2];
       s3_transform(T12, b.x, b.y, b.z, X);    // mvX3Dc2 into camera 1
-      s3_project(kb1, cam1, X, uv1);
+      cam_project(kb1, cam1, X, uv1);
       s3_transform(T21, a.x, a.y, a.z, X);    // mvX3Dc1 into camera 2
-      s3_project(kb2, cam2, X, uv2);
+      cam_project(kb2, cam2, X, uv2);
       const float d1x = p.x - uv1[0], d1y = p.y - uv1[1], d2x = uv2[0] - p.z, d2y = uv2[1] - p.w;
       const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
       in = err1 < a.w && err2 < b.w;   // no depth test; NaN and inf are outliers

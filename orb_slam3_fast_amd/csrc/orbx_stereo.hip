@@ -3,7 +3,7 @@
 #include <mutex>
 
 #include "orbx_device.h"
-#include "orbx_nullvec.h"
+#include "orbx_linalg.h"
 #include "orbx_kb8.h"
 
 namespace orbx {

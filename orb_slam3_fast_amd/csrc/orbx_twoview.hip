@@ -11,17 +11,18 @@
 //   k_tv_finish      (pairs) x 256            the acceptance rules, the winner's points and flags, R -> quaternion
 // Sums are reduced by a fixed xor butterfly and across waves in wave order; counters are integers: run-to-run identical, and a
 // pair's result does not depend on the other pairs of the launch.  The host side of both entries is at the end.
+#include "orbx_device.h"
 #include "orbx_host.h"
-#include "orbx_nullvec.h"
+#include "orbx_linalg.h"
 #include <cmath>
 
 namespace {
 
-using orbx::jacobi_cs;
+using orbx::det3;
 using orbx::null_vector4;
-using orbx::rcp64;
-using orbx::rsqrt64;
+using orbx::null_vector_sym;
 using orbx::svd3;
+using orbx::wave_sum;
 
 constexpr int kTvMaxKps = 15000;
 constexpr int kTvMaxIter = 4096;
@@ -58,12 +59,6 @@ struct TvArgs {
   int n1, n2, N;
 };
 
-template <class T>
-__device__ __forceinline__ T tv_wave_sum(T v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // ---- small float matrices, products summed in index order like Eigen's 3 x 3 lazy product
 __device__ __forceinline__ void mul3(const float* a, const float* b, float* c) {
 #pragma unroll
@@ -76,9 +71,6 @@ __device__ __forceinline__ void transpose3(const float* a, float* t) {
   for (int i = 0; i < 3; i++)
 #pragma unroll
     for (int j = 0; j < 3; j++) t[3 * i + j] = a[3 * j + i];
-}
-__device__ __forceinline__ float det3(const float* m) {
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
 }
 // inverse of a float 3 x 3 by cofactors, evaluated in double and narrowed
 __device__ __forceinline__ void inverse3(const float* mf, float* inv) {
@@ -96,45 +88,6 @@ __device__ __forceinline__ void inverse3(const float* mf, float* inv) {
   inv[6] = (float)(c02 * id);
   inv[7] = (float)((m[1] * m[6] - m[0] * m[7]) * id);
   inv[8] = (float)((m[0] * m[4] - m[1] * m[3]) * id);
-}
-
-// Right singular vector of the smallest singular value of a (<= 16) x 9 matrix, one wave.  Lane l holds row (l & 15) of the
-// matrix in x (zero rows pad it) and row (l & 15) of V in y (rows >= 9 are zero): the four 16-lane groups run the same
-// arithmetic, so every decision is wave-uniform and no broadcast is needed.  Cyclic one-sided Jacobi on the matrix itself in
-// double (no Gram matrix: the float matrix's conditioning is not squared); the (p, q) order is unrolled so that x and y stay
-// in registers.  Returns the column of V whose rotated matrix column is shortest (all nine components in every lane).
-__device__ __forceinline__ double sum16(double v) {
-  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ void null_vector9(double (&x)[9], double (&y)[9], int lane, double (&out)[9]) {
-  for (int sweep = 0; sweep < 40; sweep++) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 8; p++)
-#pragma unroll
-      for (int q = p + 1; q < 9; q++) {
-        const double alpha = sum16(x[p] * x[p]), beta = sum16(x[q] * x[q]), gamma = sum16(x[p] * x[q]);
-        double c, s;
-        if (!jacobi_cs(alpha, beta, gamma, c, s)) continue;
-        rotated = true;
-        const double xp = x[p], xq = x[q], yp = y[p], yq = y[q];
-        x[p] = c * xp - s * xq;
-        x[q] = s * xp + c * xq;
-        y[p] = c * yp - s * yq;
-        y[q] = s * yp + c * yq;
-      }
-    if (!rotated) break;
-  }
-  double best = sum16(x[0] * x[0]), sel = y[0];
-#pragma unroll
-  for (int j = 1; j < 9; j++) {
-    const double nj = sum16(x[j] * x[j]);
-    if (nj < best) { best = nj; sel = y[j]; }
-  }
-#pragma unroll
-  for (int i = 0; i < 9; i++) out[i] = __shfl(sel, i);
-  (void)lane;
 }
 
 // ---- CheckHomography / CheckFundamental for one match (:315-481): adds the match's terms to score, returns bIn
@@ -192,8 +145,8 @@ __global__ __launch_bounds__(kTvBS) void k_tv_prepare(const TvArgs* __restrict__
   __shared__ float red[kTvNW][2];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const auto block_sum2 = [&](float& a, float& b) {
-    a = tv_wave_sum(a);
-    b = tv_wave_sum(b);
+    a = wave_sum(a);
+    b = wave_sum(b);
     __syncthreads();
     if (lane == 0) { red[wid][0] = a; red[wid][1] = b; }
     __syncthreads();
@@ -260,7 +213,7 @@ __global__ __launch_bounds__(64) void k_tv_hypotheses(const TvArgs* __restrict__
       y[i] = r == i ? 1.0 : 0.0;
     }
   }
-  null_vector9(x, y, lane, v);
+  null_vector_sym<9>(x, y, v);
   // the 3 x 3 work, the same in every lane
   const float T1[9] = {s1x, 0.f, -m1x * s1x, 0.f, s1y, -m1y * s1y, 0.f, 0.f, 1.f};
   const float T2[9] = {s2x, 0.f, -m2x * s2x, 0.f, s2y, -m2y * s2y, 0.f, 0.f, 1.f};
@@ -299,7 +252,7 @@ __global__ __launch_bounds__(64) void k_tv_hypotheses(const TvArgs* __restrict__
     for (int k = lane; k < A.N; k += 64) check_h(M, Mi, A.quad[k], iss, score);
   else
     for (int k = lane; k < A.N; k += 64) check_f(M, A.quad[k], iss, score);
-  score = tv_wave_sum(score);
+  score = wave_sum(score);
   if (lane == 0) A.scores[(size_t)model * cam.iterations + it] = score;
 }
 
@@ -367,7 +320,7 @@ __global__ __launch_bounds__(kTvBS) void k_tv_select(const TvArgs* __restrict__ 
     A.inl[k] = in;
     cnt += in;
   }
-  cnt = tv_wave_sum(cnt);
+  cnt = wave_sum(cnt);
   if (lane == 0) s_cnt[wid] = cnt;
   __syncthreads();
   if (tid != 0) return;
@@ -550,7 +503,7 @@ __global__ __launch_bounds__(kTvBS) void k_tv_check_rt(const TvArgs* __restrict_
     good[k] = g;
     P[3 * k] = X[0]; P[3 * k + 1] = X[1]; P[3 * k + 2] = X[2];
   }
-  nGood = tv_wave_sum(nGood);
+  nGood = wave_sum(nGood);
   if (lane == 0) s_cnt[wid] = nGood;
   hist[tid] = 0;
   __syncthreads();   // (also orders this block's cosv stores before its loads below)
