@@ -6,17 +6,8 @@
 
 namespace {
 
-bool finite_all(const float* v, int n) {
-  for (int i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 const char* np_camera_error(const orbx_np_camera& c) {
-  if (c.model != ORBX_CAMERA_PINHOLE && c.model != ORBX_CAMERA_KB8) return "camera model is neither pinhole nor KB8";
-  if (!finite_all(c.p, c.model == ORBX_CAMERA_KB8 ? 8 : 4) || !(c.p[0] > 0) || !(c.p[1] > 0))
-    return "camera parameters not finite, or fx / fy not positive";
-  if (c.model == ORBX_CAMERA_KB8 && !(std::isfinite(c.kb8_precision) && c.kb8_precision > 0)) return "kb8_precision not finite and positive";
+  if (const char* e = camera_error(c.model, c.p, c.kb8_precision)) return e;
   if (!finite_all(c.Tcw, 12) || !finite_all(c.Ow, 3)) return "key frame pose not finite";
   return nullptr;
 }

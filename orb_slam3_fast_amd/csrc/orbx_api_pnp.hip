@@ -4,7 +4,6 @@
 #include "orbx_mlpnp.h"
 
 #include <algorithm>
-#include <climits>
 
 namespace {
 
@@ -20,17 +19,8 @@ struct MlProblem {
   std::vector<float> wpos;
 };
 
-bool finite_all(const float* v, int n) {
-  for (int i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 const char* ml_params_error(const orbx_mlpnp_params& p) {
-  if (p.model != ORBX_CAMERA_PINHOLE && p.model != ORBX_CAMERA_KB8) return "camera model is neither pinhole nor KB8";
-  if (!finite_all(p.cam, p.model == ORBX_CAMERA_KB8 ? 8 : 4) || !(p.cam[0] > 0) || !(p.cam[1] > 0))
-    return "camera parameters not finite, or fx / fy not positive";
-  if (p.model == ORBX_CAMERA_KB8 && !(std::isfinite(p.kb8_precision) && p.kb8_precision > 0)) return "kb8_precision not finite and positive";
+  if (const char* e = camera_error(p.model, p.cam, p.kb8_precision)) return e;
   if (!(std::isfinite(p.th2) && p.th2 > 0)) return "th2 not finite and positive";
   if (p.min_set != kMlSet) return "min_set other than 6";
   if (p.min_inliers < kMlSet) return "min_inliers below min_set";
@@ -45,18 +35,6 @@ const char* ml_state_error(const orbx_mlpnp_state& s) {
   return nullptr;
 }
 
-// the correspondence list (i < nUse, has_point[i]) in ascending i, with their world positions; false: a position not finite
-bool ml_gather(MlProblem& p, const float* worldPos, const uint8_t* hasPoint, int nUse) {
-  for (int i = 0; i < nUse; i++) {
-    if (!hasPoint[i]) continue;
-    const float* w = worldPos + 3 * (size_t)i;
-    if (!finite_all(w, 3)) return false;
-    p.kidx.push_back(i);
-    p.wpos.insert(p.wpos.end(), w, w + 3);
-  }
-  return true;
-}
-
 // K = the passes iterate's loop (:125) can make from this state; then the state's flags and the sets it will read
 const char* ml_plan(MlProblem& p, int nSets) {
   const int N = (int)p.kidx.size();
@@ -68,15 +46,7 @@ const char* ml_plan(MlProblem& p, int nSets) {
   p.K = std::max(std::max(p.prm.max_iterations - p.st.iterations, p.prm.call_iterations), 0);
   if (p.K > nSets) return "n_sets below max(max_iterations - state.iterations, call_iterations)";
   if (p.K && !p.sets) return "null argument";
-  for (int j = 0; j < p.K; j++) {
-    const int32_t* s = p.sets + kMlSet * (size_t)j;
-    for (int a = 0; a < kMlSet; a++) {
-      if (s[a] < 0 || s[a] >= N) return "set index outside [0, n_correspondences)";
-      for (int b = 0; b < a; b++)
-        if (s[b] == s[a]) return "set index repeated within its set";
-    }
-  }
-  return nullptr;
+  return sets_error<kMlSet>(p.sets, p.K, N);
 }
 
 // outputs of problem f: results[f], states[f], and rows f of bestMasks / inliers (stride bytes apart) / hypInliers (nSets apart)
@@ -85,77 +55,58 @@ int ml_run(std::vector<MlProblem>& probs, const float* sigma2, int nlevels, int 
   const int P = (int)probs.size();
   Pack pk;
   std::vector<MlArgs> args(P);
-  std::vector<size_t> oK(P), oI(P), oW(P), oS(P), oM(P);
-  const auto atLeast = [](size_t b) { return std::max<size_t>(b, 16); };
   int maxK = 0;
-  for (int f = 0; f < P; f++) {
+  for (int f = 0; f < P; f++) {   // the scalar fields and the inputs
     const MlProblem& p = probs[f];
-    const size_t N = p.kidx.size(), n = (size_t)p.n;
-    if (p.kpsHost) oK[f] = pk.add(p.kpsHost, atLeast(n * sizeof(orbx_keypoint)), n * sizeof(orbx_keypoint));
-    oI[f] = pk.add(p.kidx.data(), atLeast(N * sizeof(int)), N * sizeof(int));
-    oW[f] = pk.add(p.wpos.data(), atLeast(N * 3 * sizeof(float)), N * 3 * sizeof(float));
-    oS[f] = pk.add(p.sets, atLeast((size_t)p.K * kMlSet * sizeof(int)), (size_t)p.K * kMlSet * sizeof(int));
-    oM[f] = pk.add(p.maskIn, atLeast(n), n);
+    MlArgs& a = args[f];
+    const size_t n = (size_t)p.n, N = p.kidx.size(), K = (size_t)p.K;
+    a.prm = p.prm;
+    a.st = p.st;
+    a.n = p.n;
+    a.N = (int)N;
+    a.K = p.K;
+    a.W = (a.N + 63) / 64;
+    a.nSets = nSets;
+    if (p.kpsHost) pk.in(a.kps, p.kpsHost, n, 16);
+    else a.kps = p.kpsDev;
+    pk.in(a.kidx, p.kidx.data(), N, 16);
+    pk.in(a.wpos, p.wpos.data(), N * 3, 16);
+    pk.in(a.sets, p.sets, K * kMlSet, 16);
+    pk.in(a.maskIn, p.maskIn, n, 16);
     maxK = std::max(maxK, p.K);
   }
   const size_t oSig = pk.add(sigma2, (size_t)nlevels * sizeof(float));
   const size_t oArgs = pk.add(args.data(), (size_t)P * sizeof(MlArgs));
-  std::vector<size_t> oGeo(P), oObs(P), oMw(P), oHf(P), oRf(P), oHp(P), oHc(P);
-  for (int f = 0; f < P; f++) {
-    const MlProblem& p = probs[f];
-    const size_t N = p.kidx.size(), W = (N + 63) / 64, K = (size_t)p.K;
-    oGeo[f] = pk.add(nullptr, atLeast(N * kMlGeo * sizeof(double)));
-    oObs[f] = pk.add(nullptr, atLeast(N * kMlObs * sizeof(float)));
-    oMw[f] = pk.add(nullptr, atLeast(W * 8));
-    oHf[f] = pk.add(nullptr, atLeast(K * W * 8));
-    oRf[f] = pk.add(nullptr, atLeast(W * 8));
-    oHp[f] = pk.add(nullptr, atLeast(K * 12 * sizeof(double)));
-    oHc[f] = pk.add(nullptr, atLeast(K * sizeof(int)));
+  for (MlArgs& a : args) {   // scratch
+    const size_t N = (size_t)a.N, W = (size_t)a.W, K = (size_t)a.K;
+    pk.bind(a.sigma2, oSig);
+    pk.area(a.geo, N * kMlGeo, 16);
+    pk.area(a.obs, N * kMlObs, 16);
+    pk.area(a.maskW, W, 16);
+    pk.area(a.hflags, K * W, 16);
+    pk.area(a.rflags, W, 16);
+    pk.area(a.hpose, K * 12, 16);
+    pk.area(a.hcount, K, 16);
   }
   // outputs: one contiguous area
+  const size_t hyBytes = std::max<size_t>((size_t)P * nSets * sizeof(int), 16);
   const size_t oRes = pk.add(nullptr, (size_t)P * sizeof(orbx_mlpnp_result));
   const size_t oSt = pk.add(nullptr, (size_t)P * sizeof(orbx_mlpnp_state));
-  const size_t oHy = pk.add(nullptr, atLeast((size_t)P * nSets * sizeof(int)));
+  const size_t oHy = pk.add(nullptr, hyBytes);
   std::vector<size_t> oBm(P), oIn(P);
-  size_t outEnd = oHy + atLeast((size_t)P * nSets * sizeof(int));
+  size_t outEnd = oHy + hyBytes;
   for (int f = 0; f < P; f++) {
-    const size_t n = (size_t)probs[f].n;
-    oBm[f] = pk.add(nullptr, atLeast(n));
-    oIn[f] = pk.add(nullptr, atLeast(n));
-    outEnd = oIn[f] + atLeast(n);
-  }
-  hipError_t e = pk.reserve();
-  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  for (int f = 0; f < P; f++) {
-    const MlProblem& p = probs[f];
     MlArgs& a = args[f];
-    a = MlArgs{};
-    a.kps = p.kpsHost ? pk.ptr<orbx_keypoint>(oK[f]) : p.kpsDev;
-    a.kidx = pk.ptr<int>(oI[f]);
-    a.wpos = pk.ptr<float>(oW[f]);
-    a.sigma2 = pk.ptr<float>(oSig);
-    a.sets = pk.ptr<int>(oS[f]);
-    a.maskIn = pk.ptr<uint8_t>(oM[f]);
-    a.geo = pk.ptr<double>(oGeo[f]);
-    a.obs = pk.ptr<float>(oObs[f]);
-    a.maskW = pk.ptr<unsigned long long>(oMw[f]);
-    a.hflags = pk.ptr<unsigned long long>(oHf[f]);
-    a.rflags = pk.ptr<unsigned long long>(oRf[f]);
-    a.hpose = pk.ptr<double>(oHp[f]);
-    a.hcount = pk.ptr<int>(oHc[f]);
-    a.result = pk.ptr<orbx_mlpnp_result>(oRes) + f;
-    a.stateOut = pk.ptr<orbx_mlpnp_state>(oSt) + f;
-    a.maskOut = pk.ptr<uint8_t>(oBm[f]);
-    a.inliers = pk.ptr<uint8_t>(oIn[f]);
-    a.hypInliers = pk.ptr<int>(oHy) + (size_t)f * nSets;
-    a.prm = p.prm;
-    a.st = p.st;
-    a.n = p.n;
-    a.N = (int)p.kidx.size();
-    a.K = p.K;
-    a.W = (a.N + 63) / 64;
-    a.nSets = nSets;
+    const size_t n = (size_t)a.n;
+    pk.bind(a.result, oRes, f);
+    pk.bind(a.stateOut, oSt, f);
+    pk.bind(a.hypInliers, oHy, (size_t)f * nSets);
+    oBm[f] = pk.area(a.maskOut, n, 16);
+    oIn[f] = pk.area(a.inliers, n, 16);
+    outEnd = oIn[f] + std::max<size_t>(n, 16);
   }
+  hipError_t e = pk.reserve();   // writes every bound pointer of args
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   e = pk.commit();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   HIPC(launch_mlpnp(pk.ptr<MlArgs>(oArgs), P, maxK));
@@ -188,11 +139,7 @@ int orbx_mlpnp_ransac_parameters(int n_correspondences, double probability, int 
   int nIterations = 1;
   if (N > 0) {
     if (mRansacEpsilon < (float)nMinInliers / N) mRansacEpsilon = (float)nMinInliers / N;
-    if (nMinInliers != N) {
-      // minInliers > N makes epsilon > 1 and the quotient NaN; the reference's conversion of it to int is x86's INT_MIN
-      const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(mRansacEpsilon, 3)));
-      nIterations = (std::isfinite(v) && std::fabs(v) < 2147483648.0) ? (int)v : INT_MIN;
-    }
+    if (nMinInliers != N) nIterations = ransac_iterations(probability, mRansacEpsilon);
   }
   // (N == 0: the reference divides by it; one iteration, which iterate never runs since N < minInliers)
   if (min_inliers_out) *min_inliers_out = nMinInliers;
@@ -221,7 +168,7 @@ int orbx_mlpnp_iterate(int device, const orbx_keypoint* kps_un, int n, int n_lef
   p.prm = *params;
   p.st = *state;
   p.n = n;
-  if (!ml_gather(p, world_pos, has_point, n_left)) return fail(ORBX_E_BADARG, "world position not finite");
+  if ((err = gather_flagged(has_point, world_pos, n_left, nullptr, 0, p.kidx, p.wpos))) return fail(ORBX_E_BADARG, err);
   for (int k : p.kidx) {
     if (kps_un[k].octave < 0 || kps_un[k].octave >= nlevels) return fail(ORBX_E_BADARG, "keypoint octave outside [0, nlevels)");
     if (!std::isfinite(kps_un[k].x) || !std::isfinite(kps_un[k].y)) return fail(ORBX_E_BADARG, "keypoint not finite");
@@ -263,9 +210,9 @@ int orbx_mlpnp_iterate_batch(orbx_extractor* ex, int n_problems, const int32_t* 
     p.prm = params[f];
     p.st = states[f];
     p.n = counts[image[f]];
-    if (!ml_gather(p, world_pos + 3 * (size_t)f * cap, has_point + (size_t)f * cap, p.n))
-      return fail(ORBX_E_BADARG, "world position not finite");
-    if (const char* err = ml_plan(p, n_sets)) return fail(ORBX_E_BADARG, err);
+    const char* err = gather_flagged(has_point + (size_t)f * cap, world_pos + 3 * (size_t)f * cap, p.n, nullptr, 0, p.kidx, p.wpos);
+    if (!err) err = ml_plan(p, n_sets);
+    if (err) return fail(ORBX_E_BADARG, err);
   }
   return ml_run(probs, ex->sig2.data(), ex->prm.nlevels, n_sets, states, results, best_masks, inliers, (size_t)cap, hyp_inliers);
 }

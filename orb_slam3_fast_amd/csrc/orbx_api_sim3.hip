@@ -4,7 +4,6 @@
 #include "orbx_sim3.h"
 
 #include <algorithm>
-#include <climits>
 
 static_assert(sizeof(orbx_sim3_params) == 92, "orbx_sim3_params");
 static_assert(sizeof(orbx_sim3_state) == 60, "orbx_sim3_state");
@@ -27,23 +26,9 @@ struct S3Problem {
   int n = 0, N = 0, K = 0;
 };
 
-bool s3_finite(const float* v, int n) {
-  for (int i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
-const char* s3_camera_error(int model, const float* cam, float precision) {
-  if (model != ORBX_CAMERA_PINHOLE && model != ORBX_CAMERA_KB8) return "camera model is neither pinhole nor KB8";
-  if (!s3_finite(cam, model == ORBX_CAMERA_KB8 ? 8 : 4) || !(cam[0] > 0) || !(cam[1] > 0))
-    return "camera parameters not finite, or fx / fy not positive";
-  if (model == ORBX_CAMERA_KB8 && !(std::isfinite(precision) && precision > 0)) return "kb8_precision not finite and positive";
-  return nullptr;
-}
-
 const char* s3_params_error(const orbx_sim3_params& p) {
-  if (const char* e = s3_camera_error(p.model1, p.cam1, p.kb8_precision)) return e;
-  if (const char* e = s3_camera_error(p.model2, p.cam2, p.kb8_precision)) return e;
+  if (const char* e = camera_error(p.model1, p.cam1, p.kb8_precision)) return e;
+  if (const char* e = camera_error(p.model2, p.cam2, p.kb8_precision)) return e;
   if (p.min_inliers < kS3Set) return "min_inliers below 3";
   if (p.max_iterations < 1 || p.max_iterations > kS3MaxIter) return "max_iterations outside [1, 4096]";
   if (p.call_iterations < 0 || p.call_iterations > kS3MaxIter) return "call_iterations outside [0, 4096]";
@@ -52,7 +37,7 @@ const char* s3_params_error(const orbx_sim3_params& p) {
 
 const char* s3_state_error(const orbx_sim3_state& s) {
   if (s.iterations < 0 || s.best_inliers < 0) return "negative state counter";
-  if (!s3_finite(s.best_R, 9) || !s3_finite(s.best_t, 3) || !std::isfinite(s.best_s)) return "state transformation not finite";
+  if (!finite_all(s.best_R, 9) || !finite_all(s.best_t, 3) || !std::isfinite(s.best_s)) return "state transformation not finite";
   return nullptr;
 }
 
@@ -65,11 +50,11 @@ const char* s3_sigma_error(const float* s, int nlevels) {
 
 // the correspondences' inputs, N, K = the passes iterate's loop (:166) can make from this state, and the sets it will read
 const char* s3_plan(S3Problem& p, int nlevels1, int nlevels2, int nSets) {
-  if (!s3_finite(p.Tcw1, 12) || !s3_finite(p.Tcw2, 12)) return "key-frame pose not finite";
+  if (!finite_all(p.Tcw1, 12) || !finite_all(p.Tcw2, 12)) return "key-frame pose not finite";
   int N = 0, best = 0;
   for (int i = 0; i < p.n; i++) {
     if (!p.matched[i]) continue;
-    if (!s3_finite(p.wpos1 + 3 * (size_t)i, 3) || !s3_finite(p.wpos2 + 3 * (size_t)i, 3)) return "world position not finite";
+    if (!finite_all(p.wpos1 + 3 * (size_t)i, 3) || !finite_all(p.wpos2 + 3 * (size_t)i, 3)) return "world position not finite";
     if (p.oct1[i] < 0 || p.oct1[i] >= nlevels1 || p.oct2[i] < 0 || p.oct2[i] >= nlevels2) return "octave outside [0, nlevels)";
     best += p.maskIn[i] != 0;
     N++;
@@ -81,15 +66,7 @@ const char* s3_plan(S3Problem& p, int nlevels1, int nlevels2, int nSets) {
   p.K = std::max(std::min(p.prm.max_iterations - p.st.iterations, p.prm.call_iterations), 0);
   if (p.K > nSets) return "n_sets below min(max_iterations - state.iterations, call_iterations)";
   if (p.K && !p.sets) return "null argument";
-  for (int j = 0; j < p.K; j++) {
-    const int32_t* s = p.sets + kS3Set * (size_t)j;
-    for (int a = 0; a < kS3Set; a++) {
-      if (s[a] < 0 || s[a] >= N) return "set index outside [0, n_correspondences)";
-      for (int b = 0; b < a; b++)
-        if (s[b] == s[a]) return "set index repeated within its set";
-    }
-  }
-  return nullptr;
+  return sets_error<kS3Set>(p.sets, p.K, N);
 }
 
 // outputs of problem f: results[f], states[f], and rows f of bestMasks / inliers (stride bytes apart) / hypInliers (nSets apart)
@@ -99,77 +76,11 @@ int s3_run(std::vector<S3Problem>& probs, const float* sigma1, int nlevels1, con
   const int P = (int)probs.size();
   Pack pk;
   std::vector<S3Args> args(P);
-  std::vector<size_t> oW1(P), oW2(P), oMt(P), oO1(P), oO2(P), oS(P), oM(P);
-  const auto atLeast = [](size_t b) { return std::max<size_t>(b, 16); };
   int maxK = 0;
-  for (int f = 0; f < P; f++) {
-    const S3Problem& p = probs[f];
-    const size_t n = (size_t)p.n;
-    oW1[f] = pk.add(p.wpos1, atLeast(n * 3 * sizeof(float)), n * 3 * sizeof(float));
-    oW2[f] = pk.add(p.wpos2, atLeast(n * 3 * sizeof(float)), n * 3 * sizeof(float));
-    oMt[f] = pk.add(p.matched, atLeast(n), n);
-    oO1[f] = pk.add(p.oct1, atLeast(n * sizeof(int)), n * sizeof(int));
-    oO2[f] = pk.add(p.oct2, atLeast(n * sizeof(int)), n * sizeof(int));
-    oS[f] = pk.add(p.sets, atLeast((size_t)p.K * kS3Set * sizeof(int)), (size_t)p.K * kS3Set * sizeof(int));
-    oM[f] = pk.add(p.maskIn, atLeast(n), n);
-    maxK = std::max(maxK, p.K);
-  }
-  const size_t oSig1 = pk.add(sigma1, (size_t)nlevels1 * sizeof(float));
-  const size_t oSig2 = pk.add(sigma2, (size_t)nlevels2 * sizeof(float));
-  const size_t oArgs = pk.add(args.data(), (size_t)P * sizeof(S3Args));
-  std::vector<size_t> oKi(P), oC1(P), oC2(P), oIm(P), oMw(P), oHf(P), oHp(P), oHc(P);
-  for (int f = 0; f < P; f++) {
-    const S3Problem& p = probs[f];
-    const size_t N = (size_t)p.N, W = (N + 63) / 64, K = (size_t)p.K;
-    oKi[f] = pk.add(nullptr, atLeast(N * sizeof(int)));
-    oC1[f] = pk.add(nullptr, atLeast(N * sizeof(float4)));
-    oC2[f] = pk.add(nullptr, atLeast(N * sizeof(float4)));
-    oIm[f] = pk.add(nullptr, atLeast(N * sizeof(float4)));
-    oMw[f] = pk.add(nullptr, atLeast(W * 8));
-    oHf[f] = pk.add(nullptr, atLeast(K * W * 8));
-    oHp[f] = pk.add(nullptr, atLeast(K * kS3Pose * sizeof(float)));
-    oHc[f] = pk.add(nullptr, atLeast(K * sizeof(int)));
-  }
-  // outputs: one contiguous area
-  const size_t oRes = pk.add(nullptr, (size_t)P * sizeof(orbx_sim3_result));
-  const size_t oSt = pk.add(nullptr, (size_t)P * sizeof(orbx_sim3_state));
-  const size_t oHy = pk.add(nullptr, atLeast((size_t)P * nSets * sizeof(int)));
-  std::vector<size_t> oBm(P), oIn(P);
-  size_t outEnd = oHy + atLeast((size_t)P * nSets * sizeof(int));
-  for (int f = 0; f < P; f++) {
-    const size_t n = (size_t)probs[f].n;
-    oBm[f] = pk.add(nullptr, atLeast(n));
-    oIn[f] = pk.add(nullptr, atLeast(n));
-    outEnd = oIn[f] + atLeast(n);
-  }
-  hipError_t e = pk.reserve();
-  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  for (int f = 0; f < P; f++) {
+  for (int f = 0; f < P; f++) {   // the scalar fields and the inputs
     const S3Problem& p = probs[f];
     S3Args& a = args[f];
-    a = S3Args{};
-    a.wpos1 = pk.ptr<float>(oW1[f]);
-    a.wpos2 = pk.ptr<float>(oW2[f]);
-    a.matched = pk.ptr<uint8_t>(oMt[f]);
-    a.oct1 = pk.ptr<int>(oO1[f]);
-    a.oct2 = pk.ptr<int>(oO2[f]);
-    a.sigma2_1 = pk.ptr<float>(oSig1);
-    a.sigma2_2 = pk.ptr<float>(oSig2);
-    a.sets = pk.ptr<int>(oS[f]);
-    a.maskIn = pk.ptr<uint8_t>(oM[f]);
-    a.kidx = pk.ptr<int>(oKi[f]);
-    a.c1 = pk.ptr<float4>(oC1[f]);
-    a.c2 = pk.ptr<float4>(oC2[f]);
-    a.im = pk.ptr<float4>(oIm[f]);
-    a.maskW = pk.ptr<unsigned long long>(oMw[f]);
-    a.hflags = pk.ptr<unsigned long long>(oHf[f]);
-    a.hpose = pk.ptr<float>(oHp[f]);
-    a.hcount = pk.ptr<int>(oHc[f]);
-    a.result = pk.ptr<orbx_sim3_result>(oRes) + f;
-    a.stateOut = pk.ptr<orbx_sim3_state>(oSt) + f;
-    a.maskOut = pk.ptr<uint8_t>(oBm[f]);
-    a.inliers = pk.ptr<uint8_t>(oIn[f]);
-    a.hypInliers = pk.ptr<int>(oHy) + (size_t)f * nSets;
+    const size_t n = (size_t)p.n, K = (size_t)p.K;
     a.prm = p.prm;
     a.st = p.st;
     std::memcpy(a.Tcw1, p.Tcw1, sizeof a.Tcw1);
@@ -179,7 +90,50 @@ int s3_run(std::vector<S3Problem>& probs, const float* sigma1, int nlevels1, con
     a.K = p.K;
     a.W = (p.N + 63) / 64;
     a.nSets = nSets;
+    pk.in(a.wpos1, p.wpos1, n * 3, 16);
+    pk.in(a.wpos2, p.wpos2, n * 3, 16);
+    pk.in(a.matched, p.matched, n, 16);
+    pk.in(a.oct1, p.oct1, n, 16);
+    pk.in(a.oct2, p.oct2, n, 16);
+    pk.in(a.sets, p.sets, K * kS3Set, 16);
+    pk.in(a.maskIn, p.maskIn, n, 16);
+    maxK = std::max(maxK, p.K);
   }
+  const size_t oSig1 = pk.add(sigma1, (size_t)nlevels1 * sizeof(float));
+  const size_t oSig2 = pk.add(sigma2, (size_t)nlevels2 * sizeof(float));
+  const size_t oArgs = pk.add(args.data(), (size_t)P * sizeof(S3Args));
+  for (S3Args& a : args) {   // scratch
+    const size_t N = (size_t)a.N, W = (size_t)a.W, K = (size_t)a.K;
+    pk.bind(a.sigma2_1, oSig1);
+    pk.bind(a.sigma2_2, oSig2);
+    pk.area(a.kidx, N, 16);
+    pk.area(a.c1, N, 16);
+    pk.area(a.c2, N, 16);
+    pk.area(a.im, N, 16);
+    pk.area(a.maskW, W, 16);
+    pk.area(a.hflags, K * W, 16);
+    pk.area(a.hpose, K * kS3Pose, 16);
+    pk.area(a.hcount, K, 16);
+  }
+  // outputs: one contiguous area
+  const size_t hyBytes = std::max<size_t>((size_t)P * nSets * sizeof(int), 16);
+  const size_t oRes = pk.add(nullptr, (size_t)P * sizeof(orbx_sim3_result));
+  const size_t oSt = pk.add(nullptr, (size_t)P * sizeof(orbx_sim3_state));
+  const size_t oHy = pk.add(nullptr, hyBytes);
+  std::vector<size_t> oBm(P), oIn(P);
+  size_t outEnd = oHy + hyBytes;
+  for (int f = 0; f < P; f++) {
+    S3Args& a = args[f];
+    const size_t n = (size_t)a.n;
+    pk.bind(a.result, oRes, f);
+    pk.bind(a.stateOut, oSt, f);
+    pk.bind(a.hypInliers, oHy, (size_t)f * nSets);
+    oBm[f] = pk.area(a.maskOut, n, 16);
+    oIn[f] = pk.area(a.inliers, n, 16);
+    outEnd = oIn[f] + std::max<size_t>(n, 16);
+  }
+  hipError_t e = pk.reserve();   // writes every bound pointer of args
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   e = pk.commit();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   HIPC(launch_sim3(pk.ptr<S3Args>(oArgs), P, maxK));
@@ -207,10 +161,7 @@ int orbx_sim3_ransac_parameters(int n_correspondences, double probability, int m
   const int N = n_correspondences;
   int nIterations = 1;
   if (N > 0 && min_inliers != N) {
-    const float epsilon = (float)min_inliers / N;
-    // minInliers > N makes epsilon > 1 and the quotient NaN; the reference's conversion of it to int is x86's INT_MIN
-    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3)));
-    nIterations = (std::isfinite(v) && std::fabs(v) < 2147483648.0) ? (int)v : INT_MIN;
+    nIterations = ransac_iterations(probability, (float)min_inliers / N);
   }
   // (N == 0: the reference divides by it; one iteration, which iterate never runs since N < minInliers)
   if (max_iterations_out) *max_iterations_out = std::max(1, std::min(nIterations, max_iterations));

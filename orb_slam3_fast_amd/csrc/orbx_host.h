@@ -11,12 +11,14 @@ static inline void cpu_pause() {}
 #include <memory>
 #include <new>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "orbx_internal.h"
@@ -179,12 +181,27 @@ class Pack {
     if (src && bytes) inputEnd_ = total_;
     return off;
   }
-  // allocates the device block for everything added so far: ptr<>() is valid from here on, while the input items' host
-  // sources are still only read by commit() -- an argument block that holds device pointers INTO the pack can be filled in
-  // between (the batched matchers).  No item may be added after it.
+  // Typed add that also remembers where the area's device address belongs: `field` is a T* / const T* member of the caller's
+  // argument record, and reserve() stores the address there.  in: count elements copied from src (nullptr: reserved only), at
+  // least minBytes reserved; area: scratch / output; bind: element `index` of an area added before (a slice of a shared area).
+  // A bound field must stay where it is until reserve(): size the std::vector of records before the first binding, never resize it.
+  template <class T>
+  size_t in(T*& field, const typename std::remove_const<T>::type* src, size_t count, size_t minBytes = 0) {
+    return bind(field, add(src, std::max(count * sizeof(T), minBytes), count * sizeof(T)));
+  }
+  template <class T> size_t area(T*& field, size_t count, size_t minBytes = 0) { return in(field, nullptr, count, minBytes); }
+  template <class T> size_t bind(T*& field, size_t off, size_t index = 0) { binds_.push_back({&field, off + index * sizeof(T)}); return off; }
+  // allocates the device block for everything added so far and stores the bound fields' addresses: ptr<>() is valid from here
+  // on, while the input items' host sources are still only read by commit() -- an argument block that holds device pointers
+  // INTO the pack is complete before it is read.  No item may be added after it.
   hipError_t reserve() {
     if (dev_.p) return hipSuccess;
-    return dev_.alloc(std::max<size_t>(total_, 256));
+    const hipError_t e = dev_.alloc(std::max<size_t>(total_, 256));
+    for (const Bind& b : binds_) {
+      const uint8_t* p = dev_.p + b.off;   // (a failed allocation: the caller returns without reading the fields)
+      std::memcpy(b.field, &p, sizeof p);
+    }
+    return e;
   }
   hipError_t commit() {
     hipError_t e = reserve();
@@ -223,6 +240,7 @@ class Pack {
 
  private:
   struct Item { const void* src; size_t bytes, off; };
+  struct Bind { void* field; size_t off; };
   static uint8_t* pinned(size_t bytes) {
     thread_local uint8_t* buf = nullptr;
     thread_local size_t cap = 0;
@@ -238,6 +256,7 @@ class Pack {
     return buf;
   }
   std::vector<Item> items_;
+  std::vector<Bind> binds_;
   size_t total_ = 0, inputEnd_ = 0;
   bool pending_ = false;
   ScratchBuf<uint8_t> dev_;
@@ -245,6 +264,55 @@ class Pack {
 
 
 int set_device(int device);  // makes `device` current; ORBX_E_NODEVICE without a GPU (there is no host path)
+
+// ---- argument checks shared by the geometric solvers' entries (pose, two-view, PnP, Sim3, new map points)
+inline bool finite_all(const float* v, int n) {
+  for (int i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+// a camera model (ORBX_CAMERA_*) and its parameters: fx fy cx cy, and k0..k3 for KB8
+inline const char* camera_error(int model, const float* cam, float kb8_precision) {
+  if (model != ORBX_CAMERA_PINHOLE && model != ORBX_CAMERA_KB8) return "camera model is neither pinhole nor KB8";
+  if (!finite_all(cam, model == ORBX_CAMERA_KB8 ? 8 : 4) || !(cam[0] > 0) || !(cam[1] > 0))
+    return "camera parameters not finite, or fx / fy not positive";
+  if (model == ORBX_CAMERA_KB8 && !(std::isfinite(kb8_precision) && kb8_precision > 0)) return "kb8_precision not finite and positive";
+  return nullptr;
+}
+// K RANSAC sets of kSetSize indices: every index inside [0, N) and distinct within its set.  The set size is a template
+// parameter: with it at run time the loops are not unrolled, and 32 solvers' 300 triples cost 45 us instead of 19.
+template <int kSetSize>
+inline const char* sets_error(const int32_t* sets, int K, int N) {
+  for (int j = 0; j < K; j++) {
+    const int32_t* s = sets + kSetSize * (size_t)j;
+    for (int a = 0; a < kSetSize; a++) {
+      if (s[a] < 0 || s[a] >= N) return "set index outside [0, n_correspondences)";
+      for (int b = 0; b < a; b++)
+        if (s[b] == s[a]) return "set index repeated within its set";
+    }
+  }
+  return nullptr;
+}
+// SetRansacParameters' iteration count (MLPnPsolver.cpp:246, Sim3Solver.cc:140).  min inliers > N makes epsilon > 1 and the
+// quotient NaN; the reference's conversion of it to int is x86's INT_MIN
+inline int ransac_iterations(double probability, float epsilon) {
+  const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3)));
+  return (std::isfinite(v) && std::fabs(v) < 2147483648.0) ? (int)v : INT_MIN;
+}
+// Appends (i, world_pos[i]) of the rows i < n with flag[i] set, in ascending i.  kps != nullptr: a flagged row's octave must
+// lie in [0, nlevels), tested before its position.  Returns the first rejection's message, or nullptr.
+inline const char* gather_flagged(const uint8_t* flag, const float* worldPos, int n, const orbx_keypoint* kps, int nlevels,
+                                  std::vector<int>& idx, std::vector<float>& pos) {
+  for (int i = 0; i < n; i++) {
+    if (!flag[i]) continue;
+    if (kps && (kps[i].octave < 0 || kps[i].octave >= nlevels)) return "keypoint octave outside [0, nlevels)";
+    const float* w = worldPos + 3 * (size_t)i;
+    if (!finite_all(w, 3)) return "world position not finite";
+    idx.push_back(i);
+    pos.insert(pos.end(), w, w + 3);
+  }
+  return nullptr;
+}
 
 // One key frame (or frame) of a BoW search: its FeatureVector in CSR form -- node ids, offsets into the feature list, feature
 // indices -- and its keypoints, descriptors and per-keypoint flags (valid / has a map point).

@@ -1,6 +1,6 @@
 // orbx_pose.h — what the two pose-optimisation kernels share: k_pose_opt (pinhole / rectified, orbx_pose.hip) and k_pose_opt_kb8
-// (KannalaBrandt8, orbx_pose_kb8.hip).  SE3Quat and thread 0's g2o Levenberg state machine (its 6 x 6 LDLT is orbx_linalg.h's, the wave
-// reduction orbx_device.h's).
+// (KannalaBrandt8, orbx_pose_kb8.hip), and their C ABI (orbx_api_pose.hip): the per-frame argument records, SE3Quat and thread
+// 0's g2o Levenberg state machine (its 6 x 6 LDLT is orbx_linalg.h's, the wave reduction orbx_device.h's).
 // The kernels live in separate translation units so that the pinhole kernel compiles to the code it had before KB8 existed.
 #ifndef ORBX_POSE_H
 #define ORBX_POSE_H
@@ -211,6 +211,9 @@ __device__ __forceinline__ void ctl_after_eval(Ctl& c, const double* sums) {
 
 }  // namespace
 
-// k_pose_opt_kb8 over n_frames PoseArgsKb8 records (orbx_pose_kb8.hip); lds = dynamic LDS bytes for the staged edges
+// k_pose_opt over nFrames PoseArgs records (orbx_pose.hip); lds = dynamic LDS bytes for the staged edges.  The records are in an
+// unnamed namespace (which keeps the kernels' symbols as they were), so they cross the translation units as void*.
+hipError_t launch_pose_opt(const void* d_frames, int nFrames, size_t lds, const float* d_invSigma2, int nlevels);
+// k_pose_opt_kb8 over nFrames PoseArgsKb8 records (orbx_pose_kb8.hip)
 hipError_t launch_pose_opt_kb8(const void* d_frames, int nFrames, size_t lds, const float* d_invSigma2, int nlevels);
 #endif

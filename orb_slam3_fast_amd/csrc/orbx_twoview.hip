@@ -10,10 +10,10 @@
 //                                             order statistic by a radix selection
 //   k_tv_finish      (pairs) x 256            the acceptance rules, the winner's points and flags, R -> quaternion
 // Sums are reduced by a fixed xor butterfly and across waves in wave order; counters are integers: run-to-run identical, and a
-// pair's result does not depend on the other pairs of the launch.  The host side of both entries is at the end.
+// pair's result does not depend on the other pairs of the launch.  The host side of both entries is orbx_api_twoview.hip.
 #include "orbx_device.h"
-#include "orbx_host.h"
 #include "orbx_linalg.h"
+#include "orbx_twoview.h"
 #include <cmath>
 
 namespace {
@@ -24,39 +24,13 @@ using orbx::null_vector_sym;
 using orbx::svd3;
 using orbx::wave_sum;
 
-constexpr int kTvMaxKps = 15000;
-constexpr int kTvMaxIter = 4096;
 constexpr int kTvBS = 256;
 constexpr int kTvNW = kTvBS / 64;
-constexpr int kTvMinMatches = 8;
 constexpr float kTvNoCos = 2.f;   // cosParallax slot of a match that did not pass CheckRT
 
 struct TvCam {
   float fx, fy, cx, cy, sigma, rhTh;
   int iterations;
-};
-
-// Per-pair device pointers.  `sel`: valid, model, bestH, bestF, nInliers, nHyp, SH bits, SF bits.
-struct TvArgs {
-  const orbx_keypoint* kps1;
-  const orbx_keypoint* kps2;
-  const int2* match;    // [N] (index in frame 1, index in frame 2), ascending in the first
-  const int* sets;      // [iterations][8] indices into match
-  float4* quad;         // [N] u1 v1 u2 v2
-  float* norm;          // [2][4] meanX meanY sX sY per frame
-  float* mats;          // [2][iterations][18]: H21 and H12, or F21
-  float* scores;        // [2][iterations]
-  uint8_t* inl;         // [N] inlier mask of the chosen model's winner
-  float* rt;            // [8][12] R row-major, t
-  int* sel;             // [8]
-  float* hp3d;          // [8][N][3] by match
-  float* hcos;          // [8][N] cosParallax, kTvNoCos = not counted
-  uint8_t* hgood;       // [8][N] vbGood by match
-  int* hres;            // [8][2] nGood, parallax bits
-  orbx_two_view_result* result;
-  float* p3d;           // [n1][3]
-  uint8_t* tri;         // [n1]
-  int n1, n2, N;
 };
 
 // ---- small float matrices, products summed in index order like Eigen's 3 x 3 lazy product
@@ -650,236 +624,15 @@ __global__ __launch_bounds__(kTvBS) void k_tv_finish(const TvArgs* __restrict__ 
   *A.result = r;
 }
 
-// ================================================================================================ host
+}  // namespace
 
-struct TvPair {
-  const orbx_keypoint* kps1 = nullptr;   // host
-  const orbx_keypoint* kps2Host = nullptr;
-  const orbx_keypoint* kps2Dev = nullptr;
-  const int32_t* matches12 = nullptr;
-  const int32_t* sets = nullptr;
-  int n1 = 0, n2 = 0;
-  std::vector<int2> match;
-};
-
-bool tv_params_ok(const orbx_two_view_params* p) {
-  return p && p->iterations >= 1 && p->iterations <= kTvMaxIter && std::isfinite(p->fx) && p->fx > 0 && std::isfinite(p->fy) &&
-         p->fy > 0 && std::isfinite(p->sigma) && p->sigma > 0 && std::isfinite(p->cx) && std::isfinite(p->cy) &&
-         std::isfinite(p->rh_threshold);
-}
-
-// the match list (i, matches12[i] >= 0) in ascending i; false: a target outside [-1, n2)
-bool tv_match_list(TvPair& p) {
-  p.match.clear();
-  for (int i = 0; i < p.n1; i++) {
-    const int m = p.matches12[i];
-    if (m < -1 || m >= p.n2) return false;
-    if (m >= 0) p.match.push_back(make_int2(i, m));
-  }
-  return true;
-}
-
-// every set index inside [0, N) and distinct within its set (not read for fewer than 8 matches)
-bool tv_sets_ok(const TvPair& p, int iterations) {
-  const int N = (int)p.match.size();
-  if (N < kTvMinMatches) return true;
-  for (int it = 0; it < iterations; it++) {
-    const int32_t* s = p.sets + 8 * (size_t)it;
-    for (int a = 0; a < 8; a++) {
-      if (s[a] < 0 || s[a] >= N) return false;
-      for (int b = 0; b < a; b++)
-        if (s[b] == s[a]) return false;
-    }
-  }
-  return true;
-}
-
-void tv_empty_result(orbx_two_view_result& r, int N) {
-  r = orbx_two_view_result{};
-  r.model = -1;
-  r.best_h = r.best_f = -1;
-  r.n_matches = N;
-  r.q[3] = 1.f;
-}
-
-// All pairs through one pack: inputs, the argument block, scratch, then one contiguous output area (results, scores, points,
-// flags).  outP3d / outTri / outScores receive pair f at f * stride (* 3) and f * 2 * iterations.
-int tv_run(std::vector<TvPair>& pairs, const orbx_two_view_params& prm, orbx_two_view_result* results, float* outP3d,
-           uint8_t* outTri, size_t stride, float* outScores) {
-  const int F = (int)pairs.size(), iters = prm.iterations;
-  for (int f = 0; f < F; f++) {
-    tv_empty_result(results[f], (int)pairs[f].match.size());
-    std::memset(outP3d + (size_t)f * stride * 3, 0, stride * 3 * sizeof(float));
-    std::memset(outTri + (size_t)f * stride, 0, stride);
-    if (outScores) std::memset(outScores + (size_t)f * 2 * iters, 0, (size_t)2 * iters * sizeof(float));
-  }
-  bool any = false;
-  for (const TvPair& p : pairs) any = any || (int)p.match.size() >= kTvMinMatches;
-  if (!any) return ORBX_OK;
-  Pack pk;
-  std::vector<TvArgs> args(F);
-  std::vector<size_t> oK1(F), oK2(F), oM(F), oS(F);
-  const auto atLeast = [](size_t b) { return std::max<size_t>(b, 16); };
-  for (int f = 0; f < F; f++) {
-    const TvPair& p = pairs[f];
-    const size_t N = p.match.size();
-    if ((int)N < kTvMinMatches) continue;
-    oK1[f] = pk.add(p.kps1, atLeast((size_t)p.n1 * sizeof(orbx_keypoint)), (size_t)p.n1 * sizeof(orbx_keypoint));
-    if (p.kps2Host) oK2[f] = pk.add(p.kps2Host, atLeast((size_t)p.n2 * sizeof(orbx_keypoint)), (size_t)p.n2 * sizeof(orbx_keypoint));
-    oM[f] = pk.add(p.match.data(), N * sizeof(int2));
-    oS[f] = pk.add(p.sets, (size_t)iters * 8 * sizeof(int));
-  }
-  const size_t oArgs = pk.add(args.data(), (size_t)F * sizeof(TvArgs));
-  std::vector<size_t> oQuad(F), oNorm(F), oMats(F), oInl(F), oRt(F), oSel(F), oHp(F), oHc(F), oHg(F), oHr(F);
-  for (int f = 0; f < F; f++) {
-    const size_t N = pairs[f].match.size();
-    if ((int)N < kTvMinMatches) continue;
-    oQuad[f] = pk.add(nullptr, N * sizeof(float4));
-    oNorm[f] = pk.add(nullptr, 8 * sizeof(float));
-    oMats[f] = pk.add(nullptr, (size_t)2 * iters * 18 * sizeof(float));
-    oInl[f] = pk.add(nullptr, N);
-    oRt[f] = pk.add(nullptr, 8 * 12 * sizeof(float));
-    oSel[f] = pk.add(nullptr, 8 * sizeof(int));
-    oHp[f] = pk.add(nullptr, 8 * N * 3 * sizeof(float));
-    oHc[f] = pk.add(nullptr, 8 * N * sizeof(float));
-    oHg[f] = pk.add(nullptr, 8 * N);
-    oHr[f] = pk.add(nullptr, 16 * sizeof(int));
-  }
-  // outputs
-  const size_t oRes = pk.add(nullptr, (size_t)F * sizeof(orbx_two_view_result));
-  const size_t oSc = pk.add(nullptr, (size_t)F * 2 * iters * sizeof(float));
-  std::vector<size_t> oP(F), oT(F);
-  size_t outEnd = oSc + (size_t)F * 2 * iters * sizeof(float);
-  for (int f = 0; f < F; f++) {
-    if ((int)pairs[f].match.size() < kTvMinMatches) continue;
-    const size_t n1 = (size_t)pairs[f].n1;
-    oP[f] = pk.add(nullptr, n1 * 3 * sizeof(float));
-    oT[f] = pk.add(nullptr, n1);
-    outEnd = oT[f] + n1;
-  }
-  hipError_t e = pk.reserve();
-  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  for (int f = 0; f < F; f++) {
-    const TvPair& p = pairs[f];
-    TvArgs& a = args[f];
-    a = TvArgs{};
-    a.n1 = p.n1;
-    a.n2 = p.n2;
-    a.N = (int)p.match.size();
-    if (a.N < kTvMinMatches) continue;
-    a.kps1 = pk.ptr<orbx_keypoint>(oK1[f]);
-    a.kps2 = p.kps2Host ? pk.ptr<orbx_keypoint>(oK2[f]) : p.kps2Dev;
-    a.match = pk.ptr<int2>(oM[f]);
-    a.sets = pk.ptr<int>(oS[f]);
-    a.quad = pk.ptr<float4>(oQuad[f]);
-    a.norm = pk.ptr<float>(oNorm[f]);
-    a.mats = pk.ptr<float>(oMats[f]);
-    a.scores = pk.ptr<float>(oSc) + (size_t)f * 2 * iters;
-    a.inl = pk.ptr<uint8_t>(oInl[f]);
-    a.rt = pk.ptr<float>(oRt[f]);
-    a.sel = pk.ptr<int>(oSel[f]);
-    a.hp3d = pk.ptr<float>(oHp[f]);
-    a.hcos = pk.ptr<float>(oHc[f]);
-    a.hgood = pk.ptr<uint8_t>(oHg[f]);
-    a.hres = pk.ptr<int>(oHr[f]);
-    a.result = pk.ptr<orbx_two_view_result>(oRes) + f;
-    a.p3d = pk.ptr<float>(oP[f]);
-    a.tri = pk.ptr<uint8_t>(oT[f]);
-  }
-  e = pk.commit();
-  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  const TvCam cam{prm.fx, prm.fy, prm.cx, prm.cy, prm.sigma, prm.rh_threshold, iters};
-  const TvArgs* d = pk.ptr<TvArgs>(oArgs);
+hipError_t launch_two_view(const void* d_args, const orbx_two_view_params& prm, int F) {
+  const TvCam cam{prm.fx, prm.fy, prm.cx, prm.cy, prm.sigma, prm.rh_threshold, prm.iterations};
+  const TvArgs* d = static_cast<const TvArgs*>(d_args);
   hipLaunchKernelGGL(k_tv_prepare, dim3(F), dim3(kTvBS), 0, nullptr, d);
-  hipLaunchKernelGGL(k_tv_hypotheses, dim3(iters, 2, F), dim3(64), 0, nullptr, d, cam);
+  hipLaunchKernelGGL(k_tv_hypotheses, dim3(prm.iterations, 2, F), dim3(64), 0, nullptr, d, cam);
   hipLaunchKernelGGL(k_tv_select, dim3(F), dim3(kTvBS), 0, nullptr, d, cam);
   hipLaunchKernelGGL(k_tv_check_rt, dim3(8, F), dim3(kTvBS), 0, nullptr, d, cam);
   hipLaunchKernelGGL(k_tv_finish, dim3(F), dim3(kTvBS), 0, nullptr, d, cam);
-  HIPC(hipGetLastError());
-  const uint8_t* h = pk.fetch(oRes, outEnd - oRes, &e);
-  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  for (int f = 0; f < F; f++) {
-    const TvPair& p = pairs[f];
-    if ((int)p.match.size() < kTvMinMatches) continue;
-    std::memcpy(&results[f], h + f * sizeof(orbx_two_view_result), sizeof(orbx_two_view_result));
-    if (outScores)
-      std::memcpy(outScores + (size_t)f * 2 * iters, h + (oSc - oRes) + (size_t)f * 2 * iters * sizeof(float),
-                  (size_t)2 * iters * sizeof(float));
-    if (p.n1) {
-      std::memcpy(outP3d + (size_t)f * stride * 3, h + (oP[f] - oRes), (size_t)p.n1 * 3 * sizeof(float));
-      std::memcpy(outTri + (size_t)f * stride, h + (oT[f] - oRes), (size_t)p.n1);
-    }
-  }
-  return ORBX_OK;
+  return hipGetLastError();
 }
-
-}  // namespace
-
-extern "C" {
-
-int orbx_reconstruct_two_views(int device, const orbx_keypoint* kps1, int n1, const orbx_keypoint* kps2, int n2,
-                               const int32_t* matches12, const int32_t* sets, const orbx_two_view_params* params,
-                               orbx_two_view_result* result, float* p3d, uint8_t* triangulated, float* hyp_scores) {
-  if (!result || !params || n1 < 0 || n2 < 0 || (n1 && (!kps1 || !matches12 || !p3d || !triangulated)) || (n2 && !kps2))
-    return fail(ORBX_E_BADARG, "null argument or negative count");
-  if (n1 > kTvMaxKps || n2 > kTvMaxKps) return fail(ORBX_E_BADARG, "more than 15000 keypoints");
-  if (!tv_params_ok(params))
-    return fail(ORBX_E_BADARG, "iterations outside [1, 4096], fx / fy / sigma not finite and positive, or cx / cy / rh_threshold not finite");
-  std::vector<TvPair> pairs(1);
-  TvPair& p = pairs[0];
-  p.kps1 = kps1;
-  p.kps2Host = kps2;
-  p.matches12 = matches12;
-  p.sets = sets;
-  p.n1 = n1;
-  p.n2 = n2;
-  if (!tv_match_list(p)) return fail(ORBX_E_BADARG, "match target outside [-1, n2)");
-  if ((int)p.match.size() >= kTvMinMatches && !sets) return fail(ORBX_E_BADARG, "null argument");
-  if (!tv_sets_ok(p, params->iterations)) return fail(ORBX_E_BADARG, "set index outside [0, n_matches) or repeated within its set");
-  int rc = set_device(device);
-  if (rc != ORBX_OK) return rc;
-  float dummyP[3];
-  uint8_t dummyT[1];
-  return tv_run(pairs, *params, result, n1 ? p3d : dummyP, n1 ? triangulated : dummyT, (size_t)n1, hyp_scores);
-}
-
-int orbx_reconstruct_two_views_batch(orbx_extractor* ex, int first_image, int n_frames, const orbx_keypoint* kps1,
-                                     const int32_t* n1, int stride, const int32_t* matches12, const int32_t* sets,
-                                     const orbx_two_view_params* params, orbx_two_view_result* results, float* p3d,
-                                     uint8_t* triangulated, float* hyp_scores) {
-  if (!ex || n_frames < 0 || first_image < 0 || stride < 0 || !params || (n_frames && (!n1 || !results)))
-    return fail(ORBX_E_BADARG, "bad argument");
-  if (!tv_params_ok(params))
-    return fail(ORBX_E_BADARG, "iterations outside [1, 4096], fx / fy / sigma not finite and positive, or cx / cy / rh_threshold not finite");
-  if (n_frames == 0) return ORBX_OK;
-  if (ex->lastN <= 0 || first_image + n_frames > ex->lastN) return fail(ORBX_E_BADARG, "frames outside the handle's last batch");
-  int maxN1 = 0;
-  for (int f = 0; f < n_frames; f++) {
-    if (n1[f] < 0 || n1[f] > stride || n1[f] > kTvMaxKps) return fail(ORBX_E_BADARG, "n1[f] outside [0, min(stride, 15000)]");
-    maxN1 = std::max(maxN1, n1[f]);
-  }
-  if (maxN1 && (!kps1 || !matches12 || !p3d || !triangulated)) return fail(ORBX_E_BADARG, "null argument");
-  int rc = set_device(ex->device);
-  if (rc != ORBX_OK) return rc;
-  std::vector<int> n2;
-  if ((rc = batch_counts(ex, first_image, n_frames, n2)) != ORBX_OK) return rc;
-  const int cap = ex->gmax.outCap;
-  std::vector<TvPair> pairs(n_frames);
-  for (int f = 0; f < n_frames; f++) {
-    TvPair& p = pairs[f];
-    p.kps1 = kps1 + (size_t)f * stride;
-    p.kps2Dev = ex->d_kps.p + (size_t)(first_image + f) * cap;
-    p.matches12 = matches12 + (size_t)f * stride;
-    p.sets = sets ? sets + (size_t)f * params->iterations * 8 : nullptr;
-    p.n1 = n1[f];
-    p.n2 = n2[f];
-    if (!tv_match_list(p)) return fail(ORBX_E_BADARG, "match target outside [-1, n2)");
-    if ((int)p.match.size() >= kTvMinMatches && !sets) return fail(ORBX_E_BADARG, "null argument");
-    if (!tv_sets_ok(p, params->iterations)) return fail(ORBX_E_BADARG, "set index outside [0, n_matches) or repeated within its set");
-  }
-  float dummyP[3];
-  uint8_t dummyT[1];
-  return tv_run(pairs, *params, results, stride ? p3d : dummyP, stride ? triangulated : dummyT, (size_t)stride, hyp_scores);
-}
-
-}  // extern "C"

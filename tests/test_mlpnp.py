@@ -865,6 +865,46 @@ def test_batch_equals_one_shot_bitwise_and_is_deterministic():
 
 
 @pytest.mark.gpu
+def test_batch_with_an_image_without_keypoints_equals_one_shot_bitwise():
+    """n == 0 between two ordinary problems: every area of that problem is at its minimum size, and the one-shot call with n == 0
+    (whose masks go to a placeholder) returns the same records."""
+    from orb_slam3_fast_amd.hipmem import DeviceBuffer
+    w, h, F = 640, 480, 3
+    rng = np.random.default_rng(98)
+    ex = orbx.ORBextractor(1000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=F)
+    dimg = DeviceBuffer.from_numpy(np.stack([synth.mono_frame(w, h, 950 + f, 0) for f in range(F)]))
+    ex.extract_batch_device(dimg.ptr.value, F, w, h, w, w * h)
+    ex.sync()
+    orbx._check(orbx.lib().orbx_debug_upload_results(ex._h, 1, None, None, 0, 0))
+    cap, cam, sig = ex.capacity, PIN640, ex.GetScaleSigmaSquares()
+    kpss = [ex.download(f)[1] for f in (0, 2)]
+    kpss.insert(1, kpss[0][:0])
+    assert len(kpss[0]) > 60 and len(kpss[2]) > 60
+    wp, hp = np.zeros((F, cap, 3), F32), np.zeros((F, cap), np.uint8)
+    prm, sets = np.zeros(F, orbx.MLPNP_PARAMS_DTYPE), np.zeros((F, N_SETS, 6), np.int32)
+    for p, k in enumerate(kpss):
+        n = len(k)
+        hp[p, rng.permutation(n)[:40]] = 1
+        R, t = rodrigues2rot(rng.normal(size=3) * 0.2), rng.normal(size=3)
+        d = rng.uniform(2, 20, n)
+        pc = np.stack([(k["x"] - cam[2]) / cam[0] * d, (k["y"] - cam[3]) / cam[1] * d, d], 1)
+        wp[p, :n] = (pc - t) @ R
+        N = int(hp[p].sum())
+        mi, it, _ = ransac_parameters(N, 0.99, 10, 300, 6, 0.5)
+        prm[p] = orbx.mlpnp_params(cam, mi, it, 5)[0]
+        sets[p] = orbx.mlpnp_sets(N, N_SETS, seed=600 + p)
+    res, inl, st, bm, hyp = orbx.MLPnPIterateBatch(ex, np.arange(F, dtype=np.int32), wp, hp, prm, sets, want_hyp=True)
+    for p, k in enumerate(kpss):
+        n = len(k)
+        o = orbx.MLPnPIterate(k, wp[p, :n], hp[p, :n], sig, prm[p], sets[p], want_hyp=True)
+        assert o[0].tobytes() == res[p].tobytes(), p
+        assert np.array_equal(o[1], inl[p, :n]) and not inl[p, n:].any(), p
+        assert o[2].tobytes() == st[p:p + 1].tobytes() and np.array_equal(o[3], bm[p, :n]) and np.array_equal(o[4], hyp[p]), p
+    assert res[1]["no_more"] == 1 and res[1]["ok"] == 0 and res[1]["n_correspondences"] == 0 and (hyp[1] == -1).all()
+    assert res[0]["n_correspondences"] == 40 and res[2]["n_correspondences"] == 40
+
+
+@pytest.mark.gpu
 def test_chain_into_pose_optimization():
     """orbx_mlpnp_iterate_batch -> its inliers as has_point and its Tcw as the start of orbx_pose_optimization_batch: the
     optimised pose is within tests/test_pose_opt.py's bound of the known pose (2e-3 rad, 0.05 m)."""

@@ -597,6 +597,37 @@ def test_batch_equals_one_shot_bitwise(mono):
 
 
 @pytest.mark.gpu
+def test_batch_frame_beyond_the_lds_edges_equals_one_shot_bitwise():
+    """A rig frame with one edge more than the kernel holds in LDS (kLdsEdges = 4096: 2049 left + 2048 right) stages its edges
+    in device memory: next to a small frame in one batch, and alone through the one-shot entry, bit for bit the same."""
+    F = 2
+    ex, _keep = _fisheye_batch(F, nf=2100, seed=90)
+    rng = np.random.default_rng(42)
+    cap, n2 = ex.capacity, 2 * ex.capacity
+    assert cap >= 2049
+    sig = ex.GetInverseScaleSigmaSquares()
+    wp, hp = np.zeros((F, n2, 3), F32), np.zeros((F, n2), np.uint8)
+    q0s, t0s, frames = [], [], []
+    for f, (nl, nr) in enumerate(((2049, 2048), (40, 30))):
+        kps, X, _, (q, t), rig = scene(rng, nl, nr)
+        for img, k in ((f, kps[:nl]), (F + f, kps[nl:])):
+            orbx._check(orbx.lib().orbx_debug_upload_results(ex._h, img, orbx._p(np.ascontiguousarray(k)),
+                                                             orbx._p(np.zeros((len(k), 32), np.uint8)), len(k), len(k)))
+        wp[f, :nl + nr], hp[f, :nl + nr] = X, 1
+        q0, t0 = perturb(rng, q, t)
+        q0s.append(q0.astype(F32)), t0s.append(t0.astype(F32)), frames.append((kps, nl, rig))
+    rig = frames[0][2]
+    ng, qb, tb, ob = orbx.PoseOptimizationFisheyeBatch(ex, 0, F, F, wp, hp, np.stack(q0s), np.stack(t0s), rig.k[0], rig.k[1], TRL_Q,
+                                                       TRL_T)
+    for f, (k, nl, _) in enumerate(frames):
+        n = len(k)
+        g1, q1, t1, o1 = run_gpu(k, nl, wp[f, :n], hp[f, :n], q0s[f], t0s[f], rig, sig=sig)
+        assert g1 == ng[f] and q1.tobytes() == qb[f].tobytes() and t1.tobytes() == tb[f].tobytes(), f
+        assert np.array_equal(o1, ob[f, :n]) and not ob[f, n:].any(), f
+    assert ng[0] > 3000 and ng[1] > 35
+
+
+@pytest.mark.gpu
 def test_chained_fisheye_projection_search_and_pose():
     """project_map_points_fisheye -> SearchByProjectionFisheyeBatchDevice -> PoseOptimizationFisheyeBatch: the matcher's match
     row is has_point as it stands, and the pose that generated the scene is recovered."""

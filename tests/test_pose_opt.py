@@ -593,6 +593,37 @@ def test_batch_equals_one_shot_bitwise(mode):
 
 
 @pytest.mark.gpu
+def test_batch_frame_beyond_the_lds_edges_equals_one_shot_bitwise():
+    """A frame with one edge more than the kernel holds in LDS (kLdsEdges = 4096) stages its edges in device memory: next to
+    a small frame in one batch, and alone through the one-shot entry, bit for bit the same."""
+    from orb_slam3_fast_amd.hipmem import DeviceBuffer
+    w, h, F = 640, 480, 2
+    rng = np.random.default_rng(41)
+    ex = orbx.ORBextractor(4200, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=F)
+    dimg = DeviceBuffer.from_numpy(np.stack([synth.mono_frame(w, h, 700 + f, 0) for f in range(F)]))
+    ex.extract_batch_device(dimg.ptr.value, F, w, h, w, w * h)
+    ex.sync()
+    cap = ex.capacity
+    assert cap >= 4097
+    sig = ex.GetInverseScaleSigmaSquares()
+    wp, hp = np.zeros((F, cap, 3), F32), np.zeros((F, cap), np.uint8)
+    q0s, t0s, kpss = [], [], []
+    for f, n in enumerate((4097, 60)):
+        kps, _, X, _, (q, t) = scene(rng, n, stereo=0.0)
+        orbx._check(orbx.lib().orbx_debug_upload_results(ex._h, f, orbx._p(kps), orbx._p(np.zeros((n, 32), np.uint8)), n, n))
+        wp[f, :n], hp[f, :n] = X, 1
+        q0, t0 = perturb(rng, q, t)
+        q0s.append(q0.astype(F32)), t0s.append(t0.astype(F32)), kpss.append(kps)
+    ng, qb, tb, ob = orbx.PoseOptimizationBatch(ex, 0, F, wp, hp, np.stack(q0s), np.stack(t0s), CAM)
+    for f, k in enumerate(kpss):
+        n = len(k)
+        g1, q1, t1, o1 = orbx.PoseOptimization(k, None, wp[f, :n], hp[f, :n], sig, q0s[f], t0s[f], CAM)
+        assert g1 == ng[f] and q1.tobytes() == qb[f].tobytes() and t1.tobytes() == tb[f].tobytes(), f
+        assert np.array_equal(o1, ob[f, :n]) and not ob[f, n:].any(), f
+    assert ng[0] > 3000 and ng[1] > 30
+
+
+@pytest.mark.gpu
 def test_chained_projection_search_and_pose():
     """project_map_points -> SearchByProjectionBatchDevice -> PoseOptimizationBatch on the matched map points converges to the
     pose that generated the scene."""

@@ -775,6 +775,31 @@ def test_batch_equals_one_shot_bitwise_and_is_deterministic():
 
 
 @pytest.mark.gpu
+def test_batch_with_a_problem_without_key_points_equals_one_shot_bitwise():
+    """n == 0 between two ordinary problems: every area of that problem is at its minimum size, and the one-shot call with n == 0
+    (whose masks go to a placeholder) returns the same records."""
+    nums = [4, 9]
+    a = batch_args()
+    idx = [list(SCENES).index(k) for k in nums]
+    pick = lambda x, fill: np.stack([x[idx[0]], np.full_like(x[0], fill), x[idx[1]]])
+    n = np.array([a[0][idx[0]], 0, a[0][idx[1]]], np.int32)
+    prm = np.stack([a[10][idx[0]], a[10][idx[0]], a[10][idx[1]]])
+    res, inl, st, bm, hyp = orbx.Sim3IterateBatch(n, pick(a[1], 0), pick(a[2], 0), pick(a[3], np.nan), pick(a[4], np.nan), pick(a[5], 1),
+                                                  pick(a[6], -5), pick(a[7], 77), a[8], a[9], prm, pick(a[11], 0), want_hyp=True)
+    for p, k in ((0, nums[0]), (2, nums[1])):
+        o = device_iterate(k)
+        m = scene(k)["n"]
+        assert o[0].tobytes() == res[p].tobytes() and np.array_equal(o[1], inl[p, :m]) and not inl[p, m:].any(), k
+        assert o[2].tobytes() == st[p:p + 1].tobytes() and np.array_equal(o[3], bm[p, :m]) and np.array_equal(o[4], hyp[p]), k
+    sc = scene(nums[0])
+    e = np.zeros((0, 3), F32)
+    o = orbx.Sim3Iterate(np.zeros(12, F32), np.zeros(12, F32), e, e, np.zeros(0, np.uint8), np.zeros(0, np.int32), np.zeros(0, np.int32),
+                         sc["sigma2"], sc["sigma2"], prm[1], a[11][0], want_hyp=True)
+    assert o[0].tobytes() == res[1].tobytes() and o[2].tobytes() == st[1:2].tobytes() and np.array_equal(o[4], hyp[1])
+    assert res[1]["no_more"] == 1 and res[1]["n_correspondences"] == 0 and not inl[1].any() and not bm[1].any() and (hyp[1] == -1).all()
+
+
+@pytest.mark.gpu
 def test_chain_into_search_by_sim3():
     """Sim3Iterate's T12 of scene 3 feeds the projections of the existing SearchBySim3 entry on two key-frame views made of the
     scene's correspondences: the formats fit, and the solver's inliers come back matched to their partners."""

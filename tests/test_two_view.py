@@ -874,6 +874,24 @@ def test_gpu_batch_equals_one_shot_bit_for_bit(n_pairs):
 
 
 @pytest.mark.gpu
+def test_gpu_batch_with_a_pair_below_eight_matches_between_ordinary_pairs():
+    """The pair that is not solved takes no area of the call's device block: its neighbours are bit for bit the one-shot
+    results, and its own outputs are the empty result."""
+    ex, pairs = batch_fixture(3)
+    k1, k2, m, _ = make_scene(131, n=7, extra=20)
+    orbx._check(orbx.lib().orbx_debug_upload_results(ex._h, 1, orbx._p(k2), orbx._p(np.zeros((len(k2), 32), np.uint8)), len(k2), len(k2)))
+    pairs[1] = (k1, k2, m, np.zeros((200, 8), np.int32))
+    res, p3d, tri, sc = orbx.ReconstructWithTwoViewsBatch(ex, 0, [p[0] for p in pairs], [p[2] for p in pairs], KMAT,
+                                                          sets=[p[3] for p in pairs], want_scores=True)
+    for f, (k1, k2, m, sets) in enumerate(pairs):
+        one = orbx.ReconstructWithTwoViews(k1, k2, m, KMAT, sets, want_scores=True)
+        assert one[5].tobytes() == res[f].tobytes(), f
+        assert one[3].tobytes() == p3d[f].tobytes() and np.array_equal(one[4], tri[f]) and one[6].tobytes() == sc[f].tobytes(), f
+    assert res[1]["n_matches"] == 7 and res[1]["model"] == -1 and not p3d[1].any() and not tri[1].any() and not sc[1].any()
+    assert res[0]["n_matches"] >= 8 and res[2]["n_matches"] >= 8
+
+
+@pytest.mark.gpu
 def test_gpu_chain_behind_search_for_initialization():
     """extract two synthetic views, SearchForInitializationBatch, its matches12 unchanged into ReconstructWithTwoViewsBatch; the
     model runs on the downloaded keypoints (whether or not the pair initialises)."""
