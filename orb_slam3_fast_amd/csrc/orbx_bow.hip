@@ -1,5 +1,5 @@
 // orbx_bow.hip — bag of words: DBoW2 transform and ORBmatcher::SearchByBoW.
-#include "orbx_device.h"
+#include "orbx_matching.h"
 
 namespace orbx {
 
@@ -351,11 +351,7 @@ __global__ __launch_bounds__(256) void k_bow_vote(R ar) {  // rotHist[bin].push_
   if (i >= a.nF) return;
   const int iKF = a.match[i];
   if (iKF < 0) return;
-  float rot = __fsub_rn(a.kfKps[iKF].angle, a.fKps[i].angle);
-  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-  int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-  if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+  const int bin = rot_bin(a.kfKps[iKF].angle, a.fKps[i].angle);
   a.bin[i] = bin;
   atomicAdd(&a.flags[2 + bin], 1);
 }
@@ -363,34 +359,17 @@ __global__ __launch_bounds__(256) void k_bow_vote(R ar) {  // rotHist[bin].push_
 template <class R>
 __global__ __launch_bounds__(256) void k_bow_cull(R ar) {  // :384-401 with ComputeThreeMaxima :1920-1955
   const BowMatchArgs& a = ar.get();
-  int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-  for (int i = 0; i < 30; i++) {
-    const int s = a.flags[2 + i];
-    if (s > max1) {
-      max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i;
-    } else if (s > max2) {
-      max3 = max2; max2 = s; ind3 = ind2; ind2 = i;
-    } else if (s > max3) {
-      max3 = s; ind3 = i;
-    }
-  }
-  if ((float)max2 < __fmul_rn(0.1f, (float)max1)) {
-    ind2 = -1;
-    ind3 = -1;
-  } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) {
-    ind3 = -1;
-  }
+  const ThreeMaxima top = three_maxima(a.flags + 2);
   const int i = blockIdx.x * 256 + threadIdx.x;
   bool rem = false;
   if (i < a.nF && a.match[i] >= 0) {
     const int bin = a.bin[i];
-    if (bin != ind1 && bin != ind2 && bin != ind3) {
+    if (!top.has(bin)) {
       a.match[i] = -1;
       rem = true;
     }
   }
-  const uint64_t m = __ballot(rem);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.flags[1], __popcll(m));
+  wave_count_add(&a.flags[1], rem);
 }
 template <class R>
 __global__ void k_bow_result(R ar) {
@@ -505,11 +484,7 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a) {
     a.match[idx1] = idx2;
     atomicAdd(&a.flags[0], 1);
     if (a.checkOri) {
-      float rot = __fsub_rn(kp1.angle, a.k2[idx2].angle);
-      if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-      int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-      if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+      const int bin = rot_bin(kp1.angle, a.k2[idx2].angle);
       atomicAdd(&a.flags[2 + bin], 1);
     }
   }
@@ -521,39 +496,18 @@ __global__ __launch_bounds__(1024) void k_tri_cull(TriArgs a) {
   if (threadIdx.x == 0) s_removed = 0;
   __syncthreads();
   if (a.checkOri) {
-    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < 30; i++) {
-      const int s = a.flags[2 + i];
-      if (s > max1) {
-        max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i;
-      } else if (s > max2) {
-        max3 = max2; max2 = s; ind3 = ind2; ind2 = i;
-      } else if (s > max3) {
-        max3 = s; ind3 = i;
-      }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) {
-      ind3 = -1;
-    }
+    const ThreeMaxima top = three_maxima(a.flags + 2);
     int removed = 0;
     for (int i = threadIdx.x; i < a.n1; i += 1024) {
       const int m = a.match[i];
       if (m < 0) continue;
-      float rot = __fsub_rn(a.k1[i].angle, a.k2[m].angle);
-      if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-      int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-      if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
-      if (bin != ind1 && bin != ind2 && bin != ind3) {
+      const int bin = rot_bin(a.k1[i].angle, a.k2[m].angle);
+      if (!top.has(bin)) {
         a.match[i] = -1;
         removed++;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+    removed = wave_sum(removed);
     if ((threadIdx.x & 63) == 0 && removed) atomicAdd(&s_removed, removed);
   }
   __syncthreads();
@@ -649,11 +603,7 @@ __global__ __launch_bounds__(64) void k_bow_match_kf(TriArgs a) {
           a.match[idx1] = bi;
           taken[bpos] = 1;
           if (a.checkOri) {
-            float rot = __fsub_rn(a.k1[idx1].angle, a.k2[bi].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+            const int bin = rot_bin(a.k1[idx1].angle, a.k2[bi].angle);
             atomicAdd(&a.flags[2 + bin], 1);
           }
         }

@@ -60,10 +60,19 @@ __device__ __forceinline__ uint32_t wave_min_dpp(uint32_t v) {  // minimum over 
   v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xc, 0xf, false));
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
-// The __shfl_xor butterflies of the solvers: a fixed xor tree in `double`, for which the DPP helpers above have no form.
+// The __shfl_xor butterflies of the solvers and matchers: a fixed xor tree in `double`, 64-bit keys or plain int, for which the
+// DPP helpers above have no form (or whose kernels were measured in this form).
 template <class T>
 __device__ __forceinline__ T wave_sum(T v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const T t = __shfl_xor(v, off);
+    v = t < v ? t : v;
+  }
   return v;
 }
 __device__ __forceinline__ double wave_max(double v) {

@@ -2,7 +2,7 @@
 // SearchByProjection flavours (:41-221, :1594-1806), pinhole and stereo-fisheye.
 #include <algorithm>
 
-#include "orbx_device.h"
+#include "orbx_matching.h"
 
 namespace orbx {
 
@@ -248,11 +248,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(InitArgs a) {
       const uint64_t v = ((uint64_t)(uint32_t)d << 32) | (uint32_t)(j - b);
       best = v < best ? v : best;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint64_t t = __shfl_xor((unsigned long long)best, o);
-      best = t < best ? t : best;
-    }
+    best = wave_min(best);
     if (best == ~0ull) continue;
     const int bestDist = (int)(best >> 32), bestPos = (int)(best & 0xFFFFFFFFu);
     int second = 0x7FFFFFFF;
@@ -262,8 +258,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(InitArgs a) {
       if (a.matchedDist[i2] <= d) continue;
       second = min(second, d);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) second = min(second, __shfl_xor(second, o));
+    second = wave_min(second);
     if (bestDist <= 50 && (float)bestDist < __fmul_rn((float)second, a.nnratio)) {
       if (lane == 0) {
         const int bestIdx2 = a.candIdx[b + bestPos];
@@ -277,11 +272,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(InitArgs a) {
         a.matchedDist[bestIdx2] = bestDist;
         nmatches++;
         if (a.checkOri) {
-          float rot = __fsub_rn(a.k1[i1].angle, a.k2[bestIdx2].angle);
-          if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-          int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-          if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+          const int bin = rot_bin(a.k1[i1].angle, a.k2[bestIdx2].angle);
           bins[i1] = (int8_t)bin;
           hist[bin]++;
         }
@@ -292,34 +283,16 @@ __global__ __launch_bounds__(64) void k_init_resolve(InitArgs a) {
   }
   nmatches = __shfl(nmatches, 0);
   if (a.checkOri) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < 30; i++) {  // ComputeThreeMaxima, src/ORBmatcher.cc:1920-1955
-      const int s = hist[i];
-      if (s > max1) {
-        max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i;
-      } else if (s > max2) {
-        max3 = max2; max2 = s; ind3 = ind2; ind2 = i;
-      } else if (s > max3) {
-        max3 = s; ind3 = i;
-      }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) {
-      ind3 = -1;
-    }
+    const ThreeMaxima top = three_maxima(hist);
     int removed = 0;
     for (int i = lane; i < a.n1; i += 64) {
       const int bn = bins[i];
-      if (bn >= 0 && bn != ind1 && bn != ind2 && bn != ind3 && a.matches12[i] >= 0) {
+      if (bn >= 0 && !top.has(bn) && a.matches12[i] >= 0) {
         a.matches12[i] = -1;
         removed++;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+    removed = wave_sum(removed);
     nmatches -= removed;
   }
   __syncthreads();
@@ -509,11 +482,7 @@ __global__ __launch_bounds__(256) void k_init_round(R ar, int round_no) {
       const uint64_t v = ((uint64_t)(uint32_t)d << 32) | (uint32_t)(j - b);
       best = v < best ? v : best;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint64_t t = __shfl_xor((unsigned long long)best, o);
-      best = t < best ? t : best;
-    }
+    best = wave_min(best);
     if (best != ~0ull) {
       const int bestDist = (int)(best >> 32), bestPos = (int)(best & 0xFFFFFFFFu);
       int second = 0x7FFFFFFF;
@@ -553,14 +522,7 @@ __global__ __launch_bounds__(256) void k_init_reset(R ar) {  // before round 0: 
   if (blockIdx.x == 0 && threadIdx.x < kProjChanged + 48) a.flags[threadIdx.x] = 0;
 }
 
-__device__ __forceinline__ int init_bin(const InitArgs& a, int i1, int i2) {
-  float rot = __fsub_rn(a.k1[i1].angle, a.k2[i2].angle);
-  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-  int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-  if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
-  return bin;
-}
+__device__ __forceinline__ int init_bin(const InitArgs& a, int i1, int i2) { return rot_bin(a.k1[i1].angle, a.k2[i2].angle); }
 
 template <class R>
 __global__ __launch_bounds__(256) void k_init_owner(R ar, int) {  // vnMatches21 = the last claimer; votes
@@ -616,8 +578,7 @@ __global__ __launch_bounds__(256) void k_init_finish(R ar, int) {
       a.prev[2 * i1 + 1] = a.k2[m].y;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+  kept = wave_sum(kept);
   if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&a.flags[2], kept);
 }
 
@@ -835,11 +796,7 @@ __global__ __launch_bounds__(64) void k_proj_resolve(ProjRef<B> ar) {
         a.match[bestIdx] = im;
         a.occupied[bestIdx] = a.mode == 0 ? a.mps[im].has_observations : (uint8_t)(a.claimAll | a.pts[im].has_observations);
         if (a.mode == 1 && a.checkOri) {
-          float rot = __fsub_rn(a.pts[im].angle, a.grid.k2[bestIdx].angle);
-          if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-          int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-          if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+          const int bin = rot_bin(a.pts[im].angle, a.grid.k2[bestIdx].angle);
           binIdx[nBin] = (bin << 24) | bestIdx;
           hist[bin]++;
         }
@@ -852,34 +809,17 @@ __global__ __launch_bounds__(64) void k_proj_resolve(ProjRef<B> ar) {
   }
   if (a.mode == 1 && a.checkOri) {  // rotation-consistency cull, :1780-1800 (+ ComputeThreeMaxima :1920-1955)
     __syncthreads();
-    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < 30; i++) {
-      const int s = hist[i];
-      if (s > max1) {
-        max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i;
-      } else if (s > max2) {
-        max3 = max2; max2 = s; ind3 = ind2; ind2 = i;
-      } else if (s > max3) {
-        max3 = s; ind3 = i;
-      }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) {
-      ind3 = -1;
-    }
+    const ThreeMaxima top = three_maxima(hist);
     int removed = 0;
     for (int i = lane; i < nBin; i += 64) {
       const int bn = binIdx[i] >> 24, idx = binIdx[i] & 0xFFFFFF;
-      if (bn != ind1 && bn != ind2 && bn != ind3) {
+      if (!top.has(bn)) {
         a.match[idx] = -1;  // CurrentFrame.mvpMapPoints[idx] = NULL (even if a later point re-took the slot)
         if (a.claimAll) a.occupied[idx] = 0;
         removed++;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+    removed = wave_sum(removed);
     nmatches -= removed;
   }
   if (lane == 0) a.result[0] = nmatches;
@@ -979,17 +919,12 @@ __global__ __launch_bounds__(256) void k_proj_assign(ProjRef<B> ar) {
       acc = true;
       atomicMax(&a.match[k], im);
       if (a.mode == 1 && a.checkOri) {
-        float rot = __fsub_rn(a.pts[im].angle, a.grid.k2[k].angle);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+        const int bin = rot_bin(a.pts[im].angle, a.grid.k2[k].angle);
         atomicAdd(&a.flags[3 + bin], 1);
       }
     }
   }
-  const uint64_t m = __ballot(acc);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.flags[1], __popcll(m));
+  wave_count_add(&a.flags[1], acc);
 }
 
 template <bool B>
@@ -1005,42 +940,21 @@ __global__ __launch_bounds__(256) void k_proj_cull(ProjRef<B> ar) {
 template <bool B>
 __global__ __launch_bounds__(256) void k_proj_cull2(ProjRef<B> ar) {
   const ProjArgs& a = ar.get();  // rotation-consistency cull (:1780-1800, :1920-1955)
-  int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-  for (int i = 0; i < 30; i++) {
-    const int s = a.flags[3 + i];
-    if (s > max1) {
-      max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i;
-    } else if (s > max2) {
-      max3 = max2; max2 = s; ind3 = ind2; ind2 = i;
-    } else if (s > max3) {
-      max3 = s; ind3 = i;
-    }
-  }
-  if ((float)max2 < __fmul_rn(0.1f, (float)max1)) {
-    ind2 = -1;
-    ind3 = -1;
-  } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) {
-    ind3 = -1;
-  }
+  const ThreeMaxima top = three_maxima(a.flags + 3);
   const int im = blockIdx.x * 256 + threadIdx.x;
   bool rem = false;
   if (im < a.nmp) {
     const int k = a.choice[im];
     if (k >= 0) {
-      float rot = __fsub_rn(a.pts[im].angle, a.grid.k2[k].angle);
-      if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-      int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-      if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
-      if (bin != ind1 && bin != ind2 && bin != ind3) {
+      const int bin = rot_bin(a.pts[im].angle, a.grid.k2[k].angle);
+      if (!top.has(bin)) {
         a.match[k] = -1;  // CurrentFrame.mvpMapPoints[idx] = NULL, even if a later point re-took the slot
         if (a.claimAll) a.occupied[k] = 0;
         rem = true;
       }
     }
   }
-  const uint64_t m = __ballot(rem);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.flags[2], __popcll(m));
+  wave_count_add(&a.flags[2], rem);
 }
 
 template <bool B>
@@ -1128,11 +1042,7 @@ __global__ __launch_bounds__(64) void k_proj_resolve_fe(ProjFeArgs a) {
     auto vote = [&](int slot) {
       if (a.mode == 1 && a.checkOri) {
         if (lane == 0) {
-          float rot = __fsub_rn(a.pts[im].angle, a.kps[slot].angle);
-          if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-          int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-          if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+          const int bin = rot_bin(a.pts[im].angle, a.kps[slot].angle);
           binIdx[nBin] = (bin << 24) | slot;
           hist[bin]++;
         }
@@ -1207,33 +1117,16 @@ __global__ __launch_bounds__(64) void k_proj_resolve_fe(ProjFeArgs a) {
   }
   if (a.mode == 1 && a.checkOri) {
     __syncthreads();
-    int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < 30; i++) {
-      const int s = hist[i];
-      if (s > max1) {
-        max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i;
-      } else if (s > max2) {
-        max3 = max2; max2 = s; ind3 = ind2; ind2 = i;
-      } else if (s > max3) {
-        max3 = s; ind3 = i;
-      }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) {
-      ind3 = -1;
-    }
+    const ThreeMaxima top = three_maxima(hist);
     int removed = 0;
     for (int i = lane; i < nBin; i += 64) {
       const int bn = binIdx[i] >> 24, slot = binIdx[i] & 0xFFFFFF;
-      if (bn != ind1 && bn != ind2 && bn != ind3) {
+      if (!top.has(bn)) {
         a.match[slot] = -1;
         removed++;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) removed += __shfl_xor(removed, o);
+    removed = wave_sum(removed);
     nmatches -= removed;
   }
   if (lane == 0) a.result[0] = nmatches;
@@ -1417,14 +1310,7 @@ __global__ __launch_bounds__(256) void k_proj_reset_fe(R ar) {  // before round 
   if (blockIdx.x == 0 && threadIdx.x < kProjChanged + 48) a.flags[threadIdx.x] = 0;  // overflow, counts, histogram, changed[]
 }
 
-__device__ __forceinline__ int fe_bin(const ProjFeArgs& a, int im, int slot) {
-  float rot = __fsub_rn(a.pts[im].angle, a.kps[slot].angle);
-  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-  int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-  if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
-  return bin;
-}
+__device__ __forceinline__ int fe_bin(const ProjFeArgs& a, int im, int slot) { return rot_bin(a.pts[im].angle, a.kps[slot].angle); }
 
 template <class R>
 __global__ __launch_bounds__(256) void k_proj_assign_fe(R ar, int) {  // last writer wins every slot
@@ -1447,8 +1333,7 @@ __global__ __launch_bounds__(256) void k_proj_assign_fe(R ar, int) {  // last wr
       if (w.z >= 0) atomicAdd(&a.flags[4 + fe_bin(a, im, w.z)], 1);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nw += __shfl_xor(nw, o);
+  nw = wave_sum(nw);
   if ((threadIdx.x & 63) == 0 && nw) atomicAdd(&a.flags[2], nw);
 }
 
@@ -1496,8 +1381,7 @@ __global__ __launch_bounds__(256) void k_proj_cull_fe(R ar, int) {
         }
       }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rem += __shfl_xor(rem, o);
+  rem = wave_sum(rem);
   if ((threadIdx.x & 63) == 0 && rem) atomicAdd(&a.flags[3], rem);
 }
 

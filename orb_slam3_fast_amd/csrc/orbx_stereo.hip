@@ -2,7 +2,7 @@
 // (:1293-1302) and ComputeStereoFishEyeMatches with the KannalaBrandt8 triangulation (:1273-1331).
 #include <mutex>
 
-#include "orbx_device.h"
+#include "orbx_matching.h"
 #include "orbx_linalg.h"
 #include "orbx_kb8.h"
 
@@ -965,11 +965,7 @@ __global__ __launch_bounds__(256) void k_tri_match_rig(TriArgs a) {
     a.match[idx1] = idx2;
     atomicAdd(&a.flags[0], 1);
     if (a.checkOri) {
-      float rot = kp1.angle - a.k2[idx2].angle;
-      if (rot < 0.0f) rot = rot + 360.0f;
-      int bin = (int)roundf(rot * (1.0f / 30));
-      if (bin == 30) bin = 0;
-  bin = min(max(bin, 0), 29);  // (angles outside [0, 360) or NaN: the reference asserts; here the vote stays inside the histogram)
+      const int bin = rot_bin(kp1.angle, a.k2[idx2].angle);
       atomicAdd(&a.flags[2 + bin], 1);
     }
   }
