@@ -1110,6 +1110,102 @@ int orbx_sim3_iterate_batch(int device, int n_problems, int cap, const int32_t* 
                             int nlevels2, const orbx_sim3_params* params, const int32_t* sets, int n_sets, orbx_sim3_state* states,
                             uint8_t* best_masks, orbx_sim3_result* results, uint8_t* inliers, int32_t* hyp_inliers);
 
+/* ---- loop-closing Sim3 refinement (Optimizer::OptimizeSim3) --------------------------------------------- */
+
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:2164-2424; the call sites src/LoopClosing.cc:609, 852), the step between the Sim3
+ * searches of loop closing and map merging, on the device: ONE launch, one wave per problem, for any number of problems.
+ *
+ * Edges, per key point i of key frame 1 with matched[i] != 0 (<=> vpMatches1[i] is set, key frame 1 has a map point at i and
+ * neither point is bad; the entries the reference skips without clearing or counting are the caller's): P3D1c = R1w Xw1 + t1w and
+ * P3D2c = R2w Xw2 + t2w in float (the expression of the Sim3 solver's X3Dc), widened to double.  Skipped: idx2[i] < 0 with
+ * all_points == 0, and P3D2c.z < 0 (strict: z == 0 passes).  Otherwise nCorrespondences++ and two edges: e12 = obs1 - pi1(S12
+ * P3D2c), obs1 = kps1_un[i], information mvInvLevelSigma2_1[octave]; e21 = obs2 - pi2(S12^-1 P3D1c), information
+ * mvInvLevelSigma2_2[octave2].  idx2 >= 0: obs2 and octave2 are kps2_un[idx2]'s.  idx2 < 0: obs2 = (x invz, y invz) of P3D2c
+ * with a float invz = 1 / z -- NORMALISED coordinates, not pixels -- and octave2 = track_level2[i]: the reference's behaviour
+ * with bAllPoints = true (both call sites), reproduced and not repaired; such a pair weighs on the first round under the Huber
+ * kernel and is then almost always cleared.  Both edges carry a Huber kernel of delta = (float)sqrt(th2).
+ *
+ * Sim3 arithmetic (Thirdparty/g2o/g2o/types/sim3.h): oplus = Sim3(update) * estimate, update = (omega, upsilon, sigma),
+ * update[6] = 0 with a fixed scale; Sim3(Vector7d) in its four branches (|sigma| < 1e-5, theta < 1e-5); r = Quaterniond(R) is NOT
+ * normalised (unlike SE3Quat), nor do operator* and inverse() normalise; map(x) = s (r * x) + t with Eigen's quaternion-vector
+ * formula; inverse() = (conj r, conj r * ((-1 / s) t), 1 / s).
+ *
+ * Levenberg (optimization_algorithm_levenberg.cpp:61-170), the rules of the pose optimiser in 7 dimensions: lambda = 1e-5 max
+ * diag(H); a trial solves (H + lambda I) x = b by an unpivoted LDLT, a failed factorisation gives chi2 = DBL_MAX; rho = (chi -
+ * trial chi) / (x . (lambda x + b) + 1e-3); accepted: lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)), ni = 2; rejected: lambda
+ * *= ni, ni *= 2; at most 10 trials per iteration; an iteration that gains less than 1e-3 of its chi2 three times in a row
+ * stops.  With a fixed scale row and column 6 of H hold only lambda.
+ *
+ * Rounds: optimize(5); every pair with e12.chi2() > th2 || e21.chi2() > th2 (in double, at the errors of the optimiser's LAST
+ * TRIAL, even a rejected one) is removed and its matched entry cleared (n_bad); the survivors lose their robust kernel;
+ * n_correspondences - n_bad < 10 returns 0 (early_return: matches already cleared, S12 untouched).  Then optimize(n_bad > 0 ?
+ * 10 : 5) from round one's estimate; the errors are recomputed at the final estimate, entries above th2 are cleared, the others
+ * counted (n_in); S12 becomes the estimate.  mAcumHessian is set to zero by the reference (after the early return's exit) and never
+ * accumulated: the mirrors return zeros, and leave it alone on the early return.
+ *
+ * Deliberate differences from the reference:
+ *  - the Jacobians are ANALYTIC.  Both edge classes leave linearizeOplus commented out, so g2o differentiates numerically
+ *    (central differences, delta = 1e-9, base_binary_edge.hpp:130-205), which carries rounding noise of about eps |pi| / 1e-9 per
+ *    entry that no implementation can reproduce bit for bit.  With y = S12 P3D2c, z = S12^-1 P3D1c, under the left perturbation:
+ *    J12 = -Jpi1(y) [ -[y]x | I | y ], J21 = -Jpi2(z) (1 / s) R^T [ [P3D1c]x | -I | -P3D1c ]; column 6 is zero with a fixed scale.
+ *    tests/sim3opt_cases.py checks them against central differences and measures what the difference does to the result.
+ *  - PINHOLE cameras only: a KannalaBrandt8 model is ORBX_E_BADARG.  KannalaBrandt8::project(Vector3d) takes theta and psi
+ *    through atan2f and sqrtf (KannalaBrandt8.cpp:48-66); a 1e-9 step does not move a float, so g2o's numeric Jacobian of a
+ *    fisheye edge is zero or a one-ulp spike times 5e8: there is no behaviour to be faithful to.
+ * Out of contract: a point at exactly z = 0 under an evaluated estimate (as in the pose optimiser). */
+typedef struct orbx_sim3opt_params {
+  int32_t model1;      /* camera of key frame 1: ORBX_CAMERA_PINHOLE (ORBX_CAMERA_KB8 is rejected, above) */
+  float cam1[4];       /* fx fy cx cy */
+  int32_t model2;      /* camera of key frame 2 */
+  float cam2[4];
+  float th2;           /* > 0 */
+  int32_t fix_scale;   /* bFixScale */
+  int32_t all_points;  /* bAllPoints */
+} orbx_sim3opt_params; /* 52 bytes */
+typedef struct orbx_sim3_pose {   /* g2o::Sim3 */
+  double q[4];         /* r, x y z w, not normalised */
+  double t[3];
+  double s;            /* > 0 */
+} orbx_sim3_pose;      /* 64 bytes */
+typedef struct orbx_sim3opt_result {
+  int32_t n_in;              /* the return value: nIn, 0 on the early return */
+  int32_t n_correspondences; /* nCorrespondences = edge pairs */
+  int32_t n_bad;             /* nBad of round one */
+  int32_t n_in_kf2;          /* nInKF2 */
+  int32_t n_out_kf2;         /* nOutKF2 */
+  int32_t trials;            /* Levenberg trials of both rounds */
+  int32_t early_return;      /* n_correspondences - n_bad < 10 */
+} orbx_sim3opt_result;       /* 28 bytes */
+/* One pair of key frames, from host arrays over the n = vpMatches1.size() key points of key frame 1 (n <= 15000): kps1_un [n] =
+ * mvKeysUn of key frame 1, world_pos1 / world_pos2 [n][3] = the world positions of key frame 1's map point at i and of
+ * vpMatches1[i], matched [n] (in/out, above: cleared entries become 0, the others keep their value), idx2 [n] = the index of
+ * vpMatches1[i] in key frame 2 (< 0: not observed there), kps2_un [n2] = mvKeysUn of key frame 2, track_level2 [n] =
+ * mnTrackScaleLevel of vpMatches1[i] (read, and checked, only where idx2 < 0 and all_points is set), Tcw1 / Tcw2 = the key frames'
+ * poses (top three rows, row-major),
+ * inv_level_sigma2_1 / _2 = their mvInvLevelSigma2.  Entries with matched == 0 are not read.  S12 is in/out and unchanged on the
+ * early return.  Returns n_in (>= 0).  All arguments are validated before a device is touched (null pointers, sizes, finite
+ * poses, positions, key points, cameras and tables, S12.s > 0 and a non-zero quaternion, th2 > 0, octaves and track_level2
+ * inside their tables, idx2 < n2, pinhole models); valid arguments without a device return ORBX_E_NODEVICE (there is no host
+ * optimiser). */
+int orbx_optimize_sim3(int device, int n, const orbx_keypoint* kps1_un, const float* world_pos1, const float* world_pos2,
+                       uint8_t* matched, const int32_t* idx2, const orbx_keypoint* kps2_un, int n2, const int32_t* track_level2,
+                       const float* Tcw1, const float* Tcw2, const float* inv_level_sigma2_1, int nlevels1,
+                       const float* inv_level_sigma2_2, int nlevels2, const orbx_sim3opt_params* params, orbx_sim3_pose* S12,
+                       orbx_sim3opt_result* result);
+/* n_problems pairs in one call (the candidates of a key frame: what the batched RANSAC in front of it hands over), laid out as
+ * orbx_sim3_iterate_batch lays them out: n [n_problems] key points per problem (<= cap <= 15000, 0 is allowed), kps1_un / matched
+ * / idx2 / track_level2 [n_problems][cap], world_pos1 / world_pos2 [n_problems][cap][3], kps2_un [n_problems][cap2] with n2
+ * [n_problems] <= cap2 key points each, Tcw1 / Tcw2 [n_problems][12], the two mvInvLevelSigma2 tables shared by all problems,
+ * params / S12 / results [n_problems].  Entries past n[p] are neither read nor written.  One upload, one launch, one download;
+ * problem p has the bits of the one-shot entry on the same data.  At most 65535 problems.  Validated like the one-shot entry.
+ * Returns ORBX_OK. */
+int orbx_optimize_sim3_batch(int device, int n_problems, int cap, const int32_t* n, const orbx_keypoint* kps1_un,
+                             const float* world_pos1, const float* world_pos2, uint8_t* matched, const int32_t* idx2,
+                             const orbx_keypoint* kps2_un, int cap2, const int32_t* n2, const int32_t* track_level2,
+                             const float* Tcw1, const float* Tcw2, const float* inv_level_sigma2_1, int nlevels1,
+                             const float* inv_level_sigma2_2, int nlevels2, const orbx_sim3opt_params* params,
+                             orbx_sim3_pose* S12, orbx_sim3opt_result* results);
+
 /* ---- new map points (local mapping) ------------------------------------------------------------------- */
 
 /* The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), which consumes the match list of

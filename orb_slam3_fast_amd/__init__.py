@@ -112,6 +112,8 @@ def lib():
         L.orbx_sim3_ransac_parameters.argtypes = [i, C.c_double, i, i, vp]
         L.orbx_sim3_iterate.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_sim3_iterate_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
+        L.orbx_optimize_sim3.argtypes = [i, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, i, vp, i, vp, vp, vp]
+        L.orbx_optimize_sim3_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp]
         L.orbx_triangulate_matches.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_create_new_map_points.argtypes = [i, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
@@ -1114,6 +1116,94 @@ def Sim3IterateBatch(n, Tcw1, Tcw2, worldPos1, worldPos2, matched, octave1, octa
                                          _p(res), _p(inl), _p(hyp) if want_hyp else None))
     out = (res, inl.astype(bool), states, bm)
     return out + (hyp,) if want_hyp else out
+
+
+SIM3OPT_PARAMS_DTYPE = np.dtype([("model1", "<i4"), ("cam1", "<f4", (4,)), ("model2", "<i4"), ("cam2", "<f4", (4,)), ("th2", "<f4"),
+                                 ("fix_scale", "<i4"), ("all_points", "<i4")])
+SIM3_POSE_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])   # g2o::Sim3: r (x y z w), t, s
+SIM3OPT_RESULT_DTYPE = np.dtype([("n_in", "<i4"), ("n_correspondences", "<i4"), ("n_bad", "<i4"), ("n_in_kf2", "<i4"),
+                                 ("n_out_kf2", "<i4"), ("trials", "<i4"), ("early_return", "<i4")])
+assert SIM3OPT_PARAMS_DTYPE.itemsize == 52 and SIM3_POSE_DTYPE.itemsize == 64 and SIM3OPT_RESULT_DTYPE.itemsize == 28
+
+
+def sim3opt_params(camera1, camera2, th2, fix_scale, all_points=False, n=1):
+    """orbx_sim3opt_params records: camera1 / camera2 = (fx, fy, cx, cy) of a pinhole.  Eight parameters name a KannalaBrandt8
+    camera, which the library rejects (include/orbx.h says why)."""
+    prm = np.zeros(n, SIM3OPT_PARAMS_DTYPE)
+    for k, camera in (("1", camera1), ("2", camera2)):
+        cam = np.asarray(camera, np.float32).reshape(-1)
+        prm["model" + k] = CAMERA_KB8 if len(cam) == 8 else CAMERA_PINHOLE
+        prm["cam" + k] = cam[:4]
+    prm["th2"], prm["fix_scale"], prm["all_points"] = th2, int(bool(fix_scale)), int(bool(all_points))
+    return prm
+
+
+def sim3_pose(q, t, s, n=1):
+    """orbx_sim3_pose records from r (x y z w), t and s."""
+    S = np.zeros(n, SIM3_POSE_DTYPE)
+    S["q"], S["t"], S["s"] = np.asarray(q, float), np.asarray(t, float), s
+    return S
+
+
+def OptimizeSim3(kpsUn1, worldPos1, worldPos2, matched, idx2, kpsUn2, trackLevel2, Tcw1, Tcw2, invLevelSigma2_1, invLevelSigma2_2,
+                 g2oS12, th2, bFixScale, bAllPoints=False, camera1=None, camera2=None, device=0):
+    """Optimizer::OptimizeSim3 (src/Optimizer.cc:2164-2424) on the GPU (orbx_optimize_sim3).  Over the n key points of key frame
+    1: kpsUn1 [n] KP_DTYPE, worldPos1 / worldPos2 [n][3] = the map point of key frame 1 at i and vpMatches1[i], matched [n]
+    (vpMatches1[i] is set, key frame 1 has a map point there, neither is bad), idx2 [n] = the index of vpMatches1[i] in key frame 2
+    (< 0: not there), kpsUn2 [n2], trackLevel2 [n] = mnTrackScaleLevel (read where idx2 < 0), Tcw1 / Tcw2 (3 x 4 or 4 x 4), the two
+    mvInvLevelSigma2 tables, g2oS12 = a sim3_pose record (or (q, t, s)), camera1 / camera2 = (fx, fy, cx, cy).  Returns (nIn,
+    g2oS12 record, matched [n] uint8 with the cleared entries zeroed, mAcumHessian, result record).  mAcumHessian is zeros (7, 7),
+    as the reference sets it and never accumulates, and None on the early return (result["early_return"]: fewer than 10 pairs left
+    after round one), which the reference takes before it touches the matrix."""
+    if camera1 is None or camera2 is None:
+        raise ValueError("OptimizeSim3: camera1 and camera2 = (fx, fy, cx, cy) of the two key frames are required")
+    m = np.array(matched, np.uint8).reshape(-1)
+    n = len(m)
+    k1 = np.ascontiguousarray(kpsUn1, KP_DTYPE).reshape(n)
+    k2 = np.ascontiguousarray(kpsUn2, KP_DTYPE).reshape(-1)
+    w1 = np.ascontiguousarray(worldPos1, np.float32).reshape(n, 3)
+    w2 = np.ascontiguousarray(worldPos2, np.float32).reshape(n, 3)
+    i2 = np.ascontiguousarray(idx2, np.int32).reshape(n)
+    tl = np.ascontiguousarray(trackLevel2, np.int32).reshape(n)
+    T1 = np.ascontiguousarray(np.asarray(Tcw1, np.float32).reshape(-1)[:12])
+    T2 = np.ascontiguousarray(np.asarray(Tcw2, np.float32).reshape(-1)[:12])
+    s1 = np.ascontiguousarray(invLevelSigma2_1, np.float32)
+    s2 = np.ascontiguousarray(invLevelSigma2_2, np.float32)
+    prm = sim3opt_params(camera1, camera2, th2, bFixScale, bAllPoints)
+    S = np.array(g2oS12, SIM3_POSE_DTYPE).reshape(1) if isinstance(g2oS12, np.ndarray) else sim3_pose(*g2oS12)
+    res = np.zeros(1, SIM3OPT_RESULT_DTYPE)
+    nin = _check(lib().orbx_optimize_sim3(int(device), n, _p(k1), _p(w1), _p(w2), _p(m), _p(i2), _p(k2), len(k2), _p(tl), _p(T1),
+                                          _p(T2), _p(s1), len(s1), _p(s2), len(s2), _p(prm), _p(S), _p(res)))
+    return nin, S[0], m, None if res[0]["early_return"] else np.zeros((7, 7)), res[0]
+
+
+def OptimizeSim3Batch(n, kpsUn1, worldPos1, worldPos2, matched, idx2, kpsUn2, n2, trackLevel2, Tcw1, Tcw2, invLevelSigma2_1,
+                      invLevelSigma2_2, g2oS12, params, device=0):
+    """OptimizeSim3 for P pairs in one launch (orbx_optimize_sim3_batch): n [P] key points per problem, kpsUn1 / matched / idx2 /
+    trackLevel2 [P][cap], worldPos1 / worldPos2 [P][cap][3], kpsUn2 [P][cap2] with n2 [P] key points each, Tcw1 / Tcw2 [P][12], the
+    two mvInvLevelSigma2 tables (shared), g2oS12 [P] sim3_pose records, params [P] sim3opt_params records.  Returns (results [P],
+    g2oS12 [P], matched [P][cap])."""
+    nn = np.ascontiguousarray(n, np.int32).reshape(-1)
+    P = len(nn)
+    m = np.array(matched, np.uint8).reshape(P, -1)
+    cap = m.shape[1]
+    k1 = np.ascontiguousarray(kpsUn1, KP_DTYPE).reshape(P, cap)
+    k2 = np.ascontiguousarray(kpsUn2, KP_DTYPE).reshape(P, -1)
+    nn2 = np.ascontiguousarray(n2, np.int32).reshape(P)
+    w1 = np.ascontiguousarray(worldPos1, np.float32).reshape(P, cap, 3)
+    w2 = np.ascontiguousarray(worldPos2, np.float32).reshape(P, cap, 3)
+    i2 = np.ascontiguousarray(idx2, np.int32).reshape(P, cap)
+    tl = np.ascontiguousarray(trackLevel2, np.int32).reshape(P, cap)
+    T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(P, 12)
+    T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(P, 12)
+    s1 = np.ascontiguousarray(invLevelSigma2_1, np.float32)
+    s2 = np.ascontiguousarray(invLevelSigma2_2, np.float32)
+    prm = np.ascontiguousarray(params, SIM3OPT_PARAMS_DTYPE).reshape(P)
+    S = np.array(g2oS12, SIM3_POSE_DTYPE).reshape(P)
+    res = np.zeros(P, SIM3OPT_RESULT_DTYPE)
+    _check(lib().orbx_optimize_sim3_batch(int(device), P, cap, _p(nn), _p(k1), _p(w1), _p(w2), _p(m), _p(i2), _p(k2), k2.shape[1],
+                                          _p(nn2), _p(tl), _p(T1), _p(T2), _p(s1), len(s1), _p(s2), len(s2), _p(prm), _p(S), _p(res)))
+    return res, S, m
 
 
 class _NpCamera(C.Structure):      # orbx_np_camera

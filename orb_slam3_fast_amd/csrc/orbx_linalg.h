@@ -1,8 +1,8 @@
 // orbx_linalg.h — the small dense linear algebra of the geometric solvers, one copy of each: 3-vector and 3 x 3 helpers, the
 // 16-lane sum, the null vector of a 4 x 4 system (GeometricTools::Triangulate) and the double-precision reciprocal / reciprocal
 // square root it is built on, the one-sided Jacobi rotation with the 3 x 3 SVD and the wave-layout null vector in double, and the
-// 6 x 6 LDLT.  Shared by the fisheye association (orbx_stereo.hip), the two-view reconstruction (orbx_twoview.hip), the PnP
-// solver (orbx_mlpnp.hip), the new map points (orbx_newpoints.hip) and the pose optimisers (orbx_pose.h).
+// 6 x 6 and 7 x 7 LDLT.  Shared by the fisheye association (orbx_stereo.hip), the two-view reconstruction (orbx_twoview.hip), the PnP
+// solver (orbx_mlpnp.hip), the new map points (orbx_newpoints.hip), the pose optimisers (orbx_pose.h) and the Sim3 optimiser (orbx_sim3opt.hip).
 #ifndef ORBX_LINALG_H
 #define ORBX_LINALG_H
 #include <hip/hip_runtime.h>
@@ -253,6 +253,50 @@ __device__ __forceinline__ bool ldlt6(const double* H, const double* b, double* 
     double s = y[i] / D[i];
 #pragma unroll
     for (int m = i + 1; m < 6; m++) s -= L[m][i] * x[m];
+    x[i] = s;
+  }
+  return true;
+}
+
+// (H + lambda I) x = b by the same unpivoted LDLT for the 7 x 7 normal matrix of a Sim3 vertex (upper triangle, row-major, 28
+// entries); false = a pivot <= 0 or not finite, x untouched
+__device__ __forceinline__ bool ldlt7(const double* H, const double* b, double* x, double lambda) {
+  double A[7][7], L[7][7], D[7], y[7];
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 7; r++)
+#pragma unroll
+    for (int c = r; c < 7; c++) { A[r][c] = A[c][r] = H[k++]; }
+#pragma unroll
+  for (int r = 0; r < 7; r++) A[r][r] += lambda;
+#pragma unroll
+  for (int j = 0; j < 7; j++) {
+    double d = A[j][j];
+#pragma unroll
+    for (int m = 0; m < j; m++) d -= L[j][m] * L[j][m] * D[m];
+    if (!(d > 0) || !isfinite(d)) return false;
+    D[j] = d;
+    L[j][j] = 1.0;
+#pragma unroll
+    for (int i = j + 1; i < 7; i++) {
+      double s = A[i][j];
+#pragma unroll
+      for (int m = 0; m < j; m++) s -= L[i][m] * L[j][m] * D[m];
+      L[i][j] = s / d;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 7; i++) {
+    double s = b[i];
+#pragma unroll
+    for (int m = 0; m < i; m++) s -= L[i][m] * y[m];
+    y[i] = s;
+  }
+#pragma unroll
+  for (int i = 6; i >= 0; i--) {
+    double s = y[i] / D[i];
+#pragma unroll
+    for (int m = i + 1; m < 7; m++) s -= L[m][i] * x[m];
     x[i] = s;
   }
   return true;
