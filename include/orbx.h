@@ -1206,7 +1206,106 @@ int orbx_optimize_sim3_batch(int device, int n_problems, int cap, const int32_t*
                              const float* inv_level_sigma2_2, int nlevels2, const orbx_sim3opt_params* params,
                              orbx_sim3_pose* S12, orbx_sim3opt_result* results);
 
-/* ---- new map points (local mapping) ------------------------------------------------------------------- */
+/* ---- local bundle adjustment (Optimizer::LocalBundleAdjustment) ------------------------------------------ */
+
+/* The visual Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*, int&, int&, int&, int&) (src/Optimizer.cc:1109-1516; the
+ * call site src/LocalMapping.cc, after CreateNewMapPoints and SearchInNeighbors), one problem per call, on the device: g2o's
+ * Levenberg on BlockSolver_6_3 -- pose vertices of 6, marginalised point vertices of 3 -- restated as a chain of kernels
+ * (csrc/orbx_lba.hip), all arithmetic in double.
+ *
+ * The problem is a flat graph.  Key frames: the n_local key frames of lLocalKeyFrames first (the current key frame, then its
+ * covisibles), then the n_fixed of lFixedCameras; a local key frame with fixed != 0 is the map's initial key frame (a fixed
+ * vertex); every key frame of the second group must carry fixed != 0.  Poses are Tcw as Sophus stores it (float unit quaternion
+ * x y z w, float translation), widened and normalised as SE3Quat(q, t) does.  Points: lLocalMapPoints in list order, float.
+ * Edges: in the reference's order -- points in list order (edge.point never decreases), each point's observations in the
+ * caller's order -- one per (key frame, point) at most, as a point's observations are a map.  u_right < 0: EdgeSE3ProjectXYZ
+ * (src/OptimizableTypes.cpp:136-157; error obs - Pinhole::project, float parameters times double, chi2 gate 5.991, Huber delta
+ * (float)sqrt(5.991)); u_right >= 0: g2o::EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.cpp:190-274; a FLOAT invz = 1.0f / z in
+ * the error, the Jacobian in double, gate 7.815, delta (float)sqrt(7.815)).  The information value is inv_sigma2 widened.
+ *
+ * Levenberg (optimization_algorithm_levenberg.cpp:61-184) with the Schur complement of block_solver.hpp:354-447: lambda starts
+ * at 1e-5 times the largest |H_jj| over the pose and point diagonals, or at lambda_init when that is positive (100 for inertial
+ * maps, Optimizer.cc:1200); a trial adds lambda to both diagonals, forms Dinv = (Hll + lambda I)^-1, Hschur = Hpp + lambda I -
+ * sum Hpl Dinv Hpl^T, bschur = bp - sum Hpl Dinv bl, factors the dense 6 n system by an unpivoted LDLT (a pivot <= 0 or not
+ * finite fails the solve: x keeps its value and the trial's chi2 is DBL_MAX), back-substitutes xl = Dinv (bl - Hpl^T xp) and
+ * applies SE3Quat::exp(xp) * pose and point + xl to a trial copy; rho = (chi - trial chi) / (sum over ALL of x of x (lambda x + b)
+ * + 1e-3); accept, reject, the lambda update, at most 10 trials per iteration, rho == 0 and the three-small-gains stop as in the
+ * pose optimiser.  Afterwards an edge is flagged for erasure when its chi2 -- the one it holds after the optimiser's LAST TRIAL,
+ * even a rejected one -- exceeds its gate, or when its depth at the FINAL estimates is not positive.
+ *
+ * A key frame without an edge, and a point without one, take no part (g2o's active set).  A local key frame that is not optimised
+ * (fixed, or without an edge) comes back as the widened input.  num_fixedKF = n_fixed + (a local key frame is fixed ? 1 : 0); zero
+ * returns status ORBX_LBA_ABORTED with the outputs equal to the widened inputs (Optimizer.cc:1182), as does a problem without an
+ * edge (ORBX_LBA_EMPTY) and params->stop != 0 (ORBX_LBA_STOPPED, the test of pbStopFlag at :1429).
+ *
+ * Deliberate differences from the reference:
+ *  - pbStopFlag cannot interrupt a running optimisation: a chain of launches is not interruptible.  The flag is honoured where
+ *    the reference tests it before optimising, and max_iterations (the reference passes 10, :1433) bounds the work instead.
+ *  - LinearSolverEigen factors the reduced system by a sparse Cholesky under a fill-reducing ordering; the device factors it
+ *    densely in key-frame order.  Both are exact factorisations: results differ by rounding (tests/lba_cases.py measures it).
+ *  - KannalaBrandt8 key frames and the EdgeSE3ProjectXYZToBody edges of a two-camera rig (:1383-1423) are not built: a key frame
+ *    with model == ORBX_CAMERA_KB8 or camera2 != 0 is ORBX_E_BADARG.  Neither are the map-merge overload (:3567), the inertial
+ *    variants and a batched entry.
+ * Capacity: ORBX_LBA_MAX_LOCAL optimised key frames; fixed key frames, points and edges are bounded by int32 and memory. */
+#define ORBX_LBA_MAX_LOCAL 128
+#define ORBX_LBA_DONE 0      /* optimised */
+#define ORBX_LBA_ABORTED 1   /* num_fixedKF == 0 */
+#define ORBX_LBA_STOPPED 2   /* params->stop */
+#define ORBX_LBA_EMPTY 3     /* no edge: g2o has nothing to optimise */
+/* stop_reason of an optimised problem */
+#define ORBX_LBA_STOP_ITERATIONS 0   /* max_iterations reached */
+#define ORBX_LBA_STOP_QMAX 1         /* ten rejected trials in one iteration */
+#define ORBX_LBA_STOP_RHO_ZERO 2     /* rho == 0 */
+#define ORBX_LBA_STOP_SMALL_GAIN 3   /* three iterations in a row gained less than 1e-3 of their chi2 */
+typedef struct orbx_lba_keyframe {
+  float q[4];          /* Tcw: unit quaternion x y z w */
+  float t[3];
+  float fx, fy, cx, cy, bf;
+  int32_t model;       /* ORBX_CAMERA_PINHOLE */
+  int32_t fixed;       /* != 0: a fixed vertex */
+  int32_t camera2;     /* != 0: the key frame has mpCamera2 (rejected) */
+} orbx_lba_keyframe;   /* 60 bytes */
+typedef struct orbx_lba_edge {
+  int32_t kf;          /* index into keyframes */
+  int32_t point;       /* index into points */
+  float u, v;          /* mvKeysUn[leftIndex].pt */
+  float u_right;       /* mvuRight[leftIndex]; < 0: monocular */
+  float inv_sigma2;    /* mvInvLevelSigma2[octave] */
+} orbx_lba_edge;       /* 24 bytes */
+typedef struct orbx_lba_problem {
+  const orbx_lba_keyframe* keyframes;   /* [n_local + n_fixed] */
+  const float* points;                  /* [n_points][3] */
+  const orbx_lba_edge* edges;           /* [n_edges] */
+  int32_t n_local, n_fixed, n_points, n_edges;
+} orbx_lba_problem;
+typedef struct orbx_lba_params {
+  int32_t max_iterations;   /* 1 .. 1000000; the reference's optimize(10) */
+  int32_t stop;             /* *pbStopFlag at the time of the call */
+  float lambda_init;        /* > 0: setUserLambdaInit; otherwise computed */
+} orbx_lba_params;          /* 12 bytes */
+typedef struct orbx_lba_result {
+  double* poses;            /* out [n_local][7]: q (x y z w), t */
+  double* points;           /* out [n_points][3] */
+  uint8_t* erase;           /* out [n_edges]: the edge's (key frame, point) pair belongs to vToErase */
+  double* chi2;             /* out [n_edges]: the chi2 the edge holds after the last trial */
+  uint8_t* depth_positive;  /* out [n_edges]: isDepthPositive() at the final estimates */
+  int32_t num_fixedKF, num_OptKF, num_MPs, num_edges;
+  int32_t status;           /* ORBX_LBA_DONE ... */
+  int32_t iterations;       /* solve() calls */
+  int32_t trials;           /* Levenberg trials */
+  int32_t stop_reason;      /* ORBX_LBA_STOP_* */
+  double lambda;            /* the final lambda */
+  double chi2_initial, chi2_final;   /* robust chi2 at the start and at the result */
+} orbx_lba_result;
+/* Everything is validated before a device is touched: null pointers and negative counts, finite poses (non-zero quaternion),
+ * cameras (fx, fy > 0), points and observations, the pinhole model, no second camera, the fixed flags of the second group, edge
+ * indices in range, edges grouped by ascending point without a repeated key frame, max_iterations in [1, 1000000], a finite lambda_init,
+ * at most ORBX_LBA_MAX_LOCAL key frames to optimise.  Returns ORBX_OK (see result->status); valid arguments without a device
+ * return ORBX_E_NODEVICE unless the call ends before the optimiser (aborted, stopped, empty).  Two calls on the same input
+ * agree bit for bit. */
+int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params, orbx_lba_result* result);
+
+/* ---- new map points (local mapping)------------------------------------------------------------------- */
 
 /* The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), which consumes the match list of
  * ORBmatcher::SearchForTriangulation: ray parallax and stereo parallax (:579-601), the choice between

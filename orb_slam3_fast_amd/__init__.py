@@ -114,6 +114,7 @@ def lib():
         L.orbx_sim3_iterate_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp, vp]
         L.orbx_optimize_sim3.argtypes = [i, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, i, vp, i, vp, vp, vp]
         L.orbx_optimize_sim3_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp]
+        L.orbx_local_bundle_adjustment.argtypes = [i, vp, vp, vp]
         L.orbx_triangulate_matches.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_create_new_map_points.argtypes = [i, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, C.c_ssize_t, vp, i, C.c_ssize_t, f, f, vp, vp, i, vp, vp, i, C.POINTER(i),
@@ -1204,6 +1205,70 @@ def OptimizeSim3Batch(n, kpsUn1, worldPos1, worldPos2, matched, idx2, kpsUn2, n2
     _check(lib().orbx_optimize_sim3_batch(int(device), P, cap, _p(nn), _p(k1), _p(w1), _p(w2), _p(m), _p(i2), _p(k2), k2.shape[1],
                                           _p(nn2), _p(tl), _p(T1), _p(T2), _p(s1), len(s1), _p(s2), len(s2), _p(prm), _p(S), _p(res)))
     return res, S, m
+
+
+# ---- local bundle adjustment (Optimizer::LocalBundleAdjustment)
+LBA_KEYFRAME_DTYPE = np.dtype([("q", "<f4", (4,)), ("t", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                               ("bf", "<f4"), ("model", "<i4"), ("fixed", "<i4"), ("camera2", "<i4")])
+LBA_EDGE_DTYPE = np.dtype([("kf", "<i4"), ("point", "<i4"), ("u", "<f4"), ("v", "<f4"), ("u_right", "<f4"), ("inv_sigma2", "<f4")])
+assert LBA_KEYFRAME_DTYPE.itemsize == 60 and LBA_EDGE_DTYPE.itemsize == 24
+LBA_MAX_LOCAL = 128
+LBA_DONE, LBA_ABORTED, LBA_STOPPED, LBA_EMPTY = 0, 1, 2, 3
+LBA_STOP_ITERATIONS, LBA_STOP_QMAX, LBA_STOP_RHO_ZERO, LBA_STOP_SMALL_GAIN = 0, 1, 2, 3
+
+
+class _LbaProblem(C.Structure):    # orbx_lba_problem
+    _fields_ = [("keyframes", C.c_void_p), ("points", C.c_void_p), ("edges", C.c_void_p), ("n_local", C.c_int32),
+                ("n_fixed", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32)]
+
+
+class _LbaParams(C.Structure):     # orbx_lba_params
+    _fields_ = [("max_iterations", C.c_int32), ("stop", C.c_int32), ("lambda_init", C.c_float)]
+
+
+class _LbaResult(C.Structure):     # orbx_lba_result
+    _fields_ = [("poses", C.c_void_p), ("points", C.c_void_p), ("erase", C.c_void_p), ("chi2", C.c_void_p),
+                ("depth_positive", C.c_void_p), ("num_fixedKF", C.c_int32), ("num_OptKF", C.c_int32), ("num_MPs", C.c_int32),
+                ("num_edges", C.c_int32), ("status", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32),
+                ("stop_reason", C.c_int32), ("lambda_", C.c_double), ("chi2_initial", C.c_double), ("chi2_final", C.c_double)]
+
+
+def lba_keyframes(q, t, cam, fixed, model=CAMERA_PINHOLE, camera2=0):
+    """orbx_lba_keyframe records: q [n][4] (x y z w) and t [n][3] of Tcw, cam = (fx, fy, cx, cy, bf) for all or [n][5], fixed [n]."""
+    q = np.asarray(q, np.float32).reshape(-1, 4)
+    k = np.zeros(len(q), LBA_KEYFRAME_DTYPE)
+    k["q"], k["t"] = q, np.asarray(t, np.float32).reshape(-1, 3)
+    cam = np.broadcast_to(np.asarray(cam, np.float32), (len(q), 5))
+    for j, name in enumerate(("fx", "fy", "cx", "cy", "bf")):
+        k[name] = cam[:, j]
+    k["fixed"], k["model"], k["camera2"] = fixed, model, camera2
+    return k
+
+
+def LocalBundleAdjustment(keyframes, n_local, points, edges, max_iterations=10, lambda_init=0.0, stop=False, device=0):
+    """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1109-1516) on the GPU (orbx_local_bundle_adjustment) over the flat graph
+    of include/orbx.h: keyframes = LBA_KEYFRAME_DTYPE records, the n_local local key frames first and the fixed ones behind them;
+    points [nP][3] float; edges = LBA_EDGE_DTYPE records in the reference's order (grouped by ascending point).  lambda_init = 100
+    for an inertial map; stop = *pbStopFlag.  Returns a dict: poses [n_local][7] double (q x y z w, t), points [nP][3] double, erase /
+    depth_positive [nE] uint8, chi2 [nE] double (what every edge holds after the last trial), and the counters num_fixedKF,
+    num_OptKF, num_MPs, num_edges, status (LBA_DONE / LBA_ABORTED / LBA_STOPPED / LBA_EMPTY), iterations, trials, stop_reason, lambda,
+    chi2_initial, chi2_final.  The caller applies SetPose / SetWorldPos with the float casts and erases the flagged observations."""
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ed = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    n_local = int(n_local)
+    poses, pts = np.zeros((max(n_local, 0), 7)), np.zeros((len(X), 3))
+    erase, depth, chi2 = np.zeros(len(ed), np.uint8), np.zeros(len(ed), np.uint8), np.zeros(len(ed))
+    prob = _LbaProblem(_p(kf).value, _p(X).value, _p(ed).value, n_local, len(kf) - n_local, len(X), len(ed))
+    prm = _LbaParams(int(max_iterations), int(bool(stop)), float(lambda_init))
+    res = _LbaResult(_p(poses).value, _p(pts).value, _p(erase).value, _p(chi2).value, _p(depth).value)
+    _check(lib().orbx_local_bundle_adjustment(int(device), C.byref(prob), C.byref(prm), C.byref(res)))
+    out = dict(poses=poses, points=pts, erase=erase, chi2=chi2, depth_positive=depth)
+    for name in ("num_fixedKF", "num_OptKF", "num_MPs", "num_edges", "status", "iterations", "trials", "stop_reason", "chi2_initial",
+                 "chi2_final"):
+        out[name] = getattr(res, name)
+    out["lambda"] = res.lambda_
+    return out
 
 
 class _NpCamera(C.Structure):      # orbx_np_camera

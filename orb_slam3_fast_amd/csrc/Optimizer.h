@@ -5,10 +5,14 @@
 // Optimizer::OptimizeSim3(KeyFrame*, KeyFrame*, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) (src/Optimizer.cc:
 // 2164-2424) on orbx_optimize_sim3, so that the call sites of loop closing and map merging (src/LoopClosing.cc:609, 852) read as in
 // the reference: `numOptMatches = Optimizer::OptimizeSim3(pKF1, pKF2, vpMatchedMPs, gScm, 10, mbFixScale, mHessian7x7, true)`.
+// Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*, int&, int&, int&, int&) (src/Optimizer.cc:1109-1516) on
+// orbx_local_bundle_adjustment, over a LocalMapView: the three walks of :1116-1180 (local key frames, local map points, fixed key
+// frames) and the edge listing of :1288-1426 are plain host code here (GatherLocalGraph), the optimisation is the library's.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/orbx.h"
@@ -73,8 +77,184 @@ struct Sim3Matches {
   std::vector<int32_t> indexInKF2, trackScaleLevel;
 };
 
+// ---- local bundle adjustment
+// What LocalBundleAdjustment reads of a KeyFrame.  Key frames and map points are named by their index in the LocalMapView.
+struct LbaKeyFrame {
+  unsigned long mnId = 0;
+  bool bad = false;                         // isBad()
+  int map = 0;                              // GetMap(), as an id
+  float q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0};   // GetPose(): Tcw as Sophus stores it (x y z w)
+  float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  int cameraModel = ORBX_CAMERA_PINHOLE;
+  bool hasCamera2 = false;                  // mpCamera2 != NULL (rejected by the library: include/orbx.h)
+  std::vector<orbx_keypoint> mvKeysUn;
+  std::vector<float> mvuRight;              // per key point, < 0: monocular
+  std::vector<float> mvInvLevelSigma2;
+  std::vector<int> mvpMapPoints;            // GetMapPointMatches(): per key point the map point's index, -1: none
+};
+struct LbaMapPoint {
+  unsigned long mnId = 0;
+  bool bad = false;
+  int map = 0;
+  float pos[3] = {0, 0, 0};                 // GetWorldPos()
+  std::vector<std::pair<int, int>> observations;   // GetObservations(): (key frame, left index; -1: right camera only), in the
+                                                   // order the caller's map iterates
+};
+struct LocalMapView {
+  std::vector<LbaKeyFrame> keyFrames;
+  std::vector<LbaMapPoint> mapPoints;
+  int current = 0;                          // pKF
+  std::vector<int> covisibles;              // pKF->GetVectorCovisibleKeyFrames()
+  unsigned long initKFid = 0;               // pMap->GetInitKFid()
+  bool inertial = false;                    // pMap->IsInertial(): lambda starts at 100
+  int device = 0;
+};
+// The flat graph of the call: lLocalKeyFrames, lFixedCameras and lLocalMapPoints as indices into the view, and the records of
+// orbx_lba_problem (key frames local first, edges in the reference's order with their (key frame, map point) pair).
+struct LbaGraph {
+  std::vector<int> localKFs, fixedKFs, localMPs;
+  int num_fixedKF = 0;
+  std::vector<orbx_lba_keyframe> kfs;
+  std::vector<float> points;
+  std::vector<orbx_lba_edge> edges;
+  std::vector<std::pair<int, int>> edgePair;   // per edge: (key frame, map point) of the view
+};
+// What the caller applies: SetPose / SetWorldPos (then UpdateNormalAndDepth) and, per vToErase pair, EraseMapPointMatch /
+// EraseObservation.
+struct LbaUpdate {
+  std::vector<int> keyFrames;                // lLocalKeyFrames
+  std::vector<float> poses;                  // [7] each: q (x y z w), t -- the float casts of :1498
+  std::vector<int> mapPoints;                // lLocalMapPoints
+  std::vector<float> positions;              // [3] each: the float cast of :1511
+  std::vector<std::pair<int, int>> vToErase; // (key frame, map point): monocular edges first, then stereo, as :1440-1474
+  bool optimized = false;                    // false: aborted, stopped or nothing to optimise -- nothing to apply
+  orbx_lba_result result{};
+};
+
+// :1116-1180 and :1288-1426 with the reference's order and its bad / other-map filters.  A covisible key frame is marked local
+// even when it is bad or of another map (mnBALocalForKF is set before the test), so it can not turn up as a fixed one.
+// Deliberate difference: a covisible listed twice (or the current key frame among its covisibles) is taken once; the reference
+// would push it again and add a second vertex of the same id.  GetVectorCovisibleKeyFrames() holds no key frame twice.
+inline LbaGraph GatherLocalGraph(const LocalMapView& m) {
+  LbaGraph g;
+  const int nKF = (int)m.keyFrames.size(), nMP = (int)m.mapPoints.size();
+  std::vector<char> kfLocal((size_t)nKF, 0), kfFixed((size_t)nKF, 0), mpLocal((size_t)nMP, 0);
+  const LbaKeyFrame& cur = m.keyFrames.at((size_t)m.current);
+  g.localKFs.push_back(m.current);
+  kfLocal[(size_t)m.current] = 1;
+  for (int i : m.covisibles) {
+    const LbaKeyFrame& k = m.keyFrames.at((size_t)i);
+    const bool seen = kfLocal[(size_t)i] != 0;
+    kfLocal[(size_t)i] = 1;
+    if (!seen && !k.bad && k.map == cur.map) g.localKFs.push_back(i);
+  }
+  for (int i : g.localKFs) {
+    const LbaKeyFrame& k = m.keyFrames[(size_t)i];
+    if (k.mnId == m.initKFid) g.num_fixedKF = 1;
+    for (int j : k.mvpMapPoints) {
+      if (j < 0) continue;
+      const LbaMapPoint& p = m.mapPoints.at((size_t)j);
+      if (!p.bad && p.map == cur.map && !mpLocal[(size_t)j]) {
+        g.localMPs.push_back(j);
+        mpLocal[(size_t)j] = 1;
+      }
+    }
+  }
+  for (int j : g.localMPs)
+    for (const std::pair<int, int>& ob : m.mapPoints[(size_t)j].observations) {
+      const int i = ob.first;
+      const LbaKeyFrame& k = m.keyFrames.at((size_t)i);
+      if (!kfLocal[(size_t)i] && !kfFixed[(size_t)i]) {
+        kfFixed[(size_t)i] = 1;
+        if (!k.bad && k.map == cur.map) g.fixedKFs.push_back(i);
+      }
+    }
+  g.num_fixedKF += (int)g.fixedKFs.size();
+  std::vector<int> flat((size_t)nKF, -1);
+  auto add = [&](int i, bool fixed) {
+    const LbaKeyFrame& k = m.keyFrames[(size_t)i];
+    orbx_lba_keyframe r{};
+    for (int c = 0; c < 4; c++) r.q[c] = k.q[c];
+    for (int c = 0; c < 3; c++) r.t[c] = k.t[c];
+    r.fx = k.fx; r.fy = k.fy; r.cx = k.cx; r.cy = k.cy; r.bf = k.mbf;
+    r.model = k.cameraModel;
+    r.fixed = fixed ? 1 : 0;
+    r.camera2 = k.hasCamera2 ? 1 : 0;
+    flat[(size_t)i] = (int)g.kfs.size();
+    g.kfs.push_back(r);
+  };
+  for (int i : g.localKFs) add(i, m.keyFrames[(size_t)i].mnId == m.initKFid);
+  for (int i : g.fixedKFs) add(i, true);
+  for (size_t n = 0; n < g.localMPs.size(); n++) {
+    const LbaMapPoint& p = m.mapPoints[(size_t)g.localMPs[n]];
+    g.points.insert(g.points.end(), p.pos, p.pos + 3);
+    for (const std::pair<int, int>& ob : p.observations) {
+      const LbaKeyFrame& k = m.keyFrames[(size_t)ob.first];
+      if (k.bad || k.map != cur.map || ob.second == -1 || flat[(size_t)ob.first] < 0) continue;
+      const orbx_keypoint& kp = k.mvKeysUn.at((size_t)ob.second);
+      orbx_lba_edge e{};
+      e.kf = flat[(size_t)ob.first];
+      e.point = (int)n;
+      e.u = kp.x;
+      e.v = kp.y;
+      e.u_right = k.mvuRight.at((size_t)ob.second) < 0 ? -1.f : k.mvuRight[(size_t)ob.second];
+      e.inv_sigma2 = k.mvInvLevelSigma2.at((size_t)kp.octave);
+      g.edges.push_back(e);
+      g.edgePair.push_back({ob.first, g.localMPs[n]});
+    }
+  }
+  return g;
+}
+
 class Optimizer {
  public:
+  // Gathers the local graph, honours the zero-fixed abort (:1182, the counters behind num_fixedKF stay as they were) and the stop
+  // flag (:1429), optimises on the device and returns what the caller applies.  max_iterations bounds the work: pbStopFlag can
+  // not interrupt a running optimisation (include/orbx.h).  Throws on a library error.
+  static LbaUpdate LocalBundleAdjustment(const LocalMapView& map, const bool* pbStopFlag, int& num_fixedKF, int& num_OptKF, int& num_MPs,
+                                         int& num_edges, int max_iterations = 10) {
+    const LbaGraph g = GatherLocalGraph(map);
+    LbaUpdate u;
+    num_fixedKF = g.num_fixedKF;
+    if (num_fixedKF == 0) return u;
+    num_OptKF = (int)g.localKFs.size();
+    num_MPs = (int)g.localMPs.size();
+    num_edges = (int)g.edges.size();
+    if (pbStopFlag && *pbStopFlag) return u;
+    orbx_lba_problem prob{};
+    prob.keyframes = g.kfs.data();
+    prob.points = g.points.data();
+    prob.edges = g.edges.data();
+    prob.n_local = (int)g.localKFs.size();
+    prob.n_fixed = (int)g.fixedKFs.size();
+    prob.n_points = (int)g.localMPs.size();
+    prob.n_edges = (int)g.edges.size();
+    orbx_lba_params prm{};
+    prm.max_iterations = max_iterations;
+    prm.lambda_init = map.inertial ? 100.f : 0.f;
+    std::vector<double> poses(7 * g.localKFs.size()), points(3 * g.localMPs.size()), chi2(g.edges.size());
+    std::vector<uint8_t> erase(g.edges.size()), depth(g.edges.size());
+    u.result.poses = poses.data();
+    u.result.points = points.data();
+    u.result.erase = erase.data();
+    u.result.chi2 = chi2.data();
+    u.result.depth_positive = depth.data();
+    if (orbx_local_bundle_adjustment(map.device, &prob, &prm, &u.result) != ORBX_OK)
+      throw std::runtime_error(std::string("LocalBundleAdjustment: ") + orbx_last_error());
+    u.result.poses = u.result.points = u.result.chi2 = nullptr;   // the buffers end with this call
+    u.result.erase = u.result.depth_positive = nullptr;
+    if (u.result.status != ORBX_LBA_DONE) return u;
+    u.optimized = true;
+    u.keyFrames = g.localKFs;
+    u.mapPoints = g.localMPs;
+    for (double v : poses) u.poses.push_back((float)v);
+    for (double v : points) u.positions.push_back((float)v);
+    for (int pass = 0; pass < 2; pass++)   // vpEdgesMono, then vpEdgesStereo
+      for (size_t i = 0; i < g.edges.size(); i++)
+        if (erase[i] && (g.edges[i].u_right < 0) == (pass == 0)) u.vToErase.push_back(g.edgePair[i]);
+    return u;
+  }
+
   // Returns nIn and updates vpMatches1 and g2oS12 like the reference.  mAcumHessian is set to zero, which is all the reference
   // does with it (:2401); on the early return (fewer than 10 pairs left after round one, :2394) g2oS12 and mAcumHessian are left
   // untouched, as there.  `result` (optional) receives the counters.  Throws on a library error.

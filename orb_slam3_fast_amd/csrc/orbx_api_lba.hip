@@ -1,0 +1,192 @@
+// orbx_api_lba.hip — C ABI of Optimizer::LocalBundleAdjustment (include/orbx.h, "local bundle adjustment") on the kernel chain of
+// orbx_lba.hip.  The graph, the two copies of the estimates and of the linear system, the reduced camera system and the outputs
+// live in one Pack: one upload, one chain of launches per Levenberg trial with one status word read back after each, one
+// download.  The host makes no optimiser decision: it only asks whether the device wants another trial.
+#include "orbx_lba.h"
+
+#include <algorithm>
+
+static_assert(sizeof(orbx_lba_keyframe) == 60, "orbx_lba_keyframe");
+static_assert(sizeof(orbx_lba_edge) == 24, "orbx_lba_edge");
+static_assert(sizeof(orbx_lba_params) == 12, "orbx_lba_params");
+
+namespace {
+
+constexpr int kLbaMaxIterations = 1000000;
+
+const char* lba_keyframe_error(const orbx_lba_keyframe& k, bool secondGroup) {
+  if (k.model == ORBX_CAMERA_KB8)
+    return "KannalaBrandt8 key frame: LocalBundleAdjustment is built for pinhole and rectified stereo key frames only";
+  if (k.model != ORBX_CAMERA_PINHOLE) return "camera model is not pinhole";
+  if (k.camera2) return "key frame with a second camera: the EdgeSE3ProjectXYZToBody edges of a two-camera rig are not built";
+  if (!finite_all(k.q, 4) || !finite_all(k.t, 3)) return "key-frame pose not finite";
+  if (k.q[0] == 0 && k.q[1] == 0 && k.q[2] == 0 && k.q[3] == 0) return "key-frame quaternion is zero";
+  const float cam[5] = {k.fx, k.fy, k.cx, k.cy, k.bf};
+  if (!finite_all(cam, 5) || !(k.fx > 0) || !(k.fy > 0)) return "camera parameters not finite, or fx / fy not positive";
+  if (secondGroup && !k.fixed) return "a key frame behind the local ones is not marked fixed";
+  return nullptr;
+}
+
+// the edges: indices, order and values; fills the points' edge ranges
+const char* lba_edges_error(const orbx_lba_problem& p, int nKF, std::vector<int>& ptStart) {
+  ptStart.assign((size_t)p.n_points + 1, 0);
+  std::vector<int> seen((size_t)nKF, -1);   // the last point that used the key frame
+  int last = 0;
+  for (int i = 0; i < p.n_edges; i++) {
+    const orbx_lba_edge& e = p.edges[i];
+    if (e.kf < 0 || e.kf >= nKF) return "edge key-frame index outside [0, n_local + n_fixed)";
+    if (e.point < 0 || e.point >= p.n_points) return "edge point index outside [0, n_points)";
+    if (e.point < last) return "edges not grouped by ascending point";
+    last = e.point;
+    if (seen[e.kf] == e.point) return "key frame repeated among the observations of a point";
+    seen[e.kf] = e.point;
+    const float v[4] = {e.u, e.v, e.u_right, e.inv_sigma2};
+    if (!finite_all(v, 4)) return "observation not finite";
+    ptStart[(size_t)e.point + 1]++;
+  }
+  for (int q = 0; q < p.n_points; q++) ptStart[(size_t)q + 1] += ptStart[q];
+  return nullptr;
+}
+
+// the call ends before the optimiser: the outputs are the widened inputs
+void lba_passthrough(const orbx_lba_problem& p, orbx_lba_result& r, int status) {
+  for (int i = 0; i < p.n_local; i++) {
+    for (int k = 0; k < 4; k++) r.poses[7 * (size_t)i + k] = (double)p.keyframes[i].q[k];
+    for (int k = 0; k < 3; k++) r.poses[7 * (size_t)i + 4 + k] = (double)p.keyframes[i].t[k];
+  }
+  for (size_t k = 0; k < 3 * (size_t)p.n_points; k++) r.points[k] = (double)p.points[k];
+  for (int i = 0; i < p.n_edges; i++) {
+    r.erase[i] = 0;
+    r.chi2[i] = 0;
+    r.depth_positive[i] = 0;
+  }
+  r.status = status;
+  r.iterations = r.trials = r.stop_reason = 0;
+  r.lambda = r.chi2_initial = r.chi2_final = 0;
+}
+
+}  // namespace
+
+extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params,
+                                            orbx_lba_result* result) {
+  if (!problem || !params || !result) return fail(ORBX_E_BADARG, "null argument or negative count");
+  const orbx_lba_problem& p = *problem;
+  orbx_lba_result& r = *result;
+  if (p.n_local < 0 || p.n_fixed < 0 || p.n_points < 0 || p.n_edges < 0 || (long long)p.n_local + p.n_fixed > INT_MAX ||
+      ((p.n_local || p.n_fixed) && !p.keyframes) || (p.n_points && !p.points) || (p.n_edges && !p.edges) ||
+      (p.n_local && !r.poses) || (p.n_points && !r.points) || (p.n_edges && (!r.erase || !r.chi2 || !r.depth_positive)))
+    return fail(ORBX_E_BADARG, "null argument or negative count");
+  if (params->max_iterations < 1 || params->max_iterations > kLbaMaxIterations)
+    return fail(ORBX_E_BADARG, "max_iterations outside [1, 1000000]");
+  if (!std::isfinite(params->lambda_init)) return fail(ORBX_E_BADARG, "lambda_init not finite");
+  const int nKF = p.n_local + p.n_fixed;
+  int fixedLocal = 0;
+  for (int i = 0; i < nKF; i++) {
+    if (const char* err = lba_keyframe_error(p.keyframes[i], i >= p.n_local)) return fail(ORBX_E_BADARG, err);
+    if (i < p.n_local && p.keyframes[i].fixed) fixedLocal = 1;
+  }
+  for (int i = 0; i < p.n_points; i++)
+    if (!finite_all(p.points + 3 * (size_t)i, 3)) return fail(ORBX_E_BADARG, "world position not finite");
+  std::vector<int> ptStart;
+  if (const char* err = lba_edges_error(p, nKF, ptStart)) return fail(ORBX_E_BADARG, err);
+  // the reduced system's row blocks: the local key frames that are not fixed and have an edge, in list order
+  std::vector<int> slot((size_t)nKF, -1), deg((size_t)nKF, 0);
+  for (int i = 0; i < p.n_edges; i++) deg[p.edges[i].kf]++;
+  int nOpt = 0;
+  for (int i = 0; i < p.n_local; i++)
+    if (!p.keyframes[i].fixed && deg[i] > 0) slot[i] = nOpt++;
+  if (nOpt > ORBX_LBA_MAX_LOCAL) return fail(ORBX_E_BADARG, "more than ORBX_LBA_MAX_LOCAL key frames to optimise");
+  r.num_fixedKF = p.n_fixed + fixedLocal;
+  r.num_OptKF = p.n_local;
+  r.num_MPs = p.n_points;
+  r.num_edges = p.n_edges;
+  if (r.num_fixedKF == 0) { lba_passthrough(p, r, ORBX_LBA_ABORTED); return ORBX_OK; }
+  if (params->stop) { lba_passthrough(p, r, ORBX_LBA_STOPPED); return ORBX_OK; }
+  if (p.n_edges == 0) { lba_passthrough(p, r, ORBX_LBA_EMPTY); return ORBX_OK; }
+  std::vector<int> kfStart((size_t)nOpt + 1, 0), kfEdges;
+  for (int i = 0; i < nKF; i++)
+    if (slot[i] >= 0) kfStart[(size_t)slot[i] + 1] = deg[i];
+  for (int s = 0; s < nOpt; s++) kfStart[(size_t)s + 1] += kfStart[s];
+  kfEdges.resize((size_t)kfStart[nOpt]);
+  {
+    std::vector<int> fill(kfStart.begin(), kfStart.end() - 1);
+    for (int i = 0; i < p.n_edges; i++) {
+      const int s = slot[p.edges[i].kf];
+      if (s >= 0) kfEdges[(size_t)fill[s]++] = i;
+    }
+  }
+  int rc = set_device(device);
+  if (rc != ORBX_OK) return rc;
+
+  const size_t nE = (size_t)p.n_edges, nP = (size_t)p.n_points, n = 6 * (size_t)nOpt;
+  LbaArgs a{};
+  a.nKF = nKF; a.nLocal = p.n_local; a.nP = p.n_points; a.nE = p.n_edges; a.nOpt = nOpt; a.n = (int)n;
+  a.maxIter = params->max_iterations;
+  a.lambdaInit = (double)params->lambda_init;
+  Pack pk;
+  pk.in(a.kfs, p.keyframes, (size_t)nKF, 16);
+  pk.in(a.edges, p.edges, nE, 16);
+  pk.in(a.points, p.points, 3 * nP, 16);
+  pk.in(a.slot, slot.data(), (size_t)nKF, 16);
+  pk.in(a.ptStart, ptStart.data(), nP + 1, 16);
+  pk.in(a.kfStart, kfStart.data(), (size_t)nOpt + 1, 16);
+  pk.in(a.kfEdges, kfEdges.data(), kfEdges.size(), 16);
+  for (int c = 0; c < 2; c++) {
+    pk.area(a.pose[c], (size_t)nKF, 16);
+    pk.area(a.X[c], 3 * nP, 16);
+    pk.area(a.hpl[c], nE * kLbaHpl, 16);
+    pk.area(a.hpp[c], (size_t)nOpt * kLbaApp, 16);
+    pk.area(a.hll[c], nP * kLbaAll, 16);
+  }
+  pk.area(a.eApp, nE * kLbaApp, 16);
+  pk.area(a.eAll, nE * kLbaAll, 16);
+  pk.area(a.eRho, nE, 16);
+  pk.area(a.ptChi, nP, 16);
+  pk.area(a.dinv, nP * 6, 16);
+  pk.area(a.S, n * n, 16);
+  pk.area(a.bs, n, 16);
+  pk.area(a.xp, n, 16);
+  pk.area(a.xl, 3 * nP, 16);
+  pk.area(a.st, 1, 16);
+  // outputs: one contiguous area
+  const size_t oStatus = pk.area(a.status, 1, 16);
+  const size_t oScal = pk.area(a.outScalars, 3, 16);
+  const size_t oCnt = pk.area(a.outCounters, 3, 16);
+  const size_t oPose = pk.area(a.outPose, 7 * (size_t)p.n_local, 16);
+  const size_t oPts = pk.area(a.outPts, 3 * nP, 16);
+  const size_t oChi = pk.area(a.chi2, nE, 16);
+  const size_t oErase = pk.area(a.erase, nE, 16);
+  const size_t oDepth = pk.area(a.depthPos, nE, 16);
+  const size_t outEnd = oDepth + std::max<size_t>(nE, 16);
+  hipError_t e = pk.reserve();   // writes every bound pointer of a
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+  e = pk.commit();
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+  HIPC(launch_lba_init(a));
+  HIPC(launch_lba_evaluate(a));   // solve(0): the system at the start, lambda
+  for (long long trial = 0; trial < 10LL * params->max_iterations; trial++) {   // (the device stops earlier; the bound is g2o's own)
+    HIPC(launch_lba_trial(a));
+    HIPC(launch_lba_evaluate(a));
+    const uint8_t* h = pk.fetch(oStatus, sizeof(int), &e);
+    if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+    int running;
+    std::memcpy(&running, h, sizeof running);
+    if (!running) break;
+  }
+  HIPC(launch_lba_finish(a));
+  const uint8_t* h = pk.fetch(oStatus, outEnd - oStatus, &e);
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+  double scal[3];
+  int cnt[3];
+  std::memcpy(scal, h + (oScal - oStatus), sizeof scal);
+  std::memcpy(cnt, h + (oCnt - oStatus), sizeof cnt);
+  r.status = ORBX_LBA_DONE;
+  r.lambda = scal[0]; r.chi2_initial = scal[1]; r.chi2_final = scal[2];
+  r.iterations = cnt[0]; r.trials = cnt[1]; r.stop_reason = cnt[2];
+  if (p.n_local) std::memcpy(r.poses, h + (oPose - oStatus), 7 * (size_t)p.n_local * sizeof(double));
+  std::memcpy(r.points, h + (oPts - oStatus), 3 * nP * sizeof(double));
+  std::memcpy(r.chi2, h + (oChi - oStatus), nE * sizeof(double));
+  std::memcpy(r.erase, h + (oErase - oStatus), nE);
+  std::memcpy(r.depth_positive, h + (oDepth - oStatus), nE);
+  return ORBX_OK;
+}

@@ -1,0 +1,65 @@
+// orbx_lba.h — what the local bundle adjustment's kernels (orbx_lba.hip) and its C ABI (orbx_api_lba.hip) share: the argument
+// record of the kernel chain, the device-resident Levenberg state and the launches.
+#ifndef ORBX_LBA_H
+#define ORBX_LBA_H
+#include "orbx_host.h"
+
+namespace orbx {
+
+constexpr int kLbaApp = 27;   // per edge: the key frame's 6 x 6 block (upper triangle, 21) and its share of b (6)
+constexpr int kLbaAll = 9;    // per edge: the point's 3 x 3 block (upper triangle, 6) and its share of b (3)
+constexpr int kLbaHpl = 18;   // per edge: the 6 x 3 pose-point block, row-major
+
+struct LbaPose { double q[4], t[3]; };
+
+// The optimiser's state (optimization_algorithm_levenberg.cpp), written by k_lba_decide's thread 0 only.  `cur` names the copy
+// of the estimates and of the linear system (0 / 1) that belongs to the current estimate; a trial is built in the other copy.
+struct LbaState {
+  double lambda, ni, curChi, iniChi, chiInitial;
+  int cur, stage, iter, qmax, nbadR, trials, ok, running, stopReason, pad;
+};
+
+struct LbaArgs {
+  const orbx_lba_keyframe* kfs;   // [nKF]
+  const orbx_lba_edge* edges;     // [nE]
+  const float* points;            // [nP][3]
+  const int* slot;                // [nKF] row block of the reduced system, -1: not optimised
+  const int* ptStart;             // [nP + 1] a point's edges are [ptStart[p], ptStart[p + 1])
+  const int* kfStart;             // [nOpt + 1] CSR of a slot's edges, ascending
+  const int* kfEdges;
+  LbaPose* pose[2];               // [nKF] estimates, two copies
+  double* X[2];                   // [nP][3]
+  double* hpl[2];                 // [nE][kLbaHpl]
+  double* hpp[2];                 // [nOpt][kLbaApp]: Hpp (21), bp (6)
+  double* hll[2];                 // [nP][kLbaAll]: Hll (6), bl (3)
+  double* eApp;                   // [nE][kLbaApp] the edges' terms of the pass, reduced right away
+  double* eAll;                   // [nE][kLbaAll]
+  double* eRho;                   // [nE] robust chi2 of the pass
+  double* ptChi;                  // [nP] its per-point sums
+  double* dinv;                   // [nP][6] (Hll + lambda I)^-1, upper triangle
+  double* S;                      // [n][n] the reduced camera system, row-major; the factorisation's workspace (lower triangle)
+  double* bs;                     // [n]
+  double* xp;                     // [n] pose increments
+  double* xl;                     // [nP][3] point increments
+  LbaState* st;
+  // outputs, one contiguous area
+  int* status;                    // running flag of the last decision (the host's one word per trial)
+  double* outPose;                // [nLocal][7]
+  double* outPts;                 // [nP][3]
+  double* chi2;                   // [nE] the chi2 every edge holds (written by every linearisation)
+  uint8_t* erase;                 // [nE]
+  uint8_t* depthPos;              // [nE]
+  double* outScalars;             // lambda, chi2_initial, chi2_final
+  int* outCounters;               // iterations, trials, stop_reason
+  int nKF, nLocal, nP, nE, nOpt, n, maxIter;
+  double lambdaInit;
+};
+
+// the chain on the null stream (orbx_lba.hip)
+hipError_t launch_lba_init(const LbaArgs& a);       // estimates from the inputs, the state, x = 0
+hipError_t launch_lba_evaluate(const LbaArgs& a);   // linearise at the estimate (stage 0) or the trial, reduce, decide
+hipError_t launch_lba_trial(const LbaArgs& a);      // Dinv, Schur complement, factorisation and solve, back-substitution, oplus
+hipError_t launch_lba_finish(const LbaArgs& a);     // classification and outputs
+
+}  // namespace orbx
+#endif

@@ -1,0 +1,619 @@
+// orbx_lba.hip — Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1109-1516): g2o's Levenberg on BlockSolver_6_3 as a chain
+// of kernels, all arithmetic in double.  The whole optimiser state lives on the device (LbaState); the host enqueues one chain per
+// trial and reads one word to know whether to enqueue another.  The estimates and the linear system exist twice: a trial is
+// linearised into the copy that does not belong to the current estimate, and accepting it flips LbaState::cur -- an accepted
+// trial already holds the next system, as in k_pose_opt.
+//   k_lba_linearize   one edge per thread: error, Huber weights, both Jacobians, the edge's terms of Hpp / bp, Hll / bl, Hpl
+//   k_lba_reduce_pts  one point per thread: Hll, bl and the robust chi2 over its (contiguous) edges, in edge order
+//   k_lba_reduce_kfs  one wave per optimised key frame: Hpp, bp over its CSR list, lanes striding, a fixed butterfly
+//   k_lba_decide      one workgroup: the chi2, lambda's start or computeScale, accept / reject, the stop rules
+//   k_lba_dinv        one point per thread: (Hll + lambda I)^-1
+//   k_lba_schur       one wave per block (i, j >= i) of Hpp + lambda I - sum Hpl Dinv Hpl^T, and bp - sum Hpl Dinv bl
+//   k_lba_solve       one workgroup: unpivoted LDLT of the reduced system in its HBM workspace by panels of 6 columns, b riding
+//                     along as one more row, then the back-substitution
+//   k_lba_update      one point / key frame per thread: xl = Dinv (bl - Hpl^T xp), oplus into the trial copy
+//   k_lba_finish      classification at the held chi2 and the final depth, the outputs
+// Every sum has a fixed order (serial in edge order, a strided serial sum plus a fixed tree, or wave_sum's butterfly) and there
+// is no atomic: two calls on the same input agree bit for bit.
+#include "orbx_lba.h"
+#include "orbx_pose.h"
+
+namespace {
+
+using orbx::LbaArgs;
+using orbx::LbaPose;
+using orbx::LbaState;
+using orbx::kLbaApp;
+using orbx::kLbaAll;
+using orbx::kLbaHpl;
+
+constexpr int kLbaBS = 256;
+constexpr int kSolveBS = 1024;
+
+__device__ __forceinline__ void quat_to_R(const double* q, double R[3][3]) {   // Eigen's toRotationMatrix
+  const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+  const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+  R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+  R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+  R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+}
+
+// SE3Quat::map of the edge's point, its error (rows: 2 mono, 3 stereo; the unused row is zero) and chi2 = e^T (info I) e
+__device__ __forceinline__ void lba_error(const orbx_lba_keyframe& K, const orbx_lba_edge& E, const LbaPose& P, const double* X, double Xc[3],
+                                          double e[3], double& chi) {
+  qrot(P.q, X, Xc);
+  for (int i = 0; i < 3; i++) Xc[i] += P.t[i];
+  const double fx = (double)K.fx, fy = (double)K.fy, cx = (double)K.cx, cy = (double)K.cy, info = (double)E.inv_sigma2;
+  if (E.u_right < 0.f) {   // Pinhole::project(Vector3d): float parameters times double
+    e[0] = (double)E.u - (fx * Xc[0] / Xc[2] + cx);
+    e[1] = (double)E.v - (fy * Xc[1] / Xc[2] + cy);
+    e[2] = 0;
+    chi = e[0] * (info * e[0]) + e[1] * (info * e[1]);
+  } else {                 // EdgeStereoSE3ProjectXYZ::cam_project: const float invz = 1.0f / z
+    const double invz = (double)(float)(1.0 / Xc[2]);
+    const double r0 = Xc[0] * invz * fx + cx;
+    e[0] = (double)E.u - r0;
+    e[1] = (double)E.v - (Xc[1] * invz * fy + cy);
+    e[2] = (double)E.u_right - (r0 - (double)K.bf * invz);
+    chi = e[0] * (info * e[0]) + e[1] * (info * e[1]) + e[2] * (info * e[2]);
+  }
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_init(LbaArgs A) {
+  const int i = blockIdx.x * kLbaBS + threadIdx.x;
+  if (i < A.nKF) {   // SE3Quat(q, t): normalizeRotation
+    LbaPose P;
+    for (int k = 0; k < 4; k++) P.q[k] = (double)A.kfs[i].q[k];
+    for (int k = 0; k < 3; k++) P.t[k] = (double)A.kfs[i].t[k];
+    normalize_rotation(P.q);
+    A.pose[0][i] = P;
+    A.pose[1][i] = P;
+  }
+  if (i < A.nP)
+    for (int k = 0; k < 3; k++) {
+      const double v = (double)A.points[3 * (size_t)i + k];
+      A.X[0][3 * (size_t)i + k] = v;
+      A.X[1][3 * (size_t)i + k] = v;
+      A.xl[3 * (size_t)i + k] = 0;
+    }
+  if (i < A.n) A.xp[i] = 0;
+  if (i == 0) {
+    LbaState s{};
+    s.ok = 1;
+    s.running = 1;
+    *A.st = s;
+    *A.status = 1;
+  }
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
+  const int ei = blockIdx.x * kLbaBS + threadIdx.x;
+  if (ei >= A.nE) return;
+  const LbaState& st = *A.st;
+  const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
+  const orbx_lba_edge E = A.edges[ei];
+  const orbx_lba_keyframe K = A.kfs[E.kf];
+  const LbaPose P = A.pose[tgt][E.kf];
+  const double X[3] = {A.X[tgt][3 * (size_t)E.point], A.X[tgt][3 * (size_t)E.point + 1], A.X[tgt][3 * (size_t)E.point + 2]};
+  double Xc[3], e[3], chi;
+  lba_error(K, E, P, X, Xc, e, chi);
+  const bool mono = E.u_right < 0.f;
+  const double fx = (double)K.fx, fy = (double)K.fy, bf = (double)K.bf;
+  const double x = Xc[0], y = Xc[1], z = Xc[2];
+  double R[3][3], Jp[3][6], Jl[3][3];
+  quat_to_R(P.q, R);
+  if (mono) {   // EdgeSE3ProjectXYZ::linearizeOplus: -projectJac * R, -projectJac * SE3deriv
+    const double a = fx / z, c = -fx * x / (z * z), a1 = fy / z, c1 = -fy * y / (z * z);
+    for (int j = 0; j < 3; j++) {
+      Jl[0][j] = -(a * R[0][j] + c * R[2][j]);
+      Jl[1][j] = -(a1 * R[1][j] + c1 * R[2][j]);
+      Jl[2][j] = 0;
+    }
+    Jp[0][0] = -(c * y); Jp[0][1] = -(a * z - c * x); Jp[0][2] = a * y; Jp[0][3] = -a; Jp[0][4] = 0; Jp[0][5] = -c;
+    Jp[1][0] = -(c1 * y - a1 * z); Jp[1][1] = c1 * x; Jp[1][2] = -(a1 * x); Jp[1][3] = 0; Jp[1][4] = -a1; Jp[1][5] = -c1;
+    for (int j = 0; j < 6; j++) Jp[2][j] = 0;
+  } else {      // EdgeStereoSE3ProjectXYZ::linearizeOplus
+    const double z_2 = z * z;
+    for (int j = 0; j < 3; j++) {
+      Jl[0][j] = -fx * R[0][j] / z + fx * x * R[2][j] / z_2;
+      Jl[1][j] = -fy * R[1][j] / z + fy * y * R[2][j] / z_2;
+      Jl[2][j] = Jl[0][j] - bf * R[2][j] / z_2;
+    }
+    Jp[0][0] = x * y / z_2 * fx; Jp[0][1] = -(1 + (x * x / z_2)) * fx; Jp[0][2] = y / z * fx; Jp[0][3] = -1. / z * fx; Jp[0][4] = 0;
+    Jp[0][5] = x / z_2 * fx;
+    Jp[1][0] = (1 + y * y / z_2) * fy; Jp[1][1] = -x * y / z_2 * fy; Jp[1][2] = -x / z * fy; Jp[1][3] = 0; Jp[1][4] = -1. / z * fy;
+    Jp[1][5] = y / z_2 * fy;
+    Jp[2][0] = Jp[0][0] - bf * y / z_2; Jp[2][1] = Jp[0][1] + bf * x / z_2; Jp[2][2] = Jp[0][2]; Jp[2][3] = Jp[0][3]; Jp[2][4] = 0;
+    Jp[2][5] = Jp[0][5] - bf / z_2;
+  }
+  // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
+  const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815);   // narrowed as the reference's (Optimizer.cc:1281-1282)
+  const double delta = (double)(mono ? thHuberMono : thHuberStereo);
+  const double dsqr = delta * delta;
+  double rho0 = chi, rho1 = 1.0;
+  if (!(chi <= dsqr)) {
+    const double sq = sqrt(chi);
+    rho0 = 2 * sq * delta - dsqr;
+    rho1 = delta / sq;
+  }
+  const double w = rho1 * (double)E.inv_sigma2;
+  constexpr int rows = 3;   // a monocular edge's third row is zero: its terms add nothing
+  A.chi2[ei] = chi;
+  A.eRho[ei] = rho0;
+  double* app = A.eApp + (size_t)ei * kLbaApp;
+  double* all = A.eAll + (size_t)ei * kLbaAll;
+  double* hpl = A.hpl[tgt] + (size_t)ei * kLbaHpl;
+  double wp[3][6], wl[3][3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) wp[m][a] = Jp[m][a] * w;
+#pragma unroll
+    for (int a = 0; a < 3; a++) wl[m][a] = Jl[m][a] * w;
+  }
+#pragma unroll
+  for (int a = 0, q = 0; a < 6; a++) {
+#pragma unroll
+    for (int b = a; b < 6; b++, q++) {
+      double s = 0;
+      for (int m = 0; m < rows; m++) s += wp[m][a] * Jp[m][b];
+      app[q] = s;
+    }
+    double s = 0;
+    for (int m = 0; m < rows; m++) s -= wp[m][a] * e[m];
+    app[21 + a] = s;
+    for (int c = 0; c < 3; c++) {
+      double h = 0;
+      for (int m = 0; m < rows; m++) h += wp[m][a] * Jl[m][c];
+      hpl[3 * a + c] = h;
+    }
+  }
+#pragma unroll
+  for (int a = 0, q = 0; a < 3; a++) {
+#pragma unroll
+    for (int b = a; b < 3; b++, q++) {
+      double s = 0;
+      for (int m = 0; m < rows; m++) s += wl[m][a] * Jl[m][b];
+      all[q] = s;
+    }
+    double s = 0;
+    for (int m = 0; m < rows; m++) s -= wl[m][a] * e[m];
+    all[6 + a] = s;
+  }
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_reduce_pts(LbaArgs A) {
+  const int p = blockIdx.x * kLbaBS + threadIdx.x;
+  if (p >= A.nP) return;
+  const LbaState& st = *A.st;
+  const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
+  double acc[kLbaAll], chi = 0;
+  for (int i = 0; i < kLbaAll; i++) acc[i] = 0;
+  for (int ei = A.ptStart[p]; ei < A.ptStart[p + 1]; ei++) {
+    const double* all = A.eAll + (size_t)ei * kLbaAll;
+    for (int i = 0; i < kLbaAll; i++) acc[i] += all[i];
+    chi += A.eRho[ei];
+  }
+  for (int i = 0; i < kLbaAll; i++) A.hll[tgt][(size_t)p * kLbaAll + i] = acc[i];
+  A.ptChi[p] = chi;
+}
+
+__global__ __launch_bounds__(64) void k_lba_reduce_kfs(LbaArgs A) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const LbaState& st = *A.st;
+  const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
+  double acc[kLbaApp];
+#pragma unroll
+  for (int i = 0; i < kLbaApp; i++) acc[i] = 0;
+  for (int k = A.kfStart[s] + lane; k < A.kfStart[s + 1]; k += 64) {
+    const double* app = A.eApp + (size_t)A.kfEdges[k] * kLbaApp;
+#pragma unroll
+    for (int i = 0; i < kLbaApp; i++) acc[i] += app[i];
+  }
+#pragma unroll
+  for (int i = 0; i < kLbaApp; i++) acc[i] = wave_sum(acc[i]);
+  if (lane < kLbaApp) {
+    double v = 0;
+#pragma unroll
+    for (int i = 0; i < kLbaApp; i++) v = lane == i ? acc[i] : v;
+    A.hpp[tgt][(size_t)s * kLbaApp + lane] = v;
+  }
+}
+
+// a strided serial sum per thread, then a fixed tree over the workgroup; every thread returns the result
+template <int kN>
+__device__ __forceinline__ double block_tree(double v, double* red, bool isMax) {
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = kN / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) red[threadIdx.x] = isMax ? fmax(red[threadIdx.x], red[threadIdx.x + off]) : red[threadIdx.x] + red[threadIdx.x + off];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_decide(LbaArgs A) {
+  __shared__ double red[kLbaBS];
+  LbaState& st = *A.st;
+  const int tid = threadIdx.x;
+  const int cur = st.cur, stage = st.stage;
+  const int tgt = stage == 0 ? cur : cur ^ 1;
+  double part = 0;
+  for (int p = tid; p < A.nP; p += kLbaBS) part += A.ptChi[p];
+  const double chi = block_tree<kLbaBS>(part, red, false);
+  double aux;
+  if (stage == 0) {   // computeLambdaInit: the largest |H_jj| over every active vertex
+    double m = 0;
+    for (int k = tid; k < 6 * A.nOpt; k += kLbaBS) {
+      const int s = k / 6, j = k % 6;
+      m = fmax(m, fabs(A.hpp[tgt][(size_t)s * kLbaApp + (j * (13 - j)) / 2]));   // diagonal j of a 6 x 6 upper triangle
+    }
+    for (int k = tid; k < 3 * A.nP; k += kLbaBS) {
+      const int p = k / 3, j = k % 3;
+      m = fmax(m, fabs(A.hll[tgt][(size_t)p * kLbaAll + (j * (7 - j)) / 2]));
+    }
+    aux = block_tree<kLbaBS>(m, red, true);
+  } else {            // computeScale over all of x: sum x (lambda x + b), b of the system at the estimate
+    const double lambda = st.lambda;
+    double sc = 0;
+    for (int k = tid; k < A.n; k += kLbaBS) {
+      const double x = A.xp[k];
+      sc += x * (lambda * x + A.hpp[cur][(size_t)(k / 6) * kLbaApp + 21 + k % 6]);
+    }
+    for (int k = tid; k < 3 * A.nP; k += kLbaBS) {
+      const double x = A.xl[k];
+      sc += x * (lambda * x + A.hll[cur][(size_t)(k / 3) * kLbaAll + 6 + k % 3]);
+    }
+    aux = block_tree<kLbaBS>(sc, red, false);
+  }
+  if (tid != 0) return;
+  LbaState c = st;
+  bool trial = false;
+  if (stage == 0) {
+    c.curChi = chi;
+    c.iniChi = chi;
+    c.chiInitial = chi;
+    c.lambda = A.lambdaInit > 0 ? A.lambdaInit : 1e-5 * aux;
+    c.ni = 2;
+    c.nbadR = 0;
+    c.qmax = 0;
+    c.stage = 1;
+    trial = true;
+  } else {
+    c.trials++;
+    double tempChi = chi;
+    if (!c.ok) tempChi = DBL_MAX;
+    double rho = c.curChi - tempChi;
+    const double scale = aux + 1e-3;
+    rho /= scale;
+    if (rho > 0 && isfinite(tempChi)) {
+      double alpha = 1. - pow(2 * rho - 1, 3);
+      alpha = fmin(alpha, 2. / 3.);
+      c.lambda *= fmax(1. / 3., alpha);
+      c.ni = 2;
+      c.curChi = tempChi;
+      c.cur ^= 1;
+    } else {
+      c.lambda *= c.ni;
+      c.ni *= 2;
+    }
+    c.qmax++;
+    if (rho < 0 && c.qmax < 10) {
+      trial = true;
+    } else {
+      int reason = -1;
+      if (c.qmax == 10) reason = ORBX_LBA_STOP_QMAX;
+      else if (rho == 0) reason = ORBX_LBA_STOP_RHO_ZERO;
+      if (reason < 0) {   // Raul's stop criterion
+        if ((c.iniChi - c.curChi) * 1e3 < c.iniChi) c.nbadR++; else c.nbadR = 0;
+        if (c.nbadR >= 3) reason = ORBX_LBA_STOP_SMALL_GAIN;
+      }
+      c.iter++;
+      if (reason < 0 && c.iter < A.maxIter) {   // next solve(): the errors and the system at the estimate are the ones held
+        c.iniChi = c.curChi;
+        c.qmax = 0;
+        trial = true;
+      } else {
+        c.stopReason = reason < 0 ? ORBX_LBA_STOP_ITERATIONS : reason;
+      }
+    }
+  }
+  c.running = trial ? 1 : 0;
+  st = c;
+  *A.status = c.running;
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_dinv(LbaArgs A) {
+  const int p = blockIdx.x * kLbaBS + threadIdx.x;
+  if (p >= A.nP) return;
+  const LbaState& st = *A.st;
+  const double* h = A.hll[st.cur] + (size_t)p * kLbaAll;
+  const double a = h[0] + st.lambda, b = h[1], c = h[2], d = h[3] + st.lambda, e = h[4], f = h[5] + st.lambda;
+  // Eigen's 3 x 3 inverse: cofactors over the determinant
+  const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
+  const double inv = 1.0 / (a * c00 + b * c01 + c * c02);
+  double* o = A.dinv + (size_t)p * 6;
+  o[0] = c00 * inv; o[1] = c01 * inv; o[2] = c02 * inv;
+  o[3] = (a * f - c * c) * inv; o[4] = (b * c - a * e) * inv;
+  o[5] = (a * d - b * b) * inv;
+}
+
+// Y = Hpl (6 x 3) * Dinv (symmetric, upper triangle)
+__device__ __forceinline__ void hpl_dinv(const double* hpl, const double* di, double Y[6][3]) {
+  const double D[3][3] = {{di[0], di[1], di[2]}, {di[1], di[3], di[4]}, {di[2], di[4], di[5]}};
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) Y[a][c] = hpl[3 * a] * D[0][c] + hpl[3 * a + 1] * D[1][c] + hpl[3 * a + 2] * D[2][c];
+}
+
+// block (i, j >= i) of Hschur = Hpp + lambda I - sum_p Hpl_ip Dinv_p Hpl_jp^T over the points key frame i sees, in its edge order;
+// the diagonal blocks also give bschur_i = bp_i - sum_p Hpl_ip Dinv_p bl_p.  Both triangles of S are written.
+__global__ __launch_bounds__(64) void k_lba_schur(LbaArgs A) {
+  const int i = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
+  if (j < i) return;
+  const LbaState& st = *A.st;
+  const int cur = st.cur;
+  double acc[42];
+#pragma unroll
+  for (int k = 0; k < 42; k++) acc[k] = 0;
+  for (int k = A.kfStart[i] + lane; k < A.kfStart[i + 1]; k += 64) {
+    const int ei = A.kfEdges[k];
+    const int p = A.edges[ei].point;
+    int ej = ei;
+    if (j != i) {
+      ej = -1;
+      for (int m = A.ptStart[p]; m < A.ptStart[p + 1]; m++)
+        if (A.slot[A.edges[m].kf] == j) { ej = m; break; }
+      if (ej < 0) continue;
+    }
+    double Y[6][3];
+    hpl_dinv(A.hpl[cur] + (size_t)ei * kLbaHpl, A.dinv + (size_t)p * 6, Y);
+    const double* hj = A.hpl[cur] + (size_t)ej * kLbaHpl;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+      for (int b = 0; b < 6; b++) acc[6 * a + b] += Y[a][0] * hj[3 * b] + Y[a][1] * hj[3 * b + 1] + Y[a][2] * hj[3 * b + 2];
+    if (j == i) {
+      const double* bl = A.hll[cur] + (size_t)p * kLbaAll + 6;
+#pragma unroll
+      for (int a = 0; a < 6; a++) acc[36 + a] += Y[a][0] * bl[0] + Y[a][1] * bl[1] + Y[a][2] * bl[2];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 42; k++) acc[k] = wave_sum(acc[k]);
+  double mine = 0;
+#pragma unroll
+  for (int k = 0; k < 42; k++) mine = lane == k ? acc[k] : mine;
+  const size_t n = (size_t)A.n;
+  if (lane < 36) {
+    const int a = lane / 6, b = lane % 6;
+    double v = -mine;
+    if (i == j) {
+      const int lo = a < b ? a : b, hi = a < b ? b : a;
+      v += A.hpp[cur][(size_t)i * kLbaApp + (lo * (13 - lo)) / 2 + (hi - lo)];
+      if (a == b) v += st.lambda;
+      A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
+    } else {
+      A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
+      A.S[(6 * (size_t)j + b) * n + 6 * i + a] = v;
+    }
+  } else if (lane < 42 && i == j) {
+    const int a = lane - 36;
+    A.bs[6 * i + a] = A.hpp[cur][(size_t)i * kLbaApp + 21 + a] - mine;
+  }
+}
+
+// Unpivoted LDLT of the n x n reduced system, in place in the lower triangle of S (L below the diagonal, D on it), blocked by
+// panels of kPanel columns: a panel (its rows from the diagonal down) is factored in LDS, written back, and the trailing lower
+// triangle takes the panel's rank-kPanel update from LDS -- n / kPanel passes over HBM instead of n.  Every entry receives its
+// terms (L_im L_km) D_m in ascending column order, the expression of ldlt6.  b rides along as row n of the matrix, so that the
+// forward substitution costs no pass of its own: what the factorisation leaves there is z = D^-1 L^-1 b.  A pivot <= 0 or not
+// finite fails the solve and leaves x as it was (the rule of ldlt6 / ldlt7).  Then L^T x = z, again by panels, the vector in LDS.
+constexpr int kPanel = 6;
+__global__ __launch_bounds__(kSolveBS) void k_lba_solve(LbaArgs A) {
+  __shared__ double P[(6 * ORBX_LBA_MAX_LOCAL + 1) * kPanel];
+  __shared__ double vec[6 * ORBX_LBA_MAX_LOCAL];
+  const int n = A.n, tid = threadIdx.x;   // n is a multiple of kPanel
+  double* S = A.S;
+  double* bs = A.bs;
+  bool ok = true;
+  for (int c0 = 0; c0 < n && ok; c0 += kPanel) {
+    const int rows = n + 1 - c0;          // the panel's rows c0 .. n; row n is b
+    __syncthreads();                      // the trailing update of the panel before is complete
+    for (int idx = tid; idx < rows * kPanel; idx += kSolveBS) {
+      const int i = c0 + idx / kPanel, m = idx % kPanel;
+      P[idx] = i < n ? S[(size_t)i * n + c0 + m] : bs[c0 + m];
+    }
+    for (int m = 0; m < kPanel; m++) {
+      __syncthreads();
+      const double d = P[m * kPanel + m];
+      if (!(d > 0) || !isfinite(d)) { ok = false; break; }   // uniform: every thread reads the same value
+      for (int r = m + 1 + tid; r < rows; r += kSolveBS) P[r * kPanel + m] /= d;
+      __syncthreads();
+      for (int idx = tid; idx < (rows - m - 1) * (kPanel - 1 - m); idx += kSolveBS) {   // the panel's columns right of m
+        const int r = m + 1 + idx / (kPanel - 1 - m), m2 = m + 1 + idx % (kPanel - 1 - m);
+        if (m2 <= r) P[r * kPanel + m2] -= (P[r * kPanel + m] * P[m2 * kPanel + m]) * d;
+      }
+    }
+    if (!ok) break;
+    __syncthreads();
+    for (int idx = tid; idx < rows * kPanel; idx += kSolveBS) {
+      const int r = idx / kPanel, m = idx % kPanel, i = c0 + r;
+      if (i == n) vec[c0 + m] = P[idx];
+      else if (r >= m) S[(size_t)i * n + c0 + m] = P[idx];
+    }
+    const int t0 = c0 + kPanel, trows = rows - kPanel;   // trailing rows t0 .. n, 32 rows x 32 columns of threads
+    for (int rr = tid >> 5; rr < trows; rr += kSolveBS >> 5) {
+      const int i = t0 + rr;
+      const int cmax = i < n ? rr : n - t0 - 1;          // a matrix row reaches its diagonal, b every column
+      double li[kPanel];
+#pragma unroll
+      for (int m = 0; m < kPanel; m++) li[m] = P[(kPanel + rr) * kPanel + m];
+      for (int cc = tid & 31; cc <= cmax; cc += 32) {
+        double* dst = i < n ? S + (size_t)i * n + t0 + cc : bs + t0 + cc;
+        double v = *dst;
+#pragma unroll
+        for (int m = 0; m < kPanel; m++) v -= (li[m] * P[(kPanel + cc) * kPanel + m]) * P[m * kPanel + m];
+        *dst = v;
+      }
+    }
+  }
+  __syncthreads();
+  if (ok) {
+    for (int c0 = n - kPanel; c0 >= 0; c0 -= kPanel) {
+      __syncthreads();
+      double x[kPanel];
+#pragma unroll
+      for (int m = kPanel - 1; m >= 0; m--) {   // the panel's triangle, by every thread
+        double s = vec[c0 + m];
+#pragma unroll
+        for (int m2 = m + 1; m2 < kPanel; m2++) s -= S[(size_t)(c0 + m2) * n + c0 + m] * x[m2];
+        x[m] = s;
+      }
+      __syncthreads();
+      if (tid < kPanel) {
+        double mine = 0;
+#pragma unroll
+        for (int m = 0; m < kPanel; m++) mine = tid == m ? x[m] : mine;
+        vec[c0 + tid] = mine;
+      }
+      for (int i = tid; i < c0; i += kSolveBS) {
+        double v = vec[i];
+#pragma unroll
+        for (int m = kPanel - 1; m >= 0; m--) v -= S[(size_t)(c0 + m) * n + i] * x[m];
+        vec[i] = v;
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += kSolveBS) A.xp[i] = vec[i];
+  }
+  if (tid == 0) A.st->ok = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_update(LbaArgs A) {
+  const int i = blockIdx.x * kLbaBS + threadIdx.x;
+  const LbaState& st = *A.st;
+  const int cur = st.cur, trial = cur ^ 1;
+  if (i < A.nP) {
+    const int e0 = A.ptStart[i], e1 = A.ptStart[i + 1];
+    double* xl = A.xl + 3 * (size_t)i;
+    if (st.ok && e1 > e0) {   // a failed solve leaves g2o's x as it was; a point without an edge is not active
+      const double* bl = A.hll[cur] + (size_t)i * kLbaAll + 6;
+      double r[3] = {bl[0], bl[1], bl[2]};
+      for (int ei = e0; ei < e1; ei++) {
+        const int s = A.slot[A.edges[ei].kf];
+        if (s < 0) continue;
+        const double* h = A.hpl[cur] + (size_t)ei * kLbaHpl;
+        const double* x = A.xp + 6 * s;
+        for (int c = 0; c < 3; c++) {
+          double t = 0;
+          for (int a = 0; a < 6; a++) t += h[3 * a + c] * x[a];
+          r[c] -= t;
+        }
+      }
+      const double* di = A.dinv + (size_t)i * 6;
+      xl[0] = di[0] * r[0] + di[1] * r[1] + di[2] * r[2];
+      xl[1] = di[1] * r[0] + di[3] * r[1] + di[4] * r[2];
+      xl[2] = di[2] * r[0] + di[4] * r[1] + di[5] * r[2];
+    }
+    for (int c = 0; c < 3; c++) A.X[trial][3 * (size_t)i + c] = A.X[cur][3 * (size_t)i + c] + xl[c];
+  }
+  if (i < A.nKF) {
+    const int s = A.slot[i];
+    const LbaPose Pc = A.pose[cur][i];
+    if (s < 0) {
+      A.pose[trial][i] = Pc;
+    } else {
+      Pose P, T;
+      for (int k = 0; k < 4; k++) P.q[k] = Pc.q[k];
+      for (int k = 0; k < 3; k++) P.t[k] = Pc.t[k];
+      double x[6];
+      for (int k = 0; k < 6; k++) x[k] = A.xp[6 * s + k];
+      oplus(x, P, T);
+      LbaPose To;
+      for (int k = 0; k < 4; k++) To.q[k] = T.q[k];
+      for (int k = 0; k < 3; k++) To.t[k] = T.t[k];
+      A.pose[trial][i] = To;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_finish(LbaArgs A) {
+  const int i = blockIdx.x * kLbaBS + threadIdx.x;
+  const LbaState& st = *A.st;
+  const int cur = st.cur;
+  if (i < A.nE) {   // chi2(): what the edge holds after the last trial; isDepthPositive(): at the estimates
+    const orbx_lba_edge E = A.edges[i];
+    const LbaPose P = A.pose[cur][E.kf];
+    const double X[3] = {A.X[cur][3 * (size_t)E.point], A.X[cur][3 * (size_t)E.point + 1], A.X[cur][3 * (size_t)E.point + 2]};
+    double Xc[3];
+    qrot(P.q, X, Xc);
+    const bool pos = Xc[2] + P.t[2] > 0.0;
+    const double gate = E.u_right < 0.f ? 5.991 : 7.815;
+    A.depthPos[i] = pos ? 1 : 0;
+    A.erase[i] = (A.chi2[i] > gate || !pos) ? 1 : 0;
+  }
+  if (i < A.nLocal) {
+    double* o = A.outPose + 7 * (size_t)i;
+    if (A.slot[i] < 0) {   // not optimised: the widened input
+      for (int k = 0; k < 4; k++) o[k] = (double)A.kfs[i].q[k];
+      for (int k = 0; k < 3; k++) o[4 + k] = (double)A.kfs[i].t[k];
+    } else {
+      const LbaPose P = A.pose[cur][i];
+      for (int k = 0; k < 4; k++) o[k] = P.q[k];
+      for (int k = 0; k < 3; k++) o[4 + k] = P.t[k];
+    }
+  }
+  if (i < A.nP) {
+    const bool active = A.ptStart[i + 1] > A.ptStart[i];
+    for (int k = 0; k < 3; k++)
+      A.outPts[3 * (size_t)i + k] = active ? A.X[cur][3 * (size_t)i + k] : (double)A.points[3 * (size_t)i + k];
+  }
+  if (i == 0) {
+    A.outScalars[0] = st.lambda;
+    A.outScalars[1] = st.chiInitial;
+    A.outScalars[2] = st.curChi;
+    A.outCounters[0] = st.iter;
+    A.outCounters[1] = st.trials;
+    A.outCounters[2] = st.stopReason;
+  }
+}
+
+inline int blocks(int n) { return (n + kLbaBS - 1) / kLbaBS; }
+
+}  // namespace
+
+namespace orbx {
+
+hipError_t launch_lba_init(const LbaArgs& a) {
+  const int m = std::max(std::max(a.nKF, a.nP), std::max(a.n, 1));
+  hipLaunchKernelGGL(k_lba_init, dim3(blocks(m)), dim3(kLbaBS), 0, nullptr, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lba_evaluate(const LbaArgs& a) {
+  hipLaunchKernelGGL(k_lba_linearize, dim3(blocks(a.nE)), dim3(kLbaBS), 0, nullptr, a);
+  hipLaunchKernelGGL(k_lba_reduce_pts, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
+  if (a.nOpt) hipLaunchKernelGGL(k_lba_reduce_kfs, dim3(a.nOpt), dim3(64), 0, nullptr, a);
+  hipLaunchKernelGGL(k_lba_decide, dim3(1), dim3(kLbaBS), 0, nullptr, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lba_trial(const LbaArgs& a) {
+  hipLaunchKernelGGL(k_lba_dinv, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
+  if (a.nOpt) hipLaunchKernelGGL(k_lba_schur, dim3(a.nOpt, a.nOpt), dim3(64), 0, nullptr, a);
+  hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(kSolveBS), 0, nullptr, a);
+  hipLaunchKernelGGL(k_lba_update, dim3(blocks(std::max(a.nKF, a.nP))), dim3(kLbaBS), 0, nullptr, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lba_finish(const LbaArgs& a) {
+  hipLaunchKernelGGL(k_lba_finish, dim3(blocks(std::max(std::max(a.nE, a.nP), a.nLocal))), dim3(kLbaBS), 0, nullptr, a);
+  return hipGetLastError();
+}
+
+}  // namespace orbx

@@ -1,0 +1,522 @@
+"""Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1109-1516) restated in float64 numpy on a dense system, and the seeded scenes
+of tests/test_local_ba.py and tests/test_local_ba_cpp.py.
+
+The restatement narrows to float32 exactly where the reference does: the key-frame poses, the points, the observations and the
+information values come in as floats, the camera parameters are floats widened, the Huber deltas are (float)sqrt(5.991) and
+(float)sqrt(7.815), the stereo error uses a float invz.  The Jacobians of both edge classes are analytic in the reference, so there
+is no numeric variant.  The two variants are the ways a correct implementation may legitimately differ from it:
+  V1  the edges summed in the reference's order, the Schur complement as g2o forms it (block_solver.hpp:354-447: Dinv = (Hll +
+      lambda I)^-1, Hschur = Hpp + lambda I - sum Hpl Dinv Hpl^T, bschur = bp - sum Hpl Dinv bl, xl = Dinv (bl - Hpl^T xp)), an
+      unpivoted LDLT of the reduced system (ldlt_dense: the algorithm of test_pose_opt.ldlt_solve, vectorised);
+  V2  the edges summed in reverse, the full un-reduced system (poses and points) solved by numpy.linalg.solve.
+What V1 and V2 differ by is the yardstick of the device tests (`spreads`).
+
+A key frame without an edge and a point without one are not part of the system (g2o's active set).  A local key frame that is not
+optimised comes back as the widened input, as the library returns it.
+
+Two scenes end on a rejected trial.  `rejected_last`: lambda_init = 1e-30 leaves every trial of the far start undamped, so the ten
+trials of the first iteration are the same overshooting step (lambda grows to 1e-30 * 2^45 at most), all are rejected with a margin
+and the optimiser stops on qmax: the chi2 the edges hold is the rejected trial's, the estimates are the restored ones.  `rho_zero`:
+lambda_init = 1e38 makes every increment vanish against
+its estimate, the trial equals the estimate bit for bit, rho == 0, the trial is rejected and the optimiser stops."""
+import functools
+import math
+import zlib
+
+import numpy as np
+
+import orb_slam3_fast_amd as orbx
+from test_pose_opt import normalize_rotation, oplus
+
+F32 = np.float32
+DELTA_MONO = float(F32(math.sqrt(5.991)))
+DELTA_STEREO = float(F32(math.sqrt(7.815)))
+STOP_ITERATIONS, STOP_QMAX, STOP_RHO_ZERO, STOP_SMALL_GAIN = 0, 1, 2, 3
+
+
+# ------------------------------------------------------------------------------------------------ edges
+def qrot_n(q, v):
+    """Eigen's quaternion * vector, one quaternion per row."""
+    uv = np.cross(q[:, :3], v)
+    uv = uv + uv
+    return v + q[:, 3:4] * uv + np.cross(q[:, :3], uv)
+
+
+def quat_to_R_n(q):
+    """Eigen's toRotationMatrix, one quaternion per row."""
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    R = np.empty((len(q), 3, 3))
+    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = 1 - (ty * y + tz * z), ty * x - tz * w, tz * x + ty * w
+    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = ty * x + tz * w, 1 - (tx * x + tz * z), tz * y - tx * w
+    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = tz * x - ty * w, tz * y + tx * w, 1 - (tx * x + ty * y)
+    return R
+
+
+def edge_terms(G, Q, T, X, jac=True):
+    """Errors [nE][3] (third row 0 for a monocular edge), chi2 [nE], camera-frame points and the Jacobians with respect to the pose
+    [nE][3][6] and the point [nE][3][3] at the poses (Q, T) and points X."""
+    kf, pt, mono = G["ekf"], G["ept"], G["mono"]
+    q = Q[kf]
+    Xc = qrot_n(q, X[pt]) + T[kf]
+    x, y, z = Xc[:, 0], Xc[:, 1], Xc[:, 2]
+    fx, fy, cx, cy, bf = (G["cam"][kf, j] for j in range(5))
+    obs, info = G["obs"], G["info"]
+    n = len(kf)
+    with np.errstate(all="ignore"):
+        em = np.stack([obs[:, 0] - (fx * x / z + cx), obs[:, 1] - (fy * y / z + cy), np.zeros(n)], 1)
+        invzf = (1.0 / z).astype(F32).astype(float)   # const float invz = 1.0f / trans_xyz[2]
+        r0 = x * invzf * fx + cx
+        es = np.stack([obs[:, 0] - r0, obs[:, 1] - (y * invzf * fy + cy), obs[:, 2] - (r0 - bf * invzf)], 1)
+    e = np.where(mono[:, None], em, es)
+    chi = (e * (info[:, None] * e)).sum(1)
+    if not jac:
+        return e, chi, Xc, None, None
+    R = quat_to_R_n(q)
+    with np.errstate(all="ignore"):
+        # EdgeSE3ProjectXYZ::linearizeOplus: -projectJac * R, -projectJac * SE3deriv
+        PJ = np.zeros((n, 3, 3))
+        PJ[:, 0, 0], PJ[:, 0, 2] = fx / z, -fx * x / (z * z)
+        PJ[:, 1, 1], PJ[:, 1, 2] = fy / z, -fy * y / (z * z)
+        D = np.zeros((n, 3, 6))
+        D[:, 0, 1], D[:, 0, 2], D[:, 0, 3] = z, -y, 1
+        D[:, 1, 0], D[:, 1, 2], D[:, 1, 4] = -z, x, 1
+        D[:, 2, 0], D[:, 2, 1], D[:, 2, 5] = y, -x, 1
+        Jpm = -np.einsum("nij,njk->nik", PJ, D)
+        Jlm = -np.einsum("nij,njk->nik", PJ, R)
+        # EdgeStereoSE3ProjectXYZ::linearizeOplus
+        z2 = z * z
+        Jls = np.zeros((n, 3, 3))
+        for j in range(3):
+            Jls[:, 0, j] = -fx * R[:, 0, j] / z + fx * x * R[:, 2, j] / z2
+            Jls[:, 1, j] = -fy * R[:, 1, j] / z + fy * y * R[:, 2, j] / z2
+            Jls[:, 2, j] = Jls[:, 0, j] - bf * R[:, 2, j] / z2
+        Jps = np.zeros((n, 3, 6))
+        Jps[:, 0] = np.stack([x * y / z2 * fx, -(1 + (x * x / z2)) * fx, y / z * fx, -1. / z * fx, 0 * x, x / z2 * fx], 1)
+        Jps[:, 1] = np.stack([(1 + y * y / z2) * fy, -x * y / z2 * fy, -x / z * fy, 0 * x, -1. / z * fy, y / z2 * fy], 1)
+        Jps[:, 2] = Jps[:, 0]
+        Jps[:, 2, 0] -= bf * y / z2
+        Jps[:, 2, 1] += bf * x / z2
+        Jps[:, 2, 4] = 0
+        Jps[:, 2, 5] -= bf / z2
+    Jp = np.where(mono[:, None, None], Jpm, Jps)
+    Jl = np.where(mono[:, None, None], Jlm, Jls)
+    return e, chi, Xc, Jp, Jl
+
+
+def huber(chi, delta):
+    """RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho, rho'."""
+    dsqr = delta * delta
+    big = ~(chi <= dsqr)
+    with np.errstate(all="ignore"):
+        sq = np.sqrt(chi)
+        return np.where(big, 2 * sq * delta - dsqr, chi), np.where(big, delta / sq, 1.0)
+
+
+def graph(sc):
+    """The flat graph of a scene as the arrays of the model."""
+    kf, ed = sc["keyframes"], sc["edges"]
+    nKF, nL = len(kf), sc["n_local"]
+    deg = np.bincount(ed["kf"], minlength=nKF) if len(ed) else np.zeros(nKF, int)
+    slot = np.full(nKF, -1)
+    opt = [i for i in range(nL) if not kf["fixed"][i] and deg[i] > 0]
+    slot[opt] = np.arange(len(opt))
+    cam = np.stack([kf[k].astype(float) for k in ("fx", "fy", "cx", "cy", "bf")], 1)
+    mono = ed["u_right"] < 0
+    return dict(ekf=ed["kf"].astype(int), ept=ed["point"].astype(int), mono=mono, cam=cam,
+                obs=np.stack([ed["u"], ed["v"], ed["u_right"]], 1).astype(float), info=ed["inv_sigma2"].astype(float),
+                delta=np.where(mono, DELTA_MONO, DELTA_STEREO), slot=slot, nOpt=len(opt), nKF=nKF, nL=nL, nP=len(sc["points"]),
+                active_pt=np.bincount(ed["point"], minlength=len(sc["points"])) > 0 if len(ed) else np.zeros(len(sc["points"]), bool))
+
+
+def serial_sum(v):
+    s = 0.0
+    for t in v:
+        s += t
+    return s
+
+
+def build_system(G, Q, T, X, variant):
+    """computeActiveErrors + buildSystem: Hpp [nOpt][6][6], bp [nOpt][6], Hll [nP][3][3], bl [nP][3], W = the Hpl blocks as a dense
+    [6 nOpt][3 nP], the robust chi2 and every edge's chi2.  Sums run in edge order (V1) or in reverse (V2)."""
+    e, chi, _, Jp, Jl = edge_terms(G, Q, T, X)
+    rho0, rho1 = huber(chi, G["delta"])
+    w = rho1 * G["info"]
+    App = np.einsum("n,nma,nmb->nab", w, Jp, Jp)
+    bpe = -np.einsum("n,nma,nm->na", w, Jp, e)
+    All = np.einsum("n,nma,nmb->nab", w, Jl, Jl)
+    ble = -np.einsum("n,nma,nm->na", w, Jl, e)
+    Hpl = np.einsum("n,nma,nmc->nac", w, Jp, Jl)
+    nOpt, nP = G["nOpt"], G["nP"]
+    s = G["slot"][G["ekf"]]
+    order = np.arange(len(chi))[::-1] if variant else np.arange(len(chi))
+    Hpp, bp, Hll, bl = np.zeros((nOpt, 6, 6)), np.zeros((nOpt, 6)), np.zeros((nP, 3, 3)), np.zeros((nP, 3))
+    o = order[s[order] >= 0]
+    np.add.at(Hpp, s[o], App[o])      # unbuffered: one addition per edge, in the order given
+    np.add.at(bp, s[o], bpe[o])
+    np.add.at(Hll, G["ept"][order], All[order])
+    np.add.at(bl, G["ept"][order], ble[order])
+    W = np.zeros((6 * nOpt, 3 * nP))
+    for k in np.nonzero(s >= 0)[0]:
+        W[6 * s[k]:6 * s[k] + 6, 3 * G["ept"][k]:3 * G["ept"][k] + 3] = Hpl[k]
+    return dict(Hpp=Hpp, bp=bp, Hll=Hll, bl=bl, W=W, chi=serial_sum(rho0[order]), edge_chi=chi)
+
+
+def ldlt_dense(A, b):
+    """Unpivoted LDLT, right-looking; None when a pivot is <= 0 or not finite (the rule of test_pose_opt.ldlt_solve, which it
+    equals up to rounding: test_local_ba.py checks)."""
+    A = np.array(A, float)
+    n = len(b)
+    for j in range(n):
+        d = A[j, j]
+        if not (d > 0) or not np.isfinite(d):
+            return None
+        c = A[j + 1:, j].copy()
+        l = c / d
+        A[j + 1:, j + 1:] -= np.outer(l, c)
+        A[j + 1:, j] = l
+    L = np.tril(A, -1) + np.eye(n)
+    y = np.linalg.solve(L, b) if n else np.zeros(0)
+    return np.linalg.solve(L.T, y / np.diag(A)) if n else np.zeros(0)
+
+
+def solve_schur(G, sysm, lam):
+    """V1: block_solver.hpp:354-447.  Returns (xp, xl) or None."""
+    nOpt, nP = G["nOpt"], G["nP"]
+    act = G["active_pt"]
+    Hll = sysm["Hll"] + lam * np.eye(3)
+    Hll[~act] = np.eye(3)
+    Dinv = np.linalg.inv(Hll)
+    S = np.zeros((6 * nOpt, 6 * nOpt))
+    for i in range(nOpt):
+        S[6 * i:6 * i + 6, 6 * i:6 * i + 6] = sysm["Hpp"][i] + lam * np.eye(6)
+    bs = sysm["bp"].reshape(-1).copy()
+    W = sysm["W"]
+    for p in range(nP):   # the points in order
+        Wp = W[:, 3 * p:3 * p + 3]
+        rows = np.nonzero(np.abs(Wp).sum(1))[0]
+        if not len(rows):
+            continue
+        Y = Wp[rows] @ Dinv[p]
+        S[np.ix_(rows, rows)] -= Y @ Wp[rows].T
+        bs[rows] -= Y @ sysm["bl"][p]
+    xp = ldlt_dense(S, bs)
+    if xp is None:
+        return None
+    xl = np.einsum("pij,pj->pi", Dinv, sysm["bl"] - (W.T @ xp).reshape(nP, 3))
+    xl[~act] = 0
+    return xp, xl
+
+
+def solve_full(G, sysm, lam):
+    """V2: the un-reduced system by numpy.linalg.solve."""
+    nOpt, nP = G["nOpt"], G["nP"]
+    act = G["active_pt"]
+    n = 6 * nOpt
+    A = np.zeros((n + 3 * nP, n + 3 * nP))
+    for i in range(nOpt):
+        A[6 * i:6 * i + 6, 6 * i:6 * i + 6] = sysm["Hpp"][i] + lam * np.eye(6)
+    for p in range(nP):
+        A[n + 3 * p:n + 3 * p + 3, n + 3 * p:n + 3 * p + 3] = sysm["Hll"][p] + lam * np.eye(3) if act[p] else np.eye(3)
+    A[:n, n:] = sysm["W"]
+    A[n:, :n] = sysm["W"].T
+    b = np.concatenate([sysm["bp"].reshape(-1), sysm["bl"].reshape(-1)])
+    try:
+        if not np.all(np.isfinite(A)) or not np.all(np.linalg.eigvalsh(A) > 0):
+            return None
+        x = np.linalg.solve(A, b)
+    except np.linalg.LinAlgError:
+        return None
+    xl = x[n:].reshape(nP, 3)
+    xl[~act] = 0
+    return x[:n], xl
+
+
+def apply_update(G, Q, T, X, xp, xl):
+    Q2, T2 = Q.copy(), T.copy()
+    for i in np.nonzero(G["slot"] >= 0)[0]:
+        s = G["slot"][i]
+        Q2[i], T2[i] = oplus(xp[6 * s:6 * s + 6], (Q[i], T[i]))
+    return Q2, T2, X + xl
+
+
+def lba_model(sc, variant, max_iterations=None, lambda_init=None, stop=False):
+    """LocalBundleAdjustment restated on the flat graph of a scene.  Returns a dict shaped like orbx.LocalBundleAdjustment's, plus
+    `decisions` (accept / reject per trial) and `log` (rho, gap = |chi - trial chi| relative, chi per trial)."""
+    max_iterations = sc.get("max_iterations", 10) if max_iterations is None else max_iterations
+    lambda_init = sc.get("lambda_init", 0.0) if lambda_init is None else lambda_init
+    kf, ed = sc["keyframes"], sc["edges"]
+    nL, nP, nE = sc["n_local"], len(sc["points"]), len(ed)
+    Q0, T0, X0 = kf["q"].astype(float), kf["t"].astype(float), sc["points"].astype(float)
+    res = dict(num_fixedKF=len(kf) - nL + int(kf["fixed"][:nL].any()), num_OptKF=nL, num_MPs=nP, num_edges=nE,
+               poses=np.concatenate([Q0[:nL], T0[:nL]], 1), points=X0.copy(), erase=np.zeros(nE, np.uint8), chi2=np.zeros(nE),
+               depth_positive=np.zeros(nE, np.uint8), iterations=0, trials=0, stop_reason=0, chi2_initial=0.0, chi2_final=0.0,
+               decisions=[], log=dict(rho=[], gap=[], chi=[]))
+    res["lambda"] = 0.0
+    if res["num_fixedKF"] == 0:
+        return dict(res, status=orbx.LBA_ABORTED)
+    if stop:
+        return dict(res, status=orbx.LBA_STOPPED)
+    if nE == 0:
+        return dict(res, status=orbx.LBA_EMPTY)
+    G = graph(sc)
+    Q = np.stack([normalize_rotation(q) for q in Q0])   # SE3Quat(q, t)
+    T, X = T0.copy(), X0.copy()
+    solve = solve_full if variant else solve_schur
+    sysm = build_system(G, Q, T, X, variant)
+    cur = sysm["chi"]
+    res["chi2_initial"] = cur
+    held = sysm["edge_chi"]
+    diag = [np.abs(np.einsum("kii->ki", sysm["Hpp"])).max() if G["nOpt"] else 0.0,
+            np.abs(np.einsum("kii->ki", sysm["Hll"])[G["active_pt"]]).max()]
+    lam = float(F32(lambda_init)) if lambda_init > 0 else 1e-5 * max(diag)
+    ni, nbad_r = 2.0, 0
+    xp, xl = np.zeros(6 * G["nOpt"]), np.zeros((nP, 3))
+    log = res["log"]
+    reason = STOP_ITERATIONS
+    iters = 0
+    for it in range(max_iterations):
+        ini = cur
+        qmax = 0
+        while True:
+            sol = solve(G, sysm, lam)
+            ok = sol is not None
+            if ok:
+                xp, xl = sol
+            Qt, Tt, Xt = apply_update(G, Q, T, X, xp, xl)
+            trial = build_system(G, Qt, Tt, Xt, variant)
+            held = trial["edge_chi"]
+            temp = trial["chi"] if ok else np.finfo(float).max
+            b_all = np.concatenate([sysm["bp"].reshape(-1), sysm["bl"].reshape(-1)])
+            x_all = np.concatenate([xp, xl.reshape(-1)])
+            rho = (cur - temp) / (x_all @ (lam * x_all + b_all) + 1e-3)
+            accept = bool(rho > 0 and np.isfinite(temp))
+            res["decisions"].append(accept)
+            log["rho"].append(float(rho))
+            log["gap"].append(abs(cur - temp) / max(abs(cur), abs(temp), 1e-300))
+            log["chi"].append(float(temp))
+            if accept:
+                alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
+                lam *= max(1.0 / 3.0, alpha)
+                ni, cur, Q, T, X, sysm = 2.0, temp, Qt, Tt, Xt, trial
+            else:
+                lam *= ni
+                ni *= 2
+            qmax += 1
+            if not (rho < 0 and qmax < 10):
+                break
+        iters += 1
+        if qmax == 10:
+            reason = STOP_QMAX
+            break
+        if rho == 0:
+            reason = STOP_RHO_ZERO
+            break
+        nbad_r = nbad_r + 1 if (ini - cur) * 1e3 < ini else 0
+        if nbad_r >= 3:
+            reason = STOP_SMALL_GAIN
+            break
+    _, _, Xc, _, _ = edge_terms(G, Q, T, X, jac=False)
+    pos = Xc[:, 2] > 0.0
+    gate = np.where(G["mono"], 5.991, 7.815)
+    poses = res["poses"].copy()
+    for i in range(nL):
+        if G["slot"][i] >= 0:
+            poses[i] = np.concatenate([Q[i], T[i]])
+    pts = np.where(G["active_pt"][:, None], X, X0)
+    return dict(res, status=orbx.LBA_DONE, poses=poses, points=pts, erase=((held > gate) | ~pos).astype(np.uint8), chi2=held,
+                depth_positive=pos.astype(np.uint8), iterations=iters, trials=len(res["decisions"]), stop_reason=reason,
+                chi2_final=cur, **{"lambda": lam})
+
+
+# ------------------------------------------------------------------------------------------------ scenes
+CAM = (F32(520.0), F32(518.0), F32(319.5), F32(241.25), F32(0.12 * 520.0))
+
+
+def inv_level_sigma2(nlevels=8, scale=1.2):
+    sf = [F32(1)]
+    for _ in range(1, nlevels):
+        sf.append(F32(sf[-1] * F32(scale)))
+    return np.array([F32(1) / (s * s) for s in sf], F32)
+
+
+TABLE = inv_level_sigma2()
+
+
+def rot_vec(w):
+    w = np.asarray(w, float)
+    th = np.linalg.norm(w)
+    if th == 0:
+        return np.eye(3)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / th
+    return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * K @ K
+
+
+def quat_of(R):
+    from test_pose_opt import quat_from_R
+    return normalize_rotation(quat_from_R(R))
+
+
+# name: key frames (local, fixed), points, share of stereo observations, share of gross outliers, pixel noise, and what is special
+SCENES = {
+    "mono_small": dict(nL=2, nF=1, nP=12, stereo=0.0, gross=0.0, noise=0.6),
+    "mixed_65": dict(nL=3, nF=2, nP=65, stereo=0.5, gross=0.0, noise=0.6),
+    "outliers_257": dict(nL=9, nF=4, nP=257, stereo=0.5, gross=0.10, noise=0.7),
+    "wide_22": dict(nL=22, nF=3, nP=130, stereo=0.4, gross=0.0, noise=0.6),
+    "init_local": dict(nL=4, nF=0, nP=40, stereo=0.5, gross=0.0, noise=0.6, init_local=1),           # num_fixedKF == 1
+    "edge_free_kf": dict(nL=4, nF=2, nP=40, stereo=0.5, gross=0.0, noise=0.6, edge_free=True),         # a local key frame without an edge
+    "special_points": dict(nL=3, nF=3, nP=30, stereo=0.3, gross=0.0, noise=0.5, special=True),         # fixed-only + one local; single stereo; behind
+    "lambda_100": dict(nL=3, nF=2, nP=40, stereo=0.5, gross=0.05, noise=0.6, lambda_init=100.0),
+    "rho_zero": dict(nL=3, nF=2, nP=30, stereo=0.5, gross=0.0, noise=0.6, lambda_init=1e38),           # last trial rejected (module docstring)
+    "three_iterations": dict(nL=4, nF=2, nP=50, stereo=0.5, gross=0.05, noise=0.6, max_iterations=3),
+    "far_start": dict(nL=4, nF=2, nP=60, stereo=0.3, gross=0.10, noise=0.7, start=(8.0, 0.5, 2.0)),       # a start that makes trials fail
+    # ten trials of (almost) the same undamped step, all rejected: the last trial is rejected and the held chi2 is not the result's
+    "rejected_last": dict(nL=4, nF=2, nP=60, stereo=0.3, gross=0.10, noise=0.7, start=(8.0, 0.5, 2.0), lambda_init=1e-30),
+    # no key frame to optimise (one local is the initial key frame, the other has no edge): the points move against fixed key frames
+    "points_only": dict(nL=2, nF=3, nP=30, stereo=0.5, gross=0.0, noise=0.6, init_local=0, edge_free=True),
+    "no_fixed": dict(nL=3, nF=0, nP=20, stereo=0.5, gross=0.0, noise=0.6),                             # aborts
+}
+# the number that seeds a scene (fixed, so that a new scene does not move the others)
+NUMBER = {"edge_free_kf": 0, "far_start": 1, "init_local": 2, "lambda_100": 3, "mixed_65": 4, "mono_small": 5, "no_fixed": 6, "noise_free": 7,
+          "outliers_257": 8, "rho_zero": 9, "special_points": 10, "three_iterations": 11, "wide_22": 12, "rejected_last": 13,
+          "points_only": 14}
+# not compared with the device: converges to rounding, where the variants' decisions part ways (module docstring)
+EXTRA = {"noise_free": dict(nL=3, nF=2, nP=40, stereo=0.5, gross=0.0, noise=0.0)}
+# scene -> seed: the first seed whose V1 and V2 take the same trial and stop decisions with a margin (test_v1_against_v2_spreads_and_cap
+# states the condition); see SEEDS_DISCARDED for how many were passed over
+# rho_zero, seed 0: renormalising exp(x) * q moves the last bit of key frame 2's unit quaternion (the rounding of its norm), so the
+# trial is an ulp away from the estimate and rho is rounding noise.  With seed 1 every q / |q| reproduces q; the device evaluates the
+# same expressions in the same order with correctly rounded sqrt and division (no contraction), so it reproduces them too.
+SEEDS = {"rho_zero": 1}
+SEEDS_DISCARDED = 1
+
+
+def project(Rm, t, X):
+    Xc = X @ Rm.T + t
+    return np.stack([float(CAM[0]) * Xc[:, 0] / Xc[:, 2] + float(CAM[2]), float(CAM[1]) * Xc[:, 1] / Xc[:, 2] + float(CAM[3])], 1), Xc[:, 2]
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name, seed=None):
+    """Key frames around the origin looking along +z at points 4 - 12 m away; every point is observed by 2 - 6 key frames in a
+    shuffled order (the caller's); observations carry pixel noise scaled by their level; a share is gross outliers (somewhere else
+    in the image).  The local key frames and the points start perturbed, the fixed key frames at the truth."""
+    p = SCENES[name] if name in SCENES else EXTRA[name]
+    nL, nF, nP = p["nL"], p["nF"], p["nP"]
+    nKF = nL + nF
+    rng = np.random.default_rng(9100 + 7 * NUMBER.get(name, 100 + zlib.crc32(name.encode()) % 1000) + 1000 * (SEEDS.get(name, 0) if seed is None else seed))
+    Rs = [rot_vec(rng.normal(size=3) * 0.04) for _ in range(nKF)]
+    Cs = np.stack([rng.uniform(-0.6, 0.6, nKF), rng.uniform(-0.3, 0.3, nKF), rng.uniform(-0.2, 0.8, nKF)], 1)   # camera centres
+    if p.get("special"):
+        Cs[0, 2], Cs[1, 2] = -0.2, 0.8                # the point behind key frame 1 lies between the two
+    ts = [-Rs[i] @ Cs[i] for i in range(nKF)]
+    uv = np.stack([rng.uniform(60, 580, nP), rng.uniform(60, 420, nP)], 1)
+    depth = rng.uniform(4, 12, nP)
+    Xw = np.stack([(uv[:, 0] - float(CAM[2])) / float(CAM[0]), (uv[:, 1] - float(CAM[3])) / float(CAM[1]), np.ones(nP)], 1) * depth[:, None]
+    usable = nL - 1 if p.get("edge_free") else nL     # the last local key frame stays without an edge
+    cand = list(range(usable)) + list(range(nL, nKF))
+    obs_of = []
+    for j in range(nP):
+        k = min(len(cand), int(rng.integers(*p.get("obs", (2, 7)))))
+        obs_of.append([cand[i] for i in rng.permutation(len(cand))[:k]])
+    stereo_pt = rng.uniform(size=nP) < p["stereo"]
+    if p.get("special"):
+        lo, hi = 0, 1
+        obs_of[0] = list(range(nL, nKF)) + [0]        # seen by every fixed key frame and one local
+        obs_of[1] = [1]                               # a single stereo observation
+        stereo_pt[1] = True
+        # behind key frame `hi`, in front of `lo`, close to both axes: erased by its depth alone
+        Xw[2] = np.array([0.5 * (Cs[lo, 0] + Cs[hi, 0]), 0.5 * (Cs[lo, 1] + Cs[hi, 1]), 0.5 * (Cs[lo, 2] + Cs[hi, 2])])
+        obs_of[2] = [lo, hi] + list(range(nL, nKF))
+        stereo_pt[2] = False
+    rows = []
+    for j in range(nP):
+        for i in obs_of[j]:
+            px, z = project(Rs[i], ts[i], Xw[j:j + 1])
+            lvl = int(rng.integers(0, len(TABLE)))
+            quiet = p.get("special") and j == 2
+            noise = rng.normal(size=3) * (0.0 if quiet else p["noise"] * 1.2 ** lvl)
+            u, v = px[0, 0] + noise[0], px[0, 1] + noise[1]
+            if rng.uniform() < p["gross"]:
+                u, v = rng.uniform(30, 610), rng.uniform(30, 450)
+            ur = (px[0, 0] - float(CAM[4]) / z[0] + noise[2]) if stereo_pt[j] and z[0] > 0 else -1.0
+            if ur < 0:
+                ur = -1.0                             # the right image does not see it: a monocular observation
+            rows.append((i, j, u, v, ur, TABLE[0 if quiet else lvl]))
+    edges = np.array(rows, orbx.LBA_EDGE_DTYPE) if rows else np.zeros(0, orbx.LBA_EDGE_DTYPE)
+    start = p.get("start", (0.3, 0.01, 0.02))         # degrees, metres (key frames), metres (points)
+    q0, t0 = [], []
+    for i in range(nKF):
+        if i < nL and p.get("init_local") != i:
+            dR = rot_vec(rng.normal(size=3) * math.radians(start[0]))
+            Ri, ti = dR @ Rs[i], dR @ ts[i] + rng.normal(size=3) * start[1]
+        else:
+            Ri, ti = Rs[i], ts[i]
+        q0.append(quat_of(Ri))
+        t0.append(ti)
+    fixed = np.array([int(i >= nL or p.get("init_local") == i) for i in range(nKF)])
+    kfs = orbx.lba_keyframes(np.array(q0), np.array(t0), CAM, fixed)
+    X0 = Xw + rng.normal(size=(nP, 3)) * start[2]
+    if p.get("special"):
+        X0[2] = Xw[2]
+    X0 = X0.astype(F32)
+    out = dict(name=name, keyframes=kfs, n_local=nL, points=X0, edges=edges, truth_R=Rs, truth_t=ts, truth_X=Xw, obs_of=obs_of)
+    for k in ("max_iterations", "lambda_init"):
+        if k in p:
+            out[k] = p[k]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def model(name, variant):
+    return lba_model(scene(name), variant)
+
+
+def rot_angle_q(qa, qb):
+    a, b = np.asarray(qa, float), np.asarray(qb, float)
+    a, b = a / np.linalg.norm(a), b / np.linalg.norm(b)
+    d = a[3] * b[:3] - b[3] * a[:3] - np.cross(a[:3], b[:3])
+    return 2.0 * math.atan2(np.linalg.norm(d), abs(a @ b))
+
+
+def pose_point_diff(a, b):
+    """Largest rotation angle, translation difference relative to max(1, |t|) and point difference relative to max(1, |X|)."""
+    dR = max([rot_angle_q(x[:4], y[:4]) for x, y in zip(a["poses"], b["poses"])], default=0.0)
+    dT = max([float(np.linalg.norm(x[4:] - y[4:])) / max(1.0, float(np.linalg.norm(x[4:]))) for x, y in zip(a["poses"], b["poses"])],
+             default=0.0)
+    n = np.maximum(1.0, np.linalg.norm(a["points"], axis=1))
+    dX = float((np.linalg.norm(a["points"] - b["points"], axis=1) / n).max()) if len(n) else 0.0
+    return dR, dT, dX
+
+
+def scene_class(name):
+    """Two classes of conditioning with a spread each: `init_local` fixes one key frame only, which leaves the scale of its
+    monocular part weakly observed; every other scene has key frames fixed at the truth."""
+    return "gauge" if SCENES[name].get("init_local") is not None and SCENES[name]["nF"] == 0 else "anchored"
+
+
+@functools.lru_cache(maxsize=None)
+def spreads(cls=None):
+    """The largest V1 / V2 difference over the scenes of a class (None: all): R (rad), t and X (relative), and over all scenes the
+    held chi2 relative to its gate (over the edges within 50 % of the gate) and the robust chi2 totals (relative)."""
+    dR = dT = dX = chi = tot = 0.0
+    for name in SCENES:
+        a, b = model(name, 0), model(name, 1)
+        if a["status"] != orbx.LBA_DONE:
+            continue
+        if cls is None or scene_class(name) == cls:
+            r, t, x = pose_point_diff(a, b)
+            dR, dT, dX = max(dR, r), max(dT, t), max(dX, x)
+        gate = np.where(scene(name)["edges"]["u_right"] < 0, 5.991, 7.815)
+        near = np.abs(a["chi2"] - gate) <= 0.5 * gate
+        if near.any():
+            chi = max(chi, float((np.abs(a["chi2"] - b["chi2"])[near] / gate[near]).max()))
+        for k in ("chi2_initial", "chi2_final"):
+            tot = max(tot, abs(a[k] - b[k]) / max(abs(a[k]), 1e-300))
+    return dict(R=dR, t=dT, X=dX, chi=chi, total=tot)
+
+
+def exempt(res, name, margin):
+    """The edges of a model result whose held chi2 lies within `margin` (relative) of its gate: [nE] bool."""
+    gate = np.where(scene(name)["edges"]["u_right"] < 0, 5.991, 7.815)
+    return np.abs(res["chi2"] - gate) <= margin * gate
