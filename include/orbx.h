@@ -1305,6 +1305,61 @@ typedef struct orbx_lba_result {
  * agree bit for bit. */
 int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params, orbx_lba_result* result);
 
+/* ---- full bundle adjustment (Optimizer::GlobalBundleAdjustemnt) -------------------------------------------- */
+
+/* Optimizer::BundleAdjustment (src/Optimizer.cc:47-372, behind GlobalBundleAdjustemnt: after the monocular initialisation,
+ * src/Tracking.cc:2526, 20 iterations, robust; and in the thread that finishes a loop closure or a map merge,
+ * src/LoopClosing.cc:2415, 10 iterations, not robust, mbStopGBA as its stop flag), one problem per call, on the device.  It is
+ * the g2o problem of the local bundle adjustment -- Levenberg on BlockSolver_6_3 with the same two edge classes -- and runs
+ * on the same kernel chain; see the section above for the arithmetic.  What differs:
+ *  - the problem: orbx_lba_problem as it is.  Key frames in vpKFs order, fixed != 0 for the map's initial key frame, n_fixed may be
+ *    0 (any key frame behind the first n_local must be fixed); points in vpMP order; edges grouped by ascending point.  poses
+ *    comes back for all n_local + n_fixed key frames.
+ *  - robust == 0: no robust kernel -- g2o then weighs with the information matrix alone (rho' = 1) and the chi2 is the plain
+ *    sum; robust != 0: Huber with (float)sqrt(5.99) for monocular and (float)sqrt(7.815) for stereo edges (:129 writes 5.99,
+ *    not the 5.991 of the local BA).
+ *  - nothing aborts when no key frame is fixed (:116-127 has no such test): the damping carries the gauge, and a failed pivot
+ *    is a rejected trial like any other.
+ *  - no outlier classification and no erase flags (what :307-350 counts is read by nothing).
+ *  - the linear solve.  A global map has hundreds of key frames: above the ORBX_LBA_MAX_LOCAL of the one-workgroup solver the
+ *    reduced system is factored by a blocked LDLT spread over the chip (csrc/orbx_ba.hip), up to ORBX_BA_MAX_KF optimised key
+ *    frames (6144 rows, 302 MB); beyond that a sparse method is the right tool.  solver: 0 chooses (the blocked one from
+ *    ORBX_BA_BLOCKED_FROM_KF optimised key frames on), 1 forces the blocked solver, 2 forces the one-workgroup solver
+ *    (ORBX_E_BADARG above ORBX_LBA_MAX_LOCAL).  Both are the same factorisation; their results differ by rounding.
+ *  - stop_flag (pbStopFlag, may be NULL) is read by the host when the call starts, in front of the first trial and after every
+ *    trial's status word -- where g2o asks terminate().  Set at the start: the widened inputs, ORBX_LBA_STOPPED, no device is
+ *    touched.  Seen later: no further trial is enqueued and the result is the last accepted estimate, ORBX_LBA_STOPPED.
+ * A key frame or point without an edge comes back as the widened input; a problem without an edge is ORBX_LBA_EMPTY.  status and
+ * stop_reason take the ORBX_LBA_* values.  Deliberate difference: the reference writes back the estimate's quaternion after
+ * Sophus renormalises the float cast; the library returns the double estimate and leaves the cast to the caller.
+ * KannalaBrandt8 key frames and second cameras are rejected as in the local BA; the inertial and map-merge variants are not built. */
+#define ORBX_BA_MAX_KF 1024
+/* solver == 0: fewer optimised key frames take the one-workgroup solver.  Measured on the MI355X (profiles/gba_bench.json, ms per
+ * call of 5 trials, blocked against one workgroup): 3.05 / 2.77 at 47 optimised key frames, 4.06 / 4.58 at 63, 8.17 / 20.99 at 127. */
+#define ORBX_BA_BLOCKED_FROM_KF 63
+typedef struct orbx_ba_params {
+  int32_t max_iterations;            /* 1 .. 1000000 */
+  int32_t robust;                    /* != 0: Huber kernels */
+  float lambda_init;                 /* > 0: setUserLambdaInit; otherwise computed */
+  int32_t solver;                    /* 0 automatic, 1 blocked, 2 one workgroup */
+  const volatile int32_t* stop_flag; /* may be NULL */
+} orbx_ba_params;
+typedef struct orbx_ba_result {
+  double* poses;            /* out [n_local + n_fixed][7]: q (x y z w), t */
+  double* points;           /* out [n_points][3] */
+  double* chi2;             /* out [n_edges], may be NULL: the chi2 the edge holds after the last trial */
+  int32_t status;           /* ORBX_LBA_DONE / ORBX_LBA_STOPPED / ORBX_LBA_EMPTY */
+  int32_t iterations, trials, stop_reason;
+  double lambda;
+  double chi2_initial, chi2_final;
+} orbx_ba_result;
+/* Every check of orbx_local_bundle_adjustment, then at most ORBX_BA_MAX_KF key frames to optimise and a valid solver, all
+ * before a device is touched.  Two calls on the same input agree bit for bit. */
+int orbx_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_ba_params* params, orbx_ba_result* result);
+/* The blocked solver alone, for tests and measurements: A x = b for a symmetric positive definite row-major A [n][n] in double,
+ * 1 <= n <= 6 * ORBX_BA_MAX_KF (only the lower triangle is read).  *ok = 0 when a pivot is <= 0 or not finite; x is then untouched. */
+int orbx_ba_dense_solve(int device, int n, const double* A, const double* b, double* x, int32_t* ok);
+
 /* ---- new map points (local mapping)------------------------------------------------------------------- */
 
 /* The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), which consumes the match list of

@@ -1271,6 +1271,61 @@ def LocalBundleAdjustment(keyframes, n_local, points, edges, max_iterations=10, 
     return out
 
 
+# ---- full bundle adjustment (Optimizer::GlobalBundleAdjustemnt)
+BA_MAX_KF = 1024
+BA_BLOCKED_FROM_KF = 63
+BA_SOLVER_AUTO, BA_SOLVER_BLOCKED, BA_SOLVER_ONE_WORKGROUP = 0, 1, 2
+
+
+class _BaParams(C.Structure):      # orbx_ba_params
+    _fields_ = [("max_iterations", C.c_int32), ("robust", C.c_int32), ("lambda_init", C.c_float), ("solver", C.c_int32),
+                ("stop_flag", C.c_void_p)]
+
+
+class _BaResult(C.Structure):      # orbx_ba_result
+    _fields_ = [("poses", C.c_void_p), ("points", C.c_void_p), ("chi2", C.c_void_p), ("status", C.c_int32), ("iterations", C.c_int32),
+                ("trials", C.c_int32), ("stop_reason", C.c_int32), ("lambda_", C.c_double), ("chi2_initial", C.c_double),
+                ("chi2_final", C.c_double)]
+
+
+def BundleAdjustment(keyframes, points, edges, max_iterations=5, robust=True, lambda_init=0.0, stop=None, solver=0, device=0):
+    """Optimizer::BundleAdjustment (src/Optimizer.cc:47-372, behind GlobalBundleAdjustemnt) on the GPU (orbx_bundle_adjustment):
+    keyframes = LBA_KEYFRAME_DTYPE records in vpKFs order (fixed != 0: the map's initial key frame), points [nP][3] float in vpMP
+    order, edges = LBA_EDGE_DTYPE records grouped by ascending point.  robust: Huber kernels with the deltas of :129.  stop: None, or
+    a one-element int32 numpy array the caller may set from another thread while the call runs (pbStopFlag).  solver: BA_SOLVER_*.
+    Returns a dict: poses [nKF][7] double (q x y z w, t), points [nP][3] double, chi2 [nE] double, status (LBA_DONE / LBA_STOPPED /
+    LBA_EMPTY), iterations, trials, stop_reason, lambda, chi2_initial, chi2_final."""
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ed = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    if stop is not None and not (isinstance(stop, np.ndarray) and stop.dtype == np.int32 and stop.size == 1):
+        raise TypeError("stop must be None or a one-element int32 numpy array")
+    # the fixed key frames need not come last in vpKFs: every key frame counts as local, the fixed flag says which stay
+    poses, pts, chi2 = np.zeros((len(kf), 7)), np.zeros((len(X), 3)), np.zeros(len(ed))
+    prob = _LbaProblem(_p(kf).value, _p(X).value, _p(ed).value, len(kf), 0, len(X), len(ed))
+    prm = _BaParams(int(max_iterations), int(bool(robust)), float(lambda_init), int(solver), None if stop is None else _p(stop).value)
+    res = _BaResult(_p(poses).value, _p(pts).value, _p(chi2).value)
+    _check(lib().orbx_bundle_adjustment(int(device), C.byref(prob), C.byref(prm), C.byref(res)))
+    out = dict(poses=poses, points=pts, chi2=chi2)
+    for name in ("status", "iterations", "trials", "stop_reason", "chi2_initial", "chi2_final"):
+        out[name] = getattr(res, name)
+    out["lambda"] = res.lambda_
+    return out
+
+
+def ba_dense_solve(A, b, device=0):
+    """The blocked LDLT of the full bundle adjustment alone (orbx_ba_dense_solve): A [n][n] symmetric positive definite, b [n], in
+    double.  Returns dict(x [n], ok); ok == 0: a pivot was <= 0 or not finite and x is the zeros it was created with."""
+    A = np.ascontiguousarray(A, np.float64)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1)
+    if A.ndim != 2 or A.shape != (len(b), len(b)):
+        raise ValueError("A must be [n][n] and b [n]")
+    x = np.zeros(len(b))
+    ok = C.c_int32(-1)
+    _check(lib().orbx_ba_dense_solve(int(device), len(b), _p(A), _p(b), _p(x), C.byref(ok)))
+    return dict(x=x, ok=ok.value)
+
+
 class _NpCamera(C.Structure):      # orbx_np_camera
     _fields_ = [("model", C.c_int32), ("p", C.c_float * 8), ("kb8_precision", C.c_float), ("Tcw", C.c_float * 12),
                 ("Ow", C.c_float * 3)]

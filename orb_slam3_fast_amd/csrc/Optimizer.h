@@ -8,6 +8,9 @@
 // Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*, int&, int&, int&, int&) (src/Optimizer.cc:1109-1516) on
 // orbx_local_bundle_adjustment, over a LocalMapView: the three walks of :1116-1180 (local key frames, local map points, fixed key
 // frames) and the edge listing of :1288-1426 are plain host code here (GatherLocalGraph), the optimisation is the library's.
+// Optimizer::GlobalBundleAdjustemnt(Map*, int, bool*, unsigned long, bool) (src/Optimizer.cc:47-372) on orbx_bundle_adjustment, over a
+// GlobalMapView: the vertex and edge listing of :116-278 is GatherGlobalGraph, so that the call sites (src/Tracking.cc:2526,
+// src/LoopClosing.cc:2415) read as in the reference.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
 #include <stdexcept>
@@ -206,6 +209,98 @@ inline LbaGraph GatherLocalGraph(const LocalMapView& m) {
   return g;
 }
 
+// ---- full bundle adjustment
+struct GlobalMapView {
+  std::vector<LbaKeyFrame> keyFrames;       // every key frame an observation may name
+  std::vector<LbaMapPoint> mapPoints;       // vpMP = pMap->GetAllMapPoints()
+  std::vector<int> vpKFs;                   // pMap->GetAllKeyFrames(), as indices into keyFrames
+  unsigned long initKFid = 0;               // pMap->GetInitKFid()
+  unsigned long originKFid = 0;             // pMap->GetOriginKF()->mnId
+  int device = 0;
+};
+// The graph of :116-278: the key-frame vertices (the non-bad key frames of vpKFs, in order), the map points that stay in the
+// optimiser, and the records of orbx_lba_problem.
+struct GbaGraph {
+  std::vector<int> kfs, mps;                // indices into the view
+  std::vector<char> notIncluded;            // vbNotIncludedMP, per map point of the view
+  unsigned long maxKFid = 0;
+  std::vector<orbx_lba_keyframe> records;
+  std::vector<float> points;
+  std::vector<orbx_lba_edge> edges;
+  std::vector<std::pair<int, int>> edgePair;   // per edge: (key frame, map point) of the view
+};
+// What the caller applies, per key frame and per map point: applyDirectly (nLoopKF == the origin key frame's id): SetPose /
+// SetWorldPos + UpdateNormalAndDepth; otherwise mTcwGBA / mPosGBA and mnBAGlobalForKF = nLoopKF.
+struct GbaUpdate {
+  std::vector<int> keyFrames;               // the vertices
+  std::vector<float> poses;                 // [7] each: q (x y z w), t -- the float casts of :296
+  std::vector<int> mapPoints;               // the points of :355-371 (neither bad nor vbNotIncludedMP)
+  std::vector<float> positions;             // [3] each: the float cast of :365
+  std::vector<char> notIncluded;            // vbNotIncludedMP
+  bool applyDirectly = false;
+  bool optimized = false;                   // false: nothing to optimise -- nothing to apply
+  orbx_ba_result result{};
+};
+
+// :295 / :364: the update goes straight into the map when the call belongs to the map's origin key frame
+inline bool GbaApplyDirectly(const GlobalMapView& m, unsigned long nLoopKF) { return nLoopKF == m.originKFid; }
+
+// :116-278.  maxKFid runs over the non-bad key frames of vpKFs; an observation is skipped when its key frame is bad, has an mnId
+// above maxKFid or is no vertex; nEdges counts every observation that passes, even one that yields no edge (a right-camera-only
+// observation without a second camera), and nEdges == 0 takes the point out (vbNotIncludedMP).  There is no map filter.
+inline GbaGraph GatherGlobalGraph(const GlobalMapView& m) {
+  GbaGraph g;
+  const int nKF = (int)m.keyFrames.size(), nMP = (int)m.mapPoints.size();
+  std::vector<int> vertex((size_t)nKF, -1);
+  for (int i : m.vpKFs) {
+    const LbaKeyFrame& k = m.keyFrames.at((size_t)i);
+    if (k.bad || vertex[(size_t)i] >= 0) continue;   // (a key frame listed twice is one vertex: g2o refuses the second id)
+    orbx_lba_keyframe r{};
+    for (int c = 0; c < 4; c++) r.q[c] = k.q[c];
+    for (int c = 0; c < 3; c++) r.t[c] = k.t[c];
+    r.fx = k.fx; r.fy = k.fy; r.cx = k.cx; r.cy = k.cy; r.bf = k.mbf;
+    r.model = k.cameraModel;
+    r.fixed = k.mnId == m.initKFid ? 1 : 0;
+    r.camera2 = k.hasCamera2 ? 1 : 0;
+    vertex[(size_t)i] = (int)g.kfs.size();
+    g.kfs.push_back(i);
+    g.records.push_back(r);
+    if (k.mnId > g.maxKFid) g.maxKFid = k.mnId;
+  }
+  g.notIncluded.assign((size_t)nMP, 0);
+  for (int j = 0; j < nMP; j++) {
+    const LbaMapPoint& p = m.mapPoints[(size_t)j];
+    if (p.bad) continue;
+    const size_t firstEdge = g.edges.size();
+    int nEdges = 0;
+    for (const std::pair<int, int>& ob : p.observations) {
+      const LbaKeyFrame& k = m.keyFrames.at((size_t)ob.first);
+      if (k.bad || k.mnId > g.maxKFid || vertex[(size_t)ob.first] < 0) continue;
+      nEdges++;
+      if (ob.second == -1) continue;
+      const orbx_keypoint& kp = k.mvKeysUn.at((size_t)ob.second);
+      orbx_lba_edge e{};
+      e.kf = vertex[(size_t)ob.first];
+      e.point = (int)g.mps.size();
+      e.u = kp.x;
+      e.v = kp.y;
+      e.u_right = k.mvuRight.at((size_t)ob.second) < 0 ? -1.f : k.mvuRight[(size_t)ob.second];
+      e.inv_sigma2 = k.mvInvLevelSigma2.at((size_t)kp.octave);
+      g.edges.push_back(e);
+      g.edgePair.push_back({ob.first, j});
+    }
+    if (nEdges == 0) {
+      g.notIncluded[(size_t)j] = 1;
+      g.edges.resize(firstEdge);
+      g.edgePair.resize(firstEdge);
+      continue;
+    }
+    g.mps.push_back(j);
+    g.points.insert(g.points.end(), p.pos, p.pos + 3);
+  }
+  return g;
+}
+
 class Optimizer {
  public:
   // Gathers the local graph, honours the zero-fixed abort (:1182, the counters behind num_fixedKF stay as they were) and the stop
@@ -253,6 +348,51 @@ class Optimizer {
       for (size_t i = 0; i < g.edges.size(); i++)
         if (erase[i] && (g.edges[i].u_right < 0) == (pass == 0)) u.vToErase.push_back(g.edgePair[i]);
     return u;
+  }
+
+  // Gathers the graph, optimises on the device and returns what the caller applies.  stopFlag is asked by the library while the
+  // call runs (include/orbx.h): it reads an int32_t, so GlobalBundleAdjustemnt with the reference's bool* can only ask its flag when
+  // the call starts.  solver: orbx_ba_params::solver.  Throws on a library error.
+  static GbaUpdate GlobalBundleAdjustemntWithFlag(const GlobalMapView& map, int nIterations, const volatile int32_t* stopFlag,
+                                                  const unsigned long nLoopKF, const bool bRobust, int solver = 0) {
+    const GbaGraph g = GatherGlobalGraph(map);
+    GbaUpdate u;
+    u.notIncluded = g.notIncluded;
+    u.applyDirectly = GbaApplyDirectly(map, nLoopKF);
+    orbx_lba_problem prob{};
+    prob.keyframes = g.records.data();
+    prob.points = g.points.data();
+    prob.edges = g.edges.data();
+    prob.n_local = (int)g.kfs.size();
+    prob.n_points = (int)g.mps.size();
+    prob.n_edges = (int)g.edges.size();
+    orbx_ba_params prm{};
+    prm.max_iterations = nIterations;
+    prm.robust = bRobust ? 1 : 0;
+    prm.solver = solver;
+    prm.stop_flag = stopFlag;
+    std::vector<double> poses(7 * g.kfs.size()), points(3 * g.mps.size());
+    u.result.poses = poses.data();
+    u.result.points = points.data();
+    if (orbx_bundle_adjustment(map.device, &prob, &prm, &u.result) != ORBX_OK)
+      throw std::runtime_error(std::string("GlobalBundleAdjustemnt: ") + orbx_last_error());
+    u.result.poses = u.result.points = nullptr;   // the buffers end with this call
+    if (u.result.status == ORBX_LBA_EMPTY) return u;
+    u.optimized = true;                            // a stopped optimisation is written back too, as the reference does
+    u.keyFrames = g.kfs;
+    u.mapPoints = g.mps;
+    for (double v : poses) u.poses.push_back((float)v);
+    for (double v : points) u.positions.push_back((float)v);
+    return u;
+  }
+  // The reference's signature.  NOTE: *pbStopFlag is read ONCE, when the call starts: set by then, the inputs come back unchanged;
+  // set later, it is NOT seen and the optimisation runs its nIterations -- unlike the reference, where mbStopGBA ends a running
+  // GlobalBundleAdjustemnt between trials.  A call site that needs that (src/LoopClosing.cc:2415) keeps an int32_t flag and
+  // calls GlobalBundleAdjustemntWithFlag.
+  static GbaUpdate GlobalBundleAdjustemnt(const GlobalMapView& map, int nIterations = 5, const bool* pbStopFlag = nullptr,
+                                          const unsigned long nLoopKF = 0, const bool bRobust = true) {
+    const int32_t stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+    return GlobalBundleAdjustemntWithFlag(map, nIterations, &stop, nLoopKF, bRobust, 0);
   }
 
   // Returns nIn and updates vpMatches1 and g2oS12 like the reference.  mAcumHessian is set to zero, which is all the reference

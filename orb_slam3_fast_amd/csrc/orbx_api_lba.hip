@@ -10,9 +10,9 @@ static_assert(sizeof(orbx_lba_keyframe) == 60, "orbx_lba_keyframe");
 static_assert(sizeof(orbx_lba_edge) == 24, "orbx_lba_edge");
 static_assert(sizeof(orbx_lba_params) == 12, "orbx_lba_params");
 
-namespace {
+using namespace orbx;
 
-constexpr int kLbaMaxIterations = 1000000;
+namespace {
 
 const char* lba_keyframe_error(const orbx_lba_keyframe& k, bool secondGroup) {
   if (k.model == ORBX_CAMERA_KB8)
@@ -48,64 +48,55 @@ const char* lba_edges_error(const orbx_lba_problem& p, int nKF, std::vector<int>
   return nullptr;
 }
 
+}  // namespace
+
+namespace orbx {
+
+const char* lba_graph_error(const orbx_lba_problem& p, int maxIterations, float lambdaInit, LbaLayout& g) {
+  if (maxIterations < 1 || maxIterations > kLbaMaxIterations) return "max_iterations outside [1, 1000000]";
+  if (!std::isfinite(lambdaInit)) return "lambda_init not finite";
+  const int nKF = p.n_local + p.n_fixed;
+  g.fixedLocal = 0;
+  for (int i = 0; i < nKF; i++) {
+    if (const char* err = lba_keyframe_error(p.keyframes[i], i >= p.n_local)) return err;
+    if (i < p.n_local && p.keyframes[i].fixed) g.fixedLocal = 1;
+  }
+  for (int i = 0; i < p.n_points; i++)
+    if (!finite_all(p.points + 3 * (size_t)i, 3)) return "world position not finite";
+  if (const char* err = lba_edges_error(p, nKF, g.ptStart)) return err;
+  // the reduced system's row blocks: the local key frames that are not fixed and have an edge, in list order
+  g.slot.assign((size_t)nKF, -1);
+  g.deg.assign((size_t)nKF, 0);
+  for (int i = 0; i < p.n_edges; i++) g.deg[p.edges[i].kf]++;
+  g.nOpt = 0;
+  for (int i = 0; i < p.n_local; i++)
+    if (!p.keyframes[i].fixed && g.deg[i] > 0) g.slot[i] = g.nOpt++;
+  return nullptr;
+}
+
 // the call ends before the optimiser: the outputs are the widened inputs
-void lba_passthrough(const orbx_lba_problem& p, orbx_lba_result& r, int status) {
-  for (int i = 0; i < p.n_local; i++) {
+void lba_passthrough(const orbx_lba_problem& p, int nPoses, LbaRun& r) {
+  for (int i = 0; i < nPoses; i++) {
     for (int k = 0; k < 4; k++) r.poses[7 * (size_t)i + k] = (double)p.keyframes[i].q[k];
     for (int k = 0; k < 3; k++) r.poses[7 * (size_t)i + 4 + k] = (double)p.keyframes[i].t[k];
   }
   for (size_t k = 0; k < 3 * (size_t)p.n_points; k++) r.points[k] = (double)p.points[k];
   for (int i = 0; i < p.n_edges; i++) {
-    r.erase[i] = 0;
-    r.chi2[i] = 0;
-    r.depth_positive[i] = 0;
+    if (r.erase) r.erase[i] = 0;
+    if (r.chi2) r.chi2[i] = 0;
+    if (r.depthPos) r.depthPos[i] = 0;
   }
-  r.status = status;
-  r.iterations = r.trials = r.stop_reason = 0;
-  r.lambda = r.chi2_initial = r.chi2_final = 0;
+  r.stopped = 0;
+  r.iterations = r.trials = r.stopReason = 0;
+  r.lambda = r.chiInitial = r.chiFinal = 0;
 }
 
-}  // namespace
-
-extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params,
-                                            orbx_lba_result* result) {
-  if (!problem || !params || !result) return fail(ORBX_E_BADARG, "null argument or negative count");
-  const orbx_lba_problem& p = *problem;
-  orbx_lba_result& r = *result;
-  if (p.n_local < 0 || p.n_fixed < 0 || p.n_points < 0 || p.n_edges < 0 || (long long)p.n_local + p.n_fixed > INT_MAX ||
-      ((p.n_local || p.n_fixed) && !p.keyframes) || (p.n_points && !p.points) || (p.n_edges && !p.edges) ||
-      (p.n_local && !r.poses) || (p.n_points && !r.points) || (p.n_edges && (!r.erase || !r.chi2 || !r.depth_positive)))
-    return fail(ORBX_E_BADARG, "null argument or negative count");
-  if (params->max_iterations < 1 || params->max_iterations > kLbaMaxIterations)
-    return fail(ORBX_E_BADARG, "max_iterations outside [1, 1000000]");
-  if (!std::isfinite(params->lambda_init)) return fail(ORBX_E_BADARG, "lambda_init not finite");
-  const int nKF = p.n_local + p.n_fixed;
-  int fixedLocal = 0;
-  for (int i = 0; i < nKF; i++) {
-    if (const char* err = lba_keyframe_error(p.keyframes[i], i >= p.n_local)) return fail(ORBX_E_BADARG, err);
-    if (i < p.n_local && p.keyframes[i].fixed) fixedLocal = 1;
-  }
-  for (int i = 0; i < p.n_points; i++)
-    if (!finite_all(p.points + 3 * (size_t)i, 3)) return fail(ORBX_E_BADARG, "world position not finite");
-  std::vector<int> ptStart;
-  if (const char* err = lba_edges_error(p, nKF, ptStart)) return fail(ORBX_E_BADARG, err);
-  // the reduced system's row blocks: the local key frames that are not fixed and have an edge, in list order
-  std::vector<int> slot((size_t)nKF, -1), deg((size_t)nKF, 0);
-  for (int i = 0; i < p.n_edges; i++) deg[p.edges[i].kf]++;
-  int nOpt = 0;
-  for (int i = 0; i < p.n_local; i++)
-    if (!p.keyframes[i].fixed && deg[i] > 0) slot[i] = nOpt++;
-  if (nOpt > ORBX_LBA_MAX_LOCAL) return fail(ORBX_E_BADARG, "more than ORBX_LBA_MAX_LOCAL key frames to optimise");
-  r.num_fixedKF = p.n_fixed + fixedLocal;
-  r.num_OptKF = p.n_local;
-  r.num_MPs = p.n_points;
-  r.num_edges = p.n_edges;
-  if (r.num_fixedKF == 0) { lba_passthrough(p, r, ORBX_LBA_ABORTED); return ORBX_OK; }
-  if (params->stop) { lba_passthrough(p, r, ORBX_LBA_STOPPED); return ORBX_OK; }
-  if (p.n_edges == 0) { lba_passthrough(p, r, ORBX_LBA_EMPTY); return ORBX_OK; }
+int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, const LbaConfig& cfg, LbaRun& r) {
+  const int nKF = p.n_local + p.n_fixed, nOpt = g.nOpt;
+  const std::vector<int>& slot = g.slot;
   std::vector<int> kfStart((size_t)nOpt + 1, 0), kfEdges;
   for (int i = 0; i < nKF; i++)
-    if (slot[i] >= 0) kfStart[(size_t)slot[i] + 1] = deg[i];
+    if (slot[i] >= 0) kfStart[(size_t)slot[i] + 1] = g.deg[i];
   for (int s = 0; s < nOpt; s++) kfStart[(size_t)s + 1] += kfStart[s];
   kfEdges.resize((size_t)kfStart[nOpt]);
   {
@@ -120,15 +111,19 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
 
   const size_t nE = (size_t)p.n_edges, nP = (size_t)p.n_points, n = 6 * (size_t)nOpt;
   LbaArgs a{};
-  a.nKF = nKF; a.nLocal = p.n_local; a.nP = p.n_points; a.nE = p.n_edges; a.nOpt = nOpt; a.n = (int)n;
-  a.maxIter = params->max_iterations;
-  a.lambdaInit = (double)params->lambda_init;
+  a.nKF = nKF; a.nLocal = cfg.nPoses; a.nP = p.n_points; a.nE = p.n_edges; a.nOpt = nOpt; a.n = (int)n;
+  a.maxIter = cfg.maxIterations;
+  a.lambdaInit = (double)cfg.lambdaInit;
+  a.robust = cfg.robust;
+  a.blocked = cfg.blocked;
+  a.deltaMono = (double)cfg.deltaMono;
+  a.deltaStereo = (double)cfg.deltaStereo;
   Pack pk;
   pk.in(a.kfs, p.keyframes, (size_t)nKF, 16);
   pk.in(a.edges, p.edges, nE, 16);
   pk.in(a.points, p.points, 3 * nP, 16);
   pk.in(a.slot, slot.data(), (size_t)nKF, 16);
-  pk.in(a.ptStart, ptStart.data(), nP + 1, 16);
+  pk.in(a.ptStart, g.ptStart.data(), nP + 1, 16);
   pk.in(a.kfStart, kfStart.data(), (size_t)nOpt + 1, 16);
   pk.in(a.kfEdges, kfEdges.data(), kfEdges.size(), 16);
   for (int c = 0; c < 2; c++) {
@@ -152,7 +147,7 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
   const size_t oStatus = pk.area(a.status, 1, 16);
   const size_t oScal = pk.area(a.outScalars, 3, 16);
   const size_t oCnt = pk.area(a.outCounters, 3, 16);
-  const size_t oPose = pk.area(a.outPose, 7 * (size_t)p.n_local, 16);
+  const size_t oPose = pk.area(a.outPose, 7 * (size_t)cfg.nPoses, 16);
   const size_t oPts = pk.area(a.outPts, 3 * nP, 16);
   const size_t oChi = pk.area(a.chi2, nE, 16);
   const size_t oErase = pk.area(a.erase, nE, 16);
@@ -164,7 +159,8 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   HIPC(launch_lba_init(a));
   HIPC(launch_lba_evaluate(a));   // solve(0): the system at the start, lambda
-  for (long long trial = 0; trial < 10LL * params->max_iterations; trial++) {   // (the device stops earlier; the bound is g2o's own)
+  r.stopped = cfg.stopFlag && *cfg.stopFlag ? 1 : 0;   // g2o's terminate() in front of the first trial
+  for (long long trial = 0; !r.stopped && trial < 10LL * cfg.maxIterations; trial++) {   // (the device stops earlier; the bound is g2o's own)
     HIPC(launch_lba_trial(a));
     HIPC(launch_lba_evaluate(a));
     const uint8_t* h = pk.fetch(oStatus, sizeof(int), &e);
@@ -172,6 +168,7 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
     int running;
     std::memcpy(&running, h, sizeof running);
     if (!running) break;
+    if (cfg.stopFlag && *cfg.stopFlag) r.stopped = 1;   // ... and after every trial: the estimate is the last accepted one
   }
   HIPC(launch_lba_finish(a));
   const uint8_t* h = pk.fetch(oStatus, outEnd - oStatus, &e);
@@ -180,13 +177,53 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
   int cnt[3];
   std::memcpy(scal, h + (oScal - oStatus), sizeof scal);
   std::memcpy(cnt, h + (oCnt - oStatus), sizeof cnt);
-  r.status = ORBX_LBA_DONE;
-  r.lambda = scal[0]; r.chi2_initial = scal[1]; r.chi2_final = scal[2];
-  r.iterations = cnt[0]; r.trials = cnt[1]; r.stop_reason = cnt[2];
-  if (p.n_local) std::memcpy(r.poses, h + (oPose - oStatus), 7 * (size_t)p.n_local * sizeof(double));
+  r.lambda = scal[0]; r.chiInitial = scal[1]; r.chiFinal = scal[2];
+  r.iterations = cnt[0]; r.trials = cnt[1]; r.stopReason = cnt[2];
+  if (cfg.nPoses) std::memcpy(r.poses, h + (oPose - oStatus), 7 * (size_t)cfg.nPoses * sizeof(double));
   std::memcpy(r.points, h + (oPts - oStatus), 3 * nP * sizeof(double));
-  std::memcpy(r.chi2, h + (oChi - oStatus), nE * sizeof(double));
-  std::memcpy(r.erase, h + (oErase - oStatus), nE);
-  std::memcpy(r.depth_positive, h + (oDepth - oStatus), nE);
+  if (r.chi2) std::memcpy(r.chi2, h + (oChi - oStatus), nE * sizeof(double));
+  if (r.erase) std::memcpy(r.erase, h + (oErase - oStatus), nE);
+  if (r.depthPos) std::memcpy(r.depthPos, h + (oDepth - oStatus), nE);
   return ORBX_OK;
+}
+
+}  // namespace orbx
+
+extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params,
+                                            orbx_lba_result* result) {
+  if (!problem || !params || !result) return fail(ORBX_E_BADARG, "null argument or negative count");
+  const orbx_lba_problem& p = *problem;
+  orbx_lba_result& r = *result;
+  if (p.n_local < 0 || p.n_fixed < 0 || p.n_points < 0 || p.n_edges < 0 || (long long)p.n_local + p.n_fixed > INT_MAX ||
+      ((p.n_local || p.n_fixed) && !p.keyframes) || (p.n_points && !p.points) || (p.n_edges && !p.edges) ||
+      (p.n_local && !r.poses) || (p.n_points && !r.points) || (p.n_edges && (!r.erase || !r.chi2 || !r.depth_positive)))
+    return fail(ORBX_E_BADARG, "null argument or negative count");
+  LbaLayout g;
+  if (const char* err = lba_graph_error(p, params->max_iterations, params->lambda_init, g)) return fail(ORBX_E_BADARG, err);
+  if (g.nOpt > ORBX_LBA_MAX_LOCAL) return fail(ORBX_E_BADARG, "more than ORBX_LBA_MAX_LOCAL key frames to optimise");
+  r.num_fixedKF = p.n_fixed + g.fixedLocal;
+  r.num_OptKF = p.n_local;
+  r.num_MPs = p.n_points;
+  r.num_edges = p.n_edges;
+  LbaRun run{};
+  run.poses = r.poses; run.points = r.points; run.chi2 = r.chi2; run.erase = r.erase; run.depthPos = r.depth_positive;
+  const int early = r.num_fixedKF == 0 ? ORBX_LBA_ABORTED : params->stop ? ORBX_LBA_STOPPED : p.n_edges == 0 ? ORBX_LBA_EMPTY : -1;
+  int rc = ORBX_OK;
+  if (early >= 0) {
+    lba_passthrough(p, p.n_local, run);
+  } else {
+    LbaConfig cfg{};
+    cfg.maxIterations = params->max_iterations;
+    cfg.lambdaInit = params->lambda_init;
+    cfg.robust = 1;
+    cfg.deltaMono = sqrt(5.991);     // narrowed as the reference's (Optimizer.cc:1281-1282)
+    cfg.deltaStereo = sqrt(7.815);
+    cfg.nPoses = p.n_local;
+    rc = lba_optimise(device, p, g, cfg, run);
+    if (rc != ORBX_OK) return rc;
+  }
+  r.status = early >= 0 ? early : ORBX_LBA_DONE;
+  r.lambda = run.lambda; r.chi2_initial = run.chiInitial; r.chi2_final = run.chiFinal;
+  r.iterations = run.iterations; r.trials = run.trials; r.stop_reason = run.stopReason;
+  return rc;
 }

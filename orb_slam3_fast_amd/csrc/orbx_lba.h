@@ -4,6 +4,8 @@
 #define ORBX_LBA_H
 #include "orbx_host.h"
 
+#include <vector>
+
 namespace orbx {
 
 constexpr int kLbaApp = 27;   // per edge: the key frame's 6 x 6 block (upper triangle, 21) and its share of b (6)
@@ -53,7 +55,48 @@ struct LbaArgs {
   int* outCounters;               // iterations, trials, stop_reason
   int nKF, nLocal, nP, nE, nOpt, n, maxIter;
   double lambdaInit;
+  // what the local and the full bundle adjustment differ by
+  int robust;                     // 0: no robust kernel (rho' = 1, the chi2 is the plain sum)
+  int blocked;                    // the linear solve: 0 k_lba_solve (n <= 6 ORBX_LBA_MAX_LOCAL), 1 the blocked LDLT of orbx_ba.hip
+  double deltaMono, deltaStereo;  // Huber deltas, already narrowed to float and widened as the reference holds them
 };
+
+// ---- the host side the two bundle adjustments' entries share (orbx_api_lba.hip)
+constexpr int kLbaMaxIterations = 1000000;
+
+// what the validation derives from a problem
+struct LbaLayout {
+  std::vector<int> ptStart;   // [nP + 1]
+  std::vector<int> slot;      // [nKF] row block of the reduced system, -1: not optimised
+  std::vector<int> deg;       // [nKF] edges of the key frame
+  int nOpt = 0, fixedLocal = 0;
+};
+
+struct LbaConfig {
+  int maxIterations;
+  float lambdaInit;
+  int robust, blocked;
+  float deltaMono, deltaStereo;        // narrowed, as the reference's thHuber* are floats
+  const volatile int32_t* stopFlag;    // nullptr: never asked
+  int nPoses;                          // the first nPoses key frames come back
+};
+
+// outputs of a run; chi2 / erase / depthPos may be nullptr
+struct LbaRun {
+  double* poses;
+  double* points;
+  double* chi2;
+  uint8_t* erase;
+  uint8_t* depthPos;
+  int stopped, iterations, trials, stopReason;
+  double lambda, chiInitial, chiFinal;
+};
+
+// every check of a problem that needs no device, in the order the entries report them; fills g
+const char* lba_graph_error(const orbx_lba_problem& p, int maxIterations, float lambdaInit, LbaLayout& g);
+void lba_passthrough(const orbx_lba_problem& p, int nPoses, LbaRun& r);   // the widened inputs, every counter zero
+// upload, the chain of trials (the stop flag asked in front of the first and after each), download
+int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, const LbaConfig& cfg, LbaRun& r);
 
 // the chain on the null stream (orbx_lba.hip)
 hipError_t launch_lba_init(const LbaArgs& a);       // estimates from the inputs, the state, x = 0

@@ -13,9 +13,12 @@
 //                     along as one more row, then the back-substitution
 //   k_lba_update      one point / key frame per thread: xl = Dinv (bl - Hpl^T xp), oplus into the trial copy
 //   k_lba_finish      classification at the held chi2 and the final depth, the outputs
+// The full bundle adjustment (Optimizer::BundleAdjustment, :47-372; orbx_api_ba.hip) runs the same chain: LbaArgs carries what it
+// does differently -- the robust kernel optional, its own Huber deltas, and the blocked LDLT of orbx_ba.hip in place of k_lba_solve.
 // Every sum has a fixed order (serial in edge order, a strided serial sum plus a fixed tree, or wave_sum's butterfly) and there
 // is no atomic: two calls on the same input agree bit for bit.
 #include "orbx_lba.h"
+#include "orbx_ba.h"
 #include "orbx_pose.h"
 
 namespace {
@@ -128,12 +131,11 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
     Jp[2][0] = Jp[0][0] - bf * y / z_2; Jp[2][1] = Jp[0][1] + bf * x / z_2; Jp[2][2] = Jp[0][2]; Jp[2][3] = Jp[0][3]; Jp[2][4] = 0;
     Jp[2][5] = Jp[0][5] - bf / z_2;
   }
-  // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
-  const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815);   // narrowed as the reference's (Optimizer.cc:1281-1282)
-  const double delta = (double)(mono ? thHuberMono : thHuberStereo);
+  // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91); without a kernel g2o weighs with the information alone: rho' = 1
+  const double delta = mono ? A.deltaMono : A.deltaStereo;
   const double dsqr = delta * delta;
   double rho0 = chi, rho1 = 1.0;
-  if (!(chi <= dsqr)) {
+  if (A.robust && !(chi <= dsqr)) {
     const double sq = sqrt(chi);
     rho0 = 2 * sq * delta - dsqr;
     rho1 = delta / sq;
@@ -606,7 +608,12 @@ hipError_t launch_lba_evaluate(const LbaArgs& a) {
 hipError_t launch_lba_trial(const LbaArgs& a) {
   hipLaunchKernelGGL(k_lba_dinv, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
   if (a.nOpt) hipLaunchKernelGGL(k_lba_schur, dim3(a.nOpt, a.nOpt), dim3(64), 0, nullptr, a);
-  hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(kSolveBS), 0, nullptr, a);
+  if (a.blocked) {
+    const hipError_t e = launch_ba_solve(BaSolveArgs{a.S, a.bs, a.xp, &a.st->ok, a.n});
+    if (e != hipSuccess) return e;
+  } else {
+    hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(kSolveBS), 0, nullptr, a);
+  }
   hipLaunchKernelGGL(k_lba_update, dim3(blocks(std::max(a.nKF, a.nP))), dim3(kLbaBS), 0, nullptr, a);
   return hipGetLastError();
 }
