@@ -1359,6 +1359,9 @@ int orbx_bundle_adjustment(int device, const orbx_lba_problem* problem, const or
 /* The blocked solver alone, for tests and measurements: A x = b for a symmetric positive definite row-major A [n][n] in double,
  * 1 <= n <= 6 * ORBX_BA_MAX_KF (only the lower triangle is read).  *ok = 0 when a pivot is <= 0 or not finite; x is then untouched. */
 int orbx_ba_dense_solve(int device, int n, const double* A, const double* b, double* x, int32_t* ok);
+/* The one-workgroup solver alone (the k_lba_solve of every local bundle adjustment, and of the full one below
+ * ORBX_BA_BLOCKED_FROM_KF or under solver 2), for tests: the same contract, n a multiple of 6 in [6, 6 * ORBX_LBA_MAX_LOCAL]. */
+int orbx_lba_dense_solve(int device, int n, const double* A, const double* b, double* x, int32_t* ok);
 
 /* ---- new map points (local mapping)------------------------------------------------------------------- */
 

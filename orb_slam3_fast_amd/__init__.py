@@ -1326,6 +1326,19 @@ def ba_dense_solve(A, b, device=0):
     return dict(x=x, ok=ok.value)
 
 
+def lba_dense_solve(A, b, device=0):
+    """The one-workgroup LDLT of the local bundle adjustment alone (orbx_lba_dense_solve): as ba_dense_solve, n a multiple of 6 up
+    to 6 * LBA_MAX_LOCAL."""
+    A = np.ascontiguousarray(A, np.float64)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1)
+    if A.ndim != 2 or A.shape != (len(b), len(b)):
+        raise ValueError("A must be [n][n] and b [n]")
+    x = np.zeros(len(b))
+    ok = C.c_int32(-1)
+    _check(lib().orbx_lba_dense_solve(int(device), len(b), _p(A), _p(b), _p(x), C.byref(ok)))
+    return dict(x=x, ok=ok.value)
+
+
 class _NpCamera(C.Structure):      # orbx_np_camera
     _fields_ = [("model", C.c_int32), ("p", C.c_float * 8), ("kb8_precision", C.c_float), ("Tcw", C.c_float * 12),
                 ("Ow", C.c_float * 3)]

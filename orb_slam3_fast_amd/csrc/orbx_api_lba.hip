@@ -2,6 +2,7 @@
 // orbx_lba.hip.  The graph, the two copies of the estimates and of the linear system, the reduced camera system and the outputs
 // live in one Pack: one upload, one chain of launches per Levenberg trial with one status word read back after each, one
 // download.  The host makes no optimiser decision: it only asks whether the device wants another trial.
+// orbx_lba_dense_solve runs the chain's linear solver (k_lba_solve) alone on a caller's matrix.
 #include "orbx_lba.h"
 
 #include <algorithm>
@@ -226,4 +227,30 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
   r.lambda = run.lambda; r.chi2_initial = run.chiInitial; r.chi2_final = run.chiFinal;
   r.iterations = run.iterations; r.trials = run.trials; r.stop_reason = run.stopReason;
   return rc;
+}
+
+// k_lba_solve on a caller's matrix: the argument record holds what the kernel touches (n, S, bs, xp, st) and nothing else
+extern "C" int orbx_lba_dense_solve(int device, int n, const double* A, const double* b, double* x, int32_t* ok) {
+  if (!A || !b || !x || !ok) return fail(ORBX_E_BADARG, "null argument");
+  if (n < 6 || n > 6 * ORBX_LBA_MAX_LOCAL) return fail(ORBX_E_BADARG, "n outside [6, 6 * ORBX_LBA_MAX_LOCAL]");
+  if (n % 6) return fail(ORBX_E_BADARG, "n is not a multiple of 6");
+  int rc = set_device(device);
+  if (rc != ORBX_OK) return rc;
+  LbaArgs a{};
+  a.n = n;
+  Pack pk;
+  pk.in(a.S, A, (size_t)n * n, 16);
+  pk.in(a.bs, b, (size_t)n, 16);
+  const size_t oSt = pk.area(a.st, 1, 16);
+  const size_t oX = pk.area(a.xp, (size_t)n, 16);
+  hipError_t e = pk.commit();
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+  HIPC(launch_lba_solve(a));
+  const uint8_t* h = pk.fetch(oSt, oX + (size_t)n * sizeof(double) - oSt, &e);
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+  LbaState st;
+  std::memcpy(&st, h, sizeof st);
+  *ok = st.ok ? 1 : 0;
+  if (st.ok) std::memcpy(x, h + (oX - oSt), (size_t)n * sizeof(double));
+  return ORBX_OK;
 }

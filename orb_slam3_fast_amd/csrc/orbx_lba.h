@@ -103,6 +103,8 @@ hipError_t launch_lba_init(const LbaArgs& a);       // estimates from the inputs
 hipError_t launch_lba_evaluate(const LbaArgs& a);   // linearise at the estimate (stage 0) or the trial, reduce, decide
 hipError_t launch_lba_trial(const LbaArgs& a);      // Dinv, Schur complement, factorisation and solve, back-substitution, oplus
 hipError_t launch_lba_finish(const LbaArgs& a);     // classification and outputs
+// k_lba_solve alone, as launch_lba_trial launches it: reads n, S, bs; writes xp (when every pivot holds) and st->ok
+hipError_t launch_lba_solve(const LbaArgs& a);
 
 }  // namespace orbx
 #endif

@@ -605,15 +605,16 @@ hipError_t launch_lba_evaluate(const LbaArgs& a) {
   return hipGetLastError();
 }
 
+hipError_t launch_lba_solve(const LbaArgs& a) {
+  hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(kSolveBS), 0, nullptr, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_lba_trial(const LbaArgs& a) {
   hipLaunchKernelGGL(k_lba_dinv, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
   if (a.nOpt) hipLaunchKernelGGL(k_lba_schur, dim3(a.nOpt, a.nOpt), dim3(64), 0, nullptr, a);
-  if (a.blocked) {
-    const hipError_t e = launch_ba_solve(BaSolveArgs{a.S, a.bs, a.xp, &a.st->ok, a.n});
-    if (e != hipSuccess) return e;
-  } else {
-    hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(kSolveBS), 0, nullptr, a);
-  }
+  const hipError_t e = a.blocked ? launch_ba_solve(BaSolveArgs{a.S, a.bs, a.xp, &a.st->ok, a.n}) : launch_lba_solve(a);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_lba_update, dim3(blocks(std::max(a.nKF, a.nP))), dim3(kLbaBS), 0, nullptr, a);
   return hipGetLastError();
 }

@@ -54,7 +54,21 @@ for _d in range(1, FREE_DRAWS):
 # compared with the model only where the admission rule holds (test_global_ba.py decides at run time and says which)
 GAUGE_FREE = tuple(n for n in SCENES if n.startswith("nothing_fixed"))
 
-for _name, _p in SCENES.items():
+# The one-workgroup solver of the local BA (solver 2, and solver 0 below ORBX_BA_BLOCKED_FROM_KF) on whole problems up to its cap,
+# two of them either side of the switch-over, which names them.  A registry with spreads of its own (wide_spreads): the X spread
+# of the largest exceeds the gauge class's of SCENES.
+_K = orbx.BA_BLOCKED_FROM_KF
+WIDE = {
+    "w29": dict(nL=30, nF=0, nP=150, stereo=0.5, gross=0.05, noise=0.6, init_local=0, robust=True),
+    "w%d" % (_K - 1): dict(nL=_K, nF=0, nP=250, stereo=0.5, gross=0.0, noise=0.6, init_local=0, robust=False),
+    "w%d" % _K: dict(nL=_K + 1, nF=0, nP=250, stereo=0.5, gross=0.05, noise=0.6, init_local=0, robust=True),
+    "w%d" % orbx.LBA_MAX_LOCAL: dict(nL=orbx.LBA_MAX_LOCAL + 1, nF=0, nP=400, stereo=0.5, gross=0.05, noise=0.6, init_local=0, robust=True),
+}
+# the SEEDS rule for WIDE
+WIDE_SEEDS = {}
+WIDE_SEEDS_DISCARDED = 0
+
+for _name, _p in list(SCENES.items()) + list(WIDE.items()):
     if "recipe" not in _p:
         lc.EXTRA["gba_" + _name] = {k: v for k, v in _p.items() if k not in ("robust", "extra_point")}
 
@@ -63,8 +77,8 @@ for _name, _p in SCENES.items():
 def scene(name, seed=None):
     """lba_cases.scene under the name's recipe (a `draw` is a further seed of another scene's recipe), every key frame local
     (vpKFs), plus robust / max_iterations of the call."""
-    p = SCENES[name]
-    sc = dict(lc.scene("gba_" + p.get("recipe", name), p.get("draw", 0) + (SEEDS.get(name, 0) if seed is None else seed)))
+    p = SCENES[name] if name in SCENES else WIDE[name]
+    sc = dict(lc.scene("gba_" + p.get("recipe", name), p.get("draw", 0) + (SEEDS.get(name, WIDE_SEEDS.get(name, 0)) if seed is None else seed)))
     sc["n_local"] = len(sc["keyframes"])
     if p.get("extra_point"):      # a point no key frame observes
         sc["points"] = np.concatenate([sc["points"], np.array([[1.5, -2.5, 3.5]], F32)])
@@ -186,6 +200,19 @@ def spreads(cls=None):
         if cls is None or scene_class(name) == cls:
             r, t, x = lc.pose_point_diff(a, b)
             dR, dT, dX = max(dR, r), max(dT, t), max(dX, x)
+        for k in ("chi2_initial", "chi2_final"):
+            tot = max(tot, abs(a[k] - b[k]) / max(abs(a[k]), 1e-300))
+    return dict(R=dR, t=dT, X=dX, total=tot)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_spreads():
+    """spreads() over the WIDE scenes (one class: a single fixed key frame), which enter no spread of SCENES."""
+    dR = dT = dX = tot = 0.0
+    for name in WIDE:
+        a, b = model(name, 0), model(name, 1)
+        r, t, x = lc.pose_point_diff(a, b)
+        dR, dT, dX = max(dR, r), max(dT, t), max(dX, x)
         for k in ("chi2_initial", "chi2_final"):
             tot = max(tot, abs(a[k] - b[k]) / max(abs(a[k]), 1e-300))
     return dict(R=dR, t=dT, X=dX, total=tot)

@@ -389,6 +389,19 @@ EXTRA = {"noise_free": dict(nL=3, nF=2, nP=40, stereo=0.5, gross=0.0, noise=0.0)
 # same expressions in the same order with correctly rounded sqrt and division (no contraction), so it reproduces them too.
 SEEDS = {"rho_zero": 1}
 SEEDS_DISCARDED = 1
+# The one-workgroup solver (k_lba_solve) above the 132 rows of wide_22, up to its cap, and a key frame dense enough for a fourth
+# 64-lane pass of k_lba_reduce_kfs / k_lba_schur.  A registry of its own with spreads of its own (wide_spreads): larger systems
+# spread further in some components, and inside SCENES they would loosen the bounds of every scene above.
+WIDE = {
+    "wide_29": dict(nL=29, nF=3, nP=160, stereo=0.5, gross=0.05, noise=0.6),     # 174 rows: the first panel load of two passes
+    "wide_64": dict(nL=64, nF=3, nP=260, stereo=0.5, gross=0.05, noise=0.6),     # 384 rows
+    "cap_128": dict(nL=128, nF=3, nP=420, stereo=0.5, gross=0.05, noise=0.6),    # 768 rows: ORBX_LBA_MAX_LOCAL
+    "dense_kf": dict(nL=6, nF=2, nP=300, stereo=0.5, gross=0.05, noise=0.6, obs=(5, 9)),   # more than 192 edges on a key frame
+}
+EXTRA.update(WIDE)
+# the SEEDS rule for WIDE (test_wide_scenes_v1_against_v2 checks it)
+WIDE_SEEDS = {}
+WIDE_SEEDS_DISCARDED = 0
 
 
 def project(Rm, t, X):
@@ -404,7 +417,7 @@ def scene(name, seed=None):
     p = SCENES[name] if name in SCENES else EXTRA[name]
     nL, nF, nP = p["nL"], p["nF"], p["nP"]
     nKF = nL + nF
-    rng = np.random.default_rng(9100 + 7 * NUMBER.get(name, 100 + zlib.crc32(name.encode()) % 1000) + 1000 * (SEEDS.get(name, 0) if seed is None else seed))
+    rng = np.random.default_rng(9100 + 7 * NUMBER.get(name, 100 + zlib.crc32(name.encode()) % 1000) + 1000 * (SEEDS.get(name, WIDE_SEEDS.get(name, 0)) if seed is None else seed))
     Rs = [rot_vec(rng.normal(size=3) * 0.04) for _ in range(nKF)]
     Cs = np.stack([rng.uniform(-0.6, 0.6, nKF), rng.uniform(-0.3, 0.3, nKF), rng.uniform(-0.2, 0.8, nKF)], 1)   # camera centres
     if p.get("special"):
@@ -511,6 +524,22 @@ def spreads(cls=None):
         near = np.abs(a["chi2"] - gate) <= 0.5 * gate
         if near.any():
             chi = max(chi, float((np.abs(a["chi2"] - b["chi2"])[near] / gate[near]).max()))
+        for k in ("chi2_initial", "chi2_final"):
+            tot = max(tot, abs(a[k] - b[k]) / max(abs(a[k]), 1e-300))
+    return dict(R=dR, t=dT, X=dX, chi=chi, total=tot)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_spreads():
+    """spreads() over the WIDE scenes (all anchored), which enter no spread of SCENES."""
+    dR = dT = dX = chi = tot = 0.0
+    for name in WIDE:
+        a, b = model(name, 0), model(name, 1)
+        r, t, x = pose_point_diff(a, b)
+        dR, dT, dX = max(dR, r), max(dT, t), max(dX, x)
+        gate = np.where(scene(name)["edges"]["u_right"] < 0, 5.991, 7.815)
+        near = np.abs(a["chi2"] - gate) <= 0.5 * gate
+        chi = max(chi, float((np.abs(a["chi2"] - b["chi2"])[near] / gate[near]).max()))
         for k in ("chi2_initial", "chi2_final"):
             tot = max(tot, abs(a[k] - b[k]) / max(abs(a[k]), 1e-300))
     return dict(R=dR, t=dT, X=dX, chi=chi, total=tot)

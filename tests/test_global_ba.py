@@ -5,7 +5,8 @@ The scenes follow test_local_ba.py's rule: kept only where the restatement's two
 decisions with a margin (decisions_agree).  The device must then take V1's decisions exactly and keep poses and points within 4 x
 the V1 / V2 spread of the scene's class plus one ulp; the spreads are computed here, not written down.  The solver alone is
 measured by the relative residual |Ax - b| / (|A| |x| + |b|) against 4 x that of lba_cases.ldlt_dense -- the same unpivoted
-factorisation in numpy -- on the same matrix, plus one ulp."""
+factorisation in numpy -- on the same matrix, plus one ulp.  The WIDE scenes of gba_cases run on both solvers between 29 and
+ORBX_LBA_MAX_LOCAL optimised key frames, either side of the switch-over of solver 0, with bounds from their own spread."""
 import ctypes as C
 import os
 import subprocess
@@ -17,7 +18,7 @@ import pytest
 import orb_slam3_fast_amd as orbx
 import gba_cases as gc
 import lba_cases as lc
-from gba_cases import SCENES, NB, TILE, scene, model, spreads
+from gba_cases import SCENES, WIDE, NB, TILE, scene, model, spreads
 from test_local_ba import decisions_agree
 from test_pose_opt import normalize_rotation
 
@@ -104,6 +105,32 @@ def test_v1_against_v2_spreads_and_what_the_scenes_cover():
     for name in SCENES:
         m = model(name, 0)
         assert m["status"] == orbx.LBA_DONE and m["chi2_final"] < m["chi2_initial"], name
+
+
+def test_wide_scenes_v1_against_v2():
+    """The WIDE scenes: admitted, one fixed key frame each, and the optimised key frames that bracket the switch-over."""
+    K = orbx.BA_BLOCKED_FROM_KF
+    assert list(WIDE) == ["w29", "w%d" % (K - 1), "w%d" % K, "w%d" % orbx.LBA_MAX_LOCAL] and not set(WIDE) & set(SCENES)
+    for name in WIDE:
+        a, b = model(name, 0), model(name, 1)
+        n_opt = gc.graph(scene(name), True)["nOpt"]
+        r, t, x = lc.pose_point_diff(a, b)
+        print("%-6s key frames %3d opt %3d points %3d edges %4d %s stop %d chi2 %.6g -> %.6g  R %.3g t %.3g X %.3g" % (
+            name, len(scene(name)["keyframes"]), n_opt, len(scene(name)["points"]), len(scene(name)["edges"]), decisions(a), a["stop_reason"],
+            a["chi2_initial"], a["chi2_final"], r, t, x))
+        assert decisions_agree(a, b) and gc.admitted(name), name
+        assert a["status"] == orbx.LBA_DONE and a["chi2_final"] < a["chi2_initial"], name
+        assert n_opt == int(name[1:]) <= orbx.LBA_MAX_LOCAL and gc.scene_class(name) == "gauge", name
+    sp = gc.wide_spreads()
+    print("V1 / V2 spread, WIDE scenes: R %.3g rad, t %.3g relative, X %.3g relative, chi2 totals %.3g relative; seeds discarded %d" % (
+        sp["R"], sp["t"], sp["X"], sp["total"], gc.WIDE_SEEDS_DISCARDED))
+    assert sp["total"] <= spreads()["total"]            # the totals' bound of SCENES holds for them as it is
+    assert [scene(n)["robust"] for n in WIDE] == [True, False, True, True]
+    assert sum(gc.WIDE_SEEDS.values()) == gc.WIDE_SEEDS_DISCARDED
+    for name, s in gc.WIDE_SEEDS.items():
+        for earlier in range(s):
+            sc = scene(name, earlier)
+            assert not decisions_agree(gc.gba_model(sc, 0), gc.gba_model(sc, 1)), (name, earlier)
 
 
 # ------------------------------------------------------------------------------------------------ the ABI on the CPU
@@ -294,7 +321,7 @@ def device(name, **kw):
 
 
 def bounds(name):
-    sp = spreads(gc.scene_class(name))
+    sp = gc.wide_spreads() if name in WIDE else spreads(gc.scene_class(name))
     return 4 * sp["R"] + EPS, 4 * sp["t"] + EPS, 4 * sp["X"] + EPS
 
 
@@ -309,14 +336,10 @@ def untouched_are_the_widened_inputs(name, d):
         assert np.array_equal(d["points"][j], sc["points"][j].astype(float)), (name, j)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", list(SCENES))
-def test_scene_against_v1(gpu, name):
-    """Every scene on the blocked solver.  A scene without a fixed key frame is compared with the model only where the admission
-    rule holds; otherwise its invariants are checked."""
+def against_v1(name, solver):
     a = model(name, 0)
-    d = device(name)
-    again = device(name)
+    d = device(name, solver=solver)
+    again = device(name, solver=solver)
     for k in ("poses", "points", "chi2"):
         assert d[k].tobytes() == again[k].tobytes(), (name, k)
     assert all(d[k] == again[k] for k in ("iterations", "trials", "stop_reason", "lambda", "chi2_initial", "chi2_final"))
@@ -328,7 +351,7 @@ def test_scene_against_v1(gpu, name):
         print("scene %s: V1 and V2 part ways, invariants only" % name)
         return
     got = {k: d[k] for k in ("status", "iterations", "trials", "stop_reason")}
-    print("scene %s device %s model %s" % (name, got, decisions(a)))
+    print("scene %s solver %d device %s model %s" % (name, solver, got, decisions(a)))
     for k, v in got.items():
         assert v == a[k], (name, k, v, a[k])
     dR, dT, dX = lc.pose_point_diff(a, d)
@@ -342,8 +365,23 @@ def test_scene_against_v1(gpu, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", [n for n in SCENES if gc.graph(scene(n), True)["nOpt"] <= orbx.LBA_MAX_LOCAL])
-def test_both_solvers_on_one_problem(gpu, name):
+@pytest.mark.parametrize("name", list(SCENES))
+def test_scene_against_v1(gpu, name):
+    """Every scene on the blocked solver.  A scene without a fixed key frame is compared with the model only where the admission
+    rule holds; otherwise its invariants are checked."""
+    against_v1(name, orbx.BA_SOLVER_BLOCKED)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(WIDE))
+def test_wide_scene_against_v1(gpu, name):
+    """The WIDE scenes on the one-workgroup solver and on the blocked one, each against V1 within 4 x the WIDE spread."""
+    assert gc.admitted(name)
+    for solver in (orbx.BA_SOLVER_ONE_WORKGROUP, orbx.BA_SOLVER_BLOCKED):
+        against_v1(name, solver)
+
+
+def both_solvers(name):
     one, two, auto = (device(name, solver=s) for s in (orbx.BA_SOLVER_BLOCKED, orbx.BA_SOLVER_ONE_WORKGROUP, orbx.BA_SOLVER_AUTO))
     for k in ("status", "iterations", "trials", "stop_reason"):
         assert one[k] == two[k], (name, k)
@@ -355,6 +393,24 @@ def test_both_solvers_on_one_problem(gpu, name):
     assert any(same), name
     n_opt = gc.graph(scene(name), True)["nOpt"]
     assert same[0 if n_opt >= orbx.BA_BLOCKED_FROM_KF else 1]
+    return same
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n in SCENES if gc.graph(scene(n), True)["nOpt"] <= orbx.LBA_MAX_LOCAL])
+def test_both_solvers_on_one_problem(gpu, name):
+    both_solvers(name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(WIDE))
+def test_both_solvers_and_the_automatic_choice_either_side_of_the_switch_over(gpu, name):
+    """solver 0 is the one-workgroup solver bit for bit up to ORBX_BA_BLOCKED_FROM_KF - 1 optimised key frames and the blocked one
+    from there on; the scenes are named after the switch-over, so a retuned one moves them with it."""
+    K = orbx.BA_BLOCKED_FROM_KF
+    same = both_solvers(name)
+    print("scene %s: solver 0 is bit for bit the blocked solver %s, the one-workgroup solver %s" % (name, same[0], same[1]))
+    assert same[0 if name in ("w%d" % K, "w%d" % orbx.LBA_MAX_LOCAL) else 1], name
 
 
 @pytest.mark.gpu

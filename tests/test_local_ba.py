@@ -6,9 +6,16 @@ stop decisions with a margin: every trial's relative chi2 change is at least 1e-
 in that trial's chi2, or it is exactly zero in both (the rho == 0 stop).  Under that condition the device, which sums in an order
 of its own, must take V1's decisions: counters, trial count and stop reason are compared exactly.  The erase flags are compared
 outside the edges whose held chi2 lies within 4 x the measured V1 / V2 chi2 spread of its gate (at most 0.5 % of all edges and one
-per scene: checked on the CPU below); poses and points must lie within 4 x the V1 / V2 spread of the scene's class plus one ulp."""
+per scene: checked on the CPU below); poses and points must lie within 4 x the V1 / V2 spread of the scene's class plus one ulp.
+
+The one-workgroup solver (k_lba_solve) runs alone through orbx_lba_dense_solve at every size where one of its two loops that stride
+by the workgroup gains a pass, up to its cap of 6 * ORBX_LBA_MAX_LOCAL rows, against lba_cases.ldlt_dense on the same matrix; the
+WIDE scenes of lba_cases take whole problems through it, with bounds from their own V1 / V2 spread.  Not covered: a failed solve
+inside a whole problem (st.ok == 0 in k_lba_update / k_lba_decide) needs a structurally indefinite reduced system, which no valid
+scene produces; the failed pivots are tested on the solver alone."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -16,11 +23,13 @@ import pytest
 
 import orb_slam3_fast_amd as orbx
 import lba_cases as lc
-from lba_cases import SCENES, scene, model, spreads
+from lba_cases import SCENES, WIDE, scene, model, spreads
 from test_pose_opt import ldlt_solve, oplus, normalize_rotation
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = float(np.finfo(float).eps)
+SOLVE_BS = 1024   # kSolveBS of csrc/orbx_lba.hip: threads of k_lba_solve's one workgroup
+PANEL = 6         # kPanel: columns of a panel
 
 
 def margin():
@@ -211,10 +220,91 @@ def test_v1_against_v2_spreads_and_cap():
         assert (ev[:, 0] > 1e-9 * ev[:, 2]).all(), name
 
 
+def kf_edges(name):
+    """Edges per optimised key frame: what one wave of k_lba_reduce_kfs / k_lba_schur strides over, 64 at a time."""
+    G = lc.graph(scene(name))
+    s = G["slot"][G["ekf"]]
+    return np.bincount(s[s >= 0], minlength=G["nOpt"])
+
+
+def test_wide_scenes_v1_against_v2():
+    """The WIDE scenes under the rules of the test above, with the margin and the chi2 spread of SCENES unchanged, and what they
+    reach in k_lba_solve, k_lba_reduce_kfs and k_lba_schur."""
+    for name in WIDE:
+        a, b = model(name, 0), model(name, 1)
+        assert a["status"] == orbx.LBA_DONE and decisions_agree(a, b), name
+        for k in ("num_fixedKF", "num_OptKF", "num_MPs", "num_edges", "status", "iterations", "trials", "stop_reason"):
+            assert a[k] == b[k], (name, k)
+        ex = lc.exempt(a, name, margin())
+        assert ex.sum() <= 1, (name, int(ex.sum()))
+        assert np.array_equal(a["erase"][~ex], b["erase"][~ex]) and np.array_equal(a["depth_positive"], b["depth_positive"]), name
+        r, t, x = lc.pose_point_diff(a, b)
+        print("%-10s rows %3d edges %4d densest key frame %3d iterations %2d trials %2d stop %d erase %3d exempt %d  %s  R %.3g t %.3g X %.3g" % (
+            name, 6 * lc.graph(scene(name))["nOpt"], a["num_edges"], kf_edges(name).max(), a["iterations"], a["trials"], a["stop_reason"],
+            int(a["erase"].sum()), int(ex.sum()), "".join("A" if d else "r" for d in a["decisions"]), r, t, x))
+    sp = lc.wide_spreads()
+    print("V1 / V2 spread, WIDE scenes: R %.3g rad, t %.3g relative, X %.3g relative, held chi2 %.3g of the gate, totals %.3g relative; "
+          "seeds discarded %d" % (sp["R"], sp["t"], sp["X"], sp["chi"], sp["total"], lc.WIDE_SEEDS_DISCARDED))
+    assert sp["chi"] <= spreads()["chi"] and sp["total"] <= spreads()["total"]     # margin() and the totals' bound hold for them as they are
+    assert not set(WIDE) & set(SCENES) and all(lc.EXTRA[n] is WIDE[n] for n in WIDE)
+    assert sum(lc.WIDE_SEEDS.values()) == lc.WIDE_SEEDS_DISCARDED
+    for name, s in lc.WIDE_SEEDS.items():
+        for earlier in range(s):
+            sc = scene(name, earlier)
+            assert not decisions_agree(lc.lba_model(sc, 0), lc.lba_model(sc, 1)), (name, earlier)
+    # what they reach
+    n_of = lambda name: 6 * lc.graph(scene(name))["nOpt"]
+    assert n_of("wide_29") == 6 * 29 == FIRST_LOAD[2] and load_passes(n_of("wide_29")) == 2 and load_passes(n_of("wide_22")) == 1
+    assert n_of("wide_64") == 6 * 64 and load_passes(n_of("wide_64")) == 3 and eliminate_passes(n_of("wide_64")) == 2
+    assert n_of("cap_128") == 6 * orbx.LBA_MAX_LOCAL and load_passes(n_of("cap_128")) == 5 and eliminate_passes(n_of("cap_128")) == 4
+    assert all(not all(model(n, 0)["decisions"]) for n in ("wide_29", "wide_64", "cap_128"))      # rejected trials among them
+    assert n_of("dense_kf") == 36 and -(-kf_edges("dense_kf").max() // 64) == 4
+    assert max(-(-kf_edges(n).max() // 64) for n in SCENES if len(scene(n)["edges"]) and lc.graph(scene(n))["nOpt"]) == 2
+
+
+# ------------------------------------------------------------------------------------------------ the solver's sizes
+def load_passes(n, c0=0):
+    """Passes of k_lba_solve's panel load and write-back loop (idx < rows * kPanel; idx += kSolveBS) at the panel of column c0."""
+    return -(-(n + 1 - c0) * PANEL // SOLVE_BS)
+
+
+def eliminate_passes(n):
+    """Passes of the in-panel elimination loop at its longest: the first panel's first column, (rows - 1) * (kPanel - 1) items."""
+    return -(-n * (PANEL - 1) // SOLVE_BS)
+
+
+def first_n(passes_of, k):
+    """The smallest system (a multiple of kPanel) at which the loop makes k passes."""
+    return next(n for n in range(PANEL, 6 * orbx.LBA_MAX_LOCAL + 1, PANEL) if passes_of(n) >= k)
+
+
+FIRST_LOAD = {k: first_n(load_passes, k) for k in (2, 3, 4, 5)}
+FIRST_ELIMINATE = first_n(eliminate_passes, 2)
+# one panel; wide_22's rows, the largest system the scenes of SCENES reach; either side of every pass gained; either side of the cap
+LBA_SOLVER_SIZES = sorted({PANEL, 132, 6 * orbx.LBA_MAX_LOCAL - PANEL, 6 * orbx.LBA_MAX_LOCAL} | {n - d for n in list(FIRST_LOAD.values()) + [FIRST_ELIMINATE]
+                                                                                                 for d in (PANEL, 0)})
+
+
+FAILED_N = 522                                      # four load passes at the first panel
+FAILED_C0 = (FIRST_LOAD[3] // PANEL + 1) * PANEL    # a panel past 342 rows in, where the load is down to two
+
+
+def test_solver_sizes_follow_the_kernels_constants():
+    """A change of kSolveBS or kPanel moves the sizes at which the loops gain a pass: it must fail here, not un-test the edges."""
+    src = open(os.path.join(ROOT, "orb_slam3_fast_amd", "csrc", "orbx_lba.hip")).read()
+    assert int(re.search(r"constexpr int kSolveBS = (\d+);", src).group(1)) == SOLVE_BS
+    assert int(re.search(r"constexpr int kPanel = (\d+);", src).group(1)) == PANEL == 6      # a key frame's rows are one panel
+    assert LBA_SOLVER_SIZES == [6, 132, 168, 174, 204, 210, 336, 342, 510, 516, 678, 684, 762, 768]
+    assert [load_passes(n) for n in LBA_SOLVER_SIZES] == [1, 1, 1, 2, 2, 2, 2, 3, 3, 4, 4, 5, 5, 5]
+    assert [eliminate_passes(n) for n in LBA_SOLVER_SIZES] == [1, 1, 1, 1, 1, 2, 2, 2, 3, 3, 4, 4, 4, 4]
+    assert all(n % PANEL == 0 for n in LBA_SOLVER_SIZES) and LBA_SOLVER_SIZES[-1] == 6 * orbx.LBA_MAX_LOCAL
+    assert (load_passes(FAILED_N), load_passes(FAILED_N, FAILED_C0)) == (4, 2) and FAILED_C0 > FIRST_LOAD[3] and FAILED_C0 % PANEL == 0
+
+
 # ------------------------------------------------------------------------------------------------ the ABI on the CPU
 def test_symbols_exported_and_header_compiles_as_c99(tmp_path):
     L = orbx.lib()
-    assert hasattr(L, "orbx_local_bundle_adjustment")
+    assert hasattr(L, "orbx_local_bundle_adjustment") and hasattr(L, "orbx_lba_dense_solve")
     src = tmp_path / "abi.c"
     src.write_text('#include <stddef.h>\n#include "orbx.h"\n'
                    "typedef char a0[sizeof(orbx_lba_keyframe) == 60 ? 1 : -1];\n"
@@ -304,6 +394,24 @@ def test_bad_arguments_are_rejected_before_any_device_is_touched():
     rc, _, _ = raw_call(kf0, nL, X0, ed0, device=1 << 20)
     msg = orbx.lib().orbx_last_error().decode()
     assert (rc, msg) in ((orbx.E_NODEVICE, "no HIP device available"), (orbx.E_BADARG, "device index out of range")), (rc, msg)
+    # the solver's entry
+    cap = 6 * orbx.LBA_MAX_LOCAL
+    A, b, x, ok = np.eye(cap + 6), np.ones(cap + 6), np.full(cap + 6, 7.0), C.c_int32(-1)
+
+    def solve(n, null=None):
+        a = [None if null == k else orbx._p(v) for k, v in (("A", A), ("b", b), ("x", x))]
+        rc = orbx.lib().orbx_lba_dense_solve(1 << 20, n, *a, None if null == "ok" else C.byref(ok))
+        return rc, orbx.lib().orbx_last_error().decode()
+    for k in ("A", "b", "x", "ok"):
+        assert solve(6, k) == (orbx.E_BADARG, "null argument"), k
+    RANGE = "n outside [6, 6 * ORBX_LBA_MAX_LOCAL]"
+    for n in (-6, 0, 1, 5, cap + 1, cap + 6, 2 ** 31 - 1):
+        assert solve(n) == (orbx.E_BADARG, RANGE), n
+    for n in (7, 11, 13, cap - 1):
+        assert solve(n) == (orbx.E_BADARG, "n is not a multiple of 6"), n
+    for n in (6, cap):
+        assert solve(n) in ((orbx.E_NODEVICE, "no HIP device available"), (orbx.E_BADARG, "device index out of range")), n
+    assert (x == 7.0).all() and ok.value == -1
 
 
 def check_unchanged(sc, res, status):
@@ -345,9 +453,8 @@ def device(name, **kw):
     return orbx.LocalBundleAdjustment(sc["keyframes"], sc["n_local"], sc["points"], sc["edges"], **args)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", list(SCENES))
-def test_scene_against_v1(gpu, name):
+def against_v1(name, sp=None):
+    """One device run of a scene against V1; sp: the V1 / V2 spread the pose and point bounds are made of (None: the class's)."""
     a = model(name, 0)
     d = device(name)
     got = {k: d[k] for k in ("num_fixedKF", "num_OptKF", "num_MPs", "num_edges", "status", "iterations", "trials", "stop_reason")}
@@ -356,12 +463,12 @@ def test_scene_against_v1(gpu, name):
         assert v == a[k], (name, k, v, a[k])
     if a["status"] != orbx.LBA_DONE:
         check_unchanged(scene(name), d, a["status"])
-        return
+        return d
     ex = lc.exempt(a, name, margin())
     assert ex.sum() <= 1
     assert np.array_equal(d["erase"][~ex], a["erase"][~ex]), (name, np.nonzero(d["erase"] != a["erase"])[0])
     assert np.array_equal(d["depth_positive"], a["depth_positive"]), name
-    sp = spreads(lc.scene_class(name))
+    sp = spreads(lc.scene_class(name)) if sp is None else sp
     dR, dT, dX = lc.pose_point_diff(a, d)
     bR, bT, bX = 4 * sp["R"] + EPS, 4 * sp["t"] + EPS, 4 * sp["X"] + EPS
     print("scene %s: fraction of the bound: R %.3f t %.3f X %.3f; exempt %d, erase flags differing from V1 in all %d" % (
@@ -378,6 +485,75 @@ def test_scene_against_v1(gpu, name):
     kf = scene(name)["keyframes"]
     for i in np.nonzero(G["slot"][:G["nL"]] < 0)[0]:
         assert np.array_equal(d["poses"][i], np.concatenate([kf["q"][i], kf["t"][i]]).astype(float)), (name, i)
+    return d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SCENES))
+def test_scene_against_v1(gpu, name):
+    against_v1(name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(WIDE))
+def test_wide_scene_against_v1(gpu, name):
+    """Whole problems through k_lba_solve at 174, 384 and 768 rows, and through a fourth 64-lane pass of the key-frame reductions:
+    everything test_scene_against_v1 checks, poses and points within 4 x the WIDE scenes' own V1 / V2 spread."""
+    d = against_v1(name, lc.wide_spreads())
+    assert d["status"] == orbx.LBA_DONE
+    if name == "cap_128":
+        again = device(name)
+        for k in ("poses", "points", "erase", "chi2", "depth_positive"):
+            assert d[k].tobytes() == again[k].tobytes(), (name, k)
+        for k in ("iterations", "trials", "stop_reason", "lambda", "chi2_initial", "chi2_final"):
+            assert d[k] == again[k], (name, k)
+
+
+def residual(A, x, b):
+    return float(np.linalg.norm(A @ x - b) / (np.linalg.norm(A, 2) * np.linalg.norm(x) + np.linalg.norm(b)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", LBA_SOLVER_SIZES)
+def test_lba_dense_solve_against_the_unpivoted_ldlt_in_numpy(gpu, n):
+    """k_lba_solve alone on A = B^T B + n I.  The factorisation and the order of every sum are ldlt_dense's, so the margin is the
+    one of test_global_ba's blocked solver: 4 x the numpy LDLT's relative residual on the same matrix, plus one ulp."""
+    from test_global_ba import spd
+    A, b = spd(n)
+    d = orbx.lba_dense_solve(A, b)
+    assert d["ok"] == 1
+    ref = lc.ldlt_dense(A, b)
+    got, bound = residual(A, d["x"], b), 4 * residual(A, ref, b) + EPS
+    print("n %d (%d load, %d elimination passes): residual %.3g, numpy LDLT %.3g, fraction of the bound %.3f" % (
+        n, load_passes(n), eliminate_passes(n), got, residual(A, ref, b), got / bound))
+    assert got <= bound
+    assert orbx.lba_dense_solve(A, b)["x"].tobytes() == d["x"].tobytes()
+    # the upper triangle is not read
+    U = A.copy()
+    U[np.triu_indices(n, 1)] = np.nan
+    u = orbx.lba_dense_solve(U, b)
+    assert u["ok"] == 1 and u["x"].tobytes() == d["x"].tobytes()
+
+
+@pytest.mark.gpu
+def test_lba_dense_solve_failed_pivots_leave_x_untouched(gpu):
+    """Pivots that are not positive or not finite, where the panel's load takes four passes, two and one: the solve reports them
+    (ok == 0) and leaves x alone, as the numpy LDLT does on the same matrix."""
+    from test_global_ba import spd
+    n, c0 = FAILED_N, FAILED_C0
+    A, b = spd(n)
+    L = orbx.lib()
+    cases = [("the first panel", (5, 5, -1.0)), ("a panel of two load passes", (c0 + 3, c0 + 3, -1.0)), ("the last panel", (n - 2, n - 2, -1.0)),
+             ("the last pivot", (n - 1, n - 1, -1.0)), ("a large negative pivot", (FIRST_LOAD[2], FIRST_LOAD[2], -1e9)),
+             ("NaN below the diagonal of the last panel", (n - 1, n - 3, np.nan)), ("infinite diagonal", (c0 + PANEL + 1, c0 + PANEL + 1, np.inf))]
+    for what, (i, j, v) in cases:
+        M = A.copy()
+        M[i, j] = M[j, i] = v
+        x, ok = np.full(n, 7.0), C.c_int32(-1)
+        assert L.orbx_lba_dense_solve(0, n, orbx._p(M), orbx._p(b), orbx._p(x), C.byref(ok)) == 0, what
+        assert ok.value == 0 and (x == 7.0).all(), what
+        assert lc.ldlt_dense(M, b) is None, what
+    assert orbx.lba_dense_solve(A, b)["ok"] == 1
 
 
 @pytest.mark.gpu
