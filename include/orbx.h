@@ -1583,6 +1583,36 @@ int orbx_copy_probe(int device, size_t bytes, int iters, double* gbps);
 void orbx_debug_introsort(uint64_t* v, int n);
 /* The wave-cooperative device version the quadtree kernel actually runs (n <= 4000). */
 int orbx_debug_introsort_device(int device, uint64_t* v, int n);
+/* The small dense linear algebra of the geometric solvers (csrc/orbx_linalg.h), each function alone on n items of the caller's:
+ * the kernels load an item, call the header's function and store what it returns.  in / out are packed arrays of items, doubles
+ * unless stated.  out is read as well as written: where a function leaves an output untouched (jacobi_cs returning false, a
+ * failed LDLT) the caller's value comes back.  Flags are written as 0.0 / 1.0.
+ *   op                               in, per item                                  out, per item
+ *   ORBX_LINALG_RCP64, _RSQRT64      x                                             rcp64(x) / rsqrt64(x)
+ *   ORBX_LINALG_JACOBI_CS            alpha, beta, gamma                            c, s, returned flag
+ *   ORBX_LINALG_SVD3                 A [3][3]                                      U [3][3], w [3], V [3][3]
+ *   ORBX_LINALG_NULL_VECTOR4         A [4][4], float                               v [4], float
+ *   ORBX_LINALG_LDLT6                H [21] (upper triangle, row-major), b [6]     x [6], returned flag
+ *   ORBX_LINALG_LDLT6_DAMPED         H [21], b [6], lambda                         x [6], returned flag
+ *   ORBX_LINALG_LDLT7                H [28], b [7], lambda                         x [7], returned flag
+ *   ORBX_LINALG_NULL_VECTOR_SYM9     A [16][9]  (one wave per item: lane l holds   v [4][9]: the result as lanes 0, 17, 34 and 63
+ *   ORBX_LINALG_NULL_VECTOR_SYM12    A [16][12]  row l & 15, as the call sites)    v [4][12]  of the wave hold it
+ *   ORBX_LINALG_SUM16                v [64], one value per lane of a wave          sum16(v) [64], as every lane holds it
+ * A null pointer, n outside [1, ORBX_LINALG_MAX_ITEMS] and an unknown op are ORBX_E_BADARG before any device is touched. */
+#define ORBX_LINALG_RCP64 0
+#define ORBX_LINALG_RSQRT64 1
+#define ORBX_LINALG_JACOBI_CS 2
+#define ORBX_LINALG_SVD3 3
+#define ORBX_LINALG_NULL_VECTOR4 4
+#define ORBX_LINALG_LDLT6 5
+#define ORBX_LINALG_LDLT6_DAMPED 6
+#define ORBX_LINALG_LDLT7 7
+#define ORBX_LINALG_NULL_VECTOR_SYM9 8
+#define ORBX_LINALG_NULL_VECTOR_SYM12 9
+#define ORBX_LINALG_SUM16 10
+#define ORBX_LINALG_OPS 11
+#define ORBX_LINALG_MAX_ITEMS 65536
+int orbx_debug_linalg(int device, int op, int n, const void* in, void* out);
 
 /* Shrinks (>= 320 entries) or restores (any larger value) the capacity of k_detect's LDS corner + survivor list so
  * that tests can force the paths natural images rarely reach: mid-cell flushes, the corner limit and the tile-scan

@@ -206,6 +206,7 @@ def lib():
         L.orbx_debug_introsort.argtypes = [vp, i]
         L.orbx_debug_introsort.restype = None
         L.orbx_debug_introsort_device.argtypes = [i, vp, i]
+        L.orbx_debug_linalg.argtypes = [i, i, i, vp, vp]
         L.orbx_debug_set_detect_list_cap.argtypes = [i]
         L.orbx_debug_set_detect_list_cap.restype = None
         L.orbx_debug_set_octree_global.argtypes = [i]
@@ -1337,6 +1338,28 @@ def lba_dense_solve(A, b, device=0):
     ok = C.c_int32(-1)
     _check(lib().orbx_lba_dense_solve(int(device), len(b), _p(A), _p(b), _p(x), C.byref(ok)))
     return dict(x=x, ok=ok.value)
+
+
+# orbx_debug_linalg: ORBX_LINALG_* and, per operation, the numpy type and the elements of one item of `in` and of `out`
+(LINALG_RCP64, LINALG_RSQRT64, LINALG_JACOBI_CS, LINALG_SVD3, LINALG_NULL_VECTOR4, LINALG_LDLT6, LINALG_LDLT6_DAMPED, LINALG_LDLT7,
+ LINALG_NULL_VECTOR_SYM9, LINALG_NULL_VECTOR_SYM12, LINALG_SUM16) = range(11)
+LINALG_OPS, LINALG_MAX_ITEMS = 11, 65536
+LINALG_ITEM = {LINALG_RCP64: (np.float64, 1, 1), LINALG_RSQRT64: (np.float64, 1, 1), LINALG_JACOBI_CS: (np.float64, 3, 3),
+               LINALG_SVD3: (np.float64, 9, 21), LINALG_NULL_VECTOR4: (np.float32, 16, 4), LINALG_LDLT6: (np.float64, 27, 7),
+               LINALG_LDLT6_DAMPED: (np.float64, 28, 7), LINALG_LDLT7: (np.float64, 36, 8), LINALG_NULL_VECTOR_SYM9: (np.float64, 144, 36),
+               LINALG_NULL_VECTOR_SYM12: (np.float64, 192, 48), LINALG_SUM16: (np.float64, 64, 64)}
+
+
+def debug_linalg(op, items, prefill=0.0, device=0):
+    """One function of csrc/orbx_linalg.h alone on the device (orbx_debug_linalg): items [n][elements of one input item] ->
+    [n][elements of one output item].  prefill (a scalar or an array of the output's shape) is what `out` holds going in: it comes
+    back wherever the function leaves an output untouched."""
+    dt, n_in, n_out = LINALG_ITEM[op]
+    a = np.ascontiguousarray(items, dt).reshape(-1, n_in)
+    out = np.empty((len(a), n_out), dt)
+    out[...] = prefill
+    _check(lib().orbx_debug_linalg(int(device), int(op), len(a), _p(a), _p(out)))
+    return out
 
 
 class _NpCamera(C.Structure):      # orbx_np_camera

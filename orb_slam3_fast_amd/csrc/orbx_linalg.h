@@ -31,6 +31,10 @@ __device__ __forceinline__ double sum16(double v) {   // over each group of 16 l
 // ~1e-16 instead of correctly rounded, at a fifth of the IEEE division / square-root expansions (the Jacobi sweeps below are a
 // serial chain of them per triangulated match: round 4 measured 35 us of k_fisheye_batch's 60 us there).  The rotation angles of
 // a one-sided Jacobi may be off by an ulp without changing what it converges to.
+// Domain of both: the argument and the result normal doubles, |x| in [2^-1022, 2^1022] for rcp64 and x in [2^-1022, DBL_MAX] for
+// rsqrt64; there the relative error is at most 2^-51.  Outside it nothing is promised: +-0, +-inf and NaN give NaN (fma(-0, inf, 1)
+// is NaN), not the limits, and so do a denormal whose reciprocal overflows and the root of a negative; rsqrt64 of a denormal loses the
+// bits that 0.5 * x shifts out (the smallest one comes back 2.25 times too large) (tests/test_linalg_device.py).
 __device__ __forceinline__ double rcp64(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
@@ -49,6 +53,10 @@ __device__ __forceinline__ double rsqrt64(double x) {
 // component by (s3^2 + mu) / (s4^2 + mu) >= 10^2 .. 10^4 for a pair that passes the parallax gate (:356), and the iteration stops
 // when the normalised vector has settled to 1e-13.  Against the Jacobi vector: the eigenvector of A^T A carries
 // eps (s1 / s3)^2 ~ 1e-11 of relative error, far inside the 2e-4 of the float-tail parity (tests/test_fisheye.py).
+// Domain: a finite A with at least one non-zero entry.  The all-zero matrix gives four NaNs (mu is then 1e-300, (1 / mu)^2
+// overflows and rsqrt64(inf) is NaN) where JacobiSVD gives (0, 0, 0, 1); no call site can build it from a valid camera or pose: its
+// rows hold a -1, a focal length or a rotation's rows (HISTORY.md).  Of a matrix of rank 2 or less (a pair without parallax) the result is still a unit null
+// vector to float rounding, which one is not defined.
 __device__ inline void null_vector4(const float A[16], float v[4]) {
   double B[4][4];
 #pragma unroll
@@ -97,7 +105,9 @@ __device__ inline void null_vector4(const float A[16], float v[4]) {
 }
 
 // One Jacobi rotation of a one-sided (Hestenes) SVD from the column moments alpha = |p|^2, beta = |q|^2, gamma = p.q.
-// false: the pair is already orthogonal to 1e-14 of its norms.
+// false: the pair is already orthogonal to 1e-14 of its norms.  Valid for moments whose products stay normal: column norms within
+// [2^-200, 2^200]; far outside (norms below about 1e-77 or above about 1e77) gamma^2 underflows or alpha * beta overflows, the gate
+// reads false, and svd3 and null_vector_sym return their input unrotated and report nothing.
 __device__ __forceinline__ bool jacobi_cs(double alpha, double beta, double gamma, double& c, double& s) {
   if (!(gamma * gamma > 1e-28 * (alpha * beta))) return false;
   const double zeta = (beta - alpha) * 0.5 * rcp64(gamma), az = fabs(zeta);
@@ -152,7 +162,9 @@ __device__ void null_vector_sym(double (&x)[NC], double (&y)[NC], double (&out)[
 }
 
 // SVD of a row-major 3 x 3 in double: A = U diag(w) V^T, w descending (JacobiSVD's order).  The signs of the column pairs
-// (U_j, V_j) are whatever the sweeps leave: every use below is invariant to them.
+// (U_j, V_j) are whatever the sweeps leave: every use below is invariant to them.  Of a matrix of rank 1 or 0 the
+// columns of U that belong to a zero w are zero, not completed to an orthonormal basis as JacobiSVD does (w, V and U diag(w) V^T
+// are right all the same): nearest_orthogonal of orbx_mlpnp.hip would return a matrix that is not orthogonal there.
 __device__ void svd3(const double* A, double* U, double* w, double* V) {
   double b[9], v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 #pragma unroll

@@ -1,0 +1,485 @@
+"""The small dense linear algebra of the geometric solvers (csrc/orbx_linalg.h), every function alone through orbx_debug_linalg
+(csrc/orbx_api_linalg.hip), against the references of tests/linalg_cases.py: longdouble / mpmath for rcp64, rsqrt64 and jacobi_cs,
+numpy's float64 SVD for svd3, null_vector4 and null_vector_sym, lba_cases.ldlt_dense for the LDLTs, the xor tree in numpy for sum16.
+
+On the CPU: the argument checks, the header's domain sentences, and every reference (and the numpy restatement of null_vector4) held
+to a quarter of each bound on every case, so that the inputs cannot hide a device failure.  On the device every test prints what it
+measured as a fraction of its bound.  The bounds come from the number formats and the project's own 1e-14 orthogonality gate, none
+from a device result; one of them, the reconstruction of svd3, carries a term for the gate that the first device run showed to be
+missing (linalg_cases.svd3_check; HISTORY.md has the reason and the measured fractions)."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import orb_slam3_fast_amd as orbx
+import linalg_cases as lc
+from linalg_cases import EPS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "orb_slam3_fast_amd", "csrc")
+NO_DEVICE = ((orbx.E_NODEVICE, "no HIP device available"), (orbx.E_BADARG, "device index out of range"))
+
+
+def header():
+    return " ".join(re.sub(r"^\s*//", "", line) for line in open(os.path.join(CSRC, "orbx_linalg.h")).read().splitlines())
+
+
+def hold(rows, limit=1.0, what=""):
+    """Prints every row's largest measured / bound and asserts it against limit (1: the bound; 0.25: a quarter of it)."""
+    fr = lc.fraction(rows)
+    for name, f in fr.items():
+        print("%s%s: fraction of the bound %.3g" % (what and what + ": ", name, f))
+    bad = {k: v for k, v in fr.items() if not v <= limit}
+    assert not bad, (what, bad)
+    return fr
+
+
+# ------------------------------------------------------------------------------------------------ the ABI on the CPU
+def test_symbol_exported_constants_mirrored_and_header_compiles_as_c99(tmp_path):
+    assert hasattr(orbx.lib(), "orbx_debug_linalg")
+    h = open(os.path.join(ROOT, "include", "orbx.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define ORBX_LINALG_(\w+) (\d+)", h)}
+    assert len(defs) == 13 and defs.pop("OPS") == orbx.LINALG_OPS == 11 and defs.pop("MAX_ITEMS") == orbx.LINALG_MAX_ITEMS
+    assert sorted(defs.values()) == list(range(11)) and all(getattr(orbx, "LINALG_" + k) == v for k, v in defs.items())
+    src = tmp_path / "abi.c"
+    src.write_text('#include "orbx.h"\nint (*entry)(int, int, int, const void*, void*) = orbx_debug_linalg;\n'
+                   "typedef char a0[ORBX_LINALG_SUM16 + 1 == ORBX_LINALG_OPS ? 1 : -1];\nint main(void) { return 0; }\n")
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Werror", "-Wall", "-I", os.path.join(ROOT, "include"), "-c", str(src),
+                           "-o", str(tmp_path / "abi.o")])
+    # the item sizes of the Python mirror are the kernels'
+    hip = open(os.path.join(CSRC, "orbx_api_linalg.hip")).read()
+    for name, col in (("kInBytes", 1), ("kOutBytes", 2)):
+        expr = re.search(name + r"\[ORBX_LINALG_OPS\] = \{([^}]*)\}", hip).group(1)
+        sizes = [eval(e, {"__builtins__": {}}) for e in expr.split(",")]
+        assert sizes == [np.dtype(orbx.LINALG_ITEM[op][0]).itemsize * orbx.LINALG_ITEM[op][col] for op in range(orbx.LINALG_OPS)], name
+
+
+def test_debug_kernels_call_the_header_and_restate_nothing():
+    hip = open(os.path.join(CSRC, "orbx_api_linalg.hip")).read()
+    assert '#include "orbx_linalg.h"' in hip
+    for fn in ("rcp64", "rsqrt64", "jacobi_cs", "svd3", "null_vector4", "ldlt6<true>", "ldlt6<false>", "ldlt7", "null_vector_sym<NC>", "sum16"):
+        assert "orbx::" + fn + "(" in hip, fn
+    for word in ("__builtin_amdgcn_rcp", "__builtin_amdgcn_rsq", "__shfl", "sqrt("):
+        assert word not in hip, word
+    assert "orbx_api_linalg.hip" in open(os.path.join(CSRC, "Makefile")).read()
+
+
+def test_bad_arguments_are_rejected_before_any_device_is_touched():
+    L = orbx.lib()
+    a, out = np.ones(192), np.full(192, 7.0)
+
+    def call(op, n, null=None, device=1 << 20):       # a device that does not exist: never reached by a rejected call
+        rc = L.orbx_debug_linalg(device, op, n, None if null == "in" else orbx._p(a), None if null == "out" else orbx._p(out))
+        return rc, L.orbx_last_error().decode()
+    for op in range(orbx.LINALG_OPS):
+        assert call(op, 1, "in") == (orbx.E_BADARG, "null argument") and call(op, 1, "out") == (orbx.E_BADARG, "null argument")
+        for n in (0, -1, -2 ** 31, orbx.LINALG_MAX_ITEMS + 1, 2 ** 31 - 1):
+            assert call(op, n) == (orbx.E_BADARG, "n outside [1, ORBX_LINALG_MAX_ITEMS]"), (op, n)
+        assert call(op, 1) in NO_DEVICE, op
+    for op in (-1, orbx.LINALG_OPS, 1 << 20, -2 ** 31):
+        assert call(op, 1) == (orbx.E_BADARG, "unknown operation"), op
+    assert call(-1, 0, "in") == (orbx.E_BADARG, "null argument") and call(-1, 0) == (orbx.E_BADARG, "n outside [1, ORBX_LINALG_MAX_ITEMS]")
+    assert call(0, 1, device=-1) in NO_DEVICE
+    assert (out == 7.0).all()
+
+
+# ------------------------------------------------------------------------------------------------ the header's domains
+RCP_DOMAIN = ("Domain of both: the argument and the result normal doubles, |x| in [2^-1022, 2^1022] for rcp64 and x in [2^-1022, DBL_MAX] "
+              "for rsqrt64; there the relative error is at most 2^-51.")
+RCP_OUTSIDE = ("Outside it nothing is promised: +-0, +-inf and NaN give NaN (fma(-0, inf, 1) is NaN), not the limits, and so do a denormal "
+               "whose reciprocal overflows and the root of a negative; rsqrt64 of a denormal loses the bits that 0.5 * x shifts out (the "
+               "smallest one comes back 2.25 times too large)")
+JACOBI_DOMAIN = ("Valid for moments whose products stay normal: column norms within [2^-200, 2^200]; far outside (norms below about 1e-77 "
+                 "or above about 1e77) gamma^2 underflows or alpha * beta overflows, the gate reads false, and svd3 and "
+                 "null_vector_sym return their input unrotated and report nothing.")
+NULL4_DOMAIN = ("Domain: a finite A with at least one non-zero entry.  The all-zero matrix gives four NaNs (mu is then 1e-300, "
+                "(1 / mu)^2 overflows and rsqrt64(inf) is NaN) where JacobiSVD gives (0, 0, 0, 1)")
+NULL4_RANK2 = ("Of a matrix of rank 2 or less (a pair without parallax) the result is still a unit null vector to float rounding, "
+               "which one is not defined")
+SVD3_RANK = ("Of a matrix of rank 1 or 0 the columns of U that belong to a zero w are zero, not completed to an orthonormal basis "
+             "as JacobiSVD does")
+
+
+def test_header_states_the_domains_the_tests_hold():
+    """Each sentence is asserted on the device by the test named beside it."""
+    h = header()
+    h = re.sub(r"\s+", " ", h)
+    for sentence in (RCP_DOMAIN,        # test_reciprocals_inside_the_domain
+                     RCP_OUTSIDE,       # test_reciprocals_outside_the_domain
+                     JACOBI_DOMAIN,     # test_jacobi_cs, test_jacobi_gate_outside_its_range, test_svd3 (the scaled cases)
+                     NULL4_DOMAIN,      # test_null_vector4, test_null_vector4_of_the_zero_matrix
+                     NULL4_RANK2,       # test_null_vector4 (rank 2)
+                     SVD3_RANK):        # test_svd3_of_rank_1_and_zero
+        assert re.sub(r"\s+", " ", sentence) in h, sentence
+    assert lc.RCP_DOMAIN == (2.0 ** -1022, 2.0 ** 1022) and lc.RSQRT_DOMAIN == (2.0 ** -1022, float(np.finfo(float).max)) and lc.RCP_BOUND == 2.0 ** -51
+    assert min(lc.SVD3_SCALES) == -200 and max(lc.SVD3_SCALES) == 200
+    assert "1e-28" in h and lc.JACOBI_GATE == 1e-28 and lc.ORTHO_GATE ** 2 == pytest.approx(lc.JACOBI_GATE)
+
+
+# ------------------------------------------------------------------------------------------------ the references on the CPU
+def test_reciprocal_truth_within_a_quarter_of_the_bound():
+    for rsq in (0, 1):
+        x = lc.recip_inputs(rsq)
+        t = lc.recip_truth(x, rsq)
+        rel, ulp = lc.recip_error(x, t, rsq)
+        print("%s: %d arguments, the rounded truth is off by at most %.3f ulp" % ("rsqrt64" if rsq else "rcp64", len(x), ulp.max()))
+        assert ulp.max() <= 0.5 + 1e-3
+        hold(lc.recip_check(x, t, rsq), 0.25)
+        # a result one ulp off is seen, and two ulp off fails near the top of a binade
+        off = np.nextafter(np.nextafter(t, np.inf), np.inf)
+        assert lc.fraction(lc.recip_check(x, off, rsq))[("rsqrt64" if rsq else "rcp64") + " relative error"] > 1.0
+    assert len(lc.recip_inputs(0)) > 50000 and (lc.recip_inputs(0) < 0).sum() > 5000
+
+
+def test_jacobi_reference_within_a_quarter_of_the_bounds_and_cases_cover_the_gate():
+    cases = lc.jacobi_cases()
+    for name, rows in cases.items():
+        hold(lc.jacobi_check(rows, lc.jacobi_reference(rows, 7.0)), 0.25, name)
+    g = cases["gate"]
+    flag = lc.jacobi_gate(g[:, 0], g[:, 1], g[:, 2]).reshape(-1, 9)
+    # in every run of nine neighbours the gate switches exactly once, between two adjacent doubles
+    assert (flag[:, 0] == 0).all() and (flag[:, -1] == 1).all() and ((np.diff(flag.astype(int), axis=1) != 0).sum(1) == 1).all()
+    for name in ("alpha == beta", "signs", "random", "large zeta", "columns of norm 2^-200", "columns of norm 2^200"):
+        r = cases[name]
+        assert lc.jacobi_gate(r[:, 0], r[:, 1], r[:, 2]).all(), name
+    lz = cases["large zeta"]
+    z = np.abs((lz[:, 1] - lz[:, 0]) * 0.5 / lz[:, 2])
+    assert (z >= 1e100).sum() >= 6 and (z < 1e100).sum() >= 3 and z.max() > 1e119
+    ref = lc.jacobi_reference(cases["alpha == beta"], 7.0)
+    assert np.allclose(ref[:, 0], np.sqrt(0.5), rtol=2 * EPS, atol=0) and np.allclose(np.abs(ref[:, 1]), np.sqrt(0.5), rtol=2 * EPS, atol=0)
+    s = cases["signs"]
+    assert {(np.sign(b - a), np.sign(g)) for a, b, g in s} == {(1, 1), (1, -1), (-1, 1), (-1, -1)}
+
+
+def test_svd3_reference_within_a_quarter_of_the_bounds_and_cases_are_what_they_say():
+    cases = lc.svd3_cases()
+    worst = 0.0
+    for name, A in cases.items():
+        rows = lc.svd3_check(A, lc.svd3_reference(A), degenerate=name in ("rank 1", "zero"))
+        hold([r for r in rows if "numpy" not in r[0]], 0.25, name)
+        # numpy's own singular values against the longdouble ones: LAPACK is a few ulp of s0 off, and the row that holds the device
+        # to numpy's values has to carry that (the row against the longdouble values does not)
+        worst = max(worst, hold([r for r in rows if "numpy" in r[0]], 1.0, name)["svd3 |w - s|, s numpy's"])
+    print("numpy's singular values are at most %.3f of the 8 eps s0 bound away from the longdouble ones" % worst)
+    sv =lambda n: np.linalg.svd(cases[n], compute_uv=False)
+    assert np.abs(sv("rotations") - 1).max() < 1e-14 and (np.linalg.det(cases["rotations"]) > 0).all() and (np.linalg.det(cases["reflections"]) < 0).all()
+    assert (sv("essential matrices")[:, 2] < 1e-15 * sv("essential matrices")[:, 0]).all()
+    assert (sv("rank 2, third value zeroed")[:, 2] < 1e-15 * sv("rank 2, third value zeroed")[:, 0]).all()
+    assert (np.linalg.matrix_rank(cases["rank 2, integer"]) == 2).all() and len(cases["rank 2, integer"]) > 30
+    assert (np.linalg.matrix_rank(cases["rank 1"]) == 1).all() and not cases["zero"].any()
+    d = cases["diagonal, six orderings"]
+    assert len({tuple(np.argsort(-np.abs(np.diag(m)))) for m in d}) == 6        # every order the three-swap sort can meet
+    two = sv("two equal singular values")
+    assert ((two[:, 0] - two[:, 1] < 1e-14) | (two[:, 1] - two[:, 2] < 1e-14)).all()
+    for k in lc.SVD3_SCALES:
+        if k:
+            n = np.sqrt((cases["random, scaled by 2^%d" % k] ** 2).sum(1))
+            assert (n > 2.0 ** (k - 6)).all() and (n < 2.0 ** (k + 3)).all()
+
+
+def test_null_vector4_restatement_within_a_quarter_of_the_bounds():
+    """The numpy restatement of the routine (1 / x for rcp64) on every case: at most a quarter of each bound, so a device
+    failure cannot be the inputs'.  What the iteration costs is printed per case, and pinned where the issue asked."""
+    cases = lc.null4_cases()
+    its = {}
+    for name, A in cases.items():
+        v, it = lc.null_vector4_restated(A)
+        its[name] = it
+        print("%-60s iterations %d .. %d" % (name, it.min(), it.max()))
+        if name == "zero":
+            assert np.isnan(v).all() and (it == 30).all()
+            continue
+        hold(lc.null4_check(A, v, residual_only=name == "rank 2"), 0.25, name)
+    # the parallax gates' systems settle in a few solves; a start vector orthogonal to the answer costs more, never the cap
+    assert max(its[n].max() for n in cases if n.startswith(("normalised", "pixel"))) <= 8
+    assert max(its[n].max() for n in cases if n.startswith("null vector")) <= 10
+    # exact rank 2: the two smallest eigenvalues of B + mu I are equal and the iterate stays in their plane, but it never settles
+    # to 1e-13 (each solve multiplies the rounding left along the other null direction by as much as the wanted one): every one
+    # of the 30 solves is made, and the result is a null vector all the same (the bounds above)
+    assert (its["rank 2"] == 30).all()
+    for name in ("normalised, parallax 1.15", "pixel, parallax 0.37"):
+        s = np.linalg.svd(cases[name].astype(float), compute_uv=False)
+        assert (s[:, 2] >= 10 * s[:, 3]).mean() > 0.4, name       # the angle bound applies to the low-parallax systems too
+    for name in cases:
+        if name.startswith("null vector ("):
+            s, Vt = np.linalg.svd(cases[name].astype(float))[1:]
+            start = np.abs(Vt[:, 3].sum(1)) / 2
+            print("%s: the start vector's component along the answer is at most %.3g" % (name, start.max()))
+            assert start.max() < 1e-6 and (s[:, 2] > 1e3 * s[:, 3]).all(), name
+    assert (np.linalg.matrix_rank(cases["rank 2"].astype(float)) == 2).all() and len(cases["rank 2"]) >= 15
+
+
+def test_null_vector_sym_reference_within_a_quarter_of_the_bounds():
+    for nc in (9, 12):
+        cases = lc.sym_cases(nc)
+        for name, A in cases.items():
+            hold(lc.sym_check(A, lc.sym_reference(A)), 0.25, "<%d> %s" % (nc, name))
+        for gap, text in ((1e-8, "1e-8"), (1e-3, "1e-3")):
+            s = np.linalg.svd(cases["positive semi-definite, gap " + text], compute_uv=False)
+            assert np.allclose(s[:, -2] - s[:, -1], gap, rtol=1e-3, atol=0)
+        # the gate's own case: every cosine between the columns is below 1e-10, some are above 1e-14, and the vector of the
+        # matrix left as it is (e_j of its shortest column) misses the angle bound
+        A = cases["columns orthogonal to between 1e-14 and 1e-10"]
+        G = np.einsum("nki,nkj->nij", A, A)
+        d = np.sqrt(np.einsum("nii->ni", G))
+        cosines = np.abs(G / (d[:, :, None] * d[:, None, :]))[:, ~np.eye(nc, dtype=bool)]
+        assert cosines.max() < 1e-10 and (cosines > 1e-14).mean() > 0.9
+        left = np.tile(np.eye(nc)[np.argmin(d, 1)], (1, 4))
+        assert lc.fraction(lc.sym_check(A, left))["null_vector_sym<%d> angle" % nc] > 4
+        if nc == 9:
+            s = np.linalg.svd(cases["eight-point, noisy"], compute_uv=False)
+            assert (s[:, -1] < 1e-15).all() and (s[:, -2] > 1e-6 * s[:, 0]).all()         # eight rows: an exact null vector, and a gap
+            assert not cases["eight-point, noisy"][:, 8:].any() and cases["eight-point, noisy"][:, :8].all(2).all()
+            s = np.linalg.svd(cases["eight-point, planar scene"], compute_uv=False)
+            assert (s[:, 6] < 1e-5 * s[:, 0]).all()                                         # a null space of three dimensions
+
+
+def test_ldlt_cases_fail_and_solve_in_the_numpy_ldlt():
+    for n in (6, 7):
+        for name, H, b, lam in lc.ldlt_systems(n):
+            x = lc.ldlt_dense(H + lam * np.eye(n), b)
+            assert x is not None and lc.ldlt_residual(H + lam * np.eye(n), x, b) < 1e-10, (n, name)
+        fails = lc.ldlt_failures(n)
+        assert len(fails) == 2 * n + 9
+        for name, H, b, lam in fails:
+            with np.errstate(all="ignore"):
+                assert lc.ldlt_dense(H + lam * np.eye(n), b) is None, (n, name)
+        for j in range(n):      # the failing pivot is the first that fails: the leading block in front of it factors
+            H = [f for f in fails if f[0] == "pivot -1 first at position %d" % j][0][1]
+            assert j == 0 or lc.ldlt_dense(H[:j, :j], np.ones(j)) is not None
+        h = lc.pack_upper(lc.ldlt_systems(n)[0][1])
+        assert np.array_equal(lc.unpack_upper(h, n), lc.ldlt_systems(n)[0][1]) and len(h) == n * (n + 1) // 2
+
+
+def test_sum16_reference_depends_on_the_order():
+    v = lc.sum16_inputs()
+    t = lc.sum16_xor_tree(v)
+    assert all(len({t[w, g * 16 + l].tobytes() for l in range(16)}) == 1 for w in range(len(v)) for g in range(4))
+    serial = np.array([[np.sum(v[w, g * 16:g * 16 + 16][::-1]) for g in range(4)] for w in range(len(v))])
+    seq = np.zeros((len(v), 4))
+    for l in range(16):
+        seq = seq + v.reshape(len(v), 4, 16)[:, :, l]
+    assert (t[:, ::16] != seq).any() or (t[:, ::16] != serial).any()          # another order gives other bits somewhere
+
+
+# ------------------------------------------------------------------------------------------------ the device
+@pytest.fixture(scope="module")
+def gpu():
+    if orbx.device_count() < 1:
+        pytest.fail("no HIP device visible: the gpu-marked tests must run on the MI355X box")
+    return True
+
+
+_memo = {}
+
+
+def device_cases(key, op, cases, prefill=0.0):
+    """All cases of a routine in one launch, made once per module: {name: outputs}."""
+    if key not in _memo:
+        names = list(cases)
+        items = np.concatenate([np.asarray(cases[n]).reshape(len(cases[n]), -1) for n in names])
+        out = orbx.debug_linalg(op, items, prefill)
+        again = orbx.debug_linalg(op, items, prefill)
+        assert out.tobytes() == again.tobytes(), key              # two calls are bit-identical
+        cut = np.cumsum([0] + [len(cases[n]) for n in names])
+        _memo[key] = {n: out[cut[i]:cut[i + 1]] for i, n in enumerate(names)}
+    return _memo[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rsq", [0, 1], ids=["rcp64", "rsqrt64"])
+def test_reciprocals_inside_the_domain(gpu, rsq):
+    """Relative error at most 2^-51 over the whole domain: a seed good to more than 26 bits leaves the last Newton step a handful
+    of roundings of 2^-53 each."""
+    x = lc.recip_inputs(rsq)
+    got = orbx.debug_linalg(orbx.LINALG_RSQRT64 if rsq else orbx.LINALG_RCP64, x)[:, 0]
+    rel, ulp = lc.recip_error(x, got, rsq)
+    k = int(np.argmax(ulp))
+    print("%s: %d arguments, largest error %.4f ulp at x = %r; exact in %.1f %%, within half an ulp in %.1f %%" % (
+        "rsqrt64" if rsq else "rcp64", len(x), ulp[k], float(x[k]), 100 * (ulp == 0).mean(), 100 * (ulp <= 0.5).mean()))
+    hold(lc.recip_check(x, got, rsq))
+    if not rsq:
+        neg = x < 0
+        assert np.array_equal(got[neg], -orbx.debug_linalg(orbx.LINALG_RCP64, -x[neg])[:, 0])      # odd
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rsq", [0, 1], ids=["rcp64", "rsqrt64"])
+def test_reciprocals_outside_the_domain(gpu, rsq):
+    """The header: +-0, +-inf and NaN give NaN, not the limits; so does a denormal whose reciprocal overflows and the root of a
+    negative; the other denormal arguments and results come out as the arithmetic of the two Newton steps makes them."""
+    op = orbx.LINALG_RSQRT64 if rsq else orbx.LINALG_RCP64
+    for what, x, expect in lc.recip_specials(rsq):
+        got = orbx.debug_linalg(op, x, 7.0)[:, 0]
+        print("%s: %s -> %s" % ("rsqrt64" if rsq else "rcp64", x, got))
+        with np.errstate(all="ignore"):
+            truth = lc.recip_truth(x, rsq)
+        if expect == "nan":
+            assert np.isnan(got).all(), (what, got)
+        elif expect == "bound":
+            hold(lc.recip_check(x, got, rsq), 1.0, what)
+        elif expect == "denormal":
+            assert (np.abs(got - truth) <= 2.0 ** -1073).all() and (np.abs(truth) < lc.TINY).all(), (what, got, truth)
+        else:
+            assert expect == "2.25" and np.abs(got / truth - 2.25).max() <= 8 * EPS, (what, got, truth)
+
+
+@pytest.mark.gpu
+def test_jacobi_cs(gpu):
+    cases = lc.jacobi_cases()
+    dev = device_cases("jacobi", orbx.LINALG_JACOBI_CS, cases, 7.0)
+    for name, rows in cases.items():
+        out = dev[name]
+        flag = lc.jacobi_gate(rows[:, 0], rows[:, 1], rows[:, 2])
+        assert np.array_equal(out[:, 2], flag.astype(float)), name          # the gate, to the ulp of gamma
+        assert (out[~flag, :2] == 7.0).all(), name                           # c and s untouched where it says no
+        hold(lc.jacobi_check(rows, out), 1.0, name)
+    out = dev["alpha == beta"]
+    assert np.abs(out[:, 0] - np.sqrt(0.5)).max() <= 8 * EPS and np.abs(np.abs(out[:, 1]) - np.sqrt(0.5)).max() <= 8 * EPS
+    assert (out[:, 1] > 0).all()                                             # zeta = +-0 is not below zero: t = +1 whatever gamma's sign
+    assert (dev["gate"][:, 2] == 1).sum() >= 14 and (dev["gate"][:, 2] == 0).sum() >= 14
+
+
+@pytest.mark.gpu
+def test_jacobi_gate_outside_its_range(gpu):
+    """The header: for columns of norm below about 1e-77 gamma^2 underflows, above about 1e77 alpha * beta overflows; the gate
+    reads false for a pair at 60 degrees and nothing is reported."""
+    rows = np.array([[1e-170, 1e-170, 5e-171], [1e160, 1e160, 5e159], [1e-150, 1e-150, 5e-151], [1e150, 1e150, 5e149]])
+    out = orbx.debug_linalg(orbx.LINALG_JACOBI_CS, rows, 7.0)
+    print("jacobi_cs outside and inside its range:", out.tolist())
+    assert np.array_equal(out[:2], [[7.0, 7.0, 0.0]] * 2)
+    assert (out[2:, 2] == 1).all()
+    hold(lc.jacobi_check(rows[2:], out[2:]))
+
+
+SVD3_DEGENERATE = ("rank 1", "zero")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n in lc.svd3_cases() if n not in SVD3_DEGENERATE])
+def test_svd3(gpu, name):
+    cases = lc.svd3_cases()
+    hold(lc.svd3_check(cases[name], device_cases("svd3", orbx.LINALG_SVD3, cases, 7.0)[name]), 1.0, name)
+
+
+@pytest.mark.gpu
+def test_svd3_scaling_by_a_power_of_two_only_scales_w(gpu):
+    """Inside [2^-200, 2^200] nothing underflows or overflows: the rotations are those of the unscaled matrix, bit for bit."""
+    cases = lc.svd3_cases()
+    dev = device_cases("svd3", orbx.LINALG_SVD3, cases, 7.0)
+    base = dev["random"][:200]
+    for k in lc.SVD3_SCALES:
+        if k:
+            out = dev["random, scaled by 2^%d" % k]
+            assert np.array_equal(out[:, :9], base[:, :9]) and np.array_equal(out[:, 12:], base[:, 12:]), k
+            assert np.array_equal(out[:, 9:12], base[:, 9:12] * 2.0 ** k), k
+
+
+@pytest.mark.gpu
+def test_svd3_of_rank_1_and_zero(gpu):
+    """The reconstruction, w, V and finiteness hold; U is NOT orthonormal there (the header says so, DESIGN.md names the caller)."""
+    cases = lc.svd3_cases()
+    dev = device_cases("svd3", orbx.LINALG_SVD3, cases, 7.0)
+    for name in SVD3_DEGENERATE:
+        hold(lc.svd3_check(cases[name], dev[name], degenerate=True), 1.0, name)
+    z = dev["zero"][0]
+    assert not z[:12].any() and np.array_equal(z[12:].reshape(3, 3), np.eye(3))          # U = 0, w = 0, V = I
+    # already orthogonal columns: no rotation, U = (e_k, 0, 0)
+    d = dev["rank 1"][-3:]
+    for k in range(3):
+        U = d[k, :9].reshape(3, 3)
+        assert np.array_equal(U[:, 0], np.eye(3)[k]) and not U[:, 1:].any() and np.array_equal(d[k, 9:12], [3.0, 0.0, 0.0]), k
+    U = dev["rank 1"][:, :9].reshape(-1, 3, 3)
+    defect = np.sqrt(((np.einsum("nji,njk->nik", U, U) - np.eye(3)) ** 2).sum((1, 2)))
+    w = dev["rank 1"][:, 9:12]
+    print("rank 1: |U^T U - I| between %.3g and %.3g; w1 / w0 at most %.3g; exact zero w1 in %d of %d" % (
+        defect.min(), defect.max(), (w[:, 1] / w[:, 0]).max(), int((w[:, 1] == 0).sum()), len(w)))
+    assert (defect[w[:, 1] == 0] >= 1.0).all() and (w[:, 1] == 0).sum() >= 3
+
+
+NULL4_SPECIAL = ("zero",)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n in lc.null4_cases() if n not in NULL4_SPECIAL])
+def test_null_vector4(gpu, name):
+    cases = lc.null4_cases()
+    out = device_cases("null4", orbx.LINALG_NULL_VECTOR4, cases, 7.0)[name]
+    hold(lc.null4_check(cases[name], out, residual_only=name == "rank 2"), 1.0, name)
+
+
+@pytest.mark.gpu
+def test_null_vector4_of_the_zero_matrix(gpu):
+    """Outside the domain (the header): four NaNs, as in the restatement."""
+    out = device_cases("null4", orbx.LINALG_NULL_VECTOR4, lc.null4_cases(), 7.0)["zero"]
+    print("null_vector4 of the zero matrix:", out)
+    assert np.isnan(out).all() and np.isnan(lc.null_vector4_restated(np.zeros((1, 4, 4)))[0]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nc", [9, 12])
+def test_null_vector_sym(gpu, nc):
+    cases = lc.sym_cases(nc)
+    dev = device_cases("sym%d" % nc, orbx.LINALG_NULL_VECTOR_SYM9 if nc == 9 else orbx.LINALG_NULL_VECTOR_SYM12, cases, 7.0)
+    for name, A in cases.items():
+        hold(lc.sym_check(A, dev[name]), 1.0, "<%d> %s" % (nc, name))
+    # the zero matrix: no rotation is made, the first column is the shortest: e0 in every lane
+    assert np.array_equal(dev["zero"].reshape(4, nc), np.tile(np.eye(nc)[0], (4, 1)))
+    if nc == 9:      # a power of two scales nothing but the matrix
+        for k in lc.SYM_SCALES:
+            assert np.array_equal(dev["eight-point, noisy, scaled by 2^%d" % k], dev["eight-point, noisy"]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["ldlt6<false>", "ldlt6<true>", "ldlt7"])
+def test_ldlt(gpu, which):
+    """Residual at most 4 x that of the numpy LDLT on the same matrix plus one ulp (the rule of lba_dense_solve); a failed pivot
+    returns false with x as it was, wherever the numpy LDLT returns None."""
+    n = 7 if which == "ldlt7" else 6
+    damped = which != "ldlt6<false>"
+    op = {"ldlt6<false>": orbx.LINALG_LDLT6, "ldlt6<true>": orbx.LINALG_LDLT6_DAMPED, "ldlt7": orbx.LINALG_LDLT7}[which]
+    good = [s for s in lc.ldlt_systems(n) if damped or s[3] == 0.0]
+    bad = [s for s in lc.ldlt_failures(n) if damped or s[3] == 0.0]
+    assert len(good) >= 7 and len(bad) >= 2 * n + 8
+    out = orbx.debug_linalg(op, lc.ldlt_items(good + bad, damped), lc.PREFILL)
+    assert out.tobytes() == orbx.debug_linalg(op, lc.ldlt_items(good + bad, damped), lc.PREFILL).tobytes()
+    worst = 0.0
+    for (name, H, b, lam), o in zip(good, out):
+        assert o[n] == 1.0, (which, name)
+        M = H + lam * np.eye(n)
+        ref = lc.ldlt_dense(M, b)
+        got, bound = lc.ldlt_residual(M, o[:n], b), 4 * lc.ldlt_residual(M, ref, b) + EPS
+        worst = max(worst, got / bound)
+        assert got <= bound, (which, name, got, bound)
+    print("%s: %d systems, largest residual as a fraction of the bound %.3f" % (which, len(good), worst))
+    for (name, H, b, lam), o in zip(bad, out[len(good):]):
+        assert o[n] == 0.0 and (o[:n] == lc.PREFILL).all(), (which, name, o)
+        with np.errstate(all="ignore"):
+            assert lc.ldlt_dense(H + lam * np.eye(n), b) is None, (which, name)
+    if not damped:      # lambda is not read
+        items = lc.ldlt_items(good, True)
+        items[:, -1] = 1e6
+        assert np.array_equal(orbx.debug_linalg(op, items[:, :-1], lc.PREFILL), out[:len(good)])
+
+
+@pytest.mark.gpu
+def test_sum16(gpu):
+    v = lc.sum16_inputs()
+    out = orbx.debug_linalg(orbx.LINALG_SUM16, v, 7.0)
+    assert out.tobytes() == lc.sum16_xor_tree(v).tobytes()
+    groups = out.reshape(len(v), 4, 16)
+    assert all(len({x.tobytes() for x in g}) == 1 for w in groups for g in w)
+    assert len({g[0].tobytes() for w in groups for g in w}) == 4 * len(v)
+
+
+@pytest.mark.gpu
+def test_the_last_item_of_a_part_filled_wave_is_computed_and_nothing_past_it_is_written(gpu):
+    """n = 65 and n = 1: the per-thread kernels' bound check."""
+    x = np.linspace(1.0, 2.0, 65)
+    for n in (1, 63, 64, 65):
+        out = np.full(66, 7.0)
+        assert orbx.lib().orbx_debug_linalg(0, orbx.LINALG_RCP64, n, orbx._p(x), orbx._p(out)) == 0
+        assert (out[n:] == 7.0).all() and np.abs(out[:n] * x[:n] - 1).max() <= 4 * EPS, n
