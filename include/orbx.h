@@ -1243,9 +1243,9 @@ int orbx_optimize_sim3_batch(int device, int n_problems, int cap, const int32_t*
  *    the reference tests it before optimising, and max_iterations (the reference passes 10, :1433) bounds the work instead.
  *  - LinearSolverEigen factors the reduced system by a sparse Cholesky under a fill-reducing ordering; the device factors it
  *    densely in key-frame order.  Both are exact factorisations: results differ by rounding (tests/lba_cases.py measures it).
- *  - KannalaBrandt8 key frames and the EdgeSE3ProjectXYZToBody edges of a two-camera rig (:1383-1423) are not built: a key frame
- *    with model == ORBX_CAMERA_KB8 or camera2 != 0 is ORBX_E_BADARG.  Neither are the map-merge overload (:3567), the inertial
- *    variants and a batched entry.
+ *  - KannalaBrandt8 key frames and the EdgeSE3ProjectXYZToBody edges of a two-camera rig (:1383-1423) have an entry of their
+ *    own, orbx_local_bundle_adjustment_rig (below): here a key frame with model == ORBX_CAMERA_KB8 or camera2 != 0 is
+ *    ORBX_E_BADARG.  Not built: the map-merge overload (:3567), the inertial variants and a batched entry.
  * Capacity: ORBX_LBA_MAX_LOCAL optimised key frames; fixed key frames, points and edges are bounded by int32 and memory. */
 #define ORBX_LBA_MAX_LOCAL 128
 #define ORBX_LBA_DONE 0      /* optimised */
@@ -1332,7 +1332,8 @@ int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, co
  * A key frame or point without an edge comes back as the widened input; a problem without an edge is ORBX_LBA_EMPTY.  status and
  * stop_reason take the ORBX_LBA_* values.  Deliberate difference: the reference writes back the estimate's quaternion after
  * Sophus renormalises the float cast; the library returns the double estimate and leaves the cast to the caller.
- * KannalaBrandt8 key frames and second cameras are rejected as in the local BA; the inertial and map-merge variants are not built. */
+ * KannalaBrandt8 key frames and second cameras are rejected as in the local BA and go through orbx_bundle_adjustment_rig
+ * (below); the inertial and map-merge variants are not built. */
 #define ORBX_BA_MAX_KF 1024
 /* solver == 0: fewer optimised key frames take the one-workgroup solver.  Measured on the MI355X (profiles/gba_bench.json, ms per
  * call of 5 trials, blocked against one workgroup): 3.05 / 2.77 at 47 optimised key frames, 4.06 / 4.58 at 63, 8.17 / 20.99 at 127. */
@@ -1362,6 +1363,58 @@ int orbx_ba_dense_solve(int device, int n, const double* A, const double* b, dou
 /* The one-workgroup solver alone (the k_lba_solve of every local bundle adjustment, and of the full one below
  * ORBX_BA_BLOCKED_FROM_KF or under solver 2), for tests: the same contract, n a multiple of 6 in [6, 6 * ORBX_LBA_MAX_LOCAL]. */
 int orbx_lba_dense_solve(int device, int n, const double* A, const double* b, double* x, int32_t* ok);
+
+/* ---- bundle adjustments of KannalaBrandt8 key frames and two-camera rigs ------------------------------------ */
+
+/* The two bundle adjustments above for the key frames they reject: a KannalaBrandt8 left camera and / or a second camera
+ * (mpCamera2) whose observations become EdgeSE3ProjectXYZToBody edges (src/Optimizer.cc:1383-1423 in the local, :231-262 in the
+ * full bundle adjustment).  The Levenberg state, reductions, Schur complement, both linear solvers, statuses, counters and result
+ * structs are those of the sections above.  A problem is an orbx_lba_problem plus two parallel arrays:
+ *  - cams[n_local + n_fixed], one orbx_lba_rig_camera per key frame: k[4], the left camera's KB8 mvParameters[4..7] (read when
+ *    orbx_lba_keyframe::model == ORBX_CAMERA_KB8; fx fy cx cy stay in orbx_lba_keyframe); model2 and p2[8], the second camera's
+ *    model (ORBX_CAMERA_NONE, ORBX_CAMERA_PINHOLE, ORBX_CAMERA_KB8) and mvParameters (pinhole reads the first four); trl_q / trl_t,
+ *    GetRelativePoseTrl() as a quaternion x y z w and a translation, widened and normalised as SE3Quat(q, t) does.  The second
+ *    camera is used when orbx_lba_keyframe::camera2 != 0; otherwise model2, p2 and Trl are only checked for a valid model2.
+ *  - edge_camera[n_edges]: 0 an observation of the left camera, 1 of the second camera.
+ * Edge classes.  Camera 0 on a pinhole key frame: the monocular or stereo edge of the sections above, the same arithmetic bit
+ * for bit.  Camera 0 on a KB8 key frame: EdgeSE3ProjectXYZ with pCamera = KannalaBrandt8 -- error obs - project(T.map(Xw)), where
+ * project(Vector3d) narrows theta and psi to float (KannalaBrandt8.cpp:48-66; the device rounds the double atan2 once to float),
+ * Jacobians -projectJac R and -projectJac SE3deriv (KannalaBrandt8.cpp:149-184, all double).  Camera 1: EdgeSE3ProjectXYZToBody
+ * (OptimizableTypes.cpp:189-212) -- error through (mTrl * T).map(Xw), the product normalised as SE3Quat::operator* does;
+ * Xi = -projectJac(X_r) R(mTrl * T), Xj = -projectJac(X_r) R(mTrl) SE3deriv(X_l) with X_r = mTrl.map(T.map(Xw)); its camera is
+ * the key frame's second one, pinhole or KB8.  KB8 and body edges have two rows, information inv_sigma2 I, the monocular Huber
+ * delta and the gate 5.991; isDepthPositive() of a body edge is ((mTrl * T).map(X))[2] > 0.
+ * A (key frame, point) pair carries at most two edges, one per camera; both add into the pair's Hpl block, and the Schur
+ * complement takes every pair of edges of a point, the left x right terms on the diagonal included.
+ * projectJac divides by x^2 + y^2: a point on the optical axis of a KB8 camera gives NaN Jacobians here as in the reference.
+ * Deliberate difference: u_right >= 0 on a KB8 key frame is rejected.  The reference would build a pinhole
+ * EdgeStereoSE3ProjectXYZ from the KB8 parameters there, which no real map produces.
+ * A problem of pinhole key frames without second cameras returns the bits of the entries above. */
+#define ORBX_CAMERA_NONE (-1)
+typedef struct orbx_lba_rig_camera {
+  float k[4];          /* left camera, KB8: mvParameters[4..7] */
+  int32_t model2;      /* ORBX_CAMERA_NONE | ORBX_CAMERA_PINHOLE | ORBX_CAMERA_KB8 */
+  float p2[8];         /* second camera: fx fy cx cy k1 k2 k3 k4 */
+  float trl_q[4];      /* Trl: quaternion x y z w */
+  float trl_t[3];
+} orbx_lba_rig_camera;   /* 80 bytes */
+typedef struct orbx_lba_rig_problem {
+  orbx_lba_problem base;
+  const orbx_lba_rig_camera* cams;   /* [n_local + n_fixed] */
+  const uint8_t* edge_camera;        /* [n_edges] */
+} orbx_lba_rig_problem;
+/* Validation, before a device is touched, in this order.  Null pointers and negative counts (cams with any key frame, edge_camera
+ * with any edge); max_iterations; lambda_init; per key frame in list order: the model (pinhole or KB8), the pose, the quaternion,
+ * the camera parameters, finite KB8 k (KB8 key frames), a valid model2, camera2 != 0 with model2 == ORBX_CAMERA_NONE, the second
+ * camera's parameters finite with fx, fy > 0, Trl finite, Trl's quaternion non-zero (the last four when camera2 != 0), the fixed
+ * flag of the second group; the points; per edge in order: the indices, the grouping by point, edge_camera in {0, 1}, a key
+ * frame repeated for the same camera within a point, finite observations, a camera-1 edge on a key frame without camera2, a
+ * camera-1 edge with u_right >= 0, u_right >= 0 on a KB8 key frame; then the capacity (and, for the full one, the solver).
+ * Valid arguments without a device return ORBX_E_NODEVICE unless the call ends before the optimiser.  Two calls on the same
+ * input agree bit for bit. */
+int orbx_local_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_lba_params* params,
+                                     orbx_lba_result* result);
+int orbx_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_ba_params* params, orbx_ba_result* result);
 
 /* ---- new map points (local mapping)------------------------------------------------------------------- */
 

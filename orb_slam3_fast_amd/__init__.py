@@ -1314,6 +1314,85 @@ def BundleAdjustment(keyframes, points, edges, max_iterations=5, robust=True, la
     return out
 
 
+# ---- bundle adjustments of KannalaBrandt8 key frames and two-camera rigs
+CAMERA_NONE = -1
+LBA_RIG_CAMERA_DTYPE = np.dtype([("k", "<f4", (4,)), ("model2", "<i4"), ("p2", "<f4", (8,)), ("trl_q", "<f4", (4,)),
+                                 ("trl_t", "<f4", (3,))])
+assert LBA_RIG_CAMERA_DTYPE.itemsize == 80
+
+
+class _LbaRigProblem(C.Structure):   # orbx_lba_rig_problem
+    _fields_ = [("base", _LbaProblem), ("cams", C.c_void_p), ("edge_camera", C.c_void_p)]
+
+
+def lba_rig_cameras(n, k=None, model2=CAMERA_NONE, p2=None, trl_q=(0, 0, 0, 1), trl_t=(0, 0, 0)):
+    """orbx_lba_rig_camera records for n key frames: k = the left camera's KB8 mvParameters[4..7] ([4] for all or [n][4]), model2 and
+    p2 = the second camera's model (CAMERA_NONE / CAMERA_PINHOLE / CAMERA_KB8) and its eight mvParameters, trl_q (x y z w) / trl_t =
+    GetRelativePoseTrl().  Whether a key frame uses its second camera is lba_keyframes' camera2."""
+    c = np.zeros(int(n), LBA_RIG_CAMERA_DTYPE)
+    c["k"] = 0 if k is None else np.broadcast_to(np.asarray(k, np.float32), (len(c), 4))
+    c["model2"] = model2
+    c["p2"] = 0 if p2 is None else np.broadcast_to(np.asarray(p2, np.float32), (len(c), 8))
+    c["trl_q"] = np.broadcast_to(np.asarray(trl_q, np.float32), (len(c), 4))
+    c["trl_t"] = np.broadcast_to(np.asarray(trl_t, np.float32), (len(c), 3))
+    return c
+
+
+def _lba_rig_problem(kf, X, ed, cams, edge_camera, n_local):
+    cm = np.ascontiguousarray(cams, LBA_RIG_CAMERA_DTYPE).reshape(-1)
+    ec = np.ascontiguousarray(edge_camera, np.uint8).reshape(-1)
+    if len(cm) != len(kf) or len(ec) != len(ed):
+        raise ValueError("cams must have one record per key frame and edge_camera one entry per edge")
+    prob = _LbaRigProblem(_LbaProblem(_p(kf).value, _p(X).value, _p(ed).value, n_local, len(kf) - n_local, len(X), len(ed)),
+                          _p(cm).value, _p(ec).value)
+    return prob, (cm, ec)
+
+
+def LocalBundleAdjustmentRig(keyframes, cams, n_local, points, edges, edge_camera, max_iterations=10, lambda_init=0.0, stop=False,
+                             device=0):
+    """LocalBundleAdjustment for KannalaBrandt8 key frames and two-camera rigs (orbx_local_bundle_adjustment_rig): the arguments of
+    LocalBundleAdjustment plus cams = LBA_RIG_CAMERA_DTYPE records, one per key frame (lba_rig_cameras), and edge_camera [nE] uint8 (0
+    an observation of the left camera, 1 of the second one: an EdgeSE3ProjectXYZToBody edge).  keyframes["model"] may be CAMERA_KB8 and
+    keyframes["camera2"] says whether the second camera is used.  Returns LocalBundleAdjustment's dict."""
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ed = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    n_local = int(n_local)
+    prob, keep = _lba_rig_problem(kf, X, ed, cams, edge_camera, n_local)
+    poses, pts = np.zeros((max(n_local, 0), 7)), np.zeros((len(X), 3))
+    erase, depth, chi2 = np.zeros(len(ed), np.uint8), np.zeros(len(ed), np.uint8), np.zeros(len(ed))
+    prm = _LbaParams(int(max_iterations), int(bool(stop)), float(lambda_init))
+    res = _LbaResult(_p(poses).value, _p(pts).value, _p(erase).value, _p(chi2).value, _p(depth).value)
+    _check(lib().orbx_local_bundle_adjustment_rig(int(device), C.byref(prob), C.byref(prm), C.byref(res)))
+    out = dict(poses=poses, points=pts, erase=erase, chi2=chi2, depth_positive=depth)
+    for name in ("num_fixedKF", "num_OptKF", "num_MPs", "num_edges", "status", "iterations", "trials", "stop_reason", "chi2_initial",
+                 "chi2_final"):
+        out[name] = getattr(res, name)
+    out["lambda"] = res.lambda_
+    return out
+
+
+def BundleAdjustmentRig(keyframes, cams, points, edges, edge_camera, max_iterations=5, robust=True, lambda_init=0.0, stop=None,
+                        solver=0, device=0):
+    """BundleAdjustment for KannalaBrandt8 key frames and two-camera rigs (orbx_bundle_adjustment_rig): the arguments of
+    BundleAdjustment plus cams and edge_camera as LocalBundleAdjustmentRig takes them.  Returns BundleAdjustment's dict."""
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ed = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    if stop is not None and not (isinstance(stop, np.ndarray) and stop.dtype == np.int32 and stop.size == 1):
+        raise TypeError("stop must be None or a one-element int32 numpy array")
+    prob, keep = _lba_rig_problem(kf, X, ed, cams, edge_camera, len(kf))
+    poses, pts, chi2 = np.zeros((len(kf), 7)), np.zeros((len(X), 3)), np.zeros(len(ed))
+    prm = _BaParams(int(max_iterations), int(bool(robust)), float(lambda_init), int(solver), None if stop is None else _p(stop).value)
+    res = _BaResult(_p(poses).value, _p(pts).value, _p(chi2).value)
+    _check(lib().orbx_bundle_adjustment_rig(int(device), C.byref(prob), C.byref(prm), C.byref(res)))
+    out = dict(poses=poses, points=pts, chi2=chi2)
+    for name in ("status", "iterations", "trials", "stop_reason", "chi2_initial", "chi2_final"):
+        out[name] = getattr(res, name)
+    out["lambda"] = res.lambda_
+    return out
+
+
 def ba_dense_solve(A, b, device=0):
     """The blocked LDLT of the full bundle adjustment alone (orbx_ba_dense_solve): A [n][n] symmetric positive definite, b [n], in
     double.  Returns dict(x [n], ok); ok == 0: a pivot was <= 0 or not finite and x is the zeros it was created with."""

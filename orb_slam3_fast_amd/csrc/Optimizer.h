@@ -89,11 +89,19 @@ struct LbaKeyFrame {
   float q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0};   // GetPose(): Tcw as Sophus stores it (x y z w)
   float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
   int cameraModel = ORBX_CAMERA_PINHOLE;
-  bool hasCamera2 = false;                  // mpCamera2 != NULL (rejected by the library: include/orbx.h)
+  bool hasCamera2 = false;                  // mpCamera2 != NULL: the view goes through the rig entries (include/orbx.h)
   std::vector<orbx_keypoint> mvKeysUn;
   std::vector<float> mvuRight;              // per key point, < 0: monocular
   std::vector<float> mvInvLevelSigma2;
-  std::vector<int> mvpMapPoints;            // GetMapPointMatches(): per key point the map point's index, -1: none
+  std::vector<int> mvpMapPoints;            // GetMapPointMatches(): per key point the map point's index, -1: none (a rig: the
+                                            // NLeft left key points, then the right ones)
+  // KannalaBrandt8 key frames and two-camera rigs (defaults: a pinhole key frame without a second camera)
+  float kb8Left[4] = {0, 0, 0, 0};          // mpCamera's mvParameters[4..7] (cameraModel == ORBX_CAMERA_KB8; fx fy cx cy above)
+  int camera2Model = ORBX_CAMERA_NONE;      // mpCamera2's model
+  float camera2[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mpCamera2's mvParameters
+  float trl_q[4] = {0, 0, 0, 1}, trl_t[3] = {0, 0, 0};   // GetRelativePoseTrl()
+  int NLeft = -1;                           // a right observation's index counts from here
+  std::vector<orbx_keypoint> mvKeysRight;
 };
 struct LbaMapPoint {
   unsigned long mnId = 0;
@@ -102,7 +110,53 @@ struct LbaMapPoint {
   float pos[3] = {0, 0, 0};                 // GetWorldPos()
   std::vector<std::pair<int, int>> observations;   // GetObservations(): (key frame, left index; -1: right camera only), in the
                                                    // order the caller's map iterates
+  std::vector<int> rightIndex;                     // get<1>(mit->second) per observation, -1: none; empty: none at all
 };
+
+// mpCamera of KannalaBrandt8 or a second camera: the view belongs to the rig entries
+inline bool LbaIsRigKeyFrame(const LbaKeyFrame& k) { return k.cameraModel == ORBX_CAMERA_KB8 || k.hasCamera2; }
+inline orbx_lba_rig_camera LbaRigCamera(const LbaKeyFrame& k) {
+  orbx_lba_rig_camera c{};
+  for (int i = 0; i < 4; i++) { c.k[i] = k.kb8Left[i]; c.trl_q[i] = k.trl_q[i]; }
+  for (int i = 0; i < 3; i++) c.trl_t[i] = k.trl_t[i];
+  for (int i = 0; i < 8; i++) c.p2[i] = k.camera2[i];
+  c.model2 = k.camera2Model;
+  return c;
+}
+// The edges of one observation (:1301-1425, :170-270): the left key point's monocular or stereo edge, then -- with a second
+// camera -- the body edge of the right key point rightIndex - NLeft, at its own octave.  An observation of the right camera
+// alone yields the body edge only.  flat / point: the edge's indices; returns the edges appended.
+inline int LbaObservationEdges(const LbaKeyFrame& k, int left, int right, int flat, int point, std::vector<orbx_lba_edge>& edges,
+                               std::vector<uint8_t>& edgeCam) {
+  int n = 0;
+  if (left != -1) {
+    const orbx_keypoint& kp = k.mvKeysUn.at((size_t)left);
+    orbx_lba_edge e{};
+    e.kf = flat;
+    e.point = point;
+    e.u = kp.x;
+    e.v = kp.y;
+    e.u_right = k.mvuRight.at((size_t)left) < 0 ? -1.f : k.mvuRight[(size_t)left];
+    e.inv_sigma2 = k.mvInvLevelSigma2.at((size_t)kp.octave);
+    edges.push_back(e);
+    edgeCam.push_back(0);
+    n++;
+  }
+  if (k.hasCamera2 && right != -1) {
+    const orbx_keypoint& kp = k.mvKeysRight.at((size_t)(right - k.NLeft));
+    orbx_lba_edge e{};
+    e.kf = flat;
+    e.point = point;
+    e.u = kp.x;
+    e.v = kp.y;
+    e.u_right = -1.f;
+    e.inv_sigma2 = k.mvInvLevelSigma2.at((size_t)kp.octave);
+    edges.push_back(e);
+    edgeCam.push_back(1);
+    n++;
+  }
+  return n;
+}
 struct LocalMapView {
   std::vector<LbaKeyFrame> keyFrames;
   std::vector<LbaMapPoint> mapPoints;
@@ -121,6 +175,9 @@ struct LbaGraph {
   std::vector<float> points;
   std::vector<orbx_lba_edge> edges;
   std::vector<std::pair<int, int>> edgePair;   // per edge: (key frame, map point) of the view
+  std::vector<orbx_lba_rig_camera> cams;       // per record of kfs, and per edge its camera: the rig entry's arrays
+  std::vector<uint8_t> edgeCam;
+  bool rig = false;                            // a key frame of the graph is KannalaBrandt8 or has a second camera
 };
 // What the caller applies: SetPose / SetWorldPos (then UpdateNormalAndDepth) and, per vToErase pair, EraseMapPointMatch /
 // EraseObservation.
@@ -129,7 +186,7 @@ struct LbaUpdate {
   std::vector<float> poses;                  // [7] each: q (x y z w), t -- the float casts of :1498
   std::vector<int> mapPoints;                // lLocalMapPoints
   std::vector<float> positions;              // [3] each: the float cast of :1511
-  std::vector<std::pair<int, int>> vToErase; // (key frame, map point): monocular edges first, then stereo, as :1440-1474
+  std::vector<std::pair<int, int>> vToErase; // (key frame, map point): monocular edges first, then body, then stereo, as :1440-1474
   bool optimized = false;                    // false: aborted, stopped or nothing to optimise -- nothing to apply
   orbx_lba_result result{};
 };
@@ -185,25 +242,21 @@ inline LbaGraph GatherLocalGraph(const LocalMapView& m) {
     r.camera2 = k.hasCamera2 ? 1 : 0;
     flat[(size_t)i] = (int)g.kfs.size();
     g.kfs.push_back(r);
+    g.cams.push_back(LbaRigCamera(k));
+    if (LbaIsRigKeyFrame(k)) g.rig = true;
   };
   for (int i : g.localKFs) add(i, m.keyFrames[(size_t)i].mnId == m.initKFid);
   for (int i : g.fixedKFs) add(i, true);
   for (size_t n = 0; n < g.localMPs.size(); n++) {
     const LbaMapPoint& p = m.mapPoints[(size_t)g.localMPs[n]];
     g.points.insert(g.points.end(), p.pos, p.pos + 3);
-    for (const std::pair<int, int>& ob : p.observations) {
+    for (size_t o = 0; o < p.observations.size(); o++) {
+      const std::pair<int, int>& ob = p.observations[o];
       const LbaKeyFrame& k = m.keyFrames[(size_t)ob.first];
-      if (k.bad || k.map != cur.map || ob.second == -1 || flat[(size_t)ob.first] < 0) continue;
-      const orbx_keypoint& kp = k.mvKeysUn.at((size_t)ob.second);
-      orbx_lba_edge e{};
-      e.kf = flat[(size_t)ob.first];
-      e.point = (int)n;
-      e.u = kp.x;
-      e.v = kp.y;
-      e.u_right = k.mvuRight.at((size_t)ob.second) < 0 ? -1.f : k.mvuRight[(size_t)ob.second];
-      e.inv_sigma2 = k.mvInvLevelSigma2.at((size_t)kp.octave);
-      g.edges.push_back(e);
-      g.edgePair.push_back({ob.first, g.localMPs[n]});
+      if (k.bad || k.map != cur.map || flat[(size_t)ob.first] < 0) continue;
+      const int right = p.rightIndex.empty() ? -1 : p.rightIndex.at(o);
+      const int added = LbaObservationEdges(k, ob.second, right, flat[(size_t)ob.first], (int)n, g.edges, g.edgeCam);
+      for (int a = 0; a < added; a++) g.edgePair.push_back({ob.first, g.localMPs[n]});
     }
   }
   return g;
@@ -228,6 +281,9 @@ struct GbaGraph {
   std::vector<float> points;
   std::vector<orbx_lba_edge> edges;
   std::vector<std::pair<int, int>> edgePair;   // per edge: (key frame, map point) of the view
+  std::vector<orbx_lba_rig_camera> cams;       // per record, and per edge its camera: the rig entry's arrays
+  std::vector<uint8_t> edgeCam;
+  bool rig = false;                            // a vertex is KannalaBrandt8 or has a second camera
 };
 // What the caller applies, per key frame and per map point: applyDirectly (nLoopKF == the origin key frame's id): SetPose /
 // SetWorldPos + UpdateNormalAndDepth; otherwise mTcwGBA / mPosGBA and mnBAGlobalForKF = nLoopKF.
@@ -265,6 +321,8 @@ inline GbaGraph GatherGlobalGraph(const GlobalMapView& m) {
     vertex[(size_t)i] = (int)g.kfs.size();
     g.kfs.push_back(i);
     g.records.push_back(r);
+    g.cams.push_back(LbaRigCamera(k));
+    if (LbaIsRigKeyFrame(k)) g.rig = true;
     if (k.mnId > g.maxKFid) g.maxKFid = k.mnId;
   }
   g.notIncluded.assign((size_t)nMP, 0);
@@ -273,25 +331,19 @@ inline GbaGraph GatherGlobalGraph(const GlobalMapView& m) {
     if (p.bad) continue;
     const size_t firstEdge = g.edges.size();
     int nEdges = 0;
-    for (const std::pair<int, int>& ob : p.observations) {
+    for (size_t o = 0; o < p.observations.size(); o++) {
+      const std::pair<int, int>& ob = p.observations[o];
       const LbaKeyFrame& k = m.keyFrames.at((size_t)ob.first);
       if (k.bad || k.mnId > g.maxKFid || vertex[(size_t)ob.first] < 0) continue;
       nEdges++;
-      if (ob.second == -1) continue;
-      const orbx_keypoint& kp = k.mvKeysUn.at((size_t)ob.second);
-      orbx_lba_edge e{};
-      e.kf = vertex[(size_t)ob.first];
-      e.point = (int)g.mps.size();
-      e.u = kp.x;
-      e.v = kp.y;
-      e.u_right = k.mvuRight.at((size_t)ob.second) < 0 ? -1.f : k.mvuRight[(size_t)ob.second];
-      e.inv_sigma2 = k.mvInvLevelSigma2.at((size_t)kp.octave);
-      g.edges.push_back(e);
-      g.edgePair.push_back({ob.first, j});
+      const int right = p.rightIndex.empty() ? -1 : p.rightIndex.at(o);
+      const int added = LbaObservationEdges(k, ob.second, right, vertex[(size_t)ob.first], (int)g.mps.size(), g.edges, g.edgeCam);
+      for (int a = 0; a < added; a++) g.edgePair.push_back({ob.first, j});
     }
     if (nEdges == 0) {
       g.notIncluded[(size_t)j] = 1;
       g.edges.resize(firstEdge);
+      g.edgeCam.resize(firstEdge);
       g.edgePair.resize(firstEdge);
       continue;
     }
@@ -334,7 +386,12 @@ class Optimizer {
     u.result.erase = erase.data();
     u.result.chi2 = chi2.data();
     u.result.depth_positive = depth.data();
-    if (orbx_local_bundle_adjustment(map.device, &prob, &prm, &u.result) != ORBX_OK)
+    orbx_lba_rig_problem rig{};   // a view with a KannalaBrandt8 or two-camera key frame: the rig entry; other views keep their call
+    rig.base = prob;
+    rig.cams = g.cams.data();
+    rig.edge_camera = g.edgeCam.data();
+    if ((g.rig ? orbx_local_bundle_adjustment_rig(map.device, &rig, &prm, &u.result)
+               : orbx_local_bundle_adjustment(map.device, &prob, &prm, &u.result)) != ORBX_OK)
       throw std::runtime_error(std::string("LocalBundleAdjustment: ") + orbx_last_error());
     u.result.poses = u.result.points = u.result.chi2 = nullptr;   // the buffers end with this call
     u.result.erase = u.result.depth_positive = nullptr;
@@ -344,9 +401,11 @@ class Optimizer {
     u.mapPoints = g.localMPs;
     for (double v : poses) u.poses.push_back((float)v);
     for (double v : points) u.positions.push_back((float)v);
-    for (int pass = 0; pass < 2; pass++)   // vpEdgesMono, then vpEdgesStereo
-      for (size_t i = 0; i < g.edges.size(); i++)
-        if (erase[i] && (g.edges[i].u_right < 0) == (pass == 0)) u.vToErase.push_back(g.edgePair[i]);
+    for (int pass = 0; pass < 3; pass++)   // vpEdgesMono, vpEdgesBody, then vpEdgesStereo
+      for (size_t i = 0; i < g.edges.size(); i++) {
+        const int cls = g.edgeCam[i] ? 1 : g.edges[i].u_right < 0 ? 0 : 2;
+        if (erase[i] && cls == pass) u.vToErase.push_back(g.edgePair[i]);
+      }
     return u;
   }
 
@@ -374,7 +433,12 @@ class Optimizer {
     std::vector<double> poses(7 * g.kfs.size()), points(3 * g.mps.size());
     u.result.poses = poses.data();
     u.result.points = points.data();
-    if (orbx_bundle_adjustment(map.device, &prob, &prm, &u.result) != ORBX_OK)
+    orbx_lba_rig_problem rig{};   // as in LocalBundleAdjustment
+    rig.base = prob;
+    rig.cams = g.records.empty() ? nullptr : g.cams.data();
+    rig.edge_camera = g.edgeCam.data();
+    if ((g.rig ? orbx_bundle_adjustment_rig(map.device, &rig, &prm, &u.result)
+               : orbx_bundle_adjustment(map.device, &prob, &prm, &u.result)) != ORBX_OK)
       throw std::runtime_error(std::string("GlobalBundleAdjustemnt: ") + orbx_last_error());
     u.result.poses = u.result.points = nullptr;   // the buffers end with this call
     if (u.result.status == ORBX_LBA_EMPTY) return u;

@@ -11,17 +11,26 @@ static_assert(orbx::kBaNB % 6 == 0, "a key frame's rows stay in one block column
 
 using namespace orbx;
 
-extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_ba_params* params,
-                                      orbx_ba_result* result) {
+namespace {
+
+// both entries; rig: cams / edgeCam belong to the problem
+int bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_rig_camera* cams, const uint8_t* edgeCam, bool rig,
+                      const orbx_ba_params* params, orbx_ba_result* result) {
   if (!problem || !params || !result) return fail(ORBX_E_BADARG, "null argument or negative count");
   const orbx_lba_problem& p = *problem;
   orbx_ba_result& r = *result;
   if (p.n_local < 0 || p.n_fixed < 0 || p.n_points < 0 || p.n_edges < 0 || (long long)p.n_local + p.n_fixed > INT_MAX ||
       ((p.n_local || p.n_fixed) && !p.keyframes) || (p.n_points && !p.points) || (p.n_edges && !p.edges) ||
-      ((p.n_local || p.n_fixed) && !r.poses) || (p.n_points && !r.points))
+      ((p.n_local || p.n_fixed) && !r.poses) || (p.n_points && !r.points) ||
+      (rig && (((p.n_local || p.n_fixed) && !cams) || (p.n_edges && !edgeCam))))
     return fail(ORBX_E_BADARG, "null argument or negative count");
+  static const orbx_lba_rig_camera noCams{};   // a rig problem without a key frame still takes the rig checks
+  static const uint8_t noEdgeCam = 0;
+  if (rig && !cams) cams = &noCams;
+  if (rig && !edgeCam) edgeCam = &noEdgeCam;
   LbaLayout g;
-  if (const char* err = lba_graph_error(p, params->max_iterations, params->lambda_init, g)) return fail(ORBX_E_BADARG, err);
+  if (const char* err = lba_graph_error(p, params->max_iterations, params->lambda_init, g, cams, edgeCam))
+    return fail(ORBX_E_BADARG, err);
   if (g.nOpt > ORBX_BA_MAX_KF) return fail(ORBX_E_BADARG, "more than ORBX_BA_MAX_KF key frames to optimise");
   if (params->solver < 0 || params->solver > 2) return fail(ORBX_E_BADARG, "solver outside [0, 2]");
   if (params->solver == 2 && g.nOpt > ORBX_LBA_MAX_LOCAL)
@@ -42,6 +51,8 @@ extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem* proble
     cfg.deltaStereo = sqrt(7.815);
     cfg.stopFlag = params->stop_flag;
     cfg.nPoses = nKF;
+    cfg.cams = cams;
+    cfg.edgeCam = edgeCam;
     const int rc = lba_optimise(device, p, g, cfg, run);
     if (rc != ORBX_OK) return rc;
   }
@@ -49,6 +60,19 @@ extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem* proble
   r.lambda = run.lambda; r.chi2_initial = run.chiInitial; r.chi2_final = run.chiFinal;
   r.iterations = run.iterations; r.trials = run.trials; r.stop_reason = run.stopReason;
   return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_ba_params* params,
+                                      orbx_ba_result* result) {
+  return bundle_adjustment(device, problem, nullptr, nullptr, false, params, result);
+}
+
+extern "C" int orbx_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_ba_params* params,
+                                          orbx_ba_result* result) {
+  if (!problem) return fail(ORBX_E_BADARG, "null argument or negative count");
+  return bundle_adjustment(device, &problem->base, problem->cams, problem->edge_camera, true, params, result);
 }
 
 extern "C" int orbx_ba_dense_solve(int device, int n, const double* A, const double* b, double* x, int32_t* ok) {

@@ -10,6 +10,7 @@
 static_assert(sizeof(orbx_lba_keyframe) == 60, "orbx_lba_keyframe");
 static_assert(sizeof(orbx_lba_edge) == 24, "orbx_lba_edge");
 static_assert(sizeof(orbx_lba_params) == 12, "orbx_lba_params");
+static_assert(sizeof(orbx_lba_rig_camera) == 80, "orbx_lba_rig_camera");
 
 using namespace orbx;
 
@@ -28,10 +29,31 @@ const char* lba_keyframe_error(const orbx_lba_keyframe& k, bool secondGroup) {
   return nullptr;
 }
 
-// the edges: indices, order and values; fills the points' edge ranges
-const char* lba_edges_error(const orbx_lba_problem& p, int nKF, std::vector<int>& ptStart) {
+// a key frame of the rig entries: either camera model on the left, a second camera or none
+const char* lba_rig_keyframe_error(const orbx_lba_keyframe& k, const orbx_lba_rig_camera& c, bool secondGroup) {
+  if (k.model != ORBX_CAMERA_PINHOLE && k.model != ORBX_CAMERA_KB8) return "camera model is not pinhole or KannalaBrandt8";
+  if (!finite_all(k.q, 4) || !finite_all(k.t, 3)) return "key-frame pose not finite";
+  if (k.q[0] == 0 && k.q[1] == 0 && k.q[2] == 0 && k.q[3] == 0) return "key-frame quaternion is zero";
+  const float cam[5] = {k.fx, k.fy, k.cx, k.cy, k.bf};
+  if (!finite_all(cam, 5) || !(k.fx > 0) || !(k.fy > 0)) return "camera parameters not finite, or fx / fy not positive";
+  if (k.model == ORBX_CAMERA_KB8 && !finite_all(c.k, 4)) return "KannalaBrandt8 parameters of the left camera not finite";
+  if (c.model2 != ORBX_CAMERA_NONE && c.model2 != ORBX_CAMERA_PINHOLE && c.model2 != ORBX_CAMERA_KB8)
+    return "second camera model is not none, pinhole or KannalaBrandt8";
+  if (k.camera2) {
+    if (c.model2 == ORBX_CAMERA_NONE) return "key frame with camera2 set and no second camera model";
+    if (!finite_all(c.p2, 8) || !(c.p2[0] > 0) || !(c.p2[1] > 0)) return "second camera parameters not finite, or fx / fy not positive";
+    if (!finite_all(c.trl_q, 4) || !finite_all(c.trl_t, 3)) return "Trl not finite";
+    if (c.trl_q[0] == 0 && c.trl_q[1] == 0 && c.trl_q[2] == 0 && c.trl_q[3] == 0) return "Trl quaternion is zero";
+  }
+  if (secondGroup && !k.fixed) return "a key frame behind the local ones is not marked fixed";
+  return nullptr;
+}
+
+// the edges: indices, order and values; fills the points' edge ranges.  edgeCam != nullptr (the rig entries): a key frame may
+// appear once per camera within a point
+const char* lba_edges_error(const orbx_lba_problem& p, int nKF, std::vector<int>& ptStart, const uint8_t* edgeCam) {
   ptStart.assign((size_t)p.n_points + 1, 0);
-  std::vector<int> seen((size_t)nKF, -1);   // the last point that used the key frame
+  std::vector<int> seen((size_t)nKF * (edgeCam ? 2 : 1), -1);   // the last point that used the key frame (rig: and the camera)
   int last = 0;
   for (int i = 0; i < p.n_edges; i++) {
     const orbx_lba_edge& e = p.edges[i];
@@ -39,10 +61,18 @@ const char* lba_edges_error(const orbx_lba_problem& p, int nKF, std::vector<int>
     if (e.point < 0 || e.point >= p.n_points) return "edge point index outside [0, n_points)";
     if (e.point < last) return "edges not grouped by ascending point";
     last = e.point;
-    if (seen[e.kf] == e.point) return "key frame repeated among the observations of a point";
-    seen[e.kf] = e.point;
+    const int cam = edgeCam ? edgeCam[i] : 0;
+    if (cam > 1) return "edge camera is not 0 or 1";
+    int& last_seen = seen[edgeCam ? 2 * (size_t)e.kf + cam : (size_t)e.kf];
+    if (last_seen == e.point)
+      return edgeCam ? "key frame repeated for the same camera among the observations of a point"
+                     : "key frame repeated among the observations of a point";
+    last_seen = e.point;
     const float v[4] = {e.u, e.v, e.u_right, e.inv_sigma2};
     if (!finite_all(v, 4)) return "observation not finite";
+    if (cam == 1 && !p.keyframes[e.kf].camera2) return "second-camera edge on a key frame without a second camera";
+    if (cam == 1 && !(e.u_right < 0)) return "second-camera edge with u_right >= 0";
+    if (edgeCam && p.keyframes[e.kf].model == ORBX_CAMERA_KB8 && !(e.u_right < 0)) return "u_right >= 0 on a KannalaBrandt8 key frame";
     ptStart[(size_t)e.point + 1]++;
   }
   for (int q = 0; q < p.n_points; q++) ptStart[(size_t)q + 1] += ptStart[q];
@@ -53,18 +83,21 @@ const char* lba_edges_error(const orbx_lba_problem& p, int nKF, std::vector<int>
 
 namespace orbx {
 
-const char* lba_graph_error(const orbx_lba_problem& p, int maxIterations, float lambdaInit, LbaLayout& g) {
+const char* lba_graph_error(const orbx_lba_problem& p, int maxIterations, float lambdaInit, LbaLayout& g,
+                            const orbx_lba_rig_camera* cams, const uint8_t* edgeCam) {
   if (maxIterations < 1 || maxIterations > kLbaMaxIterations) return "max_iterations outside [1, 1000000]";
   if (!std::isfinite(lambdaInit)) return "lambda_init not finite";
   const int nKF = p.n_local + p.n_fixed;
   g.fixedLocal = 0;
   for (int i = 0; i < nKF; i++) {
-    if (const char* err = lba_keyframe_error(p.keyframes[i], i >= p.n_local)) return err;
+    if (const char* err = cams ? lba_rig_keyframe_error(p.keyframes[i], cams[i], i >= p.n_local)
+                               : lba_keyframe_error(p.keyframes[i], i >= p.n_local))
+      return err;
     if (i < p.n_local && p.keyframes[i].fixed) g.fixedLocal = 1;
   }
   for (int i = 0; i < p.n_points; i++)
     if (!finite_all(p.points + 3 * (size_t)i, 3)) return "world position not finite";
-  if (const char* err = lba_edges_error(p, nKF, g.ptStart)) return err;
+  if (const char* err = lba_edges_error(p, nKF, g.ptStart, edgeCam)) return err;
   // the reduced system's row blocks: the local key frames that are not fixed and have an edge, in list order
   g.slot.assign((size_t)nKF, -1);
   g.deg.assign((size_t)nKF, 0);
@@ -127,6 +160,11 @@ int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, cons
   pk.in(a.ptStart, g.ptStart.data(), nP + 1, 16);
   pk.in(a.kfStart, kfStart.data(), (size_t)nOpt + 1, 16);
   pk.in(a.kfEdges, kfEdges.data(), kfEdges.size(), 16);
+  if (cfg.cams) {   // the rig chain: the kernels choose by a.cams
+    pk.in(a.cams, cfg.cams, (size_t)nKF, 16);
+    pk.in(a.edgeCam, cfg.edgeCam, nE, 16);
+    pk.area(a.trl, (size_t)nKF, 16);
+  }
   for (int c = 0; c < 2; c++) {
     pk.area(a.pose[c], (size_t)nKF, 16);
     pk.area(a.X[c], 3 * nP, 16);
@@ -190,17 +228,26 @@ int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, cons
 
 }  // namespace orbx
 
-extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params,
-                                            orbx_lba_result* result) {
+namespace {
+
+// both local entries; cams / edgeCam != nullptr: the rig entry
+int local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_rig_camera* cams, const uint8_t* edgeCam,
+                            bool rig, const orbx_lba_params* params, orbx_lba_result* result) {
   if (!problem || !params || !result) return fail(ORBX_E_BADARG, "null argument or negative count");
   const orbx_lba_problem& p = *problem;
   orbx_lba_result& r = *result;
   if (p.n_local < 0 || p.n_fixed < 0 || p.n_points < 0 || p.n_edges < 0 || (long long)p.n_local + p.n_fixed > INT_MAX ||
       ((p.n_local || p.n_fixed) && !p.keyframes) || (p.n_points && !p.points) || (p.n_edges && !p.edges) ||
-      (p.n_local && !r.poses) || (p.n_points && !r.points) || (p.n_edges && (!r.erase || !r.chi2 || !r.depth_positive)))
+      (p.n_local && !r.poses) || (p.n_points && !r.points) || (p.n_edges && (!r.erase || !r.chi2 || !r.depth_positive)) ||
+      (rig && (((p.n_local || p.n_fixed) && !cams) || (p.n_edges && !edgeCam))))
     return fail(ORBX_E_BADARG, "null argument or negative count");
+  static const orbx_lba_rig_camera noCams{};   // a rig problem without a key frame still takes the rig checks
+  static const uint8_t noEdgeCam = 0;
+  if (rig && !cams) cams = &noCams;
+  if (rig && !edgeCam) edgeCam = &noEdgeCam;
   LbaLayout g;
-  if (const char* err = lba_graph_error(p, params->max_iterations, params->lambda_init, g)) return fail(ORBX_E_BADARG, err);
+  if (const char* err = lba_graph_error(p, params->max_iterations, params->lambda_init, g, cams, edgeCam))
+    return fail(ORBX_E_BADARG, err);
   if (g.nOpt > ORBX_LBA_MAX_LOCAL) return fail(ORBX_E_BADARG, "more than ORBX_LBA_MAX_LOCAL key frames to optimise");
   r.num_fixedKF = p.n_fixed + g.fixedLocal;
   r.num_OptKF = p.n_local;
@@ -220,6 +267,8 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
     cfg.deltaMono = sqrt(5.991);     // narrowed as the reference's (Optimizer.cc:1281-1282)
     cfg.deltaStereo = sqrt(7.815);
     cfg.nPoses = p.n_local;
+    cfg.cams = cams;
+    cfg.edgeCam = edgeCam;
     rc = lba_optimise(device, p, g, cfg, run);
     if (rc != ORBX_OK) return rc;
   }
@@ -227,6 +276,19 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* 
   r.lambda = run.lambda; r.chi2_initial = run.chiInitial; r.chi2_final = run.chiFinal;
   r.iterations = run.iterations; r.trials = run.trials; r.stop_reason = run.stopReason;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_lba_params* params,
+                                            orbx_lba_result* result) {
+  return local_bundle_adjustment(device, problem, nullptr, nullptr, false, params, result);
+}
+
+extern "C" int orbx_local_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_lba_params* params,
+                                                orbx_lba_result* result) {
+  if (!problem) return fail(ORBX_E_BADARG, "null argument or negative count");
+  return local_bundle_adjustment(device, &problem->base, problem->cams, problem->edge_camera, true, params, result);
 }
 
 // k_lba_solve on a caller's matrix: the argument record holds what the kernel touches (n, S, bs, xp, st) and nothing else

@@ -13,6 +13,7 @@ constexpr int kLbaAll = 9;    // per edge: the point's 3 x 3 block (upper triang
 constexpr int kLbaHpl = 18;   // per edge: the 6 x 3 pose-point block, row-major
 
 struct LbaPose { double q[4], t[3]; };
+struct LbaRigTrl { LbaPose T; double R[3][3]; };   // SE3Quat(Trl) normalised, and its toRotationMatrix
 
 // The optimiser's state (optimization_algorithm_levenberg.cpp), written by k_lba_decide's thread 0 only.  `cur` names the copy
 // of the estimates and of the linear system (0 / 1) that belongs to the current estimate; a trial is built in the other copy.
@@ -59,6 +60,12 @@ struct LbaArgs {
   int robust;                     // 0: no robust kernel (rho' = 1, the chi2 is the plain sum)
   int blocked;                    // the linear solve: 0 k_lba_solve (n <= 6 ORBX_LBA_MAX_LOCAL), 1 the blocked LDLT of orbx_ba.hip
   double deltaMono, deltaStereo;  // Huber deltas, already narrowed to float and widened as the reference holds them
+  // The rig entries only.  cams == nullptr is the pinhole chain, which reads none of these, and the launches choose the kernels
+  // by it: every site that fills an LbaArgs or an LbaConfig value-initialises it (`LbaArgs a{}`, `LbaConfig cfg{}`), and the old
+  // entries leave these fields alone.  A record built any other way must set cams = nullptr itself.
+  const orbx_lba_rig_camera* cams;   // [nKF]
+  const uint8_t* edgeCam;            // [nE] 0 left, 1 second camera
+  LbaRigTrl* trl;                    // [nKF] mTrl as the edges hold it, written by k_lba_rig_init
 };
 
 // ---- the host side the two bundle adjustments' entries share (orbx_api_lba.hip)
@@ -79,6 +86,8 @@ struct LbaConfig {
   float deltaMono, deltaStereo;        // narrowed, as the reference's thHuber* are floats
   const volatile int32_t* stopFlag;    // nullptr: never asked
   int nPoses;                          // the first nPoses key frames come back
+  const orbx_lba_rig_camera* cams;     // the rig entries: the kernels of the rig chain; nullptr: the pinhole chain
+  const uint8_t* edgeCam;
 };
 
 // outputs of a run; chi2 / erase / depthPos may be nullptr
@@ -93,13 +102,16 @@ struct LbaRun {
 };
 
 // every check of a problem that needs no device, in the order the entries report them; fills g
-const char* lba_graph_error(const orbx_lba_problem& p, int maxIterations, float lambdaInit, LbaLayout& g);
+// cams != nullptr: the checks of the rig entries (KB8 key frames, second cameras, one edge per camera and pair)
+const char* lba_graph_error(const orbx_lba_problem& p, int maxIterations, float lambdaInit, LbaLayout& g,
+                            const orbx_lba_rig_camera* cams = nullptr, const uint8_t* edgeCam = nullptr);
 void lba_passthrough(const orbx_lba_problem& p, int nPoses, LbaRun& r);   // the widened inputs, every counter zero
 // upload, the chain of trials (the stop flag asked in front of the first and after each), download
 int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, const LbaConfig& cfg, LbaRun& r);
 
 // the chain on the null stream (orbx_lba.hip)
-hipError_t launch_lba_init(const LbaArgs& a);       // estimates from the inputs, the state, x = 0
+// a.cams != nullptr: k_lba_linearize_rig, k_lba_schur_rig and k_lba_finish_rig take the places of the pinhole kernels
+hipError_t launch_lba_init(const LbaArgs& a);       // estimates from the inputs, the state, x = 0 (rig: and every mTrl)
 hipError_t launch_lba_evaluate(const LbaArgs& a);   // linearise at the estimate (stage 0) or the trial, reduce, decide
 hipError_t launch_lba_trial(const LbaArgs& a);      // Dinv, Schur complement, factorisation and solve, back-substitution, oplus
 hipError_t launch_lba_finish(const LbaArgs& a);     // classification and outputs

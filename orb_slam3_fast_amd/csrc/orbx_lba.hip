@@ -15,11 +15,14 @@
 //   k_lba_finish      classification at the held chi2 and the final depth, the outputs
 // The full bundle adjustment (Optimizer::BundleAdjustment, :47-372; orbx_api_ba.hip) runs the same chain: LbaArgs carries what it
 // does differently -- the robust kernel optional, its own Huber deltas, and the blocked LDLT of orbx_ba.hip in place of k_lba_solve.
+// The rig entries (KannalaBrandt8 key frames, second cameras: orbx_local_bundle_adjustment_rig, orbx_bundle_adjustment_rig) swap
+// three kernels, chosen on the host: k_lba_linearize_rig (the edge class per thread; a left pinhole edge runs k_lba_linearize's
+// code), k_lba_schur_rig (a (key frame, point) pair may carry one edge per camera) and k_lba_finish_rig (a body edge's depth).
 // Every sum has a fixed order (serial in edge order, a strided serial sum plus a fixed tree, or wave_sum's butterfly) and there
 // is no atomic: two calls on the same input agree bit for bit.
 #include "orbx_lba.h"
 #include "orbx_ba.h"
-#include "orbx_pose.h"
+#include "orbx_kb8_edge.h"
 
 namespace {
 
@@ -91,21 +94,15 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_init(LbaArgs A) {
   }
 }
 
-__global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
-  const int ei = blockIdx.x * kLbaBS + threadIdx.x;
-  if (ei >= A.nE) return;
-  const LbaState& st = *A.st;
-  const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
-  const orbx_lba_edge E = A.edges[ei];
-  const orbx_lba_keyframe K = A.kfs[E.kf];
-  const LbaPose P = A.pose[tgt][E.kf];
-  const double X[3] = {A.X[tgt][3 * (size_t)E.point], A.X[tgt][3 * (size_t)E.point + 1], A.X[tgt][3 * (size_t)E.point + 2]};
-  double Xc[3], e[3], chi;
+// a pinhole edge of the left camera (mono: EdgeSE3ProjectXYZ, otherwise g2o::EdgeStereoSE3ProjectXYZ): error, chi2, both Jacobians
+__device__ __forceinline__ void lba_pinhole_edge(const orbx_lba_keyframe& K, const orbx_lba_edge& E, const LbaPose& P, const double* X,
+                                                 double e[3], double& chi, double Jp[3][6], double Jl[3][3]) {
+  double Xc[3];
   lba_error(K, E, P, X, Xc, e, chi);
   const bool mono = E.u_right < 0.f;
   const double fx = (double)K.fx, fy = (double)K.fy, bf = (double)K.bf;
   const double x = Xc[0], y = Xc[1], z = Xc[2];
-  double R[3][3], Jp[3][6], Jl[3][3];
+  double R[3][3];
   quat_to_R(P.q, R);
   if (mono) {   // EdgeSE3ProjectXYZ::linearizeOplus: -projectJac * R, -projectJac * SE3deriv
     const double a = fx / z, c = -fx * x / (z * z), a1 = fy / z, c1 = -fy * y / (z * z);
@@ -131,6 +128,12 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
     Jp[2][0] = Jp[0][0] - bf * y / z_2; Jp[2][1] = Jp[0][1] + bf * x / z_2; Jp[2][2] = Jp[0][2]; Jp[2][3] = Jp[0][3]; Jp[2][4] = 0;
     Jp[2][5] = Jp[0][5] - bf / z_2;
   }
+}
+
+// the robust weight of an edge and its terms of Hpp / bp, Hll / bl, Hpl (rows: 2 or 3; an unused third row is zero)
+__device__ __forceinline__ void lba_edge_store(const LbaArgs& A, int ei, int tgt, const orbx_lba_edge& E, const double e[3], double chi,
+                                               const double Jp[3][6], const double Jl[3][3]) {
+  const bool mono = E.u_right < 0.f;
   // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91); without a kernel g2o weighs with the information alone: rho' = 1
   const double delta = mono ? A.deltaMono : A.deltaStereo;
   const double dsqr = delta * delta;
@@ -184,6 +187,127 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
     for (int m = 0; m < rows; m++) s -= wl[m][a] * e[m];
     all[6 + a] = s;
   }
+}
+
+__global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
+  const int ei = blockIdx.x * kLbaBS + threadIdx.x;
+  if (ei >= A.nE) return;
+  const LbaState& st = *A.st;
+  const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
+  const orbx_lba_edge E = A.edges[ei];
+  const orbx_lba_keyframe K = A.kfs[E.kf];
+  const LbaPose P = A.pose[tgt][E.kf];
+  const double X[3] = {A.X[tgt][3 * (size_t)E.point], A.X[tgt][3 * (size_t)E.point + 1], A.X[tgt][3 * (size_t)E.point + 2]};
+  double e[3], chi, Jp[3][6], Jl[3][3];
+  lba_pinhole_edge(K, E, P, X, e, chi, Jp, Jl);
+  lba_edge_store(A, ei, tgt, E, e, chi, Jp, Jl);
+}
+
+__device__ __forceinline__ Pose to_pose(const LbaPose& P) {
+  Pose T;
+  for (int k = 0; k < 4; k++) T.q[k] = P.q[k];
+  for (int k = 0; k < 3; k++) T.t[k] = P.t[k];
+  return T;
+}
+
+// mTrl of every key frame as its body edges hold it: SE3Quat(q, t) normalises
+__global__ __launch_bounds__(kLbaBS) void k_lba_rig_init(LbaArgs A) {
+  const int i = blockIdx.x * kLbaBS + threadIdx.x;
+  if (i >= A.nKF) return;
+  orbx::LbaRigTrl G;
+  for (int k = 0; k < 4; k++) G.T.q[k] = (double)A.cams[i].trl_q[k];
+  for (int k = 0; k < 3; k++) G.T.t[k] = (double)A.cams[i].trl_t[k];
+  if (A.kfs[i].camera2) normalize_rotation(G.T.q);   // (without a second camera nothing reads it)
+  quat_to_R(G.T.q, G.R);
+  A.trl[i] = G;
+}
+
+// A KB8 edge of the left camera (EdgeSE3ProjectXYZ, pCamera = KannalaBrandt8) or an edge of the second camera
+// (EdgeSE3ProjectXYZToBody, pinhole or KB8): two rows, the third is zero
+__device__ __forceinline__ void lba_rig_edge(const LbaArgs& A, const orbx_lba_keyframe& K, const orbx_lba_edge& E, bool right,
+                                             const LbaPose& P, const double* X, double e[3], double& chi, double Jp[3][6],
+                                             double Jl[3][3]) {
+  const orbx_lba_rig_camera C = A.cams[E.kf];
+  float k[8];
+  bool kb8;
+  if (right) {
+    for (int i = 0; i < 8; i++) k[i] = C.p2[i];
+    kb8 = C.model2 == ORBX_CAMERA_KB8;
+  } else {
+    k[0] = K.fx; k[1] = K.fy; k[2] = K.cx; k[3] = K.cy;
+    for (int i = 0; i < 4; i++) k[4 + i] = C.k[i];
+    kb8 = true;
+  }
+  const Pose T = to_pose(P);
+  double Xl[3], Xe[3], Xj[3], Rw[3][3];
+  se3_map(T, X, Xl);
+  if (right) {   // the error through (mTrl * T).map(Xw), the Jacobians at mTrl.map(T.map(Xw))
+    const Pose Trl = to_pose(A.trl[E.kf].T);
+    Pose TR;
+    se3_compose(Trl, T, TR);
+    se3_map(TR, X, Xe);
+    se3_map(Trl, Xl, Xj);
+    quat_to_R(TR.q, Rw);
+  } else {
+    for (int i = 0; i < 3; i++) Xe[i] = Xj[i] = Xl[i];
+    quat_to_R(T.q, Rw);
+  }
+  double u, v, PJ[2][3];
+  if (kb8) {
+    kb8_project(k, Xe, u, v);
+    kb8_project_jac(k, Xj, PJ);
+  } else {       // Pinhole::project(Vector3d), Pinhole::projectJac: float parameters times double
+    const double fx = (double)k[0], fy = (double)k[1];
+    u = fx * Xe[0] / Xe[2] + (double)k[2];
+    v = fy * Xe[1] / Xe[2] + (double)k[3];
+    PJ[0][0] = fx / Xj[2]; PJ[0][1] = 0; PJ[0][2] = -fx * Xj[0] / (Xj[2] * Xj[2]);
+    PJ[1][0] = 0; PJ[1][1] = fy / Xj[2]; PJ[1][2] = -fy * Xj[1] / (Xj[2] * Xj[2]);
+  }
+  const double info = (double)E.inv_sigma2;
+  e[0] = (double)E.u - u;
+  e[1] = (double)E.v - v;
+  e[2] = 0;
+  chi = e[0] * (info * e[0]) + e[1] * (info * e[1]);
+  double Pb[2][3];   // projectJac, for a body edge times R(mTrl)
+  for (int r = 0; r < 2; r++)
+    for (int c = 0; c < 3; c++) {
+      Jl[r][c] = -(PJ[r][0] * Rw[0][c] + PJ[r][1] * Rw[1][c] + PJ[r][2] * Rw[2][c]);
+      Pb[r][c] = PJ[r][c];
+    }
+  if (right) {
+    const orbx::LbaRigTrl& G = A.trl[E.kf];
+    for (int r = 0; r < 2; r++)
+      for (int c = 0; c < 3; c++) Pb[r][c] = PJ[r][0] * G.R[0][c] + PJ[r][1] * G.R[1][c] + PJ[r][2] * G.R[2][c];
+  }
+  const double x = Xl[0], y = Xl[1], z = Xl[2];
+  for (int r = 0; r < 2; r++) {   // -Pb * SE3deriv, its zero products dropped
+    Jp[r][0] = -(Pb[r][1] * -z + Pb[r][2] * y);
+    Jp[r][1] = -(Pb[r][0] * z + Pb[r][2] * -x);
+    Jp[r][2] = -(Pb[r][0] * -y + Pb[r][1] * x);
+    Jp[r][3] = -Pb[r][0];
+    Jp[r][4] = -Pb[r][1];
+    Jp[r][5] = -Pb[r][2];
+  }
+  for (int j = 0; j < 3; j++) Jl[2][j] = 0;
+  for (int j = 0; j < 6; j++) Jp[2][j] = 0;
+}
+
+// k_lba_linearize of the rig entries: the edge's class is chosen per thread; a pinhole edge of the left camera runs the code of
+// k_lba_linearize
+__global__ __launch_bounds__(kLbaBS) void k_lba_linearize_rig(LbaArgs A) {
+  const int ei = blockIdx.x * kLbaBS + threadIdx.x;
+  if (ei >= A.nE) return;
+  const LbaState& st = *A.st;
+  const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
+  const orbx_lba_edge E = A.edges[ei];
+  const orbx_lba_keyframe K = A.kfs[E.kf];
+  const LbaPose P = A.pose[tgt][E.kf];
+  const double X[3] = {A.X[tgt][3 * (size_t)E.point], A.X[tgt][3 * (size_t)E.point + 1], A.X[tgt][3 * (size_t)E.point + 2]};
+  const bool right = A.edgeCam[ei] != 0;
+  double e[3], chi, Jp[3][6], Jl[3][3];
+  if (!right && K.model == ORBX_CAMERA_PINHOLE) lba_pinhole_edge(K, E, P, X, e, chi, Jp, Jl);
+  else lba_rig_edge(A, K, E, right, P, X, e, chi, Jp, Jl);
+  lba_edge_store(A, ei, tgt, E, e, chi, Jp, Jl);
 }
 
 __global__ __launch_bounds__(kLbaBS) void k_lba_reduce_pts(LbaArgs A) {
@@ -352,6 +476,33 @@ __device__ __forceinline__ void hpl_dinv(const double* hpl, const double* di, do
     for (int c = 0; c < 3; c++) Y[a][c] = hpl[3 * a] * D[0][c] + hpl[3 * a + 1] * D[1][c] + hpl[3 * a + 2] * D[2][c];
 }
 
+// the lanes' sums of a block over the wave, then S (both triangles) and, on the diagonal, bschur
+__device__ __forceinline__ void schur_write(const LbaArgs& A, const LbaState& st, int i, int j, int lane, double acc[42]) {
+  const int cur = st.cur;
+#pragma unroll
+  for (int k = 0; k < 42; k++) acc[k] = wave_sum(acc[k]);
+  double mine = 0;
+#pragma unroll
+  for (int k = 0; k < 42; k++) mine = lane == k ? acc[k] : mine;
+  const size_t n = (size_t)A.n;
+  if (lane < 36) {
+    const int a = lane / 6, b = lane % 6;
+    double v = -mine;
+    if (i == j) {
+      const int lo = a < b ? a : b, hi = a < b ? b : a;
+      v += A.hpp[cur][(size_t)i * kLbaApp + (lo * (13 - lo)) / 2 + (hi - lo)];
+      if (a == b) v += st.lambda;
+      A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
+    } else {
+      A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
+      A.S[(6 * (size_t)j + b) * n + 6 * i + a] = v;
+    }
+  } else if (lane < 42 && i == j) {
+    const int a = lane - 36;
+    A.bs[6 * i + a] = A.hpp[cur][(size_t)i * kLbaApp + 21 + a] - mine;
+  }
+}
+
 // block (i, j >= i) of Hschur = Hpp + lambda I - sum_p Hpl_ip Dinv_p Hpl_jp^T over the points key frame i sees, in its edge order;
 // the diagonal blocks also give bschur_i = bp_i - sum_p Hpl_ip Dinv_p bl_p.  Both triangles of S are written.
 __global__ __launch_bounds__(64) void k_lba_schur(LbaArgs A) {
@@ -385,28 +536,40 @@ __global__ __launch_bounds__(64) void k_lba_schur(LbaArgs A) {
       for (int a = 0; a < 6; a++) acc[36 + a] += Y[a][0] * bl[0] + Y[a][1] * bl[1] + Y[a][2] * bl[2];
     }
   }
+  schur_write(A, st, i, j, lane, acc);
+}
+
+// k_lba_schur where a (key frame, point) pair may carry two edges, one per camera: block (i, j) takes every pair (e of slot i,
+// e' of slot j) of a point's edges -- on the diagonal the edge with itself and with its sibling of the other camera -- in the
+// edge order of key frame i, then of the point.  bschur takes each edge of slot i once.
+__global__ __launch_bounds__(64) void k_lba_schur_rig(LbaArgs A) {
+  const int i = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
+  if (j < i) return;
+  const LbaState& st = *A.st;
+  const int cur = st.cur;
+  double acc[42];
 #pragma unroll
-  for (int k = 0; k < 42; k++) acc[k] = wave_sum(acc[k]);
-  double mine = 0;
+  for (int k = 0; k < 42; k++) acc[k] = 0;
+  for (int k = A.kfStart[i] + lane; k < A.kfStart[i + 1]; k += 64) {
+    const int ei = A.kfEdges[k];
+    const int p = A.edges[ei].point;
+    double Y[6][3];
+    hpl_dinv(A.hpl[cur] + (size_t)ei * kLbaHpl, A.dinv + (size_t)p * 6, Y);
+    for (int m = A.ptStart[p]; m < A.ptStart[p + 1]; m++) {
+      if (A.slot[A.edges[m].kf] != j) continue;
+      const double* hj = A.hpl[cur] + (size_t)m * kLbaHpl;
 #pragma unroll
-  for (int k = 0; k < 42; k++) mine = lane == k ? acc[k] : mine;
-  const size_t n = (size_t)A.n;
-  if (lane < 36) {
-    const int a = lane / 6, b = lane % 6;
-    double v = -mine;
-    if (i == j) {
-      const int lo = a < b ? a : b, hi = a < b ? b : a;
-      v += A.hpp[cur][(size_t)i * kLbaApp + (lo * (13 - lo)) / 2 + (hi - lo)];
-      if (a == b) v += st.lambda;
-      A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
-    } else {
-      A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
-      A.S[(6 * (size_t)j + b) * n + 6 * i + a] = v;
+      for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) acc[6 * a + b] += Y[a][0] * hj[3 * b] + Y[a][1] * hj[3 * b + 1] + Y[a][2] * hj[3 * b + 2];
     }
-  } else if (lane < 42 && i == j) {
-    const int a = lane - 36;
-    A.bs[6 * i + a] = A.hpp[cur][(size_t)i * kLbaApp + 21 + a] - mine;
+    if (j == i) {
+      const double* bl = A.hll[cur] + (size_t)p * kLbaAll + 6;
+#pragma unroll
+      for (int a = 0; a < 6; a++) acc[36 + a] += Y[a][0] * bl[0] + Y[a][1] * bl[1] + Y[a][2] * bl[2];
+    }
   }
+  schur_write(A, st, i, j, lane, acc);
 }
 
 // Unpivoted LDLT of the n x n reduced system, in place in the lower triangle of S (L below the diagonal, D on it), blocked by
@@ -544,7 +707,9 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_update(LbaArgs A) {
   }
 }
 
-__global__ __launch_bounds__(kLbaBS) void k_lba_finish(LbaArgs A) {
+// kRig: a second-camera edge's depth is ((mTrl * T).map(X))[2]; its gate is the monocular one (u_right < 0)
+template <bool kRig>
+__device__ __forceinline__ void lba_finish(const LbaArgs& A) {
   const int i = blockIdx.x * kLbaBS + threadIdx.x;
   const LbaState& st = *A.st;
   const int cur = st.cur;
@@ -553,8 +718,16 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_finish(LbaArgs A) {
     const LbaPose P = A.pose[cur][E.kf];
     const double X[3] = {A.X[cur][3 * (size_t)E.point], A.X[cur][3 * (size_t)E.point + 1], A.X[cur][3 * (size_t)E.point + 2]};
     double Xc[3];
-    qrot(P.q, X, Xc);
-    const bool pos = Xc[2] + P.t[2] > 0.0;
+    bool pos;
+    if (kRig && A.edgeCam[i] != 0) {
+      Pose TR;
+      se3_compose(to_pose(A.trl[E.kf].T), to_pose(P), TR);
+      se3_map(TR, X, Xc);
+      pos = Xc[2] > 0.0;
+    } else {
+      qrot(P.q, X, Xc);
+      pos = Xc[2] + P.t[2] > 0.0;
+    }
     const double gate = E.u_right < 0.f ? 5.991 : 7.815;
     A.depthPos[i] = pos ? 1 : 0;
     A.erase[i] = (A.chi2[i] > gate || !pos) ? 1 : 0;
@@ -585,6 +758,9 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_finish(LbaArgs A) {
   }
 }
 
+__global__ __launch_bounds__(kLbaBS) void k_lba_finish(LbaArgs A) { lba_finish<false>(A); }
+__global__ __launch_bounds__(kLbaBS) void k_lba_finish_rig(LbaArgs A) { lba_finish<true>(A); }
+
 inline int blocks(int n) { return (n + kLbaBS - 1) / kLbaBS; }
 
 }  // namespace
@@ -594,11 +770,13 @@ namespace orbx {
 hipError_t launch_lba_init(const LbaArgs& a) {
   const int m = std::max(std::max(a.nKF, a.nP), std::max(a.n, 1));
   hipLaunchKernelGGL(k_lba_init, dim3(blocks(m)), dim3(kLbaBS), 0, nullptr, a);
+  if (a.cams) hipLaunchKernelGGL(k_lba_rig_init, dim3(blocks(a.nKF)), dim3(kLbaBS), 0, nullptr, a);
   return hipGetLastError();
 }
 
 hipError_t launch_lba_evaluate(const LbaArgs& a) {
-  hipLaunchKernelGGL(k_lba_linearize, dim3(blocks(a.nE)), dim3(kLbaBS), 0, nullptr, a);
+  if (a.cams) hipLaunchKernelGGL(k_lba_linearize_rig, dim3(blocks(a.nE)), dim3(kLbaBS), 0, nullptr, a);
+  else hipLaunchKernelGGL(k_lba_linearize, dim3(blocks(a.nE)), dim3(kLbaBS), 0, nullptr, a);
   hipLaunchKernelGGL(k_lba_reduce_pts, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
   if (a.nOpt) hipLaunchKernelGGL(k_lba_reduce_kfs, dim3(a.nOpt), dim3(64), 0, nullptr, a);
   hipLaunchKernelGGL(k_lba_decide, dim3(1), dim3(kLbaBS), 0, nullptr, a);
@@ -612,7 +790,8 @@ hipError_t launch_lba_solve(const LbaArgs& a) {
 
 hipError_t launch_lba_trial(const LbaArgs& a) {
   hipLaunchKernelGGL(k_lba_dinv, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
-  if (a.nOpt) hipLaunchKernelGGL(k_lba_schur, dim3(a.nOpt, a.nOpt), dim3(64), 0, nullptr, a);
+  if (a.nOpt && a.cams) hipLaunchKernelGGL(k_lba_schur_rig, dim3(a.nOpt, a.nOpt), dim3(64), 0, nullptr, a);
+  else if (a.nOpt) hipLaunchKernelGGL(k_lba_schur, dim3(a.nOpt, a.nOpt), dim3(64), 0, nullptr, a);
   const hipError_t e = a.blocked ? launch_ba_solve(BaSolveArgs{a.S, a.bs, a.xp, &a.st->ok, a.n}) : launch_lba_solve(a);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_lba_update, dim3(blocks(std::max(a.nKF, a.nP))), dim3(kLbaBS), 0, nullptr, a);
@@ -620,7 +799,9 @@ hipError_t launch_lba_trial(const LbaArgs& a) {
 }
 
 hipError_t launch_lba_finish(const LbaArgs& a) {
-  hipLaunchKernelGGL(k_lba_finish, dim3(blocks(std::max(std::max(a.nE, a.nP), a.nLocal))), dim3(kLbaBS), 0, nullptr, a);
+  const dim3 grid(blocks(std::max(std::max(a.nE, a.nP), a.nLocal)));
+  if (a.cams) hipLaunchKernelGGL(k_lba_finish_rig, grid, dim3(kLbaBS), 0, nullptr, a);
+  else hipLaunchKernelGGL(k_lba_finish, grid, dim3(kLbaBS), 0, nullptr, a);
   return hipGetLastError();
 }
 
