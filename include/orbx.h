@@ -1666,6 +1666,50 @@ int orbx_debug_introsort_device(int device, uint64_t* v, int n);
 #define ORBX_LINALG_OPS 11
 #define ORBX_LINALG_MAX_ITEMS 65536
 int orbx_debug_linalg(int device, int op, int n, const void* in, void* out);
+/* The camera models and the SE3 / Sim3 maps of the solvers (csrc/orbx_kb8.h, orbx_kb8_edge.h, orbx_pose.h, orbx_sim3opt.h,
+ * orbx_mlpnp.h), each function alone on n items of the caller's, one item per thread, as orbx_debug_linalg does for the linear
+ * algebra.  Items of the three camera operations are floats, all others doubles; out is read as well as written.  Quaternions are
+ * x y z w, a Pose is q [4], t [3], a Sim3 is q [4] (not normalised), t [3], s; matrices are row-major.  The model flag selects
+ * KannalaBrandt8 (non-zero) or pinhole (zero); fixScale is 0.0 / 1.0.
+ *   op                                       in, per item                                   out, per item
+ *   ORBX_GEOM_CAM_PROJECT                    model flag, cam [8], X [3]        (float)      uv [2]
+ *   ORBX_GEOM_CAM_UNPROJECT, _ROUNDED_TAN    model flag, cam [8], precision, u, v (float)   ray [3]
+ *   ORBX_GEOM_KB8_PROJECT_D                  k [8] as floats (32 bytes), X [3] double       u, v
+ *   ORBX_GEOM_KB8_PROJECT_JAC                the same (56 bytes = 7 doubles)                PJ [2][3]
+ *   ORBX_GEOM_SE3_MAP                        Pose, X [3]                                    Y [3]
+ *   ORBX_GEOM_SE3_COMPOSE                    Pose a, Pose b                                 Pose a * b
+ *   ORBX_GEOM_QMUL                           a [4], b [4]                                   a * b [4]
+ *   ORBX_GEOM_QROT                           q [4], v [3]                                   q * v [3]
+ *   ORBX_GEOM_NORMALIZE_ROTATION             q [4]                                          q [4]
+ *   ORBX_GEOM_QUAT_FROM_R                    R [3][3]                                       q [4]
+ *   ORBX_GEOM_OPLUS                          x [6], Pose                                    Pose
+ *   ORBX_GEOM_SIM3_EXP                       x [7]                                          Sim3
+ *   ORBX_GEOM_SIM3_OPLUS                     x [7], fixScale, Sim3                          Sim3
+ *   ORBX_GEOM_SO_INVERSE                     Sim3                                           qc [4], ti [3], si, Ri [3][3]
+ *   ORBX_GEOM_RODRIGUES2ROT                  w [3]                                          R [3][3]
+ *   ORBX_GEOM_ROT2RODRIGUES                  R [3][3]                                       w [3]
+ * No operation indexes memory by a computed value and every loop is bounded (Newton's has 10 steps): NaN, inf and denormal items
+ * are safe.  A null pointer, n outside [1, ORBX_GEOM_MAX_ITEMS] and an unknown op are ORBX_E_BADARG before any device is touched. */
+#define ORBX_GEOM_CAM_PROJECT 0
+#define ORBX_GEOM_CAM_UNPROJECT 1
+#define ORBX_GEOM_CAM_UNPROJECT_ROUNDED_TAN 2
+#define ORBX_GEOM_KB8_PROJECT_D 3
+#define ORBX_GEOM_KB8_PROJECT_JAC 4
+#define ORBX_GEOM_SE3_MAP 5
+#define ORBX_GEOM_SE3_COMPOSE 6
+#define ORBX_GEOM_QMUL 7
+#define ORBX_GEOM_QROT 8
+#define ORBX_GEOM_NORMALIZE_ROTATION 9
+#define ORBX_GEOM_QUAT_FROM_R 10
+#define ORBX_GEOM_OPLUS 11
+#define ORBX_GEOM_SIM3_EXP 12
+#define ORBX_GEOM_SIM3_OPLUS 13
+#define ORBX_GEOM_SO_INVERSE 14
+#define ORBX_GEOM_RODRIGUES2ROT 15
+#define ORBX_GEOM_ROT2RODRIGUES 16
+#define ORBX_GEOM_OPS 17
+#define ORBX_GEOM_MAX_ITEMS 65536
+int orbx_debug_geometry(int device, int op, int n, const void* in, void* out);
 
 /* Shrinks (>= 320 entries) or restores (any larger value) the capacity of k_detect's LDS corner + survivor list so
  * that tests can force the paths natural images rarely reach: mid-cell flushes, the corner limit and the tile-scan

@@ -207,6 +207,7 @@ def lib():
         L.orbx_debug_introsort.restype = None
         L.orbx_debug_introsort_device.argtypes = [i, vp, i]
         L.orbx_debug_linalg.argtypes = [i, i, i, vp, vp]
+        L.orbx_debug_geometry.argtypes = [i, i, i, vp, vp]
         L.orbx_debug_set_detect_list_cap.argtypes = [i]
         L.orbx_debug_set_detect_list_cap.restype = None
         L.orbx_debug_set_octree_global.argtypes = [i]
@@ -1438,6 +1439,40 @@ def debug_linalg(op, items, prefill=0.0, device=0):
     out = np.empty((len(a), n_out), dt)
     out[...] = prefill
     _check(lib().orbx_debug_linalg(int(device), int(op), len(a), _p(a), _p(out)))
+    return out
+
+
+# orbx_debug_geometry: ORBX_GEOM_* and, per operation, the numpy type and the elements of one item of `in` and of `out`
+(GEOM_CAM_PROJECT, GEOM_CAM_UNPROJECT, GEOM_CAM_UNPROJECT_ROUNDED_TAN, GEOM_KB8_PROJECT_D, GEOM_KB8_PROJECT_JAC, GEOM_SE3_MAP,
+ GEOM_SE3_COMPOSE, GEOM_QMUL, GEOM_QROT, GEOM_NORMALIZE_ROTATION, GEOM_QUAT_FROM_R, GEOM_OPLUS, GEOM_SIM3_EXP, GEOM_SIM3_OPLUS,
+ GEOM_SO_INVERSE, GEOM_RODRIGUES2ROT, GEOM_ROT2RODRIGUES) = range(17)
+GEOM_OPS, GEOM_MAX_ITEMS = 17, 65536
+GEOM_ITEM = {GEOM_CAM_PROJECT: (np.float32, 12, 2), GEOM_CAM_UNPROJECT: (np.float32, 12, 3),
+             GEOM_CAM_UNPROJECT_ROUNDED_TAN: (np.float32, 12, 3), GEOM_KB8_PROJECT_D: (np.float64, 7, 2),
+             GEOM_KB8_PROJECT_JAC: (np.float64, 7, 6), GEOM_SE3_MAP: (np.float64, 10, 3), GEOM_SE3_COMPOSE: (np.float64, 14, 7),
+             GEOM_QMUL: (np.float64, 8, 4), GEOM_QROT: (np.float64, 7, 3), GEOM_NORMALIZE_ROTATION: (np.float64, 4, 4),
+             GEOM_QUAT_FROM_R: (np.float64, 9, 4), GEOM_OPLUS: (np.float64, 13, 7), GEOM_SIM3_EXP: (np.float64, 7, 8),
+             GEOM_SIM3_OPLUS: (np.float64, 16, 8), GEOM_SO_INVERSE: (np.float64, 8, 17), GEOM_RODRIGUES2ROT: (np.float64, 3, 9),
+             GEOM_ROT2RODRIGUES: (np.float64, 9, 3)}
+
+
+def geom_kb8_items(k, X):
+    """Items of GEOM_KB8_PROJECT_D / _JAC: k [n][8] float32 in the first 32 bytes, X [n][3] float64 behind them, as [n][7] doubles."""
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+    items = np.empty((len(X), 7), np.float64)
+    items[:, :4].view(np.float32)[...] = np.broadcast_to(np.asarray(k, np.float32).reshape(-1, 8), (len(X), 8))
+    items[:, 4:] = X
+    return items
+
+
+def debug_geometry(op, items, prefill=0.0, device=0):
+    """One camera model or SE3 / Sim3 map of the solvers alone on the device (orbx_debug_geometry): items [n][elements of one
+    input item] -> [n][elements of one output item]; prefill is what `out` holds going in."""
+    dt, n_in, n_out = GEOM_ITEM[op]
+    a = np.ascontiguousarray(items, dt).reshape(-1, n_in)
+    out = np.empty((len(a), n_out), dt)
+    out[...] = prefill
+    _check(lib().orbx_debug_geometry(int(device), int(op), len(a), _p(a), _p(out)))
     return out
 
 

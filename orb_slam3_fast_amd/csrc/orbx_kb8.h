@@ -35,6 +35,13 @@ __device__ __forceinline__ void kb8_project(const KB8Cam& c, const float X[3], f
 // kRoundedTan: std::tan(float) as the double tangent rounded once to float -- what a correctly rounded tanf returns -- and not
 // the device's tanf.  The PnP solver asks for it: a bearing vector that is one float ulp off moves a six-point pose by 1e-7,
 // four orders above what the solver's own arithmetic leaves open.
+// Domain: a pixel whose theta_d = |((u - cx) / fx, (v - cy) / fy)| the polynomial theta (1 + k0 theta^2 + ...) reaches at a theta
+// below pi / 2.  theta_d is clamped to pi / 2, so every pixel beyond the clamp returns the scale of the clamp; where Newton ends
+// past pi / 2 the tangent is negative and the ray points backwards (TUM-VI: scale -49.8 at theta_d = 1.566, -34.98 for every pixel
+// beyond the clamp).  The break reads |theta_fix| < precision in float: a precision below float resolution (1e-9) ends the loop
+// only on a theta_fix of exactly 0 or after the 10 steps, and arithmetic that rounds a quotient or a root differently may break
+// one step earlier or later.  All of it is KannalaBrandt8::unproject's (KannalaBrandt8.cpp:116-147), reproduced and not repaired
+// (tests/test_geometry_device.py).
 template <bool kRoundedTan = false>
 __device__ __forceinline__ void kb8_unproject(const KB8Cam& c, float u, float v, float ray[3]) {  // :116-147
   const float pwx = (u - c.p[2]) / c.p[0], pwy = (v - c.p[3]) / c.p[1];

@@ -14,7 +14,9 @@ __device__ __forceinline__ double atan2f_d(float y, float x) { return (double)(f
 // KannalaBrandt8::project(const Eigen::Vector3d&) (:48-66): theta and psi narrowed to float, the polynomial and cos / sin in double
 __device__ __forceinline__ void kb8_project(const float* k, const double* X, double& u, double& v) {
   const double x2_plus_y2 = X[0] * X[0] + X[1] * X[1];
-  const double theta = atan2f_d(__fsqrt_rn((float)x2_plus_y2), (float)X[2]);
+  // sqrtf, the correctly rounded root the reference's sqrtf is: __fsqrt_rn is the hardware's approximate root on this toolchain
+  // (1 ulp), which moved theta by a float ulp on some points (tests/test_geometry_device.py, HISTORY.md)
+  const double theta = atan2f_d(sqrtf((float)x2_plus_y2), (float)X[2]);
   const double psi = atan2f_d((float)X[1], (float)X[0]);
   const double theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2,
                theta9 = theta7 * theta2;
@@ -25,7 +27,12 @@ __device__ __forceinline__ void kb8_project(const float* k, const double* X, dou
   v = (double)k[1] * r * sp + (double)k[3];
 }
 
-// KannalaBrandt8::projectJac (:149-184), all double; `3 * mvParameters[4]` is a float product there
+// KannalaBrandt8::projectJac (:149-184), all double; `3 * mvParameters[4]` is a float product there.
+// Domain: r = sqrt(x^2 + y^2) > 0 with r^3 a normal double (r above about 3e-103).  On the axis (r = 0) the first two columns are
+// NaN (0 / 0) and the third is a signed zero; once r^3 underflows to zero (r below about 1e-108) the first two columns are inf or
+// NaN; and as r / z -> 0 the two terms of every entry cancel, so digits are lost long before that: the off-diagonal entries keep 10
+// digits at r / z = 5e-4 and none at 5e-9.  This is the reference's own arithmetic (KannalaBrandt8.cpp:149-184), reproduced and not
+// repaired: one point near the axis of a KB8 frame puts these entries into H as they are (tests/test_geometry_device.py).
 __device__ __forceinline__ void kb8_project_jac(const float* k, const double* X, double PJ[2][3]) {
   const double x = X[0], y = X[1], z = X[2];
   const double x2 = x * x, y2 = y * y, z2 = z * z;

@@ -19,7 +19,6 @@
 namespace orbx {
 namespace {
 
-constexpr double kEps = 2.220446049250313e-16;   // std::numeric_limits<double>::epsilon()
 constexpr int kPrepBS = 256;
 
 // U V^T of the SVD of a row-major 3 x 3: the rotation (or reflection) nearest to it in the Frobenius sense
@@ -107,34 +106,6 @@ __device__ int rank3_fullpiv(const double* M) {
 // index of (a, c), a <= c, in the row-major upper triangle of an n x n symmetric matrix
 __device__ __forceinline__ int tri_index(int a, int c, int n) { return a * n - a * (a - 1) / 2 + (c - a); }
 __device__ __forceinline__ int sym_index(int a, int c, int n) { return a <= c ? tri_index(a, c, n) : tri_index(c, a, n); }
-
-// rodrigues2rot (:668-682)
-__device__ __forceinline__ void rodrigues2rot(const double* w, double* R) {
-  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  const double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-#pragma unroll
-  for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  if (n > kEps) {
-    const double a = sin(n) / n, b = (1 - cos(n)) / (n * n);
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-        R[3 * i + j] += a * W[3 * i + j] + b * (W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j]);
-  }
-}
-// rot2rodrigues (:684-698)
-__device__ __forceinline__ void rot2rodrigues(const double* R, double* w) {
-  w[0] = w[1] = w[2] = 0.0;
-  const double trace = R[0] + R[4] + R[8] - 1.0;
-  const double wnorm = acos(trace / 2.0);
-  if (wnorm > kEps) {
-    const double sc = wnorm / (2.0 * sin(wnorm));
-    w[0] = (R[7] - R[5]) * sc;
-    w[1] = (R[2] - R[6]) * sc;
-    w[2] = (R[3] - R[1]) * sc;
-  }
-}
 
 struct Corr {
   double X[3], f[3], r[3], s[3];

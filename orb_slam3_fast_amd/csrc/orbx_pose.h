@@ -60,6 +60,9 @@ __device__ __forceinline__ void qrot(const double* q, const double* v, double* r
   cross3(q, uv, c);
   for (int i = 0; i < 3; i++) r[i] = v[i] + q[3] * uv[i] + c[i];
 }
+// Domain: a quaternion whose norm is finite and not zero, and whose squared norm neither overflows nor underflows.  The zero
+// quaternion gives four NaNs (0 / 0); no call site passes one: each normalises a product of unit quaternions or the quaternion of
+// I + W + W^2.  SE3Quat::normalizeRotation is se3quat.h:280-285 (tests/test_geometry_device.py).
 __device__ __forceinline__ void normalize_rotation(double* q) {   // SE3Quat::normalizeRotation: w >= 0, unit norm
   if (q[3] < 0) for (int i = 0; i < 4; i++) q[i] = -q[i];
   const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
