@@ -1716,8 +1716,16 @@ int orbx_debug_geometry(int device, int op, int n, const void* in, void* out);
  * NMS behind it. */
 void orbx_debug_set_detect_list_cap(int cap);
 /* Test hook: != 0 forces k_octree's global-memory candidate path (normally taken only when one (image, level) has more
- * than 16384 FAST candidates); 0 restores the register-resident path. */
+ * than 32 FAST candidates per thread of its block: 16384 with 512 threads); 0 restores the register-resident path. */
 void orbx_debug_set_octree_global(int on);
+/* Test hook of k_octree's workgroup size: 128, 256 or 512 = every level of every launch runs with workgroups of that many threads;
+ * 0 (or anything else) restores the product: for batches the plan below, for a single frame 512 threads at every level.  With
+ * 128 / 256 a level of more than 32 candidates per thread takes the global-memory candidate path; the results never change. */
+void orbx_debug_set_octree_class(int nt);
+/* k_octree's plan at this frame size (host only, no device): per level the class -- the threads of the level's workgroup that work
+ * in a batch's launch: 128 / 256 / 512, non-increasing with the level; the launch has 512-thread workgroups and the waves past
+ * the class end at once -- and the dynamic LDS bytes of that launch. */
+int orbx_debug_octree_plan(const orbx_params* p, int width, int height, int32_t* nt_per_level, int32_t* lds_bytes_per_level);
 /* Test hook of ComputeStereoMatches' two forms (src/Frame.cc:921-1084): calls with up to max_pairs pairs (and at most 4096
  * result slots per image) run the DIRECT form -- k_stereo_band selects its keypoints from the unsorted arrays itself, no
  * k_stereo_sort launch in front --, larger ones the row-sorted form.  Default 1 (the single-frame path); 0 = never; < 0

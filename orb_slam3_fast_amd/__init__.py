@@ -212,6 +212,10 @@ def lib():
         L.orbx_debug_set_detect_list_cap.restype = None
         L.orbx_debug_set_octree_global.argtypes = [i]
         L.orbx_debug_set_octree_global.restype = None
+        if hasattr(L, "orbx_debug_set_octree_class"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
+            L.orbx_debug_set_octree_class.argtypes = [i]
+            L.orbx_debug_set_octree_class.restype = None
+            L.orbx_debug_octree_plan.argtypes = [vp, i, i, vp, vp]
         L.orbx_debug_set_stereo_direct.argtypes = [i]
         L.orbx_debug_set_stereo_direct.restype = None
         L.orbx_debug_set_clahe_cell_kernel.argtypes = [i]
@@ -1869,6 +1873,15 @@ def front_tables(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, h
     _check(lib().orbx_debug_front_tables(C.byref(prm), width, height, _p(cells), cells.size, _p(tiles) if tiles.size else None,
                                          tiles.size, _p(info)))
     return cells, tiles, int(info[2]), int(info[3])
+
+
+def octree_plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height):
+    """k_octree's plan at this frame size (orbx_debug_octree_plan; host only, no device): (working threads of the level's workgroup,
+    dynamic LDS bytes of the batch's launch), one entry per level."""
+    prm = _Params(int(nfeatures), float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
+    nt, lds = np.zeros(int(nlevels), np.int32), np.zeros(int(nlevels), np.int32)
+    _check(lib().orbx_debug_octree_plan(C.byref(prm), width, height, _p(nt), _p(lds)))
+    return nt, lds
 
 
 class ORBVocabulary:

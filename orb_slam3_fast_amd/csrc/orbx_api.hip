@@ -164,7 +164,7 @@ int build_geom(const orbx_extractor* ex, int w, int h, Geom& g, std::string& why
     why = "scale factor too large for the LDS-staged resize footprint";
     return ORBX_E_UNSUPPORTED;
   }
-  if (octree_lds_bytes(g) > 160 * 1024 - 2048) {
+  if (octree_lds_bytes(g, 0, g.nlevels) > 160 * 1024 - 2048) {
     why = "nfeatures too large for the LDS-resident quadtree";
     return ORBX_E_UNSUPPORTED;
   }
@@ -512,6 +512,7 @@ int configure(orbx_extractor* ex, int w, int h) {
     build_cell_records(g, recs);
     HIPC(hipMemcpy(ex->d_cellRec.p, recs.data(), recs.size() * sizeof(CellRec), hipMemcpyHostToDevice));
   }
+  build_octree_plan(g, ex->octPlan);
   HIPC(prepare_kernels(g));
   std::vector<TailPlan> plans;
   std::vector<TailBand> bands;
@@ -724,9 +725,19 @@ int record_pipeline(orbx_extractor* ex, int n, bool lapTrivial, bool capturing, 
     HIPC(launch_detect(g, ex->pyr, ex->d_cellRec.p, n, ex->d_cellCand.p, ex->d_cellCount.p, 0, g.nlevels, ex->d_dbgScore.p, s));
   }
   {
+    // A batch runs every level with its class of the plan, in ONE launch (k_octree_mixed): a light level's workgroup keeps 4 or 2
+    // waves (x 128 VGPRs) while its node lists keep one wave busy, instead of 8.  Launches of up to g_lat_max_images images (a
+    // single frame, graph capture) keep 512 threads for every level: they do not fill the chip, and the narrower workgroups of the
+    // light levels live 0.5 - 3.5 us longer.
     StageTimer t(ex, s, ORBX_STAGE_OCTREE);
-    HIPC(launch_octree(g, n, ex->d_cellCand.p, ex->d_cellCount.p, ex->d_cellPrefix.p, ex->d_cand.p,
-                       ex->d_candCount.p, ex->d_knode.p, ex->d_sel.p, ex->d_selCount.p, 0, g.nlevels, s));
+    const int forced = debug_octree_class();
+    if (!forced && n > g_lat_max_images) {
+      HIPC(launch_octree_mixed(g, ex->octPlan, n, ex->d_cellCand.p, ex->d_cellCount.p, ex->d_cand.p, ex->d_candCount.p,
+                               ex->d_knode.p, ex->d_sel.p, ex->d_selCount.p, s));
+    } else {
+      HIPC(launch_octree(g, n, ex->d_cellCand.p, ex->d_cellCount.p, ex->d_cellPrefix.p, ex->d_cand.p, ex->d_candCount.p,
+                         ex->d_knode.p, ex->d_sel.p, ex->d_selCount.p, 0, g.nlevels, forced ? forced : 512, s));
+    }
   }
   if (!lapTrivial) {
     StageTimer t(ex, s, ORBX_STAGE_SLOTS);
@@ -1550,6 +1561,26 @@ int orbx_debug_front_tables(const orbx_params* p, int width, int height, uint32_
   return ORBX_OK;
 }
 
+int orbx_debug_octree_plan(const orbx_params* p, int width, int height, int32_t* nt_per_level, int32_t* lds_bytes_per_level) {
+  if (!p || !nt_per_level || !lds_bytes_per_level || width < 1 || height < 1 || p->nlevels < 1 || p->nlevels > ORBX_MAX_LEVELS ||
+      p->nfeatures < 1 || !(p->scale_factor > 1.0f))
+    return fail(ORBX_E_BADARG, "bad argument");
+  std::unique_ptr<orbx_extractor> ex(new orbx_extractor());   // parameters and tables only: no device, no buffers
+  ex->prm = *p;
+  build_tables(ex.get());
+  Geom g;
+  std::string why;
+  const int rc = build_geom(ex.get(), width, height, g, why);
+  if (rc != ORBX_OK) return fail(rc, why);
+  OctPlan op;
+  build_octree_plan(g, op);
+  for (int l = 0; l < g.nlevels; l++) {
+    nt_per_level[l] = op.nt[l];
+    lds_bytes_per_level[l] = op.lds[l];
+  }
+  return ORBX_OK;
+}
+
 int orbx_hamming256(const void* a, const void* b) {
   const uint32_t* x = (const uint32_t*)a;
   const uint32_t* y = (const uint32_t*)b;
@@ -1854,6 +1885,7 @@ void orbx_debug_set_detect_list_cap(int cap) { debug_set_detect_list_cap(cap); }
 void orbx_debug_set_clahe_cell_kernel(int on) { debug_set_clahe_cell_kernel(on); }
 void orbx_debug_set_remap_lds(int on) { debug_set_remap_lds(on); }
 void orbx_debug_set_octree_global(int on) { debug_set_octree_global(on); }
+void orbx_debug_set_octree_class(int nt) { debug_set_octree_class(nt); }
 void orbx_debug_set_stereo_direct(int max_pairs) { debug_set_stereo_direct(max_pairs); }
 void orbx_debug_set_resize_tail(int first_level, int max_levels, int band_rows) {
   orbx_host::g_tail_first = first_level;

@@ -395,6 +395,7 @@ struct orbx_extractor {
   DevBuf<uint4> d_xtab;  // k_resize's per-column table (build_coefs)
   DevBuf<uint32_t> d_rsRec;  // k_resize's tile records and tile-row blocks of the configured size (build_resize_records)
   DevBuf<orbx::CellRec> d_cellRec;  // k_detect's per-cell records of the configured size (build_cell_records)
+  orbx::OctPlan octPlan{};          // k_octree's class per level at the configured size (build_octree_plan)
   DevBuf<int> d_packCtr;    // arrival counter of the single-frame gather workgroups (launch_stereo_match)
   uint32_t packSeq = 0;     // sequence number of the last single stereo frame (hostResults + hr_flag())
   bool packCtrDirty = false; // a fused single-frame launch is (or may be, after a failure) in flight: d_packCtr is cleared before the next one

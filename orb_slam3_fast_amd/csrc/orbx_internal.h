@@ -137,15 +137,23 @@ int resize_records_layout(const Geom& g, int level, int& tileOff, int& rowOff);
 constexpr uint32_t kTileFast = 1u, kTileWhole = 2u;   // flags of a tile record (k_resize, orbx_kernels.hip)
 hipError_t launch_detect(const Geom& g, const Pyr& p, const CellRec* cellRec, int nimg, uint32_t* cellCand, int* cellCount,
                          int level0, int level1, uint8_t* dbgScore, hipStream_t s);
+// levels [level0, level1) with blocks of nt threads (128 / 256 / 512); its dynamic LDS is sized for that level range
 hipError_t launch_octree(const Geom& g, int nimg, const uint32_t* cellCand, const int* cellCount, int* cellPrefix,
                          uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, int level0,
-                         int level1, hipStream_t s);
+                         int level1, int nt, hipStream_t s);
+// k_octree's class per level of a configured size (128 / 256 / 512 working threads) and the dynamic LDS of the batch's launch
+struct OctPlan {
+  int nt[ORBX_MAX_LEVELS], lds[ORBX_MAX_LEVELS];
+};
+void build_octree_plan(const Geom& g, OctPlan& p);
+hipError_t launch_octree_mixed(const Geom& g, const OctPlan& plan, int nimg, const uint32_t* cellCand, const int* cellCount,
+                               uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, hipStream_t s);
 hipError_t launch_blur(const Geom& g, const Pyr& p, int nimg, int level0, int level1, hipStream_t s);
 hipError_t launch_slots(const Geom& g, int nimg, const uint32_t* sel, const int* selCount, const int* lap,
                         int* slot, int* nOut, int* mono, hipStream_t s);
 hipError_t launch_describe(const Geom& g, const Pyr& p, int nimg, const uint32_t* sel, const int* selCount,
                            const int* slot, orbx_keypoint* kps, uint8_t* desc, int* nOut, int* mono, hipStream_t s);
-size_t octree_lds_bytes(const Geom& g);
+size_t octree_lds_bytes(const Geom& g, int level0, int level1);   // of a launch that serves levels [level0, level1)
 size_t resize_lds_bytes(const Geom& g);
 
 struct StereoArgs {
@@ -574,6 +582,8 @@ void debug_introsort_host(uint64_t* v, int n);
 void debug_set_detect_list_cap(int cap);
 void debug_set_clahe_cell_kernel(int on);
 void debug_set_octree_global(int on);
+void debug_set_octree_class(int nt);   // test hook: 0 = the plan, 128 / 256 / 512 = that block size for every level, one launch
+int debug_octree_class();
 hipError_t launch_debug_sort(uint64_t* d_v, int n, hipStream_t s);
 hipError_t launch_debug_sincos(const float* ang, int n, int fused, float* s, float* c, hipStream_t st);
 

@@ -692,8 +692,9 @@ __device__ int partition_reg2(uint64_t* a, int first, int last, uint64_t* box, i
 // of `a`, stopper lists at the segment's own offset of Li / Ri), children longer than 16 go to the next level's list.
 // Identical result, log(n / 16) rounds instead of n / 16 sequential partitions (17 -> ~5 us for the ~130 expandable
 // nodes of a level-0 quadtree).  segs: 2 x 256 packed segments + 2 counters (u32).
-__device__ __forceinline__ void introsort_block(uint64_t* a, int n, uint64_t* tmp, uint16_t* Li, uint16_t* Ri, uint32_t* segs) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6, nt = blockDim.x;
+// nt: the threads that call it (the first nt of the workgroup; the rest may have ended)
+__device__ __forceinline__ void introsort_block(uint64_t* a, int n, uint64_t* tmp, uint16_t* Li, uint16_t* Ri, uint32_t* segs, int nt) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
   const KeyLess less;
 #ifdef OCT_PROF
   long long smk[24]; int nsmk = 0;
@@ -791,7 +792,7 @@ __global__ __launch_bounds__(512) void k_debug_sort(uint64_t* v, int n) {
   for (int i = tid; i < n; i += blockDim.x) a[i] = v[i];
   __syncthreads();
   if (blockDim.x == 64) introsort_wave(a, n, tmp, Li, Ri, reinterpret_cast<int*>(segs), tid);
-  else introsort_block(a, n, tmp, Li, Ri, segs);
+  else introsort_block(a, n, tmp, Li, Ri, segs, (int)blockDim.x);
   __syncthreads();
   for (int i = tid; i < n; i += blockDim.x) v[i] = a[i];
 }
@@ -839,28 +840,33 @@ __host__ __device__ inline OctLds oct_layout(int maxn, int maxcells, int rep) {
   o.total = off;
   return o;
 }
-__host__ __device__ inline int oct_maxn(const Geom& g) {
+// (the maxima run over the levels [l0, l1) one launch serves: a launch of light levels holds less LDS)
+__host__ __device__ inline int oct_maxn(const Geom& g, int l0, int l1) {
   int q = 0;
-  for (int l = 0; l < g.nlevels; l++) q = g.lv[l].quota > q ? g.lv[l].quota : q;
+  for (int l = l0; l < l1; l++) q = g.lv[l].quota > q ? g.lv[l].quota : q;
   return q + 4 * kMaxIni + 8;
 }
-__host__ __device__ inline int oct_maxcells(const Geom& g) {
+__host__ __device__ inline int oct_maxcells(const Geom& g, int l0, int l1) {
   int c = 0;
-  for (int l = 0; l < g.nlevels; l++) c = g.lv[l].nCols * g.lv[l].nRows > c ? g.lv[l].nCols * g.lv[l].nRows : c;
+  for (int l = l0; l < l1; l++) c = g.lv[l].nCols * g.lv[l].nRows > c ? g.lv[l].nCols * g.lv[l].nRows : c;
   return c;
 }
 // Counter replicas: 2 (1 for very large per-level quotas).  Four replicas (rounds 1 - 4) cost 56 KB = 44 of a CU's 128 LDS
 // granules per workgroup; with two it is 50 KB = 40 granules, the workgroup itself is 1.5 us faster (fewer replicas to sum) and the
 // kernels that run beside it have room for one more workgroup per CU (+ 0.4 % pairs/s with three handles, A/B on one box).
-__host__ __device__ inline int oct_rep(const Geom& g) {
-  const int maxn = oct_maxn(g), maxcells = oct_maxcells(g);
+__host__ __device__ inline int oct_rep(const Geom& g, int l0, int l1) {
+  const int maxn = oct_maxn(g, l0, l1), maxcells = oct_maxcells(g, l0, l1);
   if (oct_layout(maxn, maxcells, 2).total <= 78 * 1024) return 2;
   return 1;
 }
-size_t octree_lds_bytes(const Geom& g) { return (size_t)oct_layout(oct_maxn(g), oct_maxcells(g), oct_rep(g)).total; }
+size_t octree_lds_bytes(const Geom& g, int l0, int l1) {
+  return (size_t)oct_layout(oct_maxn(g, l0, l1), oct_maxcells(g, l0, l1), oct_rep(g, l0, l1)).total;
+}
 
-constexpr int OCT_NT = 512;  // threads per quadtree block: halves the key-loop trip counts vs 256, 2 blocks/CU stay resident
-// Exclusive scan of n u64 values in LDS (in place) by an OCT_NT-thread block; returns the total.
+// Threads that work on one (image, level), a template parameter NT of everything below: 512 halves the key-loop trip counts of
+// the heavy levels vs 256 and keeps 2 blocks / CU resident; the light levels of a batch run with 256 or 128 (build_octree_plan),
+// since their node-list phases keep one or two waves busy whatever the block size and every parked wave holds 128 VGPRs.
+// Exclusive scan of n u64 values in LDS (in place) by an NT-thread block; returns the total.
 // Packed fields must not overflow into each other (callers keep each field < 2^21).
 // Per-thread chunk sums are scanned inside each wave with DPP row shifts / broadcasts (no barriers); only the
 // wave totals go through LDS: 2 barriers per call instead of the 18 of a Hillis-Steele scan over 256 threads.
@@ -872,9 +878,10 @@ __device__ __forceinline__ uint64_t wave0_scan_u64(uint64_t* v, int n) {
   if (lane < n) v[lane] = incl - s;
   return readlane_u64(incl, 63);
 }
+template <int NT>
 __device__ __forceinline__ uint64_t block_scan_u64(uint64_t* v, int n, uint64_t* tsum) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int per = (n + OCT_NT - 1) / OCT_NT;
+  const int per = (n + NT - 1) / NT;
   const int b = min(tid * per, n), e = min(b + per, n);
   uint64_t s = 0;
   for (int i = b; i < e; i++) s += v[i];
@@ -883,7 +890,7 @@ __device__ __forceinline__ uint64_t block_scan_u64(uint64_t* v, int n, uint64_t*
   __syncthreads();
   uint64_t wbase = 0, total = 0;
 #pragma unroll
-  for (int w = 0; w < OCT_NT / 64; w++) {
+  for (int w = 0; w < NT / 64; w++) {
     const uint64_t t = tsum[w];
     if (w < wv) wbase += t;
     total += t;
@@ -904,12 +911,12 @@ __device__ __forceinline__ int quadrant(int x, int y, int x0, int x1, int y0, in
 }
 
 // Candidates of one (image, level) as seen by the quadtree passes.  REG: every thread keeps its candidates
-// k = tid + j * OCT_NT (key and current node id) in registers for the whole kernel, so the ~12 passes over the
+// k = tid + j * NT (key and current node id) in registers for the whole kernel, so the ~12 passes over the
 // candidate set touch only registers and LDS (the passes were latency-bound on L2 round trips: 163 -> see DESIGN).
-// !REG (more than OCT_KMAX * OCT_NT candidates): keys / node ids live in global memory, same thread <-> k mapping.
+// !REG (more than OCT_KMAX * NT candidates): keys / node ids live in global memory, same thread <-> k mapping.
 constexpr int OCT_KMAX = 32;
 constexpr int OCT_GROUP = 4;  // candidates per thread processed together in a sweep
-template <bool REG>
+template <bool REG, int NT>
 struct OctCands {
   uint32_t rk[REG ? OCT_KMAX : 1];
   uint32_t rn2[REG ? OCT_KMAX / 2 : 1];  // node ids, two 16-bit ids per register (node | quadrant << 14, or kNoCand)
@@ -922,7 +929,7 @@ struct OctCands {
     if constexpr (REG) {
 #pragma unroll
       for (int j0 = 0; j0 < OCT_KMAX; j0 += OCT_GROUP) {  // (no early exit: its phi copies double the live arrays)
-        if (j0 * OCT_NT >= n) continue;  // whole group past the last candidate (uniform): a level-4 workgroup fills 9 of 32 slots
+        if (j0 * NT >= n) continue;  // whole group past the last candidate (uniform): a level-4 workgroup fills 9 of 32 slots
 #pragma unroll
         for (int j = j0; j < j0 + OCT_GROUP; j++)  // padding entries carry the sentinel node id (a per-j `k < n`
         {                                          // test would be hoisted out of every pass: 64 live SGPRs)
@@ -936,7 +943,7 @@ struct OctCands {
         __builtin_amdgcn_sched_barrier(0);  // keep the groups apart: interleaving all 32 costs > 200 VGPRs
       }
     } else {
-      for (int k = threadIdx.x; k < n; k += OCT_NT) {
+      for (int k = threadIdx.x; k < n; k += NT) {
         uint32_t nd = kn[k];
         const uint32_t nd0 = nd;
         f(k, keys[k], nd);
@@ -949,18 +956,18 @@ struct OctCands {
     if constexpr (REG) {
 #pragma unroll
       for (int j = 0; j < OCT_KMAX; j++) {  // all gather loads are issued before the first use (one latency, not 8)
-        const int k = (int)threadIdx.x + j * OCT_NT;
+        const int k = (int)threadIdx.x + j * NT;
         rk[j] = 0;
         if (k < n) rk[j] = f(k);
       }
 #pragma unroll
       for (int j = 0; j < OCT_KMAX; j++) {
-        const int k = (int)threadIdx.x + j * OCT_NT;
+        const int k = (int)threadIdx.x + j * NT;
         const uint32_t nd = k < n ? 0u : kNoCand;
         rn2[j >> 1] = (j & 1) ? rn2[j >> 1] | (nd << 16) : nd;
       }
     } else {
-      for (int k = threadIdx.x; k < n; k += OCT_NT) {
+      for (int k = threadIdx.x; k < n; k += NT) {
         keys[k] = f(k);
         kn[k] = 0;
       }
@@ -995,11 +1002,11 @@ struct OctCtx {  // node tables are double buffered: buffer b of table T sits at
 // (a few fire-and-forget ds_write per thread), so a candidate's slot address is two LDS reads; the binary search over the
 // cell prefix it replaces was ten DEPENDENT reads per candidate, 12 of a level-0 workgroup's 46 us.  The map aliases the
 // node tables, which nothing uses yet; levels with more candidates than it holds keep the search.
-template <class CD>
+template <int NT, class CD>
 __device__ __forceinline__ void octree_gather(CD& cd, const OctCtx& c, const LevelDev& L, int n, int cells,
                                               const uint32_t* __restrict__ sparse) {
   if (2 * n <= c.ownerBytes) {  // (uniform)
-    for (int cell = threadIdx.x; cell < cells; cell += OCT_NT) {
+    for (int cell = threadIdx.x; cell < cells; cell += NT) {
       const int b = c.cellpre[cell], e = min(c.cellpre[cell + 1], n);
       for (int i = b; i < e; i++) c.owner[i] = (uint16_t)cell;
     }
@@ -1022,7 +1029,7 @@ __device__ __forceinline__ void octree_gather(CD& cd, const OctCtx& c, const Lev
   }
 }
 
-template <bool REG>
+template <bool REG, int NT>
 __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, const OctCtx& c, int n, int cells,
                                             const uint32_t* __restrict__ sparse, uint32_t* __restrict__ keys,
                                             uint16_t* __restrict__ kn, uint32_t* __restrict__ out,
@@ -1036,11 +1043,11 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
 #define MK() do {} while (0)
 #endif
   MK();
-  OctCands<REG> cd;
+  OctCands<REG, NT> cd;
   cd.keys = keys;
   cd.kn = kn;
   cd.n = n;
-  octree_gather(cd, c, L, n, cells, sparse);
+  octree_gather<NT>(cd, c, L, n, cells, sparse);
   MK();
   const int N = L.quota;
   struct Buf {  // nx0[b][i] etc. as before, by address arithmetic (no pointer arrays -> no scratch)
@@ -1060,10 +1067,10 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
   uint32_t* cntr = c.cntr;
   const int nrep = c.nrep, rep = tid & (nrep - 1);
   auto zero_counters = [&](int nslots) {  // the caller syncs
-    for (int i = tid; i < nslots * nrep; i += OCT_NT) cntr[i] = 0;
+    for (int i = tid; i < nslots * nrep; i += NT) cntr[i] = 0;
   };
   auto reduce_counters = [&](int nslots) {  // cnt4[i] = sum of the replicas; the caller syncs before and after
-    for (int i = tid; i < nslots; i += OCT_NT) {
+    for (int i = tid; i < nslots; i += NT) {
       uint32_t v = 0;
       for (int r = 0; r < nrep; r++) v += cntr[i * nrep + r];
       cnt4[i] = v;
@@ -1145,7 +1152,7 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     reduce_counters(nA * 4);
     __syncthreads();
     MK();
-    for (int i = tid; i < nA; i += OCT_NT) {
+    for (int i = tid; i < nA; i += NT) {
       uint64_t cc = 0, nm = 1, ce = 0;
       if (ncnt[cur][i] > 1) {
         nm = 0;
@@ -1157,11 +1164,11 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
       scan[i] = cc | (nm << 21) | (ce << 42);
     }
     __syncthreads();
-    const uint64_t tot = block_scan_u64(scan, nA, tsum);
+    const uint64_t tot = block_scan_u64<NT>(scan, nA, tsum);
     MK();
     const int tc = (int)(tot & 0x1FFFFF), tnm = (int)((tot >> 21) & 0x1FFFFF), tce = (int)(tot >> 42);
     const int nxt = cur ^ 1;
-    for (int i = tid; i < nA; i += OCT_NT) {
+    for (int i = tid; i < nA; i += NT) {
       const uint64_t pre = scan[i];
       const int pc = (int)(pre & 0x1FFFFF), pnm = (int)((pre >> 21) & 0x1FFFFF), pce = (int)(pre >> 42);
       if (ncnt[cur][i] > 1) {
@@ -1205,7 +1212,7 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     MK();
     // (a node that is not split never had its quadrant tagged: tag 0 -> cpos[nd * 4])
     cd.sweep([&](int, uint32_t, uint32_t& v) { v = cpos[(v & 0x3FFF) * 4 + (v >> 14)]; });
-    for (int i = tid; i < tc + tnm; i += OCT_NT) nmid[i] = pack_mid(nxt, i);
+    for (int i = tid; i < tc + tnm; i += NT) nmid[i] = pack_mid(nxt, i);
     __syncthreads();
     MK();
     cur = nxt;
@@ -1226,19 +1233,19 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     uint64_t* E2 = c.ebuf + (ecur ^ 1) * c.maxn;
     // the whole workgroup sorts; scratch: scan (stopper lists), E2 (rank scatter), tsum (segment lists)
     introsort_block(E, nE, E2, reinterpret_cast<uint16_t*>(scan), reinterpret_cast<uint16_t*>(scan) + c.maxn + 4,
-                    reinterpret_cast<uint32_t*>(tsum));
+                    reinterpret_cast<uint32_t*>(tsum), NT);
     MK();
     if (tid == 0) {
       s_i[1] = nE;  // cut (exclusive count of processed) defaults to all
       s_i[2] = 0;   // broke
     }
     zero_counters(nA * 4);
-    for (int i = tid; i < nA; i += OCT_NT) {
+    for (int i = tid; i < nA; i += NT) {
       mark[i] = 0;
       nmid[i] &= 0x7FFFFFFFu;  // this pass splits exactly the nodes of the E list
     }
     __syncthreads();
-    for (int m = tid; m < nE; m += OCT_NT) {
+    for (int m = tid; m < nE; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       mark[nd] = (uint16_t)(m + 1);
       nmid[nd] |= 0x80000000u;
@@ -1256,7 +1263,7 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     reduce_counters(nA * 4);
     __syncthreads();
     // scan over the processing order m: c (children), ce (expandable children)
-    for (int m = tid; m < nE; m += OCT_NT) {
+    for (int m = tid; m < nE; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       uint64_t cc = 0, ce = 0;
       for (int q = 0; q < 4; q++) {
@@ -1266,9 +1273,9 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
       scan[m] = cc | (ce << 21);
     }
     __syncthreads();
-    block_scan_u64(scan, nE, tsum);
+    block_scan_u64<NT>(scan, nE, tsum);
     // first m at which the list reaches N nodes: size after m+1 expansions = nA + C_incl(m) - (m+1)
-    for (int m = tid; m < nE; m += OCT_NT) {
+    for (int m = tid; m < nE; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       int cc = 0;
       for (int q = 0; q < 4; q++) cc += cnt4[nd * 4 + q] > 0;
@@ -1297,7 +1304,7 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     }
     const int nxt = cur ^ 1;
     // children of processed nodes: later processed first, each group n4..n1
-    for (int m = tid; m < nP; m += OCT_NT) {
+    for (int m = tid; m < nP; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       const int x0 = nx0[cur][nd], x1 = nx1[cur][nd], y0 = ny0[cur][nd], y1 = ny1[cur][nd];
       const int hx = (x1 - x0 + 1) >> 1, hy = (y1 - y0 + 1) >> 1;
@@ -1330,10 +1337,10 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     }
     __syncthreads();
     // untouched nodes keep their relative order behind the new children
-    for (int i = tid; i < nA; i += OCT_NT) scan[i] = (mark[i] == 0 || mark[i] > nP) ? 1 : 0;
+    for (int i = tid; i < nA; i += NT) scan[i] = (mark[i] == 0 || mark[i] > nP) ? 1 : 0;
     __syncthreads();
-    const int nKeep = (int)block_scan_u64(scan, nA, tsum);
-    for (int i = tid; i < nA; i += OCT_NT) {
+    const int nKeep = (int)block_scan_u64<NT>(scan, nA, tsum);
+    for (int i = tid; i < nA; i += NT) {
       if (mark[i] == 0 || mark[i] > nP) {
         const int pos = tc + (int)scan[i];
         nx0[nxt][pos] = nx0[cur][i];
@@ -1347,7 +1354,7 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
     }
     __syncthreads();
     cd.sweep([&](int, uint32_t, uint32_t& v) { v = cpos[(v & 0x3FFF) * 4 + (v >> 14)]; });
-    for (int i = tid; i < tc + nKeep; i += OCT_NT) nmid[i] = pack_mid(nxt, i);
+    for (int i = tid; i < tc + nKeep; i += NT) nmid[i] = pack_mid(nxt, i);
     __syncthreads();
     cur = nxt;
     nA = tc + nKeep;
@@ -1366,9 +1373,9 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
   uint64_t* bestr = reinterpret_cast<uint64_t*>(cntr);  // [node][nrepB]; cntr holds maxn * 4 * nrep words
   const int nrepB = nrep >= 2 ? nrep * 2 : 1, repB = tid & (nrepB - 1);
   if (nrepB > 1)
-    for (int i = tid; i < nA * nrepB; i += OCT_NT) bestr[i] = 0;
+    for (int i = tid; i < nA * nrepB; i += NT) bestr[i] = 0;
   else
-    for (int i = tid; i < nA; i += OCT_NT) best[i] = 0;
+    for (int i = tid; i < nA; i += NT) best[i] = 0;
   __syncthreads();
   const float invH = 1.0f / (float)L.hCell, invW = 1.0f / (float)L.wCell;
   auto rank_key = [&](uint32_t key) {
@@ -1383,7 +1390,7 @@ __device__ __forceinline__ void octree_body(const Geom& g, const LevelDev& L, co
       atomicMax((unsigned long long*)&bestr[nd * nrepB + repB], rank_key(key));
     });
     __syncthreads();
-    for (int i = tid; i < nA; i += OCT_NT) {
+    for (int i = tid; i < nA; i += NT) {
       uint64_t v = 0;
       for (int r = 0; r < nrepB; r++) v = bestr[i * nrepB + r] > v ? bestr[i * nrepB + r] : v;
       best[i] = v;
@@ -1424,6 +1431,7 @@ __host__ __device__ inline bool oct_hist_fits(int nIni) {  // oct_layout reserve
 }
 
 // returns false when a node deeper than the table had to be split (caller falls back to octree_body)
+template <int NT>
 __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& L, const OctCtx& c, int n, int cells,
                                                  const uint32_t* __restrict__ sparse, uint32_t* __restrict__ keys,
                                                  uint32_t* __restrict__ out, int* __restrict__ outCount, int prof) {
@@ -1435,11 +1443,11 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
 #define HMK() do {} while (0)
 #endif
   HMK();
-  OctCands<true> cd;
+  OctCands<true, NT> cd;
   cd.keys = keys;
   cd.kn = nullptr;
   cd.n = n;
-  octree_gather(cd, c, L, n, cells, sparse);
+  octree_gather<NT>(cd, c, L, n, cells, sparse);
   HMK();  // gather
   const int N = L.quota;
   struct Buf {
@@ -1468,7 +1476,7 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
   uint64_t* tsum = c.tsum;
   int* s_i = c.s_i;
   const int nH = oct_hbase(nIni, OCT_HD + 1);
-  for (int i = tid; i < nH; i += OCT_NT) hist[i] = 0;
+  for (int i = tid; i < nH; i += NT) hist[i] = 0;
   if (tid == 0) s_i[3] = 0;  // fallback flag
   // The quadrant sequence of a candidate separates: its x bits depend on x alone (root column included), its y bits on y
   // alone -- DivideNode halves a rectangle's sides independently (:494-495).  So the depth-OCT_HD path code is px[x] + py[y]
@@ -1506,7 +1514,7 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
     return code;
   };
   if (pathTab) {
-    for (int i = tid; i < W + H; i += OCT_NT) {
+    for (int i = tid; i < W + H; i += NT) {
       if (i < W) px[i] = (uint16_t)x_path(i);
       else py[i - W] = (uint16_t)y_path(i - W);
     }
@@ -1534,7 +1542,7 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
   for (int d = OCT_HD - 1; d >= 0; d--) {  // 4-ary sums
     const uint32_t* ch = hist + oct_hbase(nIni, d + 1);
     uint32_t* pa = hist + oct_hbase(nIni, d);
-    for (int i = tid; i < (nIni << (2 * d)); i += OCT_NT) pa[i] = ch[4 * i] + ch[4 * i + 1] + ch[4 * i + 2] + ch[4 * i + 3];
+    for (int i = tid; i < (nIni << (2 * d)); i += NT) pa[i] = ch[4 * i] + ch[4 * i + 1] + ch[4 * i + 2] + ch[4 * i + 3];
     __syncthreads();
   }
   auto child_count = [&](uint32_t dc, int q) {  // candidates in child q of node (depth, code); depth < OCT_HD
@@ -1578,7 +1586,7 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
       }
     };
     const int prevSize = nA;
-      for (int i = tid; i < nA; i += OCT_NT) {
+      for (int i = tid; i < nA; i += NT) {
         uint64_t cc = 0, nm = 1, ce = 0;
         if (ncnt[cur][i] > 1) {
           nm = 0;
@@ -1597,10 +1605,10 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
       }
       sync();
       if (s_i[3]) return 3;
-      const uint64_t tot = kWave ? wave0_scan_u64(scan, nA) : block_scan_u64(scan, nA, tsum);
+      const uint64_t tot = kWave ? wave0_scan_u64(scan, nA) : block_scan_u64<NT>(scan, nA, tsum);
       const int tc = (int)(tot & 0x1FFFFF), tnm = (int)((tot >> 21) & 0x1FFFFF), tce = (int)(tot >> 42);
       const int nxt = cur ^ 1;
-      for (int i = tid; i < nA; i += OCT_NT) {
+      for (int i = tid; i < nA; i += NT) {
         const uint64_t pre = scan[i];
         const int pc = (int)(pre & 0x1FFFFF), pnm = (int)((pre >> 21) & 0x1FFFFF), pce = (int)(pre >> 42);
         if (ncnt[cur][i] > 1) {
@@ -1680,16 +1688,16 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
     uint64_t* E2 = c.ebuf + (ecur ^ 1) * c.maxn;
     // the whole workgroup sorts; scratch: scan (stopper lists), E2 (rank scatter), tsum (segment lists)
     introsort_block(E, nE, E2, reinterpret_cast<uint16_t*>(scan), reinterpret_cast<uint16_t*>(scan) + c.maxn + 4,
-                    reinterpret_cast<uint32_t*>(tsum));
+                    reinterpret_cast<uint32_t*>(tsum), NT);
     HMK();  // sort
     if (tid == 0) {
       s_i[1] = nE;  // cut (exclusive count of processed) defaults to all
       s_i[2] = 0;   // broke
     }
-    for (int i = tid; i < nA; i += OCT_NT) mark[i] = 0;
+    for (int i = tid; i < nA; i += NT) mark[i] = 0;
     __syncthreads();
     // scan over the processing order m (largest first): c (children), ce (expandable children)
-    for (int m = tid; m < nE; m += OCT_NT) {
+    for (int m = tid; m < nE; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       mark[nd] = (uint16_t)(m + 1);
       const uint32_t dc = ndc(cur)[nd];
@@ -1707,9 +1715,9 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
     }
     __syncthreads();
     if (s_i[3]) return false;
-    block_scan_u64(scan, nE, tsum);
+    block_scan_u64<NT>(scan, nE, tsum);
     // first m at which the list reaches N nodes: size after m+1 expansions = nA + C_incl(m) - (m+1)
-    for (int m = tid; m < nE; m += OCT_NT) {
+    for (int m = tid; m < nE; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       const uint32_t dc = ndc(cur)[nd];
       int cc = 0;
@@ -1742,7 +1750,7 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
     }
     const int nxt = cur ^ 1;
     // children of processed nodes: later processed first, each group n4..n1
-    for (int m = tid; m < nP; m += OCT_NT) {
+    for (int m = tid; m < nP; m += NT) {
       const int nd = (int)(E[nE - 1 - m] & 0xFFFF);
       const uint32_t dc = ndc(cur)[nd];
       const uint32_t cdc = (((dc >> 13) + 1) << 13) | ((dc & 0x1FFF) * 4);
@@ -1779,10 +1787,10 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
     }
     __syncthreads();
     // untouched nodes keep their relative order behind the new children
-    for (int i = tid; i < nA; i += OCT_NT) scan[i] = (mark[i] == 0 || mark[i] > nP) ? 1 : 0;
+    for (int i = tid; i < nA; i += NT) scan[i] = (mark[i] == 0 || mark[i] > nP) ? 1 : 0;
     __syncthreads();
-    const int nKeep = (int)block_scan_u64(scan, nA, tsum);
-    for (int i = tid; i < nA; i += OCT_NT) {
+    const int nKeep = (int)block_scan_u64<NT>(scan, nA, tsum);
+    for (int i = tid; i < nA; i += NT) {
       if (mark[i] == 0 || mark[i] > nP) {
         const int pos = tc + (int)scan[i];
         nx0[nxt][pos] = nx0[cur][i];
@@ -1803,14 +1811,14 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
   }
   // ---- candidate -> final node: every final node marks its (depth, code); a depth-OCT_HD code belongs to its deepest
   // marked ancestor
-  for (int i = tid; i < nH; i += OCT_NT) leafAt[i] = 0xFFFF;
+  for (int i = tid; i < nH; i += NT) leafAt[i] = 0xFFFF;
   __syncthreads();
-  for (int i = tid; i < nA; i += OCT_NT) {
+  for (int i = tid; i < nA; i += NT) {
     const uint32_t dc = ndc(cur)[i];
     leafAt[oct_hbase(nIni, (int)(dc >> 13)) + (int)(dc & 0x1FFF)] = (uint16_t)i;
   }
   __syncthreads();
-  for (int c5 = tid; c5 < (nIni << (2 * OCT_HD)); c5 += OCT_NT) {
+  for (int c5 = tid; c5 < (nIni << (2 * OCT_HD)); c5 += NT) {
     uint16_t v = 0xFFFF;
 #pragma unroll
     for (int d = OCT_HD; d >= 0; d--) {
@@ -1826,9 +1834,9 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
   uint64_t* bestr = reinterpret_cast<uint64_t*>(c.cntr);  // [node][nrepB]; overwrites the histogram (no longer needed)
   const int nrepB = c.nrep >= 2 ? c.nrep * 2 : 1, repB = tid & (nrepB - 1);
   if (nrepB > 1)
-    for (int i = tid; i < nA * nrepB; i += OCT_NT) bestr[i] = 0;
+    for (int i = tid; i < nA * nrepB; i += NT) bestr[i] = 0;
   else
-    for (int i = tid; i < nA; i += OCT_NT) best[i] = 0;
+    for (int i = tid; i < nA; i += NT) best[i] = 0;
   __syncthreads();
   const float invH = 1.0f / (float)L.hCell, invW = 1.0f / (float)L.wCell;
   // canonical rank of a candidate = the reference's candidate order (cell row, cell column, y, x).  The winner of a node is
@@ -1848,7 +1856,7 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
   });
   __syncthreads();
   const int nOut = min(nA, L.selCap);
-  for (int i = tid; i < nOut; i += OCT_NT) {
+  for (int i = tid; i < nOut; i += NT) {
     uint64_t v = nrepB > 1 ? 0 : best[i];
     if (nrepB > 1)
       for (int r = 0; r < nrepB; r++) v = bestr[i * nrepB + r] > v ? bestr[i * nrepB + r] : v;
@@ -1872,14 +1880,13 @@ __device__ __forceinline__ bool octree_hist_body(const Geom& g, const LevelDev& 
   return true;
 }
 
-__global__ __launch_bounds__(OCT_NT, 4) void k_octree(Geom g, const uint32_t* __restrict__ cellCand,
-                                                const int* __restrict__ cellCount, int* __restrict__ cellPrefix,
-                                                uint32_t* __restrict__ cand, int* __restrict__ candCount,
-                                                uint16_t* __restrict__ knode, uint32_t* __restrict__ sel,
-                                                int* __restrict__ selCount, int profLevel, int forceGlobal, int level0,
-                                                int nlv) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ int s_i[8];
+// one (image, level) by the first NT threads of its workgroup
+template <int NT>
+__device__ __forceinline__ void octree_block(const Geom& g, const uint32_t* __restrict__ cellCand,
+                                             const int* __restrict__ cellCount, uint32_t* __restrict__ cand,
+                                             int* __restrict__ candCount, uint16_t* __restrict__ knode,
+                                             uint32_t* __restrict__ sel, int* __restrict__ selCount, int profLevel,
+                                             int forceGlobal, int level0, int nlv, uint8_t* smem, int* s_i) {
   const int tid = threadIdx.x;
 #ifdef OCT_WG_PROF  // measurement aid: life of every (image, level) workgroup of one launch, x10 ns (make prof PROF_FLAGS=-DOCT_WG_PROF,
                     // tools/octree_frame_prof.py + tools/octwg_summary.py: resolves 0.1 us where the frame's wall time resolves 1 us)
@@ -1900,9 +1907,9 @@ __global__ __launch_bounds__(OCT_NT, 4) void k_octree(Geom g, const uint32_t* __
   wgPrint.img = img;
 #endif
   const LevelDev L = g.lv[l];
-  const int maxn = oct_maxn(g);
-  const int nrep = oct_rep(g);
-  const OctLds o = oct_layout(maxn, oct_maxcells(g), nrep);
+  const int maxn = oct_maxn(g, level0, level0 + nlv);  // (as launch_octree sized the dynamic LDS)
+  const int nrep = oct_rep(g, level0, level0 + nlv);
+  const OctLds o = oct_layout(maxn, oct_maxcells(g, level0, level0 + nlv), nrep);
   OctCtx c;
   c.nx0 = (int16_t*)(smem + o.nx0[0]);
   c.nx1 = (int16_t*)(smem + o.nx1[0]);
@@ -1933,7 +1940,7 @@ __global__ __launch_bounds__(OCT_NT, 4) void k_octree(Geom g, const uint32_t* __
   int n;
   {
     const int* cc = cellCount + (long long)img * g.totalCells + L.cellStart;
-    const int per = (cells + OCT_NT - 1) / OCT_NT;
+    const int per = (cells + NT - 1) / NT;
     const int cb = min(tid * per, cells), ce = min(cb + per, cells);
     int sum = 0;
     for (int ci = cb; ci < ce; ci++) sum += cc[ci];
@@ -1942,7 +1949,7 @@ __global__ __launch_bounds__(OCT_NT, 4) void k_octree(Geom g, const uint32_t* __
     __syncthreads();
     int wbase = 0, total = 0;
 #pragma unroll
-    for (int w = 0; w < OCT_NT / 64; w++) {
+    for (int w = 0; w < NT / 64; w++) {
       const int t = (int)c.tsum[w];
       if (w < (tid >> 6)) wbase += t;
       total += t;
@@ -1966,36 +1973,120 @@ __global__ __launch_bounds__(OCT_NT, 4) void k_octree(Geom g, const uint32_t* __
   int* outCount = selCount + img * g.nlevels + l;
   // forceGlobal (test hook): 0 = product path, 1 = global-memory candidates (octree_body<false>), 2 = register-resident
   // per-pass sweeps (octree_body<true>, the fallback of the histogram variant)
-  if (n <= OCT_KMAX * OCT_NT && forceGlobal != 1) {
+  if (n <= OCT_KMAX * NT && forceGlobal != 1) {
     const int W = L.w - 2 * kBorder, H = L.h - 2 * kBorder;
     const int nIni = (int)roundf((float)W / (float)H);
     bool done = false;
     if (forceGlobal == 0 && oct_hist_fits(nIni)) {
-      done = octree_hist_body(g, L, c, n, cells, sparse, keys, out, outCount, profLevel == l && img == 0);
+      done = octree_hist_body<NT>(g, L, c, n, cells, sparse, keys, out, outCount, profLevel == l && img == 0);
       __syncthreads();
     }
-    if (!done) octree_body<true>(g, L, c, n, cells, sparse, keys, kn, out, outCount, profLevel == l && img == 0);
+    if (!done) octree_body<true, NT>(g, L, c, n, cells, sparse, keys, kn, out, outCount, profLevel == l && img == 0);
   } else {
-    octree_body<false>(g, L, c, n, cells, sparse, keys, kn, out, outCount, profLevel == l && img == 0);
+    octree_body<false, NT>(g, L, c, n, cells, sparse, keys, kn, out, outCount, profLevel == l && img == 0);
   }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, 4) void k_octree(Geom g, const uint32_t* __restrict__ cellCand,
+                                                const int* __restrict__ cellCount, int* __restrict__ cellPrefix,
+                                                uint32_t* __restrict__ cand, int* __restrict__ candCount,
+                                                uint16_t* __restrict__ knode, uint32_t* __restrict__ sel,
+                                                int* __restrict__ selCount, int profLevel, int forceGlobal, int level0,
+                                                int nlv) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ int s_i[8];
+  octree_block<NT>(g, cellCand, cellCount, cand, candCount, knode, sel, selCount, profLevel, forceGlobal, level0, nlv, smem, s_i);
+}
+
+// Every level of a batch in ONE launch of 512-thread workgroups, each level with its class of the plan (classes: two bits per
+// level, 128 << bits): the waves past a light level's class end at once and give their registers back, the rest run the level
+// as a workgroup of that size (a barrier waits for the waves of a workgroup that have not ended).  One launch, because launches
+// per class follow each other on the handle's stream, each as long as its slowest workgroup: 37 + 36 + 27 us for 41 (HISTORY.md).
+__global__ __launch_bounds__(512, 4) void k_octree_mixed(Geom g, const uint32_t* __restrict__ cellCand,
+                                                         const int* __restrict__ cellCount, uint32_t* __restrict__ cand,
+                                                         int* __restrict__ candCount, uint16_t* __restrict__ knode,
+                                                         uint32_t* __restrict__ sel, int* __restrict__ selCount,
+                                                         int profLevel, int forceGlobal, uint32_t classes) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ int s_i[8];
+  const int l = blockIdx.x / (gridDim.x / g.nlevels);
+  const int nt = 128 << ((classes >> (2 * l)) & 3u);  // (uniform)
+  if ((int)threadIdx.x >= nt) return;
+  if (nt == 512)
+    octree_block<512>(g, cellCand, cellCount, cand, candCount, knode, sel, selCount, profLevel, forceGlobal, 0, g.nlevels, smem, s_i);
+  else if (nt == 256)
+    octree_block<256>(g, cellCand, cellCount, cand, candCount, knode, sel, selCount, profLevel, forceGlobal, 0, g.nlevels, smem, s_i);
+  else
+    octree_block<128>(g, cellCand, cellCount, cand, candCount, knode, sel, selCount, profLevel, forceGlobal, 0, g.nlevels, smem, s_i);
 }
 
 static int g_octree_force_global_host = 0;
 void debug_set_octree_global(int on) { g_octree_force_global_host = on < 0 ? 0 : (on > 2 ? 2 : on); }
+static int g_octree_class_host = 0;  // test hook: 0 = the handle's plan, 128 / 256 / 512 = that block size for every level, one launch
+void debug_set_octree_class(int nt) { g_octree_class_host = (nt == 128 || nt == 256 || nt == 512) ? nt : 0; }
+int debug_octree_class() { return g_octree_class_host; }
 
-hipError_t launch_octree(const Geom& g, int nimg, const uint32_t* cellCand, const int* cellCount, int* cellPrefix,
-                         uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, int level0,
-                         int level1, hipStream_t s) {
-  if (level1 <= level0) return hipSuccess;
+// The class of every level -- the threads of its workgroup that work --, fixed with the image size (candidate counts are known on
+// the device only): by the level's detectable area, non-increasing with the level.  The areas leave the benchmark's densest level
+// of a class >= 1.5 x head-room under the register-resident limit OCT_KMAX * NT (k_octree row, has the measured
+// counts); a level that overflows it all the same takes the global-memory path: same result, slower.
+constexpr int kOctArea256 = 300000, kOctArea128 = 70000;  // px^2: at 1280 x 720 / 1.2 levels 0 - 2 | 3 - 6 | 7
+void build_octree_plan(const Geom& g, OctPlan& p) {
+  int prev = 512;
+  for (int l = 0; l < g.nlevels; l++) {
+    const long long area = (long long)(g.lv[l].w - 2 * kBorder) * (g.lv[l].h - 2 * kBorder);
+    const int nt = area > kOctArea256 ? 512 : (area > kOctArea128 ? 256 : 128);
+    prev = p.nt[l] = nt < prev ? nt : prev;
+    p.lds[l] = (int)octree_lds_bytes(g, 0, g.nlevels);  // one launch serves every level: the LDS of the largest
+  }
+}
+
+template <int NT>
+static hipError_t launch_octree_nt(const Geom& g, int nimg, const uint32_t* cellCand, const int* cellCount, int* cellPrefix,
+                                   uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, int level0,
+                                   int level1, hipStream_t s) {
   dim3 grid((level1 - level0) * nimg);
 #ifdef OCT_PROF
   static const int profLevel = getenv("ORBX_OCTREE_PROF_LEVEL") ? atoi(getenv("ORBX_OCTREE_PROF_LEVEL")) : 0;
 #else
   const int profLevel = -1;
 #endif
-  hipLaunchKernelGGL(k_octree, grid, dim3(OCT_NT), octree_lds_bytes(g), s, g, cellCand, cellCount, cellPrefix, cand,
-                     candCount, knode, sel, selCount, profLevel, g_octree_force_global_host, level0, level1 - level0);
+  const size_t lds = octree_lds_bytes(g, level0, level1);
+  if (g_octree_class_host) {  // (a forced class serves level ranges prepare_kernels did not size it for)
+    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_octree<NT>), lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_octree<NT>, grid, dim3(NT), lds, s, g, cellCand, cellCount, cellPrefix, cand, candCount, knode, sel,
+                     selCount, profLevel, g_octree_force_global_host, level0, level1 - level0);
   return hipGetLastError();
+}
+// every level of nimg images in one launch, level l with the first plan.nt[l] threads of its workgroup
+hipError_t launch_octree_mixed(const Geom& g, const OctPlan& plan, int nimg, const uint32_t* cellCand, const int* cellCount,
+                               uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, hipStream_t s) {
+  uint32_t classes = 0;
+  for (int l = 0; l < g.nlevels; l++) classes |= (plan.nt[l] == 512 ? 2u : (plan.nt[l] == 256 ? 1u : 0u)) << (2 * l);
+#ifdef OCT_PROF
+  static const int profLevel = getenv("ORBX_OCTREE_PROF_LEVEL") ? atoi(getenv("ORBX_OCTREE_PROF_LEVEL")) : 0;
+#else
+  const int profLevel = -1;
+#endif
+  hipLaunchKernelGGL(k_octree_mixed, dim3(g.nlevels * nimg), dim3(512), octree_lds_bytes(g, 0, g.nlevels), s, g, cellCand,
+                     cellCount, cand, candCount, knode, sel, selCount, profLevel, g_octree_force_global_host, classes);
+  return hipGetLastError();
+}
+// levels [level0, level1) of nimg images with blocks of nt threads (128, 256 or 512); level-major block order
+hipError_t launch_octree(const Geom& g, int nimg, const uint32_t* cellCand, const int* cellCount, int* cellPrefix,
+                         uint32_t* cand, int* candCount, uint16_t* knode, uint32_t* sel, int* selCount, int level0,
+                         int level1, int nt, hipStream_t s) {
+  if (level1 <= level0) return hipSuccess;
+  if (nt == 128)
+    return launch_octree_nt<128>(g, nimg, cellCand, cellCount, cellPrefix, cand, candCount, knode, sel, selCount, level0, level1, s);
+  if (nt == 256)
+    return launch_octree_nt<256>(g, nimg, cellCand, cellCount, cellPrefix, cand, candCount, knode, sel, selCount, level0, level1, s);
+  if (nt == 512)
+    return launch_octree_nt<512>(g, nimg, cellCand, cellCount, cellPrefix, cand, candCount, knode, sel, selCount, level0, level1, s);
+  return hipErrorInvalidValue;
 }
 
 // ================================================================================================ blur
@@ -2727,7 +2818,10 @@ hipError_t raise_dynamic_lds(const void* fn, size_t bytes) {
 }
 
 hipError_t prepare_kernels(const Geom& g) {
-  hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_octree), octree_lds_bytes(g));
+  // (k_octree<256> / <128> run under the test hook only: launch_octree_nt raises theirs)
+  const size_t octLds = octree_lds_bytes(g, 0, g.nlevels);
+  hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_octree<512>), octLds);
+  if (e == hipSuccess) e = raise_dynamic_lds(reinterpret_cast<const void*>(k_octree_mixed), octLds);
   if (e != hipSuccess) return e;
   if (g.nlevels > 1) {
     e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<0, true>), std::max<size_t>(resize_lds_bytes(g), 1024));

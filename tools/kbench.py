@@ -26,6 +26,8 @@ else:
 imgs = np.concatenate([np.stack([base[i % 2] for i in range(B)]), np.stack([base[2 + i % 2] for i in range(B)])])
 d = DeviceBuffer.from_numpy(imgs)
 NH = int(os.environ.get("KB_HANDLES", "1"))
+if os.environ.get("KB_OCTREE_CLASS"):   # 128 / 256 / 512: k_octree with workgroups of that size at every level (orbx_debug_set_octree_class)
+    orbx.lib().orbx_debug_set_octree_class(int(os.environ["KB_OCTREE_CLASS"]))
 exs = [orbx.ORBextractor(1500, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=2 * B) for _ in range(NH)]
 ex = exs[0]
 bf, b = 0.12 * 532.03, 0.12

@@ -10,6 +10,8 @@ W = int(sys.argv[1]) if len(sys.argv) > 1 else 1280
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 720
 NF = int(sys.argv[3]) if len(sys.argv) > 3 else 1500
 L, R = synth.stereo_pair(W, H, 5)
+if os.environ.get("ORBX_OCTREE_CLASS"):   # 128 / 256 / 512: every level with workgroups of that many threads (orbx_debug_set_octree_class)
+    orbx.lib().orbx_debug_set_octree_class(int(os.environ["ORBX_OCTREE_CLASS"]))
 ex = orbx.ORBextractor(NF, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=2)
 for i in range(int(os.environ.get("PROF_FRAMES", "3"))):
     ex.extract_stereo(L, R, bf=63.8, b=0.12)
