@@ -1416,6 +1416,83 @@ int orbx_local_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* pro
                                      orbx_lba_result* result);
 int orbx_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_ba_params* params, orbx_ba_result* result);
 
+/* ---- Sim3 pose graph (Optimizer::OptimizeEssentialGraph) --------------------------------------------------- */
+
+/* The loop-closing Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+ * bFixScale) (src/Optimizer.cc:1530-1826; the call site src/LoopClosing.cc:1299, inside CorrectLoop), one graph per call, on the
+ * device: g2o's Levenberg on BlockSolver_7_3 over VertexSim3Expmap vertices and EdgeSim3 edges, restated as a chain of kernels
+ * (csrc/orbx_posegraph.hip), all arithmetic in double.
+ *
+ * The problem is a flat graph: vertices [n_vertices] = the estimates Siw (g2o::Sim3, the quaternion not normalised), fixed
+ * [n_vertices] (!= 0: setFixed, the map's initial key frame; any number may be fixed), edges [n_edges] in the reference's order.
+ * An edge holds vertex 0 = i, vertex 1 = j and the measurement Sji; its error is (Sji * S_i * S_j^-1).log()
+ * (types_seven_dof_expmap.h:106-114), its information the identity, and it has no robust kernel.  Several edges may join the same
+ * two vertices (a spanning-tree edge and a loop-connection edge, say), in either direction.  With fix_scale the seventh
+ * component of every update is zeroed inside oplus (:64-65).  points / point_ref (optional): map point positions and the vertex
+ * each is corrected through, -1: the point is neither read nor written (:1800-1822 for the others:
+ * corrected_S[r].inverse().map(S[r].map(P)) in double with S the vertices as given, cast to float).
+ *
+ * Jacobians.  EdgeSim3 has no linearizeOplus: g2o differentiates numerically through oplusImpl by central differences with step
+ * 1e-9, which leaves 1e-7 of rounding noise that no second implementation can reproduce.  The device does the same with step
+ * 1e-6 (truncation about 1e-12, rounding about 1e-10, both relative).  A fixed vertex has no Jacobian.
+ * The optimiser is optimization_algorithm_levenberg.cpp with the user's lambda_init (the reference: 1e-16, 20 iterations): a
+ * trial solves (H + lambda I) x = b by the blocked LDLT of csrc/orbx_ba.hip over the dense 7 n_opt system, applies oplus,
+ * takes rho = (chi2 - chi2_trial) / (sum x (lambda x + b) + 1e-3), accepts when rho > 0 and chi2_trial is finite (lambda *=
+ * max(1/3, min(1 - (2 rho - 1)^3, 2/3)), ni = 2) and rejects otherwise (lambda *= ni, ni *= 2, the estimates restored); a failed
+ * pivot is a rejected trial.  stop_reason takes the ORBX_LBA_STOP_* values: ten trials in one iteration (_QMAX), rho == 0, three
+ * iterations in a row that gained less than 1e-3 of their starting chi2, or max_iterations.  Nothing aborts when no vertex is
+ * fixed: the damping carries the gauge.  The rows of the system are the vertices that are not fixed and that an edge touches;
+ * the others come back as given, bit for bit.
+ * Early ends: a problem without an edge is ORBX_LBA_EMPTY, the outputs are the inputs and no device is touched.  A problem whose
+ * every edge joins two fixed vertices has nothing to optimise: ORBX_LBA_DONE with the inputs, zero counters and the edges' chi2
+ * (chi2_initial = chi2_final = their sum), which the device evaluates.
+ * result->chi2 is every edge's chi2 at the returned estimate (the reference ends with computeActiveErrors, :1778).
+ * Deliberate difference, as in the bundle adjustments: the library returns the double Sim3.  The [R | t / s] recovery of
+ * :1789-1795 and its float cast belong to the caller.
+ * Capacity: ORBX_PG_MAX_KF optimised vertices = floor(6 ORBX_BA_MAX_KF / 7), 6139 rows, inside the row count the blocked solver
+ * is tested to (302 MB); more is ORBX_E_BADARG, and a sparse factorisation is the tool beyond.  Fixed vertices, edges and points
+ * are bounded by int32 and memory.  Not built: the map-merge overload (:1828), OptimizeEssentialGraph4DoF and the inertial
+ * variants; any number of fixed vertices and any edge list are accepted, so the merge overload is a second gather. */
+#define ORBX_PG_MAX_KF 877
+typedef struct orbx_pg_edge {
+  int32_t i, j;              /* vertex 0, vertex 1 */
+  orbx_sim3_pose Sji;        /* the measurement */
+} orbx_pg_edge;              /* 72 bytes */
+typedef struct orbx_pg_problem {
+  const orbx_sim3_pose* vertices;
+  const uint8_t* fixed;      /* [n_vertices] */
+  int32_t n_vertices;
+  const orbx_pg_edge* edges;
+  int32_t n_edges;
+  int32_t fix_scale;         /* bFixScale */
+  const float* points;       /* [n_points][3], may be NULL with n_points == 0 */
+  const int32_t* point_ref;  /* [n_points] vertex index, or -1 */
+  int32_t n_points;
+} orbx_pg_problem;
+typedef struct orbx_pg_params {
+  int32_t max_iterations;    /* 1 .. 1000000; the reference: 20 */
+  double lambda_init;        /* finite and > 0; the reference: 1e-16 */
+} orbx_pg_params;
+typedef struct orbx_pg_result {
+  orbx_sim3_pose* vertices;  /* out [n_vertices] */
+  float* points;             /* out [n_points][3], may be NULL: no point is corrected */
+  double* chi2;              /* out [n_edges], may be NULL */
+  int32_t status;            /* ORBX_LBA_DONE / ORBX_LBA_EMPTY */
+  int32_t iterations, trials, stop_reason;
+  double lambda;
+  double chi2_initial, chi2_final;
+} orbx_pg_result;
+/* All arguments are validated before a device is touched, in this order: null pointers and negative counts; max_iterations;
+ * lambda_init; per vertex finite values, s > 0 and a non-zero quaternion; per edge the indices in [0, n_vertices), i != j and the
+ * measurement as a vertex; per point point_ref in [-1, n_vertices) and, where it is not -1, a finite position; at most
+ * ORBX_PG_MAX_KF vertices to optimise.  Valid arguments without a device return ORBX_E_NODEVICE unless the problem has no edge.
+ * One upload and one download per call; two calls on the same input agree bit for bit.  Returns ORBX_OK (see result->status). */
+int orbx_optimize_pose_graph(int device, const orbx_pg_problem* problem, const orbx_pg_params* params, orbx_pg_result* result);
+/* For tests: per edge the error [n_edges][7] and, where jacobians is not NULL, both Jacobians [n_edges][2][7][7] (vertex i, then
+ * vertex j; rows = error components; zero for a fixed vertex) at the given vertices, as the optimiser's first linearisation
+ * computes them.  The problem is validated as above without the capacity; points are not read. */
+int orbx_pose_graph_evaluate(int device, const orbx_pg_problem* problem, double* errors, double* jacobians);
+
 /* ---- new map points (local mapping)------------------------------------------------------------------- */
 
 /* The per-match geometry of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:504-707), which consumes the match list of

@@ -1424,6 +1424,88 @@ def lba_dense_solve(A, b, device=0):
     return dict(x=x, ok=ok.value)
 
 
+# ---- Sim3 pose graph (Optimizer::OptimizeEssentialGraph)
+PG_MAX_KF = 877
+PG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("Sji", SIM3_POSE_DTYPE)])
+assert PG_EDGE_DTYPE.itemsize == 72
+
+
+class _PgProblem(C.Structure):     # orbx_pg_problem
+    _fields_ = [("vertices", C.c_void_p), ("fixed", C.c_void_p), ("n_vertices", C.c_int32), ("edges", C.c_void_p),
+                ("n_edges", C.c_int32), ("fix_scale", C.c_int32), ("points", C.c_void_p), ("point_ref", C.c_void_p),
+                ("n_points", C.c_int32)]
+
+
+class _PgParams(C.Structure):      # orbx_pg_params
+    _fields_ = [("max_iterations", C.c_int32), ("lambda_init", C.c_double)]
+
+
+class _PgResult(C.Structure):      # orbx_pg_result
+    _fields_ = [("vertices", C.c_void_p), ("points", C.c_void_p), ("chi2", C.c_void_p), ("status", C.c_int32),
+                ("iterations", C.c_int32), ("trials", C.c_int32), ("stop_reason", C.c_int32), ("lambda_", C.c_double),
+                ("chi2_initial", C.c_double), ("chi2_final", C.c_double)]
+
+
+def pg_edges(i, j, Sji):
+    """orbx_pg_edge records: vertex 0 = i, vertex 1 = j, the measurements as SIM3_POSE_DTYPE records."""
+    i = np.asarray(i, np.int32).reshape(-1)
+    e = np.zeros(len(i), PG_EDGE_DTYPE)
+    e["i"], e["j"] = i, np.asarray(j, np.int32).reshape(-1)
+    e["Sji"] = np.asarray(Sji, SIM3_POSE_DTYPE).reshape(-1)
+    return e
+
+
+def _pg_problem(vertices, fixed, edges, fix_scale, points, point_ref):
+    V = np.ascontiguousarray(vertices, SIM3_POSE_DTYPE).reshape(-1)
+    fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    if len(fx) != len(V):
+        raise ValueError("fixed must have one entry per vertex")
+    ed = np.ascontiguousarray(edges, PG_EDGE_DTYPE).reshape(-1)
+    X = ref = None
+    if points is not None:
+        X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        ref = np.ascontiguousarray(point_ref, np.int32).reshape(-1)
+        if len(ref) != len(X):
+            raise ValueError("point_ref must have one entry per point")
+    prob = _PgProblem(_p(V).value, _p(fx).value, len(V), _p(ed).value, len(ed), int(bool(fix_scale)),
+                      None if X is None else _p(X).value, None if X is None else _p(ref).value, 0 if X is None else len(X))
+    return prob, (V, fx, ed, X, ref)
+
+
+def OptimizeEssentialGraph(vertices, fixed, edges, bFixScale, points=None, point_ref=None, max_iterations=20, lambda_init=1e-16,
+                           device=0):
+    """The optimiser and the map-point correction of the loop-closing Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1530-1826)
+    on the GPU (orbx_optimize_pose_graph) over the flat graph of include/orbx.h: vertices = SIM3_POSE_DTYPE records (Siw), fixed
+    [nV], edges = PG_EDGE_DTYPE records in the reference's order, points [nP][3] float with point_ref [nP] (the vertex each is
+    corrected through, -1: left alone), both optional.  Returns a dict: vertices [nV] SIM3_POSE_DTYPE (the double Sim3; the caller
+    recovers [R | t / s]), points [nP][3] float32 (None without points; a point with reference -1 keeps its input), chi2 [nE] at
+    the returned estimate, status (LBA_DONE / LBA_EMPTY), iterations, trials, stop_reason (LBA_STOP_*), lambda, chi2_initial,
+    chi2_final."""
+    prob, keep = _pg_problem(vertices, fixed, edges, bFixScale, points, point_ref)
+    V, ed, X = keep[0], keep[2], keep[3]
+    outV, chi2 = np.zeros(len(V), SIM3_POSE_DTYPE), np.zeros(len(ed))
+    outX = None if X is None else X.copy()
+    prm = _PgParams(int(max_iterations), float(lambda_init))
+    res = _PgResult(_p(outV).value, None if outX is None else _p(outX).value, _p(chi2).value)
+    _check(lib().orbx_optimize_pose_graph(int(device), C.byref(prob), C.byref(prm), C.byref(res)))
+    out = dict(vertices=outV, points=outX, chi2=chi2)
+    for name in ("status", "iterations", "trials", "stop_reason", "chi2_initial", "chi2_final"):
+        out[name] = getattr(res, name)
+    out["lambda"] = res.lambda_
+    return out
+
+
+def pose_graph_evaluate(vertices, fixed, edges, bFixScale, jacobians=True, device=0):
+    """orbx_pose_graph_evaluate: the errors [nE][7] of the edges at the given vertices and, with jacobians, both numeric Jacobians
+    [nE][2][7][7] (vertex i, vertex j; zero for a fixed vertex) as the optimiser's first linearisation computes them."""
+    prob, keep = _pg_problem(vertices, fixed, edges, bFixScale, None, None)
+    nE = len(keep[2])
+    err = np.zeros((nE, 7))
+    jac = np.zeros((nE, 2, 7, 7)) if jacobians else None
+    _check(lib().orbx_pose_graph_evaluate(int(device), C.byref(prob), _p(err), None if jac is None else _p(jac)))
+    return (err, jac) if jacobians else err
+
+
 # orbx_debug_linalg: ORBX_LINALG_* and, per operation, the numpy type and the elements of one item of `in` and of `out`
 (LINALG_RCP64, LINALG_RSQRT64, LINALG_JACOBI_CS, LINALG_SVD3, LINALG_NULL_VECTOR4, LINALG_LDLT6, LINALG_LDLT6_DAMPED, LINALG_LDLT7,
  LINALG_NULL_VECTOR_SYM9, LINALG_NULL_VECTOR_SYM12, LINALG_SUM16) = range(11)

@@ -11,8 +11,16 @@
 // Optimizer::GlobalBundleAdjustemnt(Map*, int, bool*, unsigned long, bool) (src/Optimizer.cc:47-372) on orbx_bundle_adjustment, over a
 // GlobalMapView: the vertex and edge listing of :116-278 is GatherGlobalGraph, so that the call sites (src/Tracking.cc:2526,
 // src/LoopClosing.cc:2415) read as in the reference.
+// Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* pLoopKF, KeyFrame* pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+// bFixScale) (src/Optimizer.cc:1530-1826, the loop-closing overload) on orbx_optimize_pose_graph, over an EssentialGraphView: the
+// vertex and edge listing of :1555-1773 is GatherEssentialGraph, the [R | t / s] recovery of :1789-1795 and the choice of every
+// map point's reference key frame (:1805-1811) are host code here, the optimisation and the points' correction are the library's;
+// the call site (src/LoopClosing.cc:1299) reads as in the reference.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
+#include <cmath>
+#include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -353,8 +361,230 @@ inline GbaGraph GatherGlobalGraph(const GlobalMapView& m) {
   return g;
 }
 
+// ---- essential graph (loop closing)
+// g2o::Sim3's operator* and inverse() (sim3.h:266-272, :233-236) with Eigen's quaternion formulas: nothing is normalised
+inline void Sim3Rotate(const double* q, const double* v, double* r) {   // q * v = v + w uv + vec x uv, uv = 2 vec x v
+  const double uv[3] = {2 * (q[1] * v[2] - q[2] * v[1]), 2 * (q[2] * v[0] - q[0] * v[2]), 2 * (q[0] * v[1] - q[1] * v[0])};
+  const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+  for (int i = 0; i < 3; i++) r[i] = v[i] + q[3] * uv[i] + c[i];
+}
+inline Sim3 Sim3Mul(const Sim3& a, const Sim3& b) {
+  Sim3 o;
+  o.q[3] = a.q[3] * b.q[3] - a.q[0] * b.q[0] - a.q[1] * b.q[1] - a.q[2] * b.q[2];
+  o.q[0] = a.q[3] * b.q[0] + a.q[0] * b.q[3] + a.q[1] * b.q[2] - a.q[2] * b.q[1];
+  o.q[1] = a.q[3] * b.q[1] + a.q[1] * b.q[3] + a.q[2] * b.q[0] - a.q[0] * b.q[2];
+  o.q[2] = a.q[3] * b.q[2] + a.q[2] * b.q[3] + a.q[0] * b.q[1] - a.q[1] * b.q[0];
+  double rt[3];
+  Sim3Rotate(a.q, b.t, rt);
+  for (int i = 0; i < 3; i++) o.t[i] = a.s * rt[i] + a.t[i];
+  o.s = a.s * b.s;
+  return o;
+}
+inline Sim3 Sim3Inverse(const Sim3& S) {
+  Sim3 o;
+  o.q[0] = -S.q[0]; o.q[1] = -S.q[1]; o.q[2] = -S.q[2]; o.q[3] = S.q[3];
+  const double m = -1. / S.s, mt[3] = {m * S.t[0], m * S.t[1], m * S.t[2]};
+  Sim3Rotate(o.q, mt, o.t);
+  o.s = 1. / S.s;
+  return o;
+}
+
+// What OptimizeEssentialGraph reads of a KeyFrame.  Key frames are named by their index in the EssentialGraphView.
+struct EgKeyFrame {
+  unsigned long mnId = 0;
+  bool bad = false;                              // isBad()
+  float q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0};   // GetPose(): Tcw as Sophus stores it (x y z w)
+  bool hasCorrected = false, hasNonCorrected = false;   // CorrectedSim3.find(pKF), NonCorrectedSim3.find(pKF)
+  Sim3 corrected, nonCorrected;
+  int parent = -1;                               // GetParent(), -1: none
+  std::vector<int> children;                     // hasChild()
+  std::vector<int> loopEdges;                    // GetLoopEdges(), in the set's order
+  std::vector<int> covisibles;                   // GetCovisiblesByWeight(100), in its order
+  bool bImu = false;
+  int prevKF = -1;                               // mPrevKF, -1: none
+};
+// LoopConnections: the map's entries in the order the caller's map iterates, each set in its order, with GetWeight of each pair
+struct EgLoopConnection {
+  int kf = -1;
+  std::vector<int> connected;
+  std::vector<int> weight;                       // pKF->GetWeight(connected[k])
+};
+struct EgMapPoint {
+  bool bad = false;
+  float pos[3] = {0, 0, 0};                      // GetWorldPos()
+  unsigned long mnCorrectedByKF = 0, mnCorrectedReference = 0;
+  int refKF = -1;                                // GetReferenceKeyFrame()
+};
+struct EssentialGraphView {
+  std::vector<EgKeyFrame> keyFrames;             // vpKFs = pMap->GetAllKeyFrames()
+  std::vector<EgMapPoint> mapPoints;             // vpMPs = pMap->GetAllMapPoints()
+  std::vector<EgLoopConnection> loopConnections;
+  unsigned long loopKFid = 0, curKFid = 0;       // pLoopKF->mnId, pCurKF->mnId
+  unsigned long initKFid = 0;                    // pMap->GetInitKFid()
+  int device = 0;
+};
+// The graph of :1555-1773 as the records of orbx_pg_problem, and the points of :1800-1811
+enum { EG_LOOP_CONNECTION = 0, EG_SPANNING_TREE = 1, EG_LOOP_EDGE = 2, EG_COVISIBILITY = 3, EG_INERTIAL = 4 };
+struct EgGraph {
+  std::vector<int> kfs;                          // vertex -> key frame of the view (the non-bad key frames, in vpKFs order)
+  std::vector<int> vertexOf;                     // key frame of the view -> vertex, -1: none
+  std::vector<orbx_sim3_pose> vertices;          // vScw
+  std::vector<uint8_t> fixed;
+  std::vector<orbx_pg_edge> edges;
+  std::vector<int> edgeClass;                    // EG_*
+  std::vector<int> mps;                          // the non-bad map points of the view
+  std::vector<float> points;                     // [3] each
+  std::vector<int32_t> pointRef;                 // the vertex of nIDr, -1: that key frame has no vertex
+};
+// What the caller applies: per vertex key frame SetPose(Tiw), per map point SetWorldPos + UpdateNormalAndDepth, then
+// pMap->IncreaseChangeIndex().
+struct EgUpdate {
+  std::vector<int> keyFrames;                    // the vertices
+  std::vector<float> poses;                      // [7] each: the SE3f of :1793 -- q (x y z w) the float cast, normalised in float as
+                                                 // Sophus does, and t = (float)translation / (float)s
+  std::vector<int> mapPoints;
+  std::vector<float> positions;                  // [3] each: the float cast of :1819
+  bool optimized = false;                        // false: the graph has no edge -- nothing to apply
+  orbx_pg_result result{};
+};
+
+// :1555-1773 in the reference's edge order.  Vertices: the non-bad key frames, the estimate CorrectedSim3 or else the pose as
+// Sim3(q, t, 1) in double (Sophus normalises the widened quaternion); fixed: mnId == GetInitKFid().  Loop-connection edges are
+// measured on vScw with the minFeat = 100 filter and its pCurKF / pLoopKF exception, and fill sInsertedEdges; then per key frame of
+// vpKFs the spanning-tree edge, the loop edges to smaller ids, the covisibility edges (not the parent, not a child, not bad, a
+// smaller id, the pair not in sInsertedEdges) and the inertial mPrevKF edge, measured on NonCorrectedSim3 where present.
+// Deliberate differences.  An edge with an endpoint that has no vertex (a bad key frame, a bad parent) is dropped: upstream
+// g2o's addEdge refuses a null vertex, the reference's copy (core/hyper_graph.cpp:99-109) would dereference it.  The pair of a
+// dropped loop connection still enters sInsertedEdges, as :1629 inserts it whatever addEdge did.
+inline EgGraph GatherEssentialGraph(const EssentialGraphView& m) {
+  EgGraph g;
+  const int minFeat = 100;
+  const int nKF = (int)m.keyFrames.size();
+  g.vertexOf.assign((size_t)nKF, -1);
+  std::vector<Sim3> vScw((size_t)nKF);           // by key frame of the view (the reference: by mnId); identity where there is no vertex
+  std::map<unsigned long, int> byId;
+  for (int i = 0; i < nKF; i++) {
+    const EgKeyFrame& k = m.keyFrames[(size_t)i];
+    if (k.bad) continue;
+    Sim3 S;
+    if (k.hasCorrected) {
+      S = k.corrected;
+    } else {
+      const double q[4] = {(double)k.q[0], (double)k.q[1], (double)k.q[2], (double)k.q[3]};
+      const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (int c = 0; c < 4; c++) S.q[c] = q[c] / n;
+      for (int c = 0; c < 3; c++) S.t[c] = (double)k.t[c];
+      S.s = 1.0;
+    }
+    vScw[(size_t)i] = S;
+    g.vertexOf[(size_t)i] = (int)g.kfs.size();
+    g.kfs.push_back(i);
+    orbx_sim3_pose r;
+    for (int c = 0; c < 4; c++) r.q[c] = S.q[c];
+    for (int c = 0; c < 3; c++) r.t[c] = S.t[c];
+    r.s = S.s;
+    g.vertices.push_back(r);
+    g.fixed.push_back(k.mnId == m.initKFid ? 1 : 0);
+    byId[k.mnId] = i;
+  }
+  auto add_edge = [&](int i, int j, const Sim3& Sji, int cls) {   // vertex 0 = i, vertex 1 = j
+    if (g.vertexOf[(size_t)i] < 0 || g.vertexOf[(size_t)j] < 0) return;
+    orbx_pg_edge e;
+    e.i = g.vertexOf[(size_t)i];
+    e.j = g.vertexOf[(size_t)j];
+    for (int c = 0; c < 4; c++) e.Sji.q[c] = Sji.q[c];
+    for (int c = 0; c < 3; c++) e.Sji.t[c] = Sji.t[c];
+    e.Sji.s = Sji.s;
+    g.edges.push_back(e);
+    g.edgeClass.push_back(cls);
+  };
+  auto non_corrected = [&](int i) { return m.keyFrames[(size_t)i].hasNonCorrected ? m.keyFrames[(size_t)i].nonCorrected : vScw[(size_t)i]; };
+  std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+  for (const EgLoopConnection& lc : m.loopConnections) {
+    const EgKeyFrame& k = m.keyFrames.at((size_t)lc.kf);
+    const Sim3 Swi = Sim3Inverse(vScw[(size_t)lc.kf]);
+    for (size_t c = 0; c < lc.connected.size(); c++) {
+      const int j = lc.connected[c];
+      const unsigned long nIDi = k.mnId, nIDj = m.keyFrames.at((size_t)j).mnId;
+      if ((nIDi != m.curKFid || nIDj != m.loopKFid) && lc.weight.at(c) < minFeat) continue;
+      add_edge(lc.kf, j, Sim3Mul(vScw[(size_t)j], Swi), EG_LOOP_CONNECTION);
+      sInsertedEdges.insert({std::min(nIDi, nIDj), std::max(nIDi, nIDj)});
+    }
+  }
+  for (int i = 0; i < nKF; i++) {
+    const EgKeyFrame& k = m.keyFrames[(size_t)i];
+    const Sim3 Swi = Sim3Inverse(non_corrected(i));
+    if (k.parent >= 0) add_edge(i, k.parent, Sim3Mul(non_corrected(k.parent), Swi), EG_SPANNING_TREE);
+    for (int l : k.loopEdges)
+      if (m.keyFrames.at((size_t)l).mnId < k.mnId) add_edge(i, l, Sim3Mul(non_corrected(l), Swi), EG_LOOP_EDGE);
+    for (int n : k.covisibles) {
+      if (n < 0 || n == k.parent) continue;
+      bool child = false;
+      for (int c : k.children) child = child || c == n;
+      if (child) continue;
+      const EgKeyFrame& kn = m.keyFrames.at((size_t)n);
+      if (kn.bad || !(kn.mnId < k.mnId)) continue;
+      if (sInsertedEdges.count({std::min(k.mnId, kn.mnId), std::max(k.mnId, kn.mnId)})) continue;
+      add_edge(i, n, Sim3Mul(non_corrected(n), Swi), EG_COVISIBILITY);
+    }
+    if (k.bImu && k.prevKF >= 0) add_edge(i, k.prevKF, Sim3Mul(non_corrected(k.prevKF), Swi), EG_INERTIAL);
+  }
+  // :1800-1811: the reference key frame of every non-bad map point, by mnId as the reference indexes vScw
+  for (int j = 0; j < (int)m.mapPoints.size(); j++) {
+    const EgMapPoint& p = m.mapPoints[(size_t)j];
+    if (p.bad) continue;
+    const unsigned long nIDr = p.mnCorrectedByKF == m.curKFid ? p.mnCorrectedReference : m.keyFrames.at((size_t)p.refKF).mnId;
+    const std::map<unsigned long, int>::const_iterator it = byId.find(nIDr);
+    g.mps.push_back(j);
+    g.points.insert(g.points.end(), p.pos, p.pos + 3);
+    g.pointRef.push_back(it == byId.end() ? -1 : g.vertexOf[(size_t)it->second]);   // no vertex: both maps are the identity
+  }
+  return g;
+}
+
 class Optimizer {
  public:
+  // The loop-closing overload (:1530-1826): gathers the graph, optimises and corrects the points on the device and returns what
+  // the caller applies.  Deliberate difference: :1787 would dereference a null vertex for a bad key frame of vpKFs; the mirror
+  // skips it.  Throws on a library error.
+  static EgUpdate OptimizeEssentialGraph(const EssentialGraphView& map, const bool& bFixScale, int nIterations = 20) {
+    const EgGraph g = GatherEssentialGraph(map);
+    EgUpdate u;
+    orbx_pg_problem prob{};
+    prob.vertices = g.vertices.data();
+    prob.fixed = g.fixed.data();
+    prob.n_vertices = (int)g.vertices.size();
+    prob.edges = g.edges.data();
+    prob.n_edges = (int)g.edges.size();
+    prob.fix_scale = bFixScale ? 1 : 0;
+    prob.points = g.points.data();
+    prob.point_ref = g.pointRef.data();
+    prob.n_points = (int)g.mps.size();
+    orbx_pg_params prm{};
+    prm.max_iterations = nIterations;
+    prm.lambda_init = 1e-16;                       // solver->setUserLambdaInit(1e-16) (:1541)
+    std::vector<orbx_sim3_pose> vertices(g.vertices.size());
+    std::vector<float> positions(g.points);        // a point without a reference vertex keeps its position
+    u.result.vertices = vertices.data();
+    u.result.points = positions.data();
+    if (orbx_optimize_pose_graph(map.device, &prob, &prm, &u.result) != ORBX_OK)
+      throw std::runtime_error(std::string("OptimizeEssentialGraph: ") + orbx_last_error());
+    u.result.vertices = nullptr;                   // the buffers end with this call
+    u.result.points = nullptr;
+    if (u.result.status == ORBX_LBA_EMPTY) return u;
+    u.optimized = true;
+    u.keyFrames = g.kfs;
+    for (const orbx_sim3_pose& S : vertices) {     // :1789-1795: Sim3 [sR t; 0 1] -> SE3 [R t / s; 0 1]
+      float q[4] = {(float)S.q[0], (float)S.q[1], (float)S.q[2], (float)S.q[3]};
+      const float n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      for (int c = 0; c < 4; c++) u.poses.push_back(q[c] / n);
+      for (int c = 0; c < 3; c++) u.poses.push_back((float)S.t[c] / (float)S.s);
+    }
+    u.mapPoints = g.mps;
+    u.positions = positions;
+    return u;
+  }
+
   // Gathers the local graph, honours the zero-fixed abort (:1182, the counters behind num_fixedKF stay as they were) and the stop
   // flag (:1429), optimises on the device and returns what the caller applies.  max_iterations bounds the work: pbStopFlag can
   // not interrupt a running optimisation (include/orbx.h).  Throws on a library error.
