@@ -1245,7 +1245,8 @@ int orbx_optimize_sim3_batch(int device, int n_problems, int cap, const int32_t*
  *    densely in key-frame order.  Both are exact factorisations: results differ by rounding (tests/lba_cases.py measures it).
  *  - KannalaBrandt8 key frames and the EdgeSE3ProjectXYZToBody edges of a two-camera rig (:1383-1423) have an entry of their
  *    own, orbx_local_bundle_adjustment_rig (below): here a key frame with model == ORBX_CAMERA_KB8 or camera2 != 0 is
- *    ORBX_E_BADARG.  Not built: the map-merge overload (:3567), the inertial variants and a batched entry.
+ *    ORBX_E_BADARG.  The map-merge overload (:3567) is orbx_merge_bundle_adjustment (below).  Not built: the inertial variants
+ *    and a batched entry.
  * Capacity: ORBX_LBA_MAX_LOCAL optimised key frames; fixed key frames, points and edges are bounded by int32 and memory. */
 #define ORBX_LBA_MAX_LOCAL 128
 #define ORBX_LBA_DONE 0      /* optimised */
@@ -1333,7 +1334,7 @@ int orbx_local_bundle_adjustment(int device, const orbx_lba_problem* problem, co
  * stop_reason take the ORBX_LBA_* values.  Deliberate difference: the reference writes back the estimate's quaternion after
  * Sophus renormalises the float cast; the library returns the double estimate and leaves the cast to the caller.
  * KannalaBrandt8 key frames and second cameras are rejected as in the local BA and go through orbx_bundle_adjustment_rig
- * (below); the inertial and map-merge variants are not built. */
+ * (below); the map-merge overload of the local BA is orbx_merge_bundle_adjustment (below); the inertial variants are not built. */
 #define ORBX_BA_MAX_KF 1024
 /* solver == 0: fewer optimised key frames take the one-workgroup solver.  Measured on the MI355X (profiles/gba_bench.json, ms per
  * call of 5 trials, blocked against one workgroup): 3.05 / 2.77 at 47 optimised key frames, 4.06 / 4.58 at 63, 8.17 / 20.99 at 127. */
@@ -1415,6 +1416,72 @@ typedef struct orbx_lba_rig_problem {
 int orbx_local_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_lba_params* params,
                                      orbx_lba_result* result);
 int orbx_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_ba_params* params, orbx_ba_result* result);
+
+/* ---- map-merge bundle adjustment (the welding BA of LoopClosing::MergeLocal) ------------------------------- */
+
+/* Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag) (src/Optimizer.cc:3567-3994; the call site
+ * src/LoopClosing.cc, inside MergeLocal, on the welding window), one problem per call, on the device.  It is the g2o problem of
+ * the local bundle adjustment -- Levenberg on BlockSolver_6_3 with the same monocular and stereo edges -- on the same kernel
+ * chain, run as TWO optimisations with a classification in between.  What differs from orbx_local_bundle_adjustment:
+ *  - the problem: orbx_lba_problem as it is.  The n_local key frames of vpAdjustKF come first and must carry fixed == 0 -- the
+ *    map's initial key frame stays free here (there is no GetInitKFid test) --, the n_fixed of vpFixedKF follow and must carry
+ *    fixed != 0; a flag that contradicts its group is ORBX_E_BADARG.  n_fixed may be 0: nothing aborts without a fixed key frame.
+ *    Points in the caller's order (the fixed key frames' points first, then the adjusted ones': :3612-3660), edges grouped by
+ *    ascending point, each point's observations in the caller's order.
+ *  - the Huber deltas are (float)sqrt(5.99) and (float)sqrt(7.815) (:3684 writes 5.99, as the full bundle adjustment does); the
+ *    chi2 gates stay 5.991 and 7.815.
+ *  - the rounds.  (1) optimize(iterations_first) over every edge with its robust kernel.  (2) Unless the stop flag is seen by
+ *    then: every edge whose chi2 -- the one it holds after round one's LAST TRIAL, even a rejected one -- exceeds its gate, or
+ *    whose depth at round one's estimates is not positive, goes to level 1 (result->level); every edge loses its robust kernel.
+ *    (3) initializeOptimization(0), optimize(iterations_second): the level-0 edges only, from round one's estimates bit for bit
+ *    (they never leave the device); a point or key frame without a level-0 edge takes no part and keeps round one's estimate;
+ *    lambda is computed afresh (or is lambda_init again), ni returns to 2, every counter starts again.  (4) erase: chi2 over the
+ *    gate or depth not positive, where a level-1 edge holds the chi2 of round one's last trial (round two never evaluates it)
+ *    and every depth is taken at the FINAL estimates -- an edge put aside for its depth alone may come back un-erased.
+ *    If every edge is put aside round two has nothing to optimise: rounds = 2, its counters are zero, round one's estimates
+ *    come back.
+ *  - stop_flag (pbStopFlag, may be NULL) is read as orbx_ba_params::stop_flag is.  Set when the call starts: the widened
+ *    inputs, ORBX_LBA_STOPPED, rounds = 0, no device is touched.  Seen during round one or right behind it (the reference's
+ *    bDoMore = false): no classification and no round two; rounds = 1, level is zero, the erase flags come from round one's
+ *    robust edges, status ORBX_LBA_STOPPED.  Seen during round two: the last accepted estimate, rounds = 2, ORBX_LBA_STOPPED.
+ * A key frame or point without any edge comes back as the widened input; a problem without an edge is ORBX_LBA_EMPTY with the
+ * widened inputs.  Per-round fields are indexed by round - 1; a round that did not run holds zeros.  lambda_init > 0 is round
+ * one's setUserLambdaInit (the reference sets none: pass 0; tests steer round one with it); round two computes its own.
+ * orbx_merge_bundle_adjustment_rig takes KannalaBrandt8 left cameras (the reference builds these edges through pKF->mpCamera)
+ * under the checks of orbx_local_bundle_adjustment_rig; this overload builds no EdgeSE3ProjectXYZToBody edge and never reads the
+ * right index, so an edge with edge_camera == 1 is ORBX_E_BADARG.  A pinhole problem through it returns the bits of the plain entry.
+ * Everything is validated before a device is touched: null pointers and negative counts, both iteration counts in
+ * [1, 1000000], every check of the local entries, the fixed flags of both groups, (rig) no camera-1 edge, at most
+ * ORBX_LBA_MAX_LOCAL key frames to optimise (MergeLocal hands over 25 + 25).  Valid arguments without a device return
+ * ORBX_E_NODEVICE unless the call ends before the optimiser.  Two calls on the same input agree bit for bit.
+ * Not built: the inertial MergeInertialBA. */
+typedef struct orbx_mba_params {
+  int32_t iterations_first;          /* 1 .. 1000000; the reference's optimize(5) */
+  int32_t iterations_second;         /* 1 .. 1000000; the reference's optimize(10) */
+  float lambda_init;                 /* > 0: round one's setUserLambdaInit; otherwise computed (the reference's) */
+  int32_t reserved;                  /* 0 */
+  const volatile int32_t* stop_flag; /* may be NULL */
+} orbx_mba_params;
+typedef struct orbx_mba_result {
+  double* poses;            /* out [n_local][7]: q (x y z w), t */
+  double* points;           /* out [n_points][3] */
+  uint8_t* erase;           /* out [n_edges]: the edge's (key frame, point) pair belongs to vToErase */
+  double* chi2;             /* out [n_edges]: the chi2 the edge holds at the end */
+  uint8_t* depth_positive;  /* out [n_edges]: isDepthPositive() at the final estimates */
+  uint8_t* level;           /* out [n_edges]: 1 = put aside after round one */
+  int32_t status;           /* ORBX_LBA_DONE / ORBX_LBA_STOPPED / ORBX_LBA_EMPTY */
+  int32_t rounds;           /* 0, 1 or 2 */
+  int32_t n_level1;         /* edges put aside */
+  int32_t reserved;
+  int32_t iterations[2], trials[2], stop_reason[2];
+  double lambda[2], chi2_initial[2], chi2_final[2];
+} orbx_mba_result;
+int orbx_merge_bundle_adjustment(int device, const orbx_lba_problem* problem, const orbx_mba_params* params, orbx_mba_result* result);
+int orbx_merge_bundle_adjustment_rig(int device, const orbx_lba_rig_problem* problem, const orbx_mba_params* params,
+                                     orbx_mba_result* result);
+/* For tests: on != 0 makes the calling thread's following merge calls behave as if the stop flag were seen right behind round
+ * one (a second thread cannot be timed to that point).  Returns the previous setting. */
+int orbx_merge_ba_stop_after_first(int on);
 
 /* ---- Sim3 pose graph (Optimizer::OptimizeEssentialGraph) --------------------------------------------------- */
 

@@ -101,6 +101,9 @@ def lib():
         L.orbx_stereo_download.argtypes = [vp, i, vp, vp, i]
         L.orbx_rgbd_depth_batch.argtypes = [vp, i, i, vp, i, C.c_ssize_t, C.c_ssize_t, f, f, vp, vp, i, vp]
         L.orbx_pose_optimization.argtypes = [i, vp, vp, vp, vp, i, vp, i, vp, vp]
+        L.orbx_merge_bundle_adjustment.argtypes = [i, vp, vp, vp]
+        L.orbx_merge_bundle_adjustment_rig.argtypes = [i, vp, vp, vp]
+        L.orbx_merge_ba_stop_after_first.argtypes = [i]
         L.orbx_pose_optimization_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
         L.orbx_pose_optimization_kb8.argtypes = [i, vp, i, i, vp, vp, vp, i, vp, vp]
         L.orbx_pose_optimization_fisheye_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
@@ -1375,6 +1378,68 @@ def LocalBundleAdjustmentRig(keyframes, cams, n_local, points, edges, edge_camer
         out[name] = getattr(res, name)
     out["lambda"] = res.lambda_
     return out
+
+
+# ---- map-merge bundle adjustment (the welding BA of LoopClosing::MergeLocal)
+class _MbaParams(C.Structure):     # orbx_mba_params
+    _fields_ = [("iterations_first", C.c_int32), ("iterations_second", C.c_int32), ("lambda_init", C.c_float), ("reserved", C.c_int32),
+                ("stop_flag", C.c_void_p)]
+
+
+class _MbaResult(C.Structure):     # orbx_mba_result
+    _fields_ = [("poses", C.c_void_p), ("points", C.c_void_p), ("erase", C.c_void_p), ("chi2", C.c_void_p),
+                ("depth_positive", C.c_void_p), ("level", C.c_void_p), ("status", C.c_int32), ("rounds", C.c_int32),
+                ("n_level1", C.c_int32), ("reserved", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2),
+                ("stop_reason", C.c_int32 * 2), ("lambda_", C.c_double * 2), ("chi2_initial", C.c_double * 2),
+                ("chi2_final", C.c_double * 2)]
+
+
+def _merge_ba(entry, prob, n_local, nP, nE, iterations_first, iterations_second, lambda_init, stop, device):
+    if stop is not None and not (isinstance(stop, np.ndarray) and stop.dtype == np.int32 and stop.size == 1):
+        raise TypeError("stop must be None or a one-element int32 numpy array")
+    fn = getattr(lib(), entry)
+    poses, pts = np.zeros((max(n_local, 0), 7)), np.zeros((nP, 3))
+    erase, depth, level, chi2 = np.zeros(nE, np.uint8), np.zeros(nE, np.uint8), np.zeros(nE, np.uint8), np.zeros(nE)
+    prm = _MbaParams(int(iterations_first), int(iterations_second), float(lambda_init), 0, None if stop is None else _p(stop).value)
+    res = _MbaResult(_p(poses).value, _p(pts).value, _p(erase).value, _p(chi2).value, _p(depth).value, _p(level).value)
+    _check(fn(int(device), C.byref(prob), C.byref(prm), C.byref(res)))
+    out = dict(poses=poses, points=pts, erase=erase, chi2=chi2, depth_positive=depth, level=level, status=res.status, rounds=res.rounds,
+               n_level1=res.n_level1)
+    for name in ("iterations", "trials", "stop_reason", "chi2_initial", "chi2_final"):
+        out[name] = list(getattr(res, name))
+    out["lambda"] = list(res.lambda_)
+    return out
+
+
+def merge_bundle_adjustment(keyframes, n_adjust, points, edges, iterations_first=5, iterations_second=10, lambda_init=0.0, stop=None,
+                            device=0):
+    """The map-merge Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag) (src/Optimizer.cc:3567-3994) on the
+    GPU (orbx_merge_bundle_adjustment): keyframes = LBA_KEYFRAME_DTYPE records, the n_adjust key frames of vpAdjustKF first (fixed ==
+    0), those of vpFixedKF behind them (fixed != 0, there may be none); points [nP][3] float; edges = LBA_EDGE_DTYPE records grouped
+    by ascending point.  stop: None, or a one-element int32 numpy array (pbStopFlag) as BundleAdjustment takes it.  Returns a dict:
+    poses [n_adjust][7] double, points [nP][3] double, erase / depth_positive / level [nE] uint8, chi2 [nE] double, status (LBA_DONE /
+    LBA_STOPPED / LBA_EMPTY), rounds, n_level1 and, per round as lists of two, iterations, trials, stop_reason, lambda, chi2_initial,
+    chi2_final."""
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ed = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    n_adjust = int(n_adjust)
+    prob = _LbaProblem(_p(kf).value, _p(X).value, _p(ed).value, n_adjust, len(kf) - n_adjust, len(X), len(ed))
+    return _merge_ba("orbx_merge_bundle_adjustment", prob, n_adjust, len(X), len(ed), iterations_first, iterations_second, lambda_init,
+                     stop, device)
+
+
+def merge_bundle_adjustment_rig(keyframes, cams, n_adjust, points, edges, edge_camera, iterations_first=5, iterations_second=10,
+                                lambda_init=0.0, stop=None, device=0):
+    """merge_bundle_adjustment for KannalaBrandt8 left cameras (orbx_merge_bundle_adjustment_rig): plus cams and edge_camera as
+    LocalBundleAdjustmentRig takes them; this overload builds no second-camera edge, so edge_camera must be all zero."""
+    kf = np.ascontiguousarray(keyframes, LBA_KEYFRAME_DTYPE).reshape(-1)
+    X = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ed = np.ascontiguousarray(edges, LBA_EDGE_DTYPE).reshape(-1)
+    n_adjust = int(n_adjust)
+    prob, keep = _lba_rig_problem(kf, X, ed, cams, edge_camera, n_adjust)
+    return _merge_ba("orbx_merge_bundle_adjustment_rig", prob, n_adjust, len(X), len(ed), iterations_first, iterations_second,
+                     lambda_init, stop, device)
 
 
 def BundleAdjustmentRig(keyframes, cams, points, edges, edge_camera, max_iterations=5, robust=True, lambda_init=0.0, stop=None,

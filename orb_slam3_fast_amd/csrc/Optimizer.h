@@ -16,8 +16,13 @@
 // vertex and edge listing of :1555-1773 is GatherEssentialGraph, the [R | t / s] recovery of :1789-1795 and the choice of every
 // map point's reference key frame (:1805-1811) are host code here, the optimisation and the points' correction are the library's;
 // the call site (src/LoopClosing.cc:1299) reads as in the reference.
+// Optimizer::LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF, vector<KeyFrame*> vpFixedKF, bool*) (src/
+// Optimizer.cc:3567-3994, the map-merge overload) on orbx_merge_bundle_adjustment, over a MergeMapView: the vertex, point and edge
+// listing of :3596-3790 is GatherMergeGraph, both optimisations and the classification between them are the library's; the call
+// site in LoopClosing::MergeLocal reads as in the reference.
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <set>
@@ -361,6 +366,104 @@ inline GbaGraph GatherGlobalGraph(const GlobalMapView& m) {
   return g;
 }
 
+// ---- map-merge bundle adjustment (the welding BA of LoopClosing::MergeLocal)
+// What Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag) (src/Optimizer.cc:3567-3994) reads.
+struct MergeMapView {
+  std::vector<LbaKeyFrame> keyFrames;       // every key frame an observation may name
+  std::vector<LbaMapPoint> mapPoints;
+  int main = 0;                             // pMainKF: its map is the current one
+  std::vector<int> adjust;                  // vpAdjustKF, as indices into keyFrames
+  std::vector<int> fixed;                   // vpFixedKF
+  int device = 0;
+};
+// The graph of :3596-3790: the vertices (adjusted key frames first, as orbx_lba_problem lists them), vpMPs and the records.
+struct MergeGraph {
+  std::vector<int> adjustKFs, fixedKFs, mps;   // indices into the view; mps is vpMPs in the order of :3616-3658
+  std::vector<orbx_lba_keyframe> kfs;
+  std::vector<float> points;
+  std::vector<orbx_lba_edge> edges;
+  std::vector<std::pair<int, int>> edgePair;   // per edge: (key frame, map point) of the view
+  std::vector<orbx_lba_rig_camera> cams;       // per record of kfs, and per edge its camera (always 0): the rig entry's arrays
+  std::vector<uint8_t> edgeCam;
+  bool rig = false;                            // a vertex is KannalaBrandt8 or has a second camera
+};
+// What the caller applies: SetPose for the adjusted key frames, SetWorldPos + UpdateNormalAndDepth for the points and, per
+// vToErase pair, EraseMapPointMatch / EraseObservation (:3891-3990).
+struct MergeBaUpdate {
+  std::vector<int> keyFrames;                // the adjusted key frames that are vertices
+  std::vector<float> poses;                  // [7] each: q (x y z w), t -- the float casts of :3979
+  std::vector<int> mapPoints;                // vpMPs
+  std::vector<float> positions;              // [3] each: the float cast of :3989
+  std::vector<std::pair<int, int>> vToErase; // (key frame, map point): monocular edges in edge order, then stereo (:3849-3881)
+  bool optimized = false;                    // false: stopped before optimize(5) or nothing to optimise -- nothing to apply
+  orbx_mba_result result{};
+};
+
+// :3596-3790 with the reference's filters and order.  The fixed key frames of vpFixedKF that are not bad and belong to pMainKF's
+// map, then the adjusted ones of vpAdjustKF under the same filter -- the map's initial key frame included: there is no
+// GetInitKFid test here; each brings the map points of its slots that are not bad and of the same map, once.  Per point of
+// vpMPs, per observation in the caller's order: skipped when its key frame is bad, is no vertex (mnBALocalForMerge) or holds no
+// map point at the observation's left index; then the left key point's monocular or stereo edge.  The right index is never read
+// and there is no body edge.
+// Deliberate differences.  GetMapPoints() iterates a std::set<MapPoint*> by pointer value; the mirror takes a key frame's points
+// in ascending view index, which changes only the order of sums.  An observation with left index -1 is skipped: the reference
+// would index mvpMapPoints[-1].  A key frame listed in both lists (or twice in one) is taken once, where it comes first -- so one
+// of both lists is fixed: g2o refuses the second vertex of an id.
+inline MergeGraph GatherMergeGraph(const MergeMapView& m) {
+  MergeGraph g;
+  const int nKF = (int)m.keyFrames.size(), nMP = (int)m.mapPoints.size();
+  const int curMap = m.keyFrames.at((size_t)m.main).map;
+  std::vector<char> vertex((size_t)nKF, 0), mpTaken((size_t)nMP, 0);
+  auto take = [&](const std::vector<int>& list, std::vector<int>& out) {
+    for (int i : list) {
+      const LbaKeyFrame& k = m.keyFrames.at((size_t)i);
+      if (k.bad || k.map != curMap || vertex[(size_t)i]) continue;
+      vertex[(size_t)i] = 1;
+      out.push_back(i);
+      std::vector<int> view;                       // GetMapPoints(): the non-bad points of the slots, each once
+      for (int j : k.mvpMapPoints)
+        if (j >= 0 && !m.mapPoints.at((size_t)j).bad) view.push_back(j);
+      std::sort(view.begin(), view.end());
+      view.erase(std::unique(view.begin(), view.end()), view.end());
+      for (int j : view)
+        if (m.mapPoints[(size_t)j].map == curMap && !mpTaken[(size_t)j]) {
+          mpTaken[(size_t)j] = 1;
+          g.mps.push_back(j);
+        }
+    }
+  };
+  take(m.fixed, g.fixedKFs);
+  take(m.adjust, g.adjustKFs);
+  std::vector<int> flat((size_t)nKF, -1);
+  auto add = [&](int i, bool fixed) {
+    const LbaKeyFrame& k = m.keyFrames[(size_t)i];
+    orbx_lba_keyframe r{};
+    for (int c = 0; c < 4; c++) r.q[c] = k.q[c];
+    for (int c = 0; c < 3; c++) r.t[c] = k.t[c];
+    r.fx = k.fx; r.fy = k.fy; r.cx = k.cx; r.cy = k.cy; r.bf = k.mbf;
+    r.model = k.cameraModel;
+    r.fixed = fixed ? 1 : 0;
+    r.camera2 = k.hasCamera2 ? 1 : 0;
+    flat[(size_t)i] = (int)g.kfs.size();
+    g.kfs.push_back(r);
+    g.cams.push_back(LbaRigCamera(k));
+    if (LbaIsRigKeyFrame(k)) g.rig = true;
+  };
+  for (int i : g.adjustKFs) add(i, false);
+  for (int i : g.fixedKFs) add(i, true);
+  for (size_t n = 0; n < g.mps.size(); n++) {
+    const LbaMapPoint& p = m.mapPoints[(size_t)g.mps[n]];
+    g.points.insert(g.points.end(), p.pos, p.pos + 3);
+    for (const std::pair<int, int>& ob : p.observations) {
+      const LbaKeyFrame& k = m.keyFrames.at((size_t)ob.first);
+      if (k.bad || flat[(size_t)ob.first] < 0 || ob.second == -1 || k.mvpMapPoints.at((size_t)ob.second) < 0) continue;
+      const int added = LbaObservationEdges(k, ob.second, -1, flat[(size_t)ob.first], (int)n, g.edges, g.edgeCam);
+      for (int a = 0; a < added; a++) g.edgePair.push_back({ob.first, g.mps[n]});
+    }
+  }
+  return g;
+}
+
 // ---- essential graph (loop closing)
 // g2o::Sim3's operator* and inverse() (sim3.h:266-272, :233-236) with Eigen's quaternion formulas: nothing is normalised
 inline void Sim3Rotate(const double* q, const double* v, double* r) {   // q * v = v + w uv + vec x uv, uv = 2 vec x v
@@ -637,6 +740,63 @@ class Optimizer {
         if (erase[i] && cls == pass) u.vToErase.push_back(g.edgePair[i]);
       }
     return u;
+  }
+
+  // The map-merge overload (:3567-3994): gathers the welding window's graph, runs both optimisations and the classification
+  // between them on the device and returns what the caller applies.  stopFlag (may be null) is asked by the library while the
+  // call runs: set when it starts, nothing is optimised (optimized == false, as the reference returns at :3793); seen later, the
+  // result is still written back, as the reference does.  A view with a KannalaBrandt8 key frame goes through the rig entry.
+  // Throws on a library error.
+  static MergeBaUpdate LocalBundleAdjustment(const MergeMapView& map, const volatile int32_t* stopFlag, int iterationsFirst = 5,
+                                             int iterationsSecond = 10) {
+    const MergeGraph g = GatherMergeGraph(map);
+    MergeBaUpdate u;
+    orbx_lba_problem prob{};
+    prob.keyframes = g.kfs.data();
+    prob.points = g.points.data();
+    prob.edges = g.edges.data();
+    prob.n_local = (int)g.adjustKFs.size();
+    prob.n_fixed = (int)g.fixedKFs.size();
+    prob.n_points = (int)g.mps.size();
+    prob.n_edges = (int)g.edges.size();
+    orbx_mba_params prm{};
+    prm.iterations_first = iterationsFirst;
+    prm.iterations_second = iterationsSecond;
+    prm.stop_flag = stopFlag;
+    std::vector<double> poses(7 * g.adjustKFs.size()), points(3 * g.mps.size()), chi2(g.edges.size());
+    std::vector<uint8_t> erase(g.edges.size()), depth(g.edges.size()), level(g.edges.size());
+    u.result.poses = poses.data();
+    u.result.points = points.data();
+    u.result.erase = erase.data();
+    u.result.chi2 = chi2.data();
+    u.result.depth_positive = depth.data();
+    u.result.level = level.data();
+    orbx_lba_rig_problem rig{};   // as in the local overload
+    rig.base = prob;
+    rig.cams = g.kfs.empty() ? nullptr : g.cams.data();
+    rig.edge_camera = g.edgeCam.data();
+    if ((g.rig ? orbx_merge_bundle_adjustment_rig(map.device, &rig, &prm, &u.result)
+               : orbx_merge_bundle_adjustment(map.device, &prob, &prm, &u.result)) != ORBX_OK)
+      throw std::runtime_error(std::string("LocalBundleAdjustment (map merge): ") + orbx_last_error());
+    u.result.poses = u.result.points = u.result.chi2 = nullptr;   // the buffers end with this call
+    u.result.erase = u.result.depth_positive = u.result.level = nullptr;
+    if (u.result.rounds == 0) return u;            // stopped at the start, or no edge
+    u.optimized = true;                            // a stopped optimisation is written back too
+    u.keyFrames = g.adjustKFs;
+    u.mapPoints = g.mps;
+    for (double v : poses) u.poses.push_back((float)v);
+    for (double v : points) u.positions.push_back((float)v);
+    for (int pass = 0; pass < 2; pass++)           // vpEdgesMono, then vpEdgesStereo
+      for (size_t i = 0; i < g.edges.size(); i++)
+        if (erase[i] && (g.edges[i].u_right < 0 ? 0 : 1) == pass) u.vToErase.push_back(g.edgePair[i]);
+    return u;
+  }
+  // The reference's signature.  NOTE: *pbStopFlag is read ONCE, when the call starts: set by then, nothing is optimised; set
+  // later, it is NOT seen and both rounds run -- unlike the reference, where the flag ends a running optimize() between trials
+  // and decides bDoMore.  A call site that needs that keeps an int32_t flag and calls the overload above.
+  static MergeBaUpdate LocalBundleAdjustment(const MergeMapView& map, const bool* pbStopFlag) {
+    const int32_t stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+    return LocalBundleAdjustment(map, &stop);
   }
 
   // Gathers the graph, optimises on the device and returns what the caller applies.  stopFlag is asked by the library while the

@@ -123,7 +123,34 @@ void lba_passthrough(const orbx_lba_problem& p, int nPoses, LbaRun& r) {
   r.stopped = 0;
   r.iterations = r.trials = r.stopReason = 0;
   r.lambda = r.chiInitial = r.chiFinal = 0;
+  if (r.level) std::memset(r.level, 0, (size_t)p.n_edges);
+  r.rounds = r.nLevel1 = 0;
+  r.firstIterations = r.firstTrials = r.firstStopReason = 0;
+  r.firstLambda = r.firstChiInitial = r.firstChiFinal = 0;
 }
+
+namespace {
+
+// One optimize(): solve(0) at the estimate, then a chain per trial with one status word read back after each.  The stop flag is
+// g2o's terminate(): asked in front of the first trial and after every trial; once seen, the estimate is the last accepted one.
+int lba_trials(const LbaArgs& a, Pack& pk, size_t oStatus, const volatile int32_t* stopFlag, int& stopped) {
+  HIPC(launch_lba_evaluate(a));   // solve(0): the system at the start, lambda
+  stopped = stopFlag && *stopFlag ? 1 : 0;
+  for (long long trial = 0; !stopped && trial < 10LL * a.maxIter; trial++) {   // (the device stops earlier; the bound is g2o's own)
+    HIPC(launch_lba_trial(a));
+    HIPC(launch_lba_evaluate(a));
+    hipError_t e;
+    const uint8_t* h = pk.fetch(oStatus, sizeof(int), &e);
+    if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+    int running;
+    std::memcpy(&running, h, sizeof running);
+    if (!running) break;
+    if (stopFlag && *stopFlag) stopped = 1;
+  }
+  return ORBX_OK;
+}
+
+}  // namespace
 
 int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, const LbaConfig& cfg, LbaRun& r) {
   const int nKF = p.n_local + p.n_fixed, nOpt = g.nOpt;
@@ -182,6 +209,17 @@ int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, cons
   pk.area(a.xp, n, 16);
   pk.area(a.xl, 3 * nP, 16);
   pk.area(a.st, 1, 16);
+  const bool merge = cfg.secondIterations > 0;
+  size_t oCounts = 0, oCounters = 0, oScalars = 0, oLevel = 0;
+  if (merge) {   // what the step between the rounds writes; counts, scalars and counters come back in one piece
+    pk.area(a.rl.ptLive, nP, 16);
+    pk.area(a.rl.slot, (size_t)nKF, 16);
+    pk.area(a.rl.row, (size_t)nOpt, 16);
+    oCounts = pk.area(a.rl.counts, 4, 16);
+    oCounters = pk.area(a.rl.counters, 4, 16);
+    oScalars = pk.area(a.rl.scalars, 3, 32);
+    oLevel = pk.area(a.rl.level, nE, 16);
+  }
   // outputs: one contiguous area
   const size_t oStatus = pk.area(a.status, 1, 16);
   const size_t oScal = pk.area(a.outScalars, 3, 16);
@@ -197,19 +235,47 @@ int lba_optimise(int device, const orbx_lba_problem& p, const LbaLayout& g, cons
   e = pk.commit();
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   HIPC(launch_lba_init(a));
-  HIPC(launch_lba_evaluate(a));   // solve(0): the system at the start, lambda
-  r.stopped = cfg.stopFlag && *cfg.stopFlag ? 1 : 0;   // g2o's terminate() in front of the first trial
-  for (long long trial = 0; !r.stopped && trial < 10LL * cfg.maxIterations; trial++) {   // (the device stops earlier; the bound is g2o's own)
-    HIPC(launch_lba_trial(a));
-    HIPC(launch_lba_evaluate(a));
-    const uint8_t* h = pk.fetch(oStatus, sizeof(int), &e);
+  rc = lba_trials(a, pk, oStatus, cfg.stopFlag, r.stopped);
+  if (rc != ORBX_OK) return rc;
+  LbaArgs fin = a;
+  r.rounds = 1;
+  r.nLevel1 = 0;
+  if (merge && !r.stopped && !cfg.stopAfterFirst && !(cfg.stopFlag && *cfg.stopFlag)) {   // bDoMore: the flag is read once more behind optimize(5)
+    HIPC(launch_lba_relevel(a));
+    const uint8_t* h = pk.fetch(oCounts, oScalars + 3 * sizeof(double) - oCounts, &e);   // round two's sizes, round one's record
     if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-    int running;
-    std::memcpy(&running, h, sizeof running);
-    if (!running) break;
-    if (cfg.stopFlag && *cfg.stopFlag) r.stopped = 1;   // ... and after every trial: the estimate is the last accepted one
+    int cnt[2], first[3];
+    double scal[3];
+    std::memcpy(cnt, h, sizeof cnt);
+    std::memcpy(first, h + (oCounters - oCounts), sizeof first);
+    std::memcpy(scal, h + (oScalars - oCounts), sizeof scal);
+    r.firstLambda = scal[0]; r.firstChiInitial = scal[1]; r.firstChiFinal = scal[2];
+    r.firstIterations = first[0]; r.firstTrials = first[1]; r.firstStopReason = first[2];
+    r.rounds = 2;
+    r.nLevel1 = cnt[1];
+    // round two: the level-0 edges without robust kernels, the slots renumbered over the key frames that keep one
+    fin.level = a.rl.level; fin.ptLive = a.rl.ptLive; fin.row = a.rl.row; fin.slot0 = a.slot; fin.slot = a.rl.slot;
+    fin.nOpt = cnt[0]; fin.n = 6 * cnt[0];
+    fin.maxIter = cfg.secondIterations;
+    fin.robust = 0;
+    fin.lambdaInit = 0;
+    if (r.nLevel1 < p.n_edges) {   // otherwise g2o has nothing to optimise: round one's estimates stand
+      rc = lba_trials(fin, pk, oStatus, cfg.stopFlag, r.stopped);
+      if (rc != ORBX_OK) return rc;
+    }
+  } else if (merge) {
+    r.stopped = 1;
   }
-  HIPC(launch_lba_finish(a));
+  HIPC(launch_lba_finish(fin));
+  if (r.level) {
+    if (r.rounds == 2) {
+      const uint8_t* hl = pk.fetch(oLevel, nE, &e);
+      if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+      std::memcpy(r.level, hl, nE);
+    } else {
+      std::memset(r.level, 0, nE);
+    }
+  }
   const uint8_t* h = pk.fetch(oStatus, outEnd - oStatus, &e);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
   double scal[3];

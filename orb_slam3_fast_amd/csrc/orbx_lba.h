@@ -22,6 +22,18 @@ struct LbaState {
   int cur, stage, iter, qmax, nbadR, trials, ok, running, stopReason, pad;
 };
 
+// What the step between the two optimisations of the map-merge bundle adjustment writes (k_lba_relevel, k_lba_relayout): round
+// two reads these through LbaArgs::level / ptLive / slot / row.
+struct LbaRelevel {
+  uint8_t* level;     // [nE] 1: the edge was put aside after round one (setLevel(1))
+  int* ptLive;        // [nP] level-0 edges of the point
+  int* slot;          // [nKF] row block of round two's reduced system, -1: not in its active set
+  int* row;           // [nOpt] round two's slot -> round one's slot, the row of kfStart
+  int* counts;        // round two's nOpt, the number of level-1 edges
+  double* scalars;    // round one's lambda, chi2_initial, chi2_final
+  int* counters;      // round one's iterations, trials, stop_reason
+};
+
 struct LbaArgs {
   const orbx_lba_keyframe* kfs;   // [nKF]
   const orbx_lba_edge* edges;     // [nE]
@@ -66,6 +78,14 @@ struct LbaArgs {
   const orbx_lba_rig_camera* cams;   // [nKF]
   const uint8_t* edgeCam;            // [nE] 0 left, 1 second camera
   LbaRigTrl* trl;                    // [nKF] mTrl as the edges hold it, written by k_lba_rig_init
+  // The map-merge entries only (orbx_api_merge_ba.hip).  level == nullptr is every other call: no edge is masked, a slot is its
+  // own row of kfStart and the points' and key frames' active sets are what ptStart and slot say.  Round two of the merge entries
+  // sets all four to LbaRelevel's arrays and slot to LbaRelevel::slot: the kernels skip level-1 edges and what has no level-0 edge.
+  const uint8_t* level;              // [nE]
+  const int* ptLive;                 // [nP]
+  const int* row;                    // [nOpt]
+  const int* slot0;                  // [nKF] round one's slot: the key frames whose estimate comes back (nullptr: slot)
+  LbaRelevel rl;
 };
 
 // ---- the host side the two bundle adjustments' entries share (orbx_api_lba.hip)
@@ -88,6 +108,10 @@ struct LbaConfig {
   int nPoses;                          // the first nPoses key frames come back
   const orbx_lba_rig_camera* cams;     // the rig entries: the kernels of the rig chain; nullptr: the pinhole chain
   const uint8_t* edgeCam;
+  // the map-merge entries: secondIterations > 0 runs a second optimize() over the edges that pass the classification, without
+  // robust kernels, unless the stop flag was seen by then
+  int secondIterations;
+  int stopAfterFirst;                  // tests: the stop flag counts as seen right behind round one
 };
 
 // outputs of a run; chi2 / erase / depthPos may be nullptr
@@ -97,8 +121,13 @@ struct LbaRun {
   double* chi2;
   uint8_t* erase;
   uint8_t* depthPos;
-  int stopped, iterations, trials, stopReason;
+  int stopped, iterations, trials, stopReason;   // of the last optimize() that ran
   double lambda, chiInitial, chiFinal;
+  // the map-merge entries (LbaConfig::secondIterations > 0)
+  uint8_t* level;                                // [nE], may be nullptr
+  int rounds, nLevel1;                           // optimize() calls that were reached; edges put aside
+  int firstIterations, firstTrials, firstStopReason;   // round one, when rounds == 2
+  double firstLambda, firstChiInitial, firstChiFinal;
 };
 
 // every check of a problem that needs no device, in the order the entries report them; fills g
@@ -115,6 +144,8 @@ hipError_t launch_lba_init(const LbaArgs& a);       // estimates from the inputs
 hipError_t launch_lba_evaluate(const LbaArgs& a);   // linearise at the estimate (stage 0) or the trial, reduce, decide
 hipError_t launch_lba_trial(const LbaArgs& a);      // Dinv, Schur complement, factorisation and solve, back-substitution, oplus
 hipError_t launch_lba_finish(const LbaArgs& a);     // classification and outputs
+// between the rounds of the map-merge entries: the levels by k_lba_finish's erase rule, round two's layout into a.rl, a fresh state
+hipError_t launch_lba_relevel(const LbaArgs& a);
 // k_lba_solve alone, as launch_lba_trial launches it: reads n, S, bs; writes xp (when every pivot holds) and st->ok
 hipError_t launch_lba_solve(const LbaArgs& a);
 

@@ -13,6 +13,10 @@
 //                     along as one more row, then the back-substitution
 //   k_lba_update      one point / key frame per thread: xl = Dinv (bl - Hpl^T xp), oplus into the trial copy
 //   k_lba_finish      classification at the held chi2 and the final depth, the outputs
+// The map-merge overload (Optimizer.cc:3567-3994; orbx_api_merge_ba.hip) runs the chain twice.  Between the rounds k_lba_relevel
+// puts aside the edges k_lba_finish would erase and k_lba_relayout renumbers the slots over the key frames that keep a level-0
+// edge and starts a fresh Levenberg state; round two's kernels skip the masked edges (LbaArgs::level) and whatever left the
+// active set, over the CSR lists as they are -- nothing is compacted, so every sum keeps the reference's edge order.
 // The full bundle adjustment (Optimizer::BundleAdjustment, :47-372; orbx_api_ba.hip) runs the same chain: LbaArgs carries what it
 // does differently -- the robust kernel optional, its own Huber deltas, and the blocked LDLT of orbx_ba.hip in place of k_lba_solve.
 // The rig entries (KannalaBrandt8 key frames, second cameras: orbx_local_bundle_adjustment_rig, orbx_bundle_adjustment_rig) swap
@@ -191,7 +195,7 @@ __device__ __forceinline__ void lba_edge_store(const LbaArgs& A, int ei, int tgt
 
 __global__ __launch_bounds__(kLbaBS) void k_lba_linearize(LbaArgs A) {
   const int ei = blockIdx.x * kLbaBS + threadIdx.x;
-  if (ei >= A.nE) return;
+  if (ei >= A.nE || (A.level && A.level[ei])) return;   // a masked edge keeps the chi2 it holds
   const LbaState& st = *A.st;
   const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
   const orbx_lba_edge E = A.edges[ei];
@@ -296,7 +300,7 @@ __device__ __forceinline__ void lba_rig_edge(const LbaArgs& A, const orbx_lba_ke
 // k_lba_linearize
 __global__ __launch_bounds__(kLbaBS) void k_lba_linearize_rig(LbaArgs A) {
   const int ei = blockIdx.x * kLbaBS + threadIdx.x;
-  if (ei >= A.nE) return;
+  if (ei >= A.nE || (A.level && A.level[ei])) return;   // a masked edge keeps the chi2 it holds
   const LbaState& st = *A.st;
   const int tgt = st.stage == 0 ? st.cur : st.cur ^ 1;
   const orbx_lba_edge E = A.edges[ei];
@@ -318,6 +322,7 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_reduce_pts(LbaArgs A) {
   double acc[kLbaAll], chi = 0;
   for (int i = 0; i < kLbaAll; i++) acc[i] = 0;
   for (int ei = A.ptStart[p]; ei < A.ptStart[p + 1]; ei++) {
+    if (A.level && A.level[ei]) continue;
     const double* all = A.eAll + (size_t)ei * kLbaAll;
     for (int i = 0; i < kLbaAll; i++) acc[i] += all[i];
     chi += A.eRho[ei];
@@ -333,8 +338,11 @@ __global__ __launch_bounds__(64) void k_lba_reduce_kfs(LbaArgs A) {
   double acc[kLbaApp];
 #pragma unroll
   for (int i = 0; i < kLbaApp; i++) acc[i] = 0;
-  for (int k = A.kfStart[s] + lane; k < A.kfStart[s + 1]; k += 64) {
-    const double* app = A.eApp + (size_t)A.kfEdges[k] * kLbaApp;
+  const int r = A.row ? A.row[s] : s;
+  for (int k = A.kfStart[r] + lane; k < A.kfStart[r + 1]; k += 64) {
+    const int ei = A.kfEdges[k];
+    if (A.level && A.level[ei]) continue;   // whole edges at the loop head: the accumulation below stays straight-line
+    const double* app = A.eApp + (size_t)ei * kLbaApp;
 #pragma unroll
     for (int i = 0; i < kLbaApp; i++) acc[i] += app[i];
   }
@@ -513,14 +521,16 @@ __global__ __launch_bounds__(64) void k_lba_schur(LbaArgs A) {
   double acc[42];
 #pragma unroll
   for (int k = 0; k < 42; k++) acc[k] = 0;
-  for (int k = A.kfStart[i] + lane; k < A.kfStart[i + 1]; k += 64) {
+  const int r = A.row ? A.row[i] : i;
+  for (int k = A.kfStart[r] + lane; k < A.kfStart[r + 1]; k += 64) {
     const int ei = A.kfEdges[k];
+    if (A.level && A.level[ei]) continue;
     const int p = A.edges[ei].point;
     int ej = ei;
     if (j != i) {
       ej = -1;
       for (int m = A.ptStart[p]; m < A.ptStart[p + 1]; m++)
-        if (A.slot[A.edges[m].kf] == j) { ej = m; break; }
+        if (A.slot[A.edges[m].kf] == j && !(A.level && A.level[m])) { ej = m; break; }
       if (ej < 0) continue;
     }
     double Y[6][3];
@@ -550,13 +560,15 @@ __global__ __launch_bounds__(64) void k_lba_schur_rig(LbaArgs A) {
   double acc[42];
 #pragma unroll
   for (int k = 0; k < 42; k++) acc[k] = 0;
-  for (int k = A.kfStart[i] + lane; k < A.kfStart[i + 1]; k += 64) {
+  const int r = A.row ? A.row[i] : i;
+  for (int k = A.kfStart[r] + lane; k < A.kfStart[r + 1]; k += 64) {
     const int ei = A.kfEdges[k];
+    if (A.level && A.level[ei]) continue;
     const int p = A.edges[ei].point;
     double Y[6][3];
     hpl_dinv(A.hpl[cur] + (size_t)ei * kLbaHpl, A.dinv + (size_t)p * 6, Y);
     for (int m = A.ptStart[p]; m < A.ptStart[p + 1]; m++) {
-      if (A.slot[A.edges[m].kf] != j) continue;
+      if (A.slot[A.edges[m].kf] != j || (A.level && A.level[m])) continue;
       const double* hj = A.hpl[cur] + (size_t)m * kLbaHpl;
 #pragma unroll
       for (int a = 0; a < 6; a++)
@@ -666,12 +678,13 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_update(LbaArgs A) {
   if (i < A.nP) {
     const int e0 = A.ptStart[i], e1 = A.ptStart[i + 1];
     double* xl = A.xl + 3 * (size_t)i;
-    if (st.ok && e1 > e0) {   // a failed solve leaves g2o's x as it was; a point without an edge is not active
+    const bool live = A.ptLive ? A.ptLive[i] > 0 : e1 > e0;
+    if (st.ok && live) {   // a failed solve leaves g2o's x as it was; a point without an edge is not active
       const double* bl = A.hll[cur] + (size_t)i * kLbaAll + 6;
       double r[3] = {bl[0], bl[1], bl[2]};
       for (int ei = e0; ei < e1; ei++) {
         const int s = A.slot[A.edges[ei].kf];
-        if (s < 0) continue;
+        if (s < 0 || (A.level && A.level[ei])) continue;
         const double* h = A.hpl[cur] + (size_t)ei * kLbaHpl;
         const double* x = A.xp + 6 * s;
         for (int c = 0; c < 3; c++) {
@@ -685,7 +698,10 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_update(LbaArgs A) {
       xl[1] = di[1] * r[0] + di[3] * r[1] + di[4] * r[2];
       xl[2] = di[2] * r[0] + di[4] * r[1] + di[5] * r[2];
     }
-    for (int c = 0; c < 3; c++) A.X[trial][3 * (size_t)i + c] = A.X[cur][3 * (size_t)i + c] + xl[c];
+    if (A.level && !live)   // left the active set: the estimate of round one, untouched
+      for (int c = 0; c < 3; c++) A.X[trial][3 * (size_t)i + c] = A.X[cur][3 * (size_t)i + c];
+    else
+      for (int c = 0; c < 3; c++) A.X[trial][3 * (size_t)i + c] = A.X[cur][3 * (size_t)i + c] + xl[c];
   }
   if (i < A.nKF) {
     const int s = A.slot[i];
@@ -707,34 +723,41 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_update(LbaArgs A) {
   }
 }
 
-// kRig: a second-camera edge's depth is ((mTrl * T).map(X))[2]; its gate is the monocular one (u_right < 0)
+// The erase rule of edge i: chi2() -- what the edge holds after the last trial -- over its gate, or isDepthPositive() false at
+// the estimates of copy `cur`.  rig: a second-camera edge's depth is ((mTrl * T).map(X))[2]; its gate is the monocular one
+// (u_right < 0).  k_lba_finish flags vToErase by it, k_lba_relevel the edges that go to level 1.
+__device__ __forceinline__ bool lba_outlier(const LbaArgs& A, int i, int cur, bool rig, bool& pos) {
+  const orbx_lba_edge E = A.edges[i];
+  const LbaPose P = A.pose[cur][E.kf];
+  const double X[3] = {A.X[cur][3 * (size_t)E.point], A.X[cur][3 * (size_t)E.point + 1], A.X[cur][3 * (size_t)E.point + 2]};
+  double Xc[3];
+  if (rig && A.edgeCam[i] != 0) {
+    Pose TR;
+    se3_compose(to_pose(A.trl[E.kf].T), to_pose(P), TR);
+    se3_map(TR, X, Xc);
+    pos = Xc[2] > 0.0;
+  } else {
+    qrot(P.q, X, Xc);
+    pos = Xc[2] + P.t[2] > 0.0;
+  }
+  const double gate = E.u_right < 0.f ? 5.991 : 7.815;
+  return A.chi2[i] > gate || !pos;
+}
+
 template <bool kRig>
 __device__ __forceinline__ void lba_finish(const LbaArgs& A) {
   const int i = blockIdx.x * kLbaBS + threadIdx.x;
   const LbaState& st = *A.st;
   const int cur = st.cur;
-  if (i < A.nE) {   // chi2(): what the edge holds after the last trial; isDepthPositive(): at the estimates
-    const orbx_lba_edge E = A.edges[i];
-    const LbaPose P = A.pose[cur][E.kf];
-    const double X[3] = {A.X[cur][3 * (size_t)E.point], A.X[cur][3 * (size_t)E.point + 1], A.X[cur][3 * (size_t)E.point + 2]};
-    double Xc[3];
+  if (i < A.nE) {
     bool pos;
-    if (kRig && A.edgeCam[i] != 0) {
-      Pose TR;
-      se3_compose(to_pose(A.trl[E.kf].T), to_pose(P), TR);
-      se3_map(TR, X, Xc);
-      pos = Xc[2] > 0.0;
-    } else {
-      qrot(P.q, X, Xc);
-      pos = Xc[2] + P.t[2] > 0.0;
-    }
-    const double gate = E.u_right < 0.f ? 5.991 : 7.815;
+    const bool out = lba_outlier(A, i, cur, kRig, pos);
     A.depthPos[i] = pos ? 1 : 0;
-    A.erase[i] = (A.chi2[i] > gate || !pos) ? 1 : 0;
+    A.erase[i] = out ? 1 : 0;
   }
   if (i < A.nLocal) {
     double* o = A.outPose + 7 * (size_t)i;
-    if (A.slot[i] < 0) {   // not optimised: the widened input
+    if ((A.slot0 ? A.slot0 : A.slot)[i] < 0) {   // never optimised: the widened input
       for (int k = 0; k < 4; k++) o[k] = (double)A.kfs[i].q[k];
       for (int k = 0; k < 3; k++) o[4 + k] = (double)A.kfs[i].t[k];
     } else {
@@ -760,6 +783,71 @@ __device__ __forceinline__ void lba_finish(const LbaArgs& A) {
 
 __global__ __launch_bounds__(kLbaBS) void k_lba_finish(LbaArgs A) { lba_finish<false>(A); }
 __global__ __launch_bounds__(kLbaBS) void k_lba_finish_rig(LbaArgs A) { lba_finish<true>(A); }
+
+// Between the rounds of the map-merge bundle adjustment (Optimizer.cc:3893-3925), one point per thread over its edges: an edge
+// the erase rule flags at the state round one left -- the chi2 of its last trial, the depth at the accepted estimates -- goes to
+// level 1; the point keeps the number of its level-0 edges.
+__global__ __launch_bounds__(kLbaBS) void k_lba_relevel(LbaArgs A) {
+  const int p = blockIdx.x * kLbaBS + threadIdx.x;
+  if (p >= A.nP) return;
+  const int cur = A.st->cur;
+  int live = 0;
+  for (int ei = A.ptStart[p]; ei < A.ptStart[p + 1]; ei++) {
+    bool pos;
+    const bool out = lba_outlier(A, ei, cur, A.cams != nullptr, pos);
+    A.rl.level[ei] = out ? 1 : 0;
+    live += out ? 0 : 1;
+  }
+  A.rl.ptLive[p] = live;
+}
+
+// initializeOptimization(0) and the start of a fresh optimize(), one workgroup: a wave per round-one slot counts the level-0
+// edges of its CSR row; thread 0 renumbers the slots that keep one, in list order (at most ORBX_LBA_MAX_LOCAL of them: the merge
+// entries' cap, which a serial scan covers); then every key frame takes its new slot, the increments return to zero, round one's
+// counters are kept for the host and the Levenberg state starts again at the accepted estimate (cur stays).
+__global__ __launch_bounds__(kLbaBS) void k_lba_relayout(LbaArgs A) {
+  __shared__ int live[ORBX_LBA_MAX_LOCAL];
+  __shared__ int renum[ORBX_LBA_MAX_LOCAL];
+  __shared__ int tot[kLbaBS / 64];
+  __shared__ int nOpt2;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int s = w; s < A.nOpt; s += kLbaBS / 64) {
+    int c = 0;
+    for (int k = A.kfStart[s] + lane; k < A.kfStart[s + 1]; k += 64) c += A.rl.level[A.kfEdges[k]] ? 0 : 1;
+    c = wave_sum(c);
+    if (lane == 0) live[s] = c;
+  }
+  int aside = 0;
+  for (int ei = tid; ei < A.nE; ei += kLbaBS) aside += A.rl.level[ei] ? 1 : 0;
+  aside = wave_sum(aside);
+  if (lane == 0) tot[w] = aside;
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int s = 0; s < A.nOpt; s++) {
+      renum[s] = live[s] > 0 ? n : -1;
+      if (live[s] > 0) A.rl.row[n++] = s;
+    }
+    nOpt2 = n;
+    int t = 0;
+    for (int k = 0; k < kLbaBS / 64; k++) t += tot[k];
+    A.rl.counts[0] = n;
+    A.rl.counts[1] = t;
+    LbaState& st = *A.st;
+    A.rl.scalars[0] = st.lambda; A.rl.scalars[1] = st.chiInitial; A.rl.scalars[2] = st.curChi;
+    A.rl.counters[0] = st.iter; A.rl.counters[1] = st.trials; A.rl.counters[2] = st.stopReason;
+    LbaState s{};
+    s.cur = st.cur;
+    s.ok = 1;
+    s.running = 1;
+    st = s;
+    *A.status = 1;
+  }
+  __syncthreads();
+  for (int i = tid; i < A.nKF; i += kLbaBS) A.rl.slot[i] = A.slot[i] < 0 ? -1 : renum[A.slot[i]];
+  for (int k = tid; k < 6 * nOpt2; k += kLbaBS) A.xp[k] = 0;
+  for (int k = tid; k < 3 * A.nP; k += kLbaBS) A.xl[k] = 0;
+}
 
 inline int blocks(int n) { return (n + kLbaBS - 1) / kLbaBS; }
 
@@ -802,6 +890,12 @@ hipError_t launch_lba_finish(const LbaArgs& a) {
   const dim3 grid(blocks(std::max(std::max(a.nE, a.nP), a.nLocal)));
   if (a.cams) hipLaunchKernelGGL(k_lba_finish_rig, grid, dim3(kLbaBS), 0, nullptr, a);
   else hipLaunchKernelGGL(k_lba_finish, grid, dim3(kLbaBS), 0, nullptr, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_lba_relevel(const LbaArgs& a) {
+  hipLaunchKernelGGL(k_lba_relevel, dim3(blocks(a.nP)), dim3(kLbaBS), 0, nullptr, a);
+  hipLaunchKernelGGL(k_lba_relayout, dim3(1), dim3(kLbaBS), 0, nullptr, a);
   return hipGetLastError();
 }
 
