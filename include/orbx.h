@@ -1206,6 +1206,133 @@ int orbx_optimize_sim3_batch(int device, int n_problems, int cap, const int32_t*
                              const float* inv_level_sigma2_2, int nlevels2, const orbx_sim3opt_params* params,
                              orbx_sim3_pose* S12, orbx_sim3opt_result* results);
 
+/* ---- inertial pose optimisation (Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame) ------------- */
+
+/* What Tracking::TrackLocalMap calls instead of PoseOptimization once the IMU is initialised (src/Tracking.cc:2896-2919):
+ * Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:4544-4931) and PoseInertialOptimizationLastFrame
+ * (:4933-5356), one workgroup per frame, the whole call in one launch (csrc/orbx_pose_inertial.hip): the frame's body pose,
+ * velocity and biases under its reprojection edges (EdgeMonoOnlyPose where u_right < 0, EdgeStereoOnlyPose otherwise), the
+ * inertial edge to the last key frame (fixed) or the previous frame (free, under its prior), the two bias random-walk edges,
+ * four rounds of ten Gauss-Newton iterations with the classification after each, the recovery pass, and the new prior:
+ * the Hessian at the final estimate, marginalised over the previous frame (last frame) and clamped to positive semi-definite.
+ * DESIGN.md lists every rule.  Scope and deliberate differences:
+ *  - pinhole / rectified frames with one camera (mpCamera2 == NULL, Nleft == -1); Pinhole::uncertainty2 is 1.  A frame with
+ *    camera_model == ORBX_CAMERA_KB8 or n_cameras != 1 is ORBX_E_BADARG.
+ *  - IMU preintegration stays with the caller: orbx_imu_preintegrated holds the fields of IMU::Preintegrated the edges read.
+ *  - the dense 15 x 15 / 30 x 30 system is solved by an unpivoted LDLT where g2o's LinearSolverDense uses Eigen's pivoted one:
+ *    the results differ by rounding.  A pivot <= 0 or not finite ends the round without applying an update and sets
+ *    ORBX_PI_SOLVE_FAILED in status (g2o would apply the stale x of the iteration before and stop the round).
+ *  - the inverse of C's 9 x 9 block is an unpivoted Gauss-Jordan (Eigen: partially pivoted LU); a block that is not positive
+ *    definite sets ORBX_PI_BAD_COVARIANCE and returns the input state, n_good 0 and H zero.
+ *  - Marginalize's pseudo-inverse comes from a symmetric eigen-decomposition (JacobiSVD in the reference): the block is
+ *    symmetric positive semi-definite, its singular values are its eigenvalues; eigenvalues <= 1e-6 are dropped alike.
+ *  - IMU::NormalizeRotation of GetDeltaRotation runs its SVD in double and rounds to float (a float JacobiSVD in the reference).
+ * Two calls on the same input agree bit for bit (fixed reduction trees, no atomics). */
+typedef struct orbx_imu_preintegrated {   /* IMU::Preintegrated, row-major floats as it stores them */
+  float dR[9], dV[3], dP[3];
+  float JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+  float C[225];          /* 15 x 15 covariance: rotation, velocity, position (9), gyro walk (3), accelerometer walk (3) */
+  float b[6];            /* the linearisation bias: bax bay baz bwx bwy bwz */
+  float dT;
+} orbx_imu_preintegrated;
+typedef struct orbx_imu_state {
+  double Rwb[9], twb[3], vwb[3], bg[3], ba[3];
+} orbx_imu_state;
+typedef struct orbx_imu_prior {           /* ConstraintPoseImu (include/G2oTypes.h:671-707) */
+  orbx_imu_state state;
+  double H[225];
+} orbx_imu_prior;
+typedef struct orbx_pose_inertial_frame { /* what ImuCamPose(Frame*) and the bias / velocity vertices read (src/G2oTypes.cc:74-118) */
+  float Rwb[9], twb[3], vwb[3];           /* GetImuRotation / GetImuPosition / GetVelocity */
+  float bias[6];                          /* mImuBias: bax bay baz bwx bwy bwz */
+  float Rcw[9], tcw[3];                   /* GetPose(): separate inputs, re-derived from the body pose only by the first update */
+  float Rcb[9], tcb[3], tbc[3];           /* mImuCalib.mTcb, mImuCalib.mTbc.translation() */
+  float fx, fy, cx, cy, bf;
+  int32_t camera_model;                   /* ORBX_CAMERA_PINHOLE (0); ORBX_CAMERA_KB8 is rejected */
+  int32_t n_cameras;                      /* 1; a second camera is rejected */
+} orbx_pose_inertial_frame;
+#define ORBX_PI_SOLVE_FAILED 1
+#define ORBX_PI_BAD_COVARIANCE 2
+typedef struct orbx_pose_inertial_result {
+  orbx_imu_state state;                   /* the optimised Rwb, twb, velocity and biases (the frame takes their float casts) */
+  double H[225];                          /* the new prior's Hessian (with `state`: the frame's ConstraintPoseImu) */
+  int32_t n_good;                         /* nInitialCorrespondences - nBad: the reference's return value */
+  int32_t n_inliers_mono, n_outliers_mono, n_inliers_stereo, n_outliers_stereo;   /* of the last classification */
+  int32_t rounds;                         /* rounds run (1 when fewer than 10 edges, else 4) */
+  int32_t status;                         /* 0, or ORBX_PI_* flags */
+  int32_t recovered;                      /* 1 when the recovery pass (nInliers < 30 && !bRecInit) ran */
+} orbx_pose_inertial_result;
+/* kps_un / u_right (NULL: every edge mono) / world_pos [n][3] / has_point / track_depth (MapPoint::mTrackDepth) by key point,
+ * n <= 15000; inv_level_sigma2 [nlevels].  outlier [n] receives mvbOutlier where has_point is set and keeps the caller's value
+ * elsewhere.  A frame with no point at all is valid (the inertial edges alone).  Validated before any device is touched: counts,
+ * octaves in [0, nlevels), everything finite, dT > 0, positive diagonals of C's 9 x 9 and two 3 x 3 blocks, a pinhole frame with
+ * one camera, and (last frame) a prior H symmetric to rounding.  Returns n_good >= 0 or a negative error; valid arguments
+ * without a device return ORBX_E_NODEVICE (there is no host path). */
+int orbx_pose_inertial_optimization_last_keyframe(int device, const orbx_keypoint* kps_un, const float* u_right,
+                                                  const float* world_pos, const uint8_t* has_point, const float* track_depth, int n,
+                                                  const float* inv_level_sigma2, int nlevels, const orbx_pose_inertial_frame* frame,
+                                                  const orbx_imu_state* keyframe_state, const orbx_imu_preintegrated* preintegrated,
+                                                  int rec_init, uint8_t* outlier, orbx_pose_inertial_result* result);
+/* prev_state: the previous frame's estimate; prior: its ConstraintPoseImu (the caller deletes it afterwards, :5352-5353);
+ * preintegrated: mpImuPreintegrated (from the last key frame: the walk edges' information); preintegrated_frame:
+ * mpImuPreintegratedFrame (from the previous frame: the inertial edge). */
+int orbx_pose_inertial_optimization_last_frame(int device, const orbx_keypoint* kps_un, const float* u_right, const float* world_pos,
+                                               const uint8_t* has_point, const float* track_depth, int n,
+                                               const float* inv_level_sigma2, int nlevels, const orbx_pose_inertial_frame* frame,
+                                               const orbx_imu_state* prev_state, const orbx_imu_prior* prior,
+                                               const orbx_imu_preintegrated* preintegrated,
+                                               const orbx_imu_preintegrated* preintegrated_frame, int rec_init, uint8_t* outlier,
+                                               orbx_pose_inertial_result* result);
+/* n_problems frames in one launch, laid out as orbx_optimize_sim3_batch lays them out: n [n_problems] key points per problem
+ * (<= cap <= 15000, 0 is allowed), kps_un / u_right (may be NULL) / has_point / track_depth / outlier [n_problems][cap],
+ * world_pos [n_problems][cap][3], one table of inv_level_sigma2, frames / states / priors / records / rec_init / results
+ * [n_problems].  Entries past n[p] are neither read nor written.  Problem p has the bits of the one-shot entry on the same data.
+ * At most 65535 problems.  Validated like the one-shot entries.  Returns ORBX_OK. */
+int orbx_pose_inertial_optimization_last_keyframe_batch(int device, int n_problems, int cap, const int32_t* n,
+                                                        const orbx_keypoint* kps_un, const float* u_right, const float* world_pos,
+                                                        const uint8_t* has_point, const float* track_depth,
+                                                        const float* inv_level_sigma2, int nlevels,
+                                                        const orbx_pose_inertial_frame* frames, const orbx_imu_state* keyframe_states,
+                                                        const orbx_imu_preintegrated* preintegrated, const int32_t* rec_init,
+                                                        uint8_t* outlier, orbx_pose_inertial_result* results);
+int orbx_pose_inertial_optimization_last_frame_batch(int device, int n_problems, int cap, const int32_t* n,
+                                                     const orbx_keypoint* kps_un, const float* u_right, const float* world_pos,
+                                                     const uint8_t* has_point, const float* track_depth,
+                                                     const float* inv_level_sigma2, int nlevels,
+                                                     const orbx_pose_inertial_frame* frames, const orbx_imu_state* prev_states,
+                                                     const orbx_imu_prior* priors, const orbx_imu_preintegrated* preintegrated,
+                                                     const orbx_imu_preintegrated* preintegrated_frame, const int32_t* rec_init,
+                                                     uint8_t* outlier, orbx_pose_inertial_result* results);
+/* Test hook: the dense pieces and SO(3) functions the inertial solvers add to csrc/orbx_linalg.h, each alone on n items of
+ * doubles (orbx_debug_linalg keeps its own operations and numbers).  One wave per item for the dense pieces, in the call
+ * sites' register layout; one thread per item for SO(3).  out is read as well as written.
+ *   op                          in, per item                        out, per item
+ *   ORBX_ILA_LDLT15 / _LDLT30   H [N][N] (lower triangle read), b [N]   x [N] (the caller's values when it fails), flag
+ *   ORBX_ILA_EIG9 / _EIG15      A [N][N] symmetric                  w [N], V [N][N] (row-major, column j pairs with w[j])
+ *   ORBX_ILA_CLAMP15            A [15][15]                          the clamped matrix [15][15]
+ *   ORBX_ILA_PINV15             A [15][15]                          the pseudo-inverse [15][15] (eigenvalues <= 1e-6 dropped)
+ *   ORBX_ILA_INVERSE9           A [9][9] positive definite          the inverse [9][9] (the caller's values when it fails), flag
+ *   ORBX_ILA_EXP_SO3            w [3]                               R [3][3]
+ *   ORBX_ILA_LOG_SO3            R [3][3]                            w [3]
+ *   ORBX_ILA_JR / _JR_INV       v [3]                               RightJacobianSO3 / InverseRightJacobianSO3 [3][3]
+ *   ORBX_ILA_NORMALIZE_F        R [3][3] (floats widened)           IMU::NormalizeRotation, floats widened [3][3]
+ * A null pointer, n outside [1, ORBX_ILA_MAX_ITEMS] and an unknown op are ORBX_E_BADARG before any device is touched. */
+#define ORBX_ILA_LDLT15 0
+#define ORBX_ILA_LDLT30 1
+#define ORBX_ILA_EIG9 2
+#define ORBX_ILA_EIG15 3
+#define ORBX_ILA_CLAMP15 4
+#define ORBX_ILA_PINV15 5
+#define ORBX_ILA_INVERSE9 6
+#define ORBX_ILA_EXP_SO3 7
+#define ORBX_ILA_LOG_SO3 8
+#define ORBX_ILA_JR 9
+#define ORBX_ILA_JR_INV 10
+#define ORBX_ILA_NORMALIZE_F 11
+#define ORBX_ILA_OPS 12
+#define ORBX_ILA_MAX_ITEMS 4096
+int orbx_debug_inertial_linalg(int device, int op, int n, const void* in, void* out);
+
 /* ---- local bundle adjustment (Optimizer::LocalBundleAdjustment) ------------------------------------------ */
 
 /* The visual Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*, int&, int&, int&, int&) (src/Optimizer.cc:1109-1516; the

@@ -211,6 +211,12 @@ def lib():
         L.orbx_debug_introsort_device.argtypes = [i, vp, i]
         L.orbx_debug_linalg.argtypes = [i, i, i, vp, vp]
         L.orbx_debug_geometry.argtypes = [i, i, i, vp, vp]
+        L.orbx_pose_inertial_optimization_last_keyframe.argtypes = [i, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, vp, vp]
+        L.orbx_pose_inertial_optimization_last_frame.argtypes = [i, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, vp, vp, i, vp, vp]
+        L.orbx_pose_inertial_optimization_last_keyframe_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp]
+        L.orbx_pose_inertial_optimization_last_frame_batch.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp,
+                                                                       vp, vp]
+        L.orbx_debug_inertial_linalg.argtypes = [i, i, i, vp, vp]
         L.orbx_debug_set_detect_list_cap.argtypes = [i]
         L.orbx_debug_set_detect_list_cap.restype = None
         L.orbx_debug_set_octree_global.argtypes = [i]
@@ -1214,6 +1220,154 @@ def OptimizeSim3Batch(n, kpsUn1, worldPos1, worldPos2, matched, idx2, kpsUn2, n2
     _check(lib().orbx_optimize_sim3_batch(int(device), P, cap, _p(nn), _p(k1), _p(w1), _p(w2), _p(m), _p(i2), _p(k2), k2.shape[1],
                                           _p(nn2), _p(tl), _p(T1), _p(T2), _p(s1), len(s1), _p(s2), len(s2), _p(prm), _p(S), _p(res)))
     return res, S, m
+
+
+# ---- inertial pose optimisation (Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame)
+IMU_PREINTEGRATED_DTYPE = np.dtype([("dR", "<f4", (9,)), ("dV", "<f4", (3,)), ("dP", "<f4", (3,)), ("JRg", "<f4", (9,)),
+                                    ("JVg", "<f4", (9,)), ("JVa", "<f4", (9,)), ("JPg", "<f4", (9,)), ("JPa", "<f4", (9,)),
+                                    ("C", "<f4", (225,)), ("b", "<f4", (6,)), ("dT", "<f4")])   # orbx_imu_preintegrated
+IMU_STATE_DTYPE = np.dtype([("Rwb", "<f8", (9,)), ("twb", "<f8", (3,)), ("vwb", "<f8", (3,)), ("bg", "<f8", (3,)),
+                            ("ba", "<f8", (3,))])                                               # orbx_imu_state
+IMU_PRIOR_DTYPE = np.dtype([("state", IMU_STATE_DTYPE), ("H", "<f8", (225,))])                  # orbx_imu_prior
+POSE_INERTIAL_FRAME_DTYPE = np.dtype([("Rwb", "<f4", (9,)), ("twb", "<f4", (3,)), ("vwb", "<f4", (3,)), ("bias", "<f4", (6,)),
+                                      ("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Rcb", "<f4", (9,)), ("tcb", "<f4", (3,)),
+                                      ("tbc", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"),
+                                      ("camera_model", "<i4"), ("n_cameras", "<i4")])           # orbx_pose_inertial_frame
+POSE_INERTIAL_RESULT_DTYPE = np.dtype([("state", IMU_STATE_DTYPE), ("H", "<f8", (225,)), ("n_good", "<i4"), ("n_inliers_mono", "<i4"),
+                                       ("n_outliers_mono", "<i4"), ("n_inliers_stereo", "<i4"), ("n_outliers_stereo", "<i4"),
+                                       ("rounds", "<i4"), ("status", "<i4"), ("recovered", "<i4")])   # orbx_pose_inertial_result
+assert IMU_PREINTEGRATED_DTYPE.itemsize == 1168 and IMU_STATE_DTYPE.itemsize == 168 and IMU_PRIOR_DTYPE.itemsize == 1968
+assert POSE_INERTIAL_FRAME_DTYPE.itemsize == 220 and POSE_INERTIAL_RESULT_DTYPE.itemsize == 2000
+PI_SOLVE_FAILED, PI_BAD_COVARIANCE = 1, 2
+
+
+def _record(value, dtype, n=1):
+    """n records of a structured dtype from records of it or from mappings of its fields (matrices in any shape)."""
+    if isinstance(value, np.ndarray) and value.dtype == dtype:
+        return np.ascontiguousarray(value).reshape(n)
+    items = [value] if isinstance(value, dict) else list(value)
+    out = np.zeros(n, dtype)
+    if len(items) != n:
+        raise ValueError("expected %d records, got %d" % (n, len(items)))
+    for r, item in zip(out, items):
+        for name in dtype.names:
+            sub = dtype.fields[name][0]
+            if sub.names:   # a nested record (orbx_imu_prior::state): its fields sit beside the outer ones in a mapping
+                r[name] = _record(item[name] if name in item else item, sub)[0]
+            elif name in item:
+                r[name] = np.asarray(item[name]).reshape(sub.shape)
+            elif name == "n_cameras":
+                r[name] = 1
+            elif name != "camera_model":
+                raise KeyError(name)
+    return out
+
+
+def _pose_inertial_arrays(kpsUn, uRight, worldPos, hasPoint, trackDepth, outlier, shape):
+    k = np.ascontiguousarray(kpsUn, KP_DTYPE).reshape(shape)
+    ur = None if uRight is None else np.ascontiguousarray(uRight, np.float32).reshape(shape)
+    w = np.ascontiguousarray(worldPos, np.float32).reshape(shape + (3,))
+    h = np.ascontiguousarray(hasPoint, np.uint8).reshape(shape)
+    d = np.ascontiguousarray(trackDepth, np.float32).reshape(shape)
+    out = np.zeros(shape, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(shape)
+    return k, ur, w, h, d, out
+
+
+def pose_inertial_optimization_last_keyframe(kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frame, keyframe_state,
+                                             preintegrated, bRecInit=False, outlier=None, device=0):
+    """Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:4544-4931) on the GPU
+    (orbx_pose_inertial_optimization_last_keyframe).  Over the frame's n key points: kpsUn [n] KP_DTYPE, uRight [n] (None: every
+    edge mono), worldPos [n][3], hasPoint [n], trackDepth [n] (MapPoint::mTrackDepth); frame = a POSE_INERTIAL_FRAME_DTYPE record or
+    a mapping of its fields, keyframe_state = IMU_STATE_DTYPE (the last key frame's Rwb, twb, vwb, bg, ba), preintegrated =
+    IMU_PREINTEGRATED_DTYPE (mpImuPreintegrated).  Returns (n_good, result record, outlier [n]): the result holds the optimised
+    state (the frame takes its float casts) and the new prior's H (with the state: the frame's ConstraintPoseImu); outlier keeps
+    the given values where there is no point."""
+    n = len(np.asarray(hasPoint).reshape(-1))
+    k, ur, w, h, d, out = _pose_inertial_arrays(kpsUn, uRight, worldPos, hasPoint, trackDepth, outlier, (n,))
+    s2 = np.ascontiguousarray(invLevelSigma2, np.float32)
+    fr, st = _record(frame, POSE_INERTIAL_FRAME_DTYPE), _record(keyframe_state, IMU_STATE_DTYPE)
+    pre = _record(preintegrated, IMU_PREINTEGRATED_DTYPE)
+    res = np.zeros(1, POSE_INERTIAL_RESULT_DTYPE)
+    ng = _check(lib().orbx_pose_inertial_optimization_last_keyframe(
+        int(device), _p(k), None if ur is None else _p(ur), _p(w), _p(h), _p(d), n, _p(s2), len(s2), _p(fr), _p(st), _p(pre),
+        int(bool(bRecInit)), _p(out), _p(res)))
+    return ng, res[0], out
+
+
+def pose_inertial_optimization_last_frame(kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frame, prev_state, prior,
+                                          preintegrated, preintegrated_frame, bRecInit=False, outlier=None, device=0):
+    """Optimizer::PoseInertialOptimizationLastFrame (src/Optimizer.cc:4933-5356) on the GPU
+    (orbx_pose_inertial_optimization_last_frame): as the last key-frame call, with prev_state = the previous frame's estimate
+    (IMU_STATE_DTYPE), prior = its ConstraintPoseImu (IMU_PRIOR_DTYPE, or a mapping with Rwb .. ba and H), preintegrated =
+    mpImuPreintegrated (the walk edges) and preintegrated_frame = mpImuPreintegratedFrame (the inertial edge).  The caller drops
+    the previous frame's prior afterwards, as the reference does."""
+    n = len(np.asarray(hasPoint).reshape(-1))
+    k, ur, w, h, d, out = _pose_inertial_arrays(kpsUn, uRight, worldPos, hasPoint, trackDepth, outlier, (n,))
+    s2 = np.ascontiguousarray(invLevelSigma2, np.float32)
+    fr, st, pr = _record(frame, POSE_INERTIAL_FRAME_DTYPE), _record(prev_state, IMU_STATE_DTYPE), _record(prior, IMU_PRIOR_DTYPE)
+    pre, pref = _record(preintegrated, IMU_PREINTEGRATED_DTYPE), _record(preintegrated_frame, IMU_PREINTEGRATED_DTYPE)
+    res = np.zeros(1, POSE_INERTIAL_RESULT_DTYPE)
+    ng = _check(lib().orbx_pose_inertial_optimization_last_frame(
+        int(device), _p(k), None if ur is None else _p(ur), _p(w), _p(h), _p(d), n, _p(s2), len(s2), _p(fr), _p(st), _p(pr), _p(pre),
+        _p(pref), int(bool(bRecInit)), _p(out), _p(res)))
+    return ng, res[0], out
+
+
+def pose_inertial_optimization_batch(n, kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frames, states, preintegrated,
+                                     bRecInit, priors=None, preintegrated_frame=None, outlier=None, device=0):
+    """P problems in one launch: orbx_pose_inertial_optimization_last_keyframe_batch, or _last_frame_batch when priors (and
+    preintegrated_frame) are given.  n [P] key points per problem, kpsUn / uRight (or None) / hasPoint / trackDepth [P][cap],
+    worldPos [P][cap][3], frames / states / records / bRecInit [P].  Returns (results [P], outlier [P][cap]); problem p has the
+    bits of the one-shot call on the same data."""
+    nn = np.ascontiguousarray(n, np.int32).reshape(-1)
+    P = len(nn)
+    cap = np.asarray(hasPoint).reshape(P, -1).shape[1]
+    k, ur, w, h, d, out = _pose_inertial_arrays(kpsUn, uRight, worldPos, hasPoint, trackDepth, outlier, (P, cap))
+    s2 = np.ascontiguousarray(invLevelSigma2, np.float32)
+    fr, st = _record(frames, POSE_INERTIAL_FRAME_DTYPE, P), _record(states, IMU_STATE_DTYPE, P)
+    pre = _record(preintegrated, IMU_PREINTEGRATED_DTYPE, P)
+    rec = np.ascontiguousarray(bRecInit, np.int32).reshape(P)
+    res = np.zeros(P, POSE_INERTIAL_RESULT_DTYPE)
+    head = (int(device), P, cap, _p(nn), _p(k), None if ur is None else _p(ur), _p(w), _p(h), _p(d), _p(s2), len(s2), _p(fr), _p(st))
+    if priors is None:
+        _check(lib().orbx_pose_inertial_optimization_last_keyframe_batch(*head, _p(pre), _p(rec), _p(out), _p(res)))
+    else:
+        pr, pref = _record(priors, IMU_PRIOR_DTYPE, P), _record(preintegrated_frame, IMU_PREINTEGRATED_DTYPE, P)
+        _check(lib().orbx_pose_inertial_optimization_last_frame_batch(*head, _p(pr), _p(pre), _p(pref), _p(rec), _p(out), _p(res)))
+    return res, out
+
+
+def pose_inertial_optimization_last_keyframe_batch(n, kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frames,
+                                                   keyframe_states, preintegrated, bRecInit, outlier=None, device=0):
+    return pose_inertial_optimization_batch(n, kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frames, keyframe_states,
+                                            preintegrated, bRecInit, outlier=outlier, device=device)
+
+
+def pose_inertial_optimization_last_frame_batch(n, kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frames, prev_states,
+                                                priors, preintegrated, preintegrated_frame, bRecInit, outlier=None, device=0):
+    return pose_inertial_optimization_batch(n, kpsUn, uRight, worldPos, hasPoint, trackDepth, invLevelSigma2, frames, prev_states,
+                                            preintegrated, bRecInit, priors=priors, preintegrated_frame=preintegrated_frame,
+                                            outlier=outlier, device=device)
+
+
+# orbx_debug_inertial_linalg: ORBX_ILA_* and, per operation, the doubles of one item of `in` and of `out`
+(ILA_LDLT15, ILA_LDLT30, ILA_EIG9, ILA_EIG15, ILA_CLAMP15, ILA_PINV15, ILA_INVERSE9, ILA_EXP_SO3, ILA_LOG_SO3, ILA_JR, ILA_JR_INV,
+ ILA_NORMALIZE_F) = range(12)
+ILA_OPS, ILA_MAX_ITEMS = 12, 4096
+ILA_ITEM = {ILA_LDLT15: (240, 16), ILA_LDLT30: (930, 31), ILA_EIG9: (81, 90), ILA_EIG15: (225, 240), ILA_CLAMP15: (225, 225),
+            ILA_PINV15: (225, 225), ILA_INVERSE9: (81, 82), ILA_EXP_SO3: (3, 9), ILA_LOG_SO3: (9, 3), ILA_JR: (3, 9),
+            ILA_JR_INV: (3, 9), ILA_NORMALIZE_F: (9, 9)}
+
+
+def debug_inertial_linalg(op, items, prefill=0.0, device=0):
+    """One of the inertial solvers' pieces of csrc/orbx_linalg.h alone on the device (orbx_debug_inertial_linalg): items
+    [n][doubles of one input item] -> [n][doubles of one output item]; prefill is what `out` holds going in."""
+    n_in, n_out = ILA_ITEM[op]
+    a = np.ascontiguousarray(items, np.float64).reshape(-1, n_in)
+    out = np.empty((len(a), n_out), np.float64)
+    out[...] = prefill
+    _check(lib().orbx_debug_inertial_linalg(int(device), int(op), len(a), _p(a), _p(out)))
+    return out
 
 
 # ---- local bundle adjustment (Optimizer::LocalBundleAdjustment)

@@ -20,11 +20,18 @@
 // Optimizer.cc:3567-3994, the map-merge overload) on orbx_merge_bundle_adjustment, over a MergeMapView: the vertex, point and edge
 // listing of :3596-3790 is GatherMergeGraph, both optimisations and the classification between them are the library's; the call
 // site in LoopClosing::MergeLocal reads as in the reference.
+// Optimizer::PoseInertialOptimizationLastKeyFrame(Frame*, bool bRecInit) and PoseInertialOptimizationLastFrame(Frame*, bool)
+// (src/Optimizer.cc:4544-4931, :4933-5356) on orbx_pose_inertial_optimization_last_keyframe / _last_frame, over a
+// FrameViewInertial, so that the call site of Tracking::TrackLocalMap (src/Tracking.cc:2909, 2915) reads as in the reference:
+// `inliers = Optimizer::PoseInertialOptimizationLastFrame(&mCurrentFrame)` when the map was not updated since the last frame,
+// `Optimizer::PoseInertialOptimizationLastKeyFrame(&mCurrentFrame)` otherwise.  The frame receives Rwb, twb, the velocity and the
+// bias as float casts and its new prior (mpcpi); the last-frame call consumes and clears the previous frame's prior (:5352-5353).
 #ifndef ORBX_OPTIMIZER_H
 #define ORBX_OPTIMIZER_H
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -63,6 +70,41 @@ struct FrameViewKB8 {
   float q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0};
   float mpCamera[8] = {}, mpCamera2[8] = {};              // KannalaBrandt8 mvParameters (fx fy cx cy k0 k1 k2 k3)
   float trl_q[4] = {0, 0, 0, 1}, trl_t[3] = {0, 0, 0};   // GetRelativePoseTrl() as Sophus stores it
+  int device = 0;
+};
+
+// What VertexPose / VertexVelocity / VertexGyroBias / VertexAccBias read of the last key frame: GetImuRotation / GetImuPosition /
+// GetVelocity / GetGyroBias / GetAccBias (floats, row-major).
+struct ImuStateView {
+  float Rwb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, twb[3] = {0, 0, 0}, vwb[3] = {0, 0, 0}, bg[3] = {0, 0, 0}, ba[3] = {0, 0, 0};
+};
+// IMU::Preintegrated's fields the edges read (dR dV dP, the five bias Jacobians, C, the linearisation bias b, dT): the caller
+// keeps the reference's preintegration and copies them here.
+struct PreintegratedView : orbx_imu_preintegrated {};
+// ConstraintPoseImu (include/G2oTypes.h:671-707): the prior a frame carries to the next last-frame call
+struct ConstraintPoseImu : orbx_imu_prior {};
+// The Frame members the inertial pose optimisations read and write: a pinhole / rectified frame (mpCamera2 == NULL, Nleft == -1).
+struct FrameViewInertial {
+  int N = 0;
+  const orbx_keypoint* mvKeysUn = nullptr;
+  const float* mvuRight = nullptr;          // nullptr: monocular
+  const float* world_pos = nullptr;         // mvpMapPoints[i]->GetWorldPos() where has_map_point[i]
+  const uint8_t* has_map_point = nullptr;
+  const float* mTrackDepth = nullptr;       // mvpMapPoints[i]->mTrackDepth
+  uint8_t* mvbOutlier = nullptr;            // in/out
+  const float* mvInvLevelSigma2 = nullptr;
+  int nlevels = 0;
+  float Rwb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, twb[3] = {0, 0, 0}, vwb[3] = {0, 0, 0};   // GetImuRotation / Position / GetVelocity: in/out
+  float mImuBias[6] = {0, 0, 0, 0, 0, 0};   // bax bay baz bwx bwy bwz: in/out
+  float Rcw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tcw[3] = {0, 0, 0};   // GetPose(): in/out (SetImuPoseVelocity re-derives it)
+  float Rcb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tcb[3] = {0, 0, 0}, tbc[3] = {0, 0, 0};   // mImuCalib.mTcb, mTbc.translation()
+  float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+  const ImuStateView* mpLastKeyFrame = nullptr;
+  FrameViewInertial* mpPrevFrame = nullptr;
+  const PreintegratedView* mpImuPreintegrated = nullptr;        // from the last key frame
+  const PreintegratedView* mpImuPreintegratedFrame = nullptr;   // from the previous frame
+  std::unique_ptr<ConstraintPoseImu> mpcpi;                     // written by both calls, consumed by the next last-frame call
+  orbx_pose_inertial_result last_result{};                      // the library's full answer (counts, rounds, status)
   int device = 0;
 };
 
@@ -646,6 +688,36 @@ inline EgGraph GatherEssentialGraph(const EssentialGraphView& m) {
 }
 
 class Optimizer {
+  static orbx_pose_inertial_frame InertialFrameRecord(const FrameViewInertial& F) {
+    orbx_pose_inertial_frame f{};
+    for (int i = 0; i < 9; i++) { f.Rwb[i] = F.Rwb[i]; f.Rcw[i] = F.Rcw[i]; f.Rcb[i] = F.Rcb[i]; }
+    for (int i = 0; i < 3; i++) { f.twb[i] = F.twb[i]; f.vwb[i] = F.vwb[i]; f.tcw[i] = F.tcw[i]; f.tcb[i] = F.tcb[i]; f.tbc[i] = F.tbc[i]; }
+    for (int i = 0; i < 6; i++) f.bias[i] = F.mImuBias[i];
+    f.fx = F.fx; f.fy = F.fy; f.cx = F.cx; f.cy = F.cy; f.bf = F.mbf;
+    f.camera_model = ORBX_CAMERA_PINHOLE;
+    f.n_cameras = 1;
+    return f;
+  }
+  // SetImuPoseVelocity(Rwb.cast<float>(), twb.cast<float>(), v.cast<float>()), mImuBias = Bias(ba, bg) as floats, and the new
+  // ConstraintPoseImu (:4881-4928).  Tcw = Tcb * Twb^-1 is formed here with float matrix products (Frame::SetImuPoseVelocity
+  // composes Sophus quaternions: the same pose to float rounding).
+  static void RecoverInertialFrame(FrameViewInertial* F, const orbx_pose_inertial_result& r) {
+    for (int i = 0; i < 9; i++) F->Rwb[i] = (float)r.state.Rwb[i];
+    for (int i = 0; i < 3; i++) {
+      F->twb[i] = (float)r.state.twb[i]; F->vwb[i] = (float)r.state.vwb[i];
+      F->mImuBias[i] = (float)r.state.ba[i]; F->mImuBias[3 + i] = (float)r.state.bg[i];
+    }
+    float tbw[3];
+    for (int i = 0; i < 3; i++) tbw[i] = -(F->Rwb[i] * F->twb[0] + F->Rwb[3 + i] * F->twb[1] + F->Rwb[6 + i] * F->twb[2]);
+    for (int i = 0; i < 3; i++) {
+      for (int k = 0; k < 3; k++) F->Rcw[3 * i + k] = F->Rcb[3 * i] * F->Rwb[3 * k] + F->Rcb[3 * i + 1] * F->Rwb[3 * k + 1] + F->Rcb[3 * i + 2] * F->Rwb[3 * k + 2];
+      F->tcw[i] = F->Rcb[3 * i] * tbw[0] + F->Rcb[3 * i + 1] * tbw[1] + F->Rcb[3 * i + 2] * tbw[2] + F->tcb[i];
+    }
+    F->mpcpi.reset(new ConstraintPoseImu());
+    F->mpcpi->state = r.state;
+    for (int i = 0; i < 225; i++) F->mpcpi->H[i] = r.H[i];
+  }
+
  public:
   // The loop-closing overload (:1530-1826): gathers the graph, optimises and corrects the points on the device and returns what
   // the caller applies.  Deliberate difference: :1787 would dereference a null vertex for a bad key frame of vpKFs; the mirror
@@ -901,6 +973,49 @@ class Optimizer {
     for (int i = 0; i < 3; i++) pFrame->t[i] = f.t[i];
     return n;
   }
+  // Both return nInitialCorrespondences - nBad, give the frame its new state (float casts), mvbOutlier and prior, and throw on
+  // a library error (bad arguments, no device: there is no CPU path).
+  static int PoseInertialOptimizationLastKeyFrame(FrameViewInertial* pFrame, bool bRecInit = false) {
+    if (!pFrame->mpLastKeyFrame || !pFrame->mpImuPreintegrated)
+      throw std::runtime_error("PoseInertialOptimizationLastKeyFrame: no last key frame or preintegration");
+    const ImuStateView& K = *pFrame->mpLastKeyFrame;
+    orbx_imu_state kf{};
+    for (int i = 0; i < 9; i++) kf.Rwb[i] = K.Rwb[i];
+    for (int i = 0; i < 3; i++) { kf.twb[i] = K.twb[i]; kf.vwb[i] = K.vwb[i]; kf.bg[i] = K.bg[i]; kf.ba[i] = K.ba[i]; }
+    const orbx_pose_inertial_frame f = InertialFrameRecord(*pFrame);
+    orbx_pose_inertial_result& r = pFrame->last_result;
+    const int n = orbx_pose_inertial_optimization_last_keyframe(pFrame->device, pFrame->mvKeysUn, pFrame->mvuRight, pFrame->world_pos,
+                                                                pFrame->has_map_point, pFrame->mTrackDepth, pFrame->N,
+                                                                pFrame->mvInvLevelSigma2, pFrame->nlevels, &f, &kf,
+                                                                pFrame->mpImuPreintegrated, bRecInit, pFrame->mvbOutlier, &r);
+    if (n < 0) throw std::runtime_error(std::string("PoseInertialOptimizationLastKeyFrame: ") + orbx_last_error());
+    RecoverInertialFrame(pFrame, r);
+    return n;
+  }
+  static int PoseInertialOptimizationLastFrame(FrameViewInertial* pFrame, bool bRecInit = false) {
+    FrameViewInertial* pFp = pFrame->mpPrevFrame;
+    if (!pFp || !pFrame->mpImuPreintegrated || !pFrame->mpImuPreintegratedFrame)
+      throw std::runtime_error("PoseInertialOptimizationLastFrame: no previous frame or preintegration");
+    if (!pFp->mpcpi)   // (the reference prints "pFp->mpcpi does not exist!!!" and dereferences null)
+      throw std::runtime_error("PoseInertialOptimizationLastFrame: the previous frame has no prior (mpcpi)");
+    orbx_imu_state prev{};
+    for (int i = 0; i < 9; i++) prev.Rwb[i] = pFp->Rwb[i];
+    for (int i = 0; i < 3; i++) {
+      prev.twb[i] = pFp->twb[i]; prev.vwb[i] = pFp->vwb[i]; prev.ba[i] = pFp->mImuBias[i]; prev.bg[i] = pFp->mImuBias[3 + i];
+    }
+    const orbx_pose_inertial_frame f = InertialFrameRecord(*pFrame);
+    orbx_pose_inertial_result& r = pFrame->last_result;
+    const int n = orbx_pose_inertial_optimization_last_frame(pFrame->device, pFrame->mvKeysUn, pFrame->mvuRight, pFrame->world_pos,
+                                                             pFrame->has_map_point, pFrame->mTrackDepth, pFrame->N,
+                                                             pFrame->mvInvLevelSigma2, pFrame->nlevels, &f, &prev, pFp->mpcpi.get(),
+                                                             pFrame->mpImuPreintegrated, pFrame->mpImuPreintegratedFrame, bRecInit,
+                                                             pFrame->mvbOutlier, &r);
+    if (n < 0) throw std::runtime_error(std::string("PoseInertialOptimizationLastFrame: ") + orbx_last_error());
+    RecoverInertialFrame(pFrame, r);
+    pFp->mpcpi.reset();   // delete pFp->mpcpi; pFp->mpcpi = NULL
+    return n;
+  }
+
   static int PoseOptimization(FrameViewKB8* pFrame) {
     orbx_pose_opt_frame_kb8 f{};
     for (int i = 0; i < 4; i++) { f.q[i] = pFrame->q[i]; f.trl_q[i] = pFrame->trl_q[i]; }

@@ -3,6 +3,9 @@
 // square root it is built on, the one-sided Jacobi rotation with the 3 x 3 SVD and the wave-layout null vector in double, and the
 // 6 x 6 and 7 x 7 LDLT.  Shared by the fisheye association (orbx_stereo.hip), the two-view reconstruction (orbx_twoview.hip), the PnP
 // solver (orbx_mlpnp.hip), the new map points (orbx_newpoints.hip), the pose optimisers (orbx_pose.h) and the Sim3 optimiser (orbx_sim3opt.hip).
+// At the end, the inertial solvers' pieces (orbx_pose_inertial.hip; later the inertial back-end): a wave-level unpivoted LDLT for
+// 15 / 30 unknowns, a wave-level symmetric eigen-decomposition (9, 15) with the clamp and pseudo-inverse built on it, the inverse
+// of a positive definite 9 x 9, and SO(3) Exp / Log / Jr / Jr^-1 in double with the float NormalizeRotation.
 #ifndef ORBX_LINALG_H
 #define ORBX_LINALG_H
 #include <hip/hip_runtime.h>
@@ -312,6 +315,225 @@ __device__ __forceinline__ bool ldlt7(const double* H, const double* b, double* 
     x[i] = s;
   }
   return true;
+}
+
+// ---- the inertial solvers' pieces (orbx_pose_inertial.hip): dense systems of 15 and 30 unknowns, the symmetric eigen-decomposition
+// behind the information clamps and the pseudo-inverse, and SO(3) in double.  The dense pieces run on one wave with row (lane) of
+// the matrix in the lane's registers: every index below is a compile-time constant after unrolling, so nothing goes to scratch.
+
+// lane src's value in every lane (src is a constant after unrolling: two v_readlane, no LDS traffic)
+__device__ __forceinline__ double lane_bcast(double v, int src) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+  return __hiloint2double(hi, lo);
+}
+
+// H x = b by an unpivoted, right-looking LDLT, one wave: lane i < N holds row i of the symmetric H in a and b[i]; lanes >= N hold
+// zero rows and b = 0.  x[i] comes back in lane i.  false (in every lane) = a pivot <= 0 or not finite: x is then not written.
+// The reference factors with Eigen's pivoted LDLT; the results differ by rounding.  a is destroyed.
+template <int N>
+__device__ __forceinline__ bool ldlt_wave(double (&a)[N], double b, double& x) {
+  const int lane = threadIdx.x & 63;
+  double dOwn = 1.0;
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    const double d = lane_bcast(a[j], j);   // the pivot, in every lane
+    if (!(d > 0) || !isfinite(d)) return false;
+    if (lane == j) dOwn = d;
+    const double l = lane > j ? a[j] / d : 0.0;   // L[lane][j]
+#pragma unroll
+    for (int c = j + 1; c < N; c++) a[c] -= l * lane_bcast(a[j], c);   // Schur complement, the whole row (it stays symmetric)
+    if (lane > j) a[j] = l;
+  }
+  // lane i now holds L[i][m] in a[m] for m < i and d_i L[m][i] in a[m] for m > i
+  double y = b;
+#pragma unroll
+  for (int m = 0; m < N - 1; m++) {
+    const double ym = lane_bcast(y, m);
+    if (lane > m) y -= a[m] * ym;
+  }
+  double v = y / dOwn;
+#pragma unroll
+  for (int m = N - 1; m > 0; m--) {
+    const double xm = lane_bcast(v, m);
+    if (lane < m) v -= (a[m] / dOwn) * xm;
+  }
+  x = v;
+  return true;
+}
+
+// Eigen-decomposition of a symmetric matrix of N <= 16 rows by a cyclic one-sided Jacobi, one wave in the layout of
+// null_vector_sym: lane l holds row (l & 15) of the matrix in x and of the identity in y (rows >= N zero), the four 16-lane
+// groups run the same arithmetic.  On return y holds the row of V, x the row of A V (orthogonal columns) and w[j] the eigenvalue
+// of column j, v_j . (A v_j), in every lane; the order is whatever the sweeps leave.  Exact for what the callers pass: positive
+// semi-definite matrices and their roundings (a pair of eigenvalues +s, -s of the same size would not be separated).
+template <int N>
+__device__ __forceinline__ void eig_sym_wave(double (&x)[N], double (&y)[N], double (&w)[N]) {
+  for (int sweep = 0; sweep < 40; sweep++) {
+    bool rotated = false;
+#pragma unroll
+    for (int p = 0; p < N - 1; p++)
+#pragma unroll
+      for (int q = p + 1; q < N; q++) {
+        const double alpha = sum16(x[p] * x[p]), beta = sum16(x[q] * x[q]), gamma = sum16(x[p] * x[q]);
+        double c, s;
+        if (!jacobi_cs(alpha, beta, gamma, c, s)) continue;
+        rotated = true;
+        const double xp = x[p], xq = x[q], yp = y[p], yq = y[q];
+        x[p] = c * xp - s * xq;
+        x[q] = s * xp + c * xq;
+        y[p] = c * yp - s * yq;
+        y[q] = s * yp + c * yq;
+      }
+    if (!rotated) break;
+  }
+#pragma unroll
+  for (int j = 0; j < N; j++) w[j] = sum16(y[j] * x[j]);
+}
+
+// Row (lane & 15) of V diag(f) V^T from eig_sym_wave's y: the recomposition of the clamp (f = w, zero below 1e-12:
+// src/G2oTypes.cc:489-493, include/G2oTypes.h:683-688) and of the pseudo-inverse (f = 1 / w, zero at or below 1e-6:
+// src/Optimizer.cc:3064-3075, an eigen-decomposition standing in for JacobiSVD on a symmetric positive semi-definite block).
+template <int N>
+__device__ __forceinline__ void recompose_wave(const double (&y)[N], const double (&f)[N], double (&row)[N]) {
+#pragma unroll
+  for (int c = 0; c < N; c++) {
+    double s = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) s += (y[j] * f[j]) * lane_bcast(y[j], c);
+    row[c] = s;
+  }
+}
+template <int N>
+__device__ __forceinline__ void clamp_psd_wave(double (&x)[N], double (&y)[N]) {   // x: row of the matrix in, of the clamped out
+  double w[N];
+  eig_sym_wave<N>(x, y, w);
+#pragma unroll
+  for (int j = 0; j < N; j++) if (w[j] < 1e-12) w[j] = 0;
+  recompose_wave<N>(y, w, x);
+}
+template <int N>
+__device__ __forceinline__ void pinv_psd_wave(double (&x)[N], double (&y)[N]) {
+  double w[N];
+  eig_sym_wave<N>(x, y, w);
+#pragma unroll
+  for (int j = 0; j < N; j++) w[j] = w[j] > 1e-6 ? 1.0 / w[j] : 0.0;
+  recompose_wave<N>(y, w, x);
+}
+
+// Inverse of a symmetric positive definite N x N (N <= 16) by an unpivoted Gauss-Jordan, one wave: lane i < N holds row i in a
+// (lanes >= N: anything finite) and receives row i of the inverse there.  (The reference inverts C's 9 x 9 block with Eigen's
+// partially pivoted LU.)  false = a pivot <= 0 or not finite.
+template <int N>
+__device__ __forceinline__ bool inverse_spd_wave(double (&a)[N]) {
+  const int lane = threadIdx.x & 63;
+  double e[N];
+#pragma unroll
+  for (int c = 0; c < N; c++) e[c] = lane == c ? 1.0 : 0.0;
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    const double piv = lane_bcast(a[j], j);
+    if (!(piv > 0) || !isfinite(piv)) return false;
+    const double f = lane == j ? 0.0 : a[j];
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+      const double pa = lane_bcast(a[c], j) / piv, pe = lane_bcast(e[c], j) / piv;   // the scaled pivot row
+      a[c] = lane == j ? pa : a[c] - f * pa;
+      e[c] = lane == j ? pe : e[c] - f * pe;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < N; c++) a[c] = e[c];
+  return true;
+}
+
+// ---- SO(3) in double, row-major 3 x 3 (src/G2oTypes.cc:796-867, include/G2oTypes.h:72-76)
+__device__ __forceinline__ void mat3_mul(const double* A, const double* B, double* C) {
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+}
+__device__ __forceinline__ void mat3_tmul(const double* A, const double* B, double* C) {   // A^T B
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) C[3 * r + c] = A[r] * B[c] + A[3 + r] * B[3 + c] + A[6 + r] * B[6 + c];
+}
+__device__ __forceinline__ void mat3_tvec(const double* A, const double* x, double* y) {   // A^T x
+#pragma unroll
+  for (int r = 0; r < 3; r++) y[r] = A[r] * x[0] + A[3 + r] * x[1] + A[6 + r] * x[2];
+}
+// NormalizeRotation: U V^T of the SVD
+__device__ __forceinline__ void normalize_rotation3(const double* R, double* out) {
+  double U[9], w[3], V[9];
+  [[clang::always_inline]] svd3(R, U, w, V);   // (its locals stay in registers)
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) out[3 * r + c] = U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1] + U[3 * r + 2] * V[3 * c + 2];
+}
+// IMU::NormalizeRotation (src/ImuTypes.cc:35-39) of a float matrix: the SVD in double, the product rounded to float (the
+// reference runs JacobiSVD in float; both are the nearest rotation to float rounding)
+__device__ __forceinline__ void normalize_rotation3f(const float* R, float* out) {
+  double Rd[9], o[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) Rd[i] = (double)R[i];
+  normalize_rotation3(Rd, o);
+#pragma unroll
+  for (int i = 0; i < 9; i++) out[i] = (float)o[i];
+}
+// W = hat(w) and W W
+__device__ __forceinline__ void hat_sq(const double* w, double* W, double* W2) {
+  W[0] = 0; W[1] = -w[2]; W[2] = w[1]; W[3] = w[2]; W[4] = 0; W[5] = -w[0]; W[6] = -w[1]; W[7] = w[0]; W[8] = 0;
+  mat3_mul(W, W, W2);
+}
+__device__ __forceinline__ void exp_so3(const double* w, double* R) {
+  const double d2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], d = sqrt(d2);
+  double W[9], W2[9], res[9];
+  hat_sq(w, W, W2);
+  if (d < 1e-5) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) res[i] = ((i & 3) == 0 ? 1.0 : 0.0) + W[i] + 0.5 * W2[i];
+  } else {
+    const double s = sin(d), c = cos(d);
+#pragma unroll
+    for (int i = 0; i < 9; i++) res[i] = ((i & 3) == 0 ? 1.0 : 0.0) + W[i] * s / d + W2[i] * (1.0 - c) / d2;
+  }
+  normalize_rotation3(res, R);
+}
+__device__ __forceinline__ void log_so3(const double* R, double* w) {
+  const double tr = R[0] + R[4] + R[8];
+  w[0] = (R[7] - R[5]) / 2; w[1] = (R[2] - R[6]) / 2; w[2] = (R[3] - R[1]) / 2;
+  const double costheta = (tr - 1.0) * 0.5;
+  if (costheta > 1 || costheta < -1) return;
+  const double theta = acos(costheta), s = sin(theta);
+  if (fabs(s) < 1e-5) return;
+#pragma unroll
+  for (int i = 0; i < 3; i++) w[i] = theta * w[i] / s;
+}
+__device__ __forceinline__ void inverse_right_jacobian_so3(const double* v, double* J) {
+  const double d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], d = sqrt(d2);
+  double W[9], W2[9];
+  hat_sq(v, W, W2);
+  const bool small = d < 1e-5;
+  const double k = small ? 0.0 : 1.0 / d2 - (1.0 + cos(d)) / (2.0 * d * sin(d));
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    const double I = (i & 3) == 0 ? 1.0 : 0.0;
+    J[i] = small ? I : I + W[i] / 2 + W2[i] * k;
+  }
+}
+__device__ __forceinline__ void right_jacobian_so3(const double* v, double* J) {
+  const double d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], d = sqrt(d2);
+  double W[9], W2[9];
+  hat_sq(v, W, W2);
+  const bool small = d < 1e-5;
+  const double k1 = small ? 0.0 : (1.0 - cos(d)) / d2, k2 = small ? 0.0 : (d - sin(d)) / (d2 * d);
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    const double I = (i & 3) == 0 ? 1.0 : 0.0;
+    J[i] = small ? I : I - W[i] * k1 + W2[i] * k2;
+  }
 }
 
 }  // namespace orbx
