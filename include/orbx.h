@@ -241,7 +241,9 @@ int orbx_hamming256(const void* a, const void* b);
 int orbx_stereo_match_batch(orbx_extractor* left, int first_left, orbx_extractor* right, int first_right,
                             int n_pairs, float bf, float b);
 int orbx_stereo_results_device(const orbx_extractor* left, const float** d_uright, const float** d_depth);
-/* Host copy of pair `pair` (synchronises): n = keypoint count of the left image. */
+/* Host copy of pair `pair` (synchronises): min(cap, cap_left) entries of each row.  The association (and the RGB-D lookup)
+ * writes the entries of the left image's keypoints; the rows past that count are neither read nor written -- they hold what
+ * the buffer held before, from an earlier and larger frame for instance -- and only entries [0, count) are results. */
 int orbx_stereo_download(orbx_extractor* left, int pair, float* uright, float* depth, int cap);
 
 /* ---- RGB-D frames ----------------------------------------------------------------------------------------------------------
@@ -2065,6 +2067,31 @@ int orbx_debug_score_level(orbx_extractor* ex, int image, int level, uint8_t* ds
  * csrc/orbx_sincos.h restates glibc's two x86-64 ifunc variants): evaluates n angles (radians, host arrays) with the FMA
  * (fused != 0) or the SSE2 variant.  tests/ compare both with the host's libm bit for bit. */
 int orbx_debug_sincos(int device, const float* angles, int n, int fused, float* sin_out, float* cos_out);
+/* Test hook of the memory the one-shot entries recycle.  Every one of them lays its inputs, scratch and outputs out in one
+ * block of a per-device pool that caches hipMalloc blocks in power-of-two size classes and hands them back as they are, and
+ * uploads its inputs through a per-thread page-locked staging buffer of which only the items' own bytes are rewritten.  A
+ * kernel that read a byte before anything of the same call wrote it would see what an EARLIER call left there.  This hook
+ * lets a test decide what that is.  All three operations run under the pool's mutex, on `device`'s pool:
+ *   ORBX_SCRATCH_STATS  out[0] = cached blocks, out[1] = cached bytes, out[2] = blocks taken from the pool so far,
+ *                       out[3] = how many of those came from the cache (the others were allocated)
+ *   ORBX_SCRATCH_FILL   waits for the device, sets every cached block to `byte` (0..255) and waits again, sets the calling
+ *                       thread's staging buffer, as far as it is allocated, to the same byte; out[0] = device bytes filled
+ *   ORBX_SCRATCH_TRIM   waits for the device and frees every cached block (out may be NULL)
+ * ORBX_E_BADARG (unknown operation, NULL out, byte outside 0..255, no such device) before any device is touched;
+ * ORBX_E_NODEVICE without a GPU.  The two counters of STATS are the hook's only cost in a product call. */
+#define ORBX_SCRATCH_STATS 0
+#define ORBX_SCRATCH_FILL 1
+#define ORBX_SCRATCH_TRIM 2
+int orbx_debug_scratch_pool(int device, int op, int byte, uint64_t* out);
+/* The same for an extractor handle's own buffers, which only ever grow: waits for the handle's streams, then sets to `byte`
+ * every device buffer that a call produces before it reads it -- candidate and selection lists, cell counts and prefixes,
+ * slots, counts, keypoints, descriptors, the frame staging and the pyramid, the row-sorted stereo records, SAD distances,
+ * uRight and depth, the fisheye association buffers, the bag-of-words buffers, the view lists of the device projections (a
+ * search that reads them needs its projection call again), the score tap -- and the blurred levels, whose validity flag it
+ * clears.  It leaves alone the tables of the configured frame size, what the caller uploaded (map, last frames, poses, lapping
+ * areas) and the single-frame gather's arrival counter; csrc/orbx_host.h classifies every member.  No buffer moves, so a
+ * captured pipeline stays valid.  Results of calls made before the hook are gone: downloads return the fill value. */
+int orbx_debug_fill_work_buffers(orbx_extractor* ex, int byte);
 
 #ifdef __cplusplus
 }

@@ -243,6 +243,8 @@ def lib():
         L.orbx_debug_score_map.argtypes = [vp, i]
         L.orbx_set_opencv_compat.argtypes = [vp, i]
         L.orbx_debug_score_level.argtypes = [vp, i, i, vp, C.c_ssize_t]
+        L.orbx_debug_scratch_pool.argtypes = [i, i, i, vp]
+        L.orbx_debug_fill_work_buffers.argtypes = [vp, i]
         _lib = L
     return _lib
 
@@ -648,6 +650,35 @@ class ORBextractor:
         out = np.zeros((cap, 3), np.int32)
         n = _check(lib().orbx_debug_candidates(self._h, image, level, _p(out), cap))
         return out[:n].copy()
+
+    def debug_fill_work_buffers(self, byte):
+        """Test hook: every device buffer of the handle that a call produces before it reads it set to `byte`
+        (orbx_debug_fill_work_buffers); tables, uploads and protocol state stay."""
+        _check(lib().orbx_debug_fill_work_buffers(self._h, int(byte)))
+
+
+SCRATCH_STATS, SCRATCH_FILL, SCRATCH_TRIM = 0, 1, 2
+
+
+def scratch_pool_stats(device=0):
+    """The one-shot entries' scratch pool on `device` (orbx_debug_scratch_pool): (cached blocks, cached bytes, blocks taken so
+    far, those served from the cache)."""
+    out = np.zeros(4, np.uint64)
+    _check(lib().orbx_debug_scratch_pool(int(device), SCRATCH_STATS, 0, _p(out)))
+    return tuple(int(v) for v in out)
+
+
+def scratch_pool_fill(byte, device=0):
+    """Sets every cached block of the pool and the calling thread's upload staging buffer to `byte`; returns the device bytes
+    filled."""
+    out = np.zeros(4, np.uint64)
+    _check(lib().orbx_debug_scratch_pool(int(device), SCRATCH_FILL, int(byte), _p(out)))
+    return int(out[0])
+
+
+def scratch_pool_trim(device=0):
+    """Frees every cached block of the pool."""
+    _check(lib().orbx_debug_scratch_pool(int(device), SCRATCH_TRIM, 0, None))
 
 
 def clock_probe_start(device=0, spin_us=2000):

@@ -1944,6 +1944,45 @@ int orbx_debug_score_level(orbx_extractor* ex, int image, int level, uint8_t* ds
   return ORBX_OK;
 }
 
+// Test hook: the scratch pool of the one-shot entries and the calling thread's Pack staging buffer (include/orbx.h).
+int orbx_debug_scratch_pool(int device, int op, int byte, uint64_t* out) {
+  if (op != ORBX_SCRATCH_STATS && op != ORBX_SCRATCH_FILL && op != ORBX_SCRATCH_TRIM) return fail(ORBX_E_BADARG, "no such operation");
+  if (op != ORBX_SCRATCH_TRIM && !out) return fail(ORBX_E_BADARG, "null output");
+  if (op == ORBX_SCRATCH_FILL && (byte < 0 || byte > 255)) return fail(ORBX_E_BADARG, "fill value outside [0, 255]");
+  int rc = set_device(device);
+  if (rc != ORBX_OK) return rc;
+  if (!ScratchPool::debug_device_ok(device)) return fail(ORBX_E_BADARG, "device index out of range");
+  if (op == ORBX_SCRATCH_STATS) {
+    ScratchPool::debug_stats(device, out);
+  } else if (op == ORBX_SCRATCH_FILL) {
+    HIPC(hipDeviceSynchronize());   // nothing of an earlier call may still read or write a cached block or the staging buffer
+    HIPC(ScratchPool::debug_fill(device, byte, out));
+    (void)Pack::debug_fill_staging(byte);
+  } else {
+    HIPC(hipDeviceSynchronize());
+    ScratchPool::debug_trim(device);
+  }
+  return ORBX_OK;
+}
+
+// Test hook: every WORK buffer of the handle (ORBX_EXTRACTOR_BUFFERS, orbx_host.h) set to `byte`, behind the handle's streams.
+// No buffer moves, so a captured pipeline stays valid.
+int orbx_debug_fill_work_buffers(orbx_extractor* ex, int byte) {
+  if (!ex) return fail(ORBX_E_BADARG, "null handle");
+  if (byte < 0 || byte > 255) return fail(ORBX_E_BADARG, "fill value outside [0, 255]");
+  HIPC(hipSetDevice(ex->device));
+  HIPC(hipStreamSynchronize(ex->stream));
+  if (ex->streamPyr) HIPC(hipStreamSynchronize(ex->streamPyr));
+  ex->blurValid = false;
+#define ORBX_FILL_(m) if (ex->m.p) HIPC(hipMemsetAsync(ex->m.p, byte, ex->m.n * sizeof(*ex->m.p), ex->stream));
+#define ORBX_KEEP_(m)
+  ORBX_EXTRACTOR_BUFFERS(ORBX_FILL_, ORBX_KEEP_, ORBX_KEEP_, ORBX_KEEP_)
+#undef ORBX_FILL_
+#undef ORBX_KEEP_
+  HIPC(hipStreamSynchronize(ex->stream));
+  return ORBX_OK;
+}
+
 int orbx_debug_sincos(int device, const float* angles, int n, int fused, float* sin_out, float* cos_out) {
   if (!angles || !sin_out || !cos_out || n < 0) return fail(ORBX_E_BADARG, "bad argument");
   if (n == 0) return ORBX_OK;

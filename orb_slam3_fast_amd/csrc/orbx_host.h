@@ -107,12 +107,14 @@ class ScratchPool {
     {
       std::lock_guard<std::mutex> lk(mu());
       auto& fl = lists()[dev];
+      takes()[dev]++;
       for (size_t i = 0; i < fl.size(); i++)
         if (fl[i].first == cls) {
           void* p = fl[i].second;
           fl[i] = fl.back();
           fl.pop_back();
           cached()[dev] -= cls;
+          hits()[dev]++;
           return p;
         }
     }
@@ -132,6 +134,33 @@ class ScratchPool {
     }
     (void)hipFree(p);
   }
+  // Test hooks (orbx_debug_scratch_pool), each under the pool's mutex; `dev` is current and inside [0, kMaxDev).
+  // stats: cached blocks, cached bytes, take() calls so far, those served from the cache
+  static void debug_stats(int dev, uint64_t out[4]) {
+    std::lock_guard<std::mutex> lk(mu());
+    out[0] = lists()[dev].size();
+    out[1] = cached()[dev];
+    out[2] = takes()[dev];
+    out[3] = hits()[dev];
+  }
+  // every cached block of the device set to `byte`; *filled: the device bytes written
+  static hipError_t debug_fill(int dev, int byte, uint64_t* filled) {
+    std::lock_guard<std::mutex> lk(mu());
+    *filled = 0;
+    for (const auto& b : lists()[dev]) {
+      const hipError_t e = hipMemset(b.second, byte, b.first);
+      if (e != hipSuccess) return e;
+      *filled += b.first;
+    }
+    return hipDeviceSynchronize();
+  }
+  static void debug_trim(int dev) {
+    std::lock_guard<std::mutex> lk(mu());
+    for (const auto& b : lists()[dev]) (void)hipFree(b.second);
+    lists()[dev].clear();
+    cached()[dev] = 0;
+  }
+  static bool debug_device_ok(int dev) { return dev >= 0 && dev < kMaxDev; }
 
  private:
   static constexpr int kMaxDev = 64;
@@ -139,6 +168,8 @@ class ScratchPool {
   static std::mutex& mu() { static std::mutex m; return m; }
   static std::vector<std::pair<size_t, void*>>* lists() { static std::vector<std::pair<size_t, void*>> l[kMaxDev]; return l; }
   static size_t* cached() { static size_t c[kMaxDev] = {0}; return c; }
+  static uint64_t* takes() { static uint64_t c[kMaxDev] = {0}; return c; }   // take() calls, and those served from the cache:
+  static uint64_t* hits() { static uint64_t c[kMaxDev] = {0}; return c; }    // read by debug_stats alone
 };
 
 template <class T>
@@ -232,6 +263,14 @@ class Pack {
   Pack(const Pack&) = delete;
   Pack& operator=(const Pack&) = delete;
   ~Pack() { release(); }
+  // Test hook (orbx_debug_scratch_pool): the calling thread's staging buffer, as far as it is allocated, set to `byte`.  No
+  // Pack of the thread is alive between two calls of the C ABI, so nothing is in flight from it.
+  static size_t debug_fill_staging(int byte) {
+    size_t cap = 0;
+    uint8_t* h = pinned(0, &cap);
+    if (h) std::memset(h, byte, cap);
+    return cap;
+  }
   void release() {  // an error path may leave the upload in flight: the staging buffer is reused by the thread's next call
     if (pending_) (void)hipStreamSynchronize(nullptr);
     pending_ = false;
@@ -241,9 +280,10 @@ class Pack {
  private:
   struct Item { const void* src; size_t bytes, off; };
   struct Bind { void* field; size_t off; };
-  static uint8_t* pinned(size_t bytes) {
+  static uint8_t* pinned(size_t bytes, size_t* capOut = nullptr) {
     thread_local uint8_t* buf = nullptr;
     thread_local size_t cap = 0;
+    if (capOut) *capOut = cap;   // (bytes = 0: the buffer as it is)
     if (bytes > cap) {
       if (buf) (void)hipHostFree(buf);
       buf = nullptr;
@@ -479,6 +519,61 @@ struct orbx_extractor {
     return evPool[evCursor++];
   }
 };
+
+// Every device buffer of orbx_extractor, one line per member, classified for orbx_debug_fill_work_buffers (a member that is
+// missing here fails tests/test_scratch_reuse.py::test_every_extractor_buffer_is_classified):
+//   WORK   a call produces it before it reads it; nothing in it outlives the call that wrote it.  The hook fills these.
+//   TABLE  written when the handle is created or configured for a frame size, read by every later call
+//   UPLOAD the caller's data (map, last frames, poses, lapping areas), read by later calls
+//   STATE  protocol state carried from one call to the next
+#define ORBX_EXTRACTOR_BUFFERS(WORK, TABLE, UPLOAD, STATE)                                                              \
+  WORK(d_pyr)          /* levels 1.. of the pyramid (the resize chain) */                                                \
+  WORK(d_blur)         /* blurred levels, made on demand: filled with blurValid cleared */                               \
+  WORK(d_stage)        /* the host entries' upload of the frame(s) */                                                    \
+  WORK(d_desc)         /* descriptors (k_describe) */                                                                    \
+  WORK(d_dbgScore)     /* test tap: cleared in front of every k_detect while it is enabled */                            \
+  WORK(d_cand)         /* candidate lists (k_octree) */                                                                  \
+  WORK(d_cellCand)     /* per-cell candidate lists (k_detect) */                                                         \
+  WORK(d_sel)          /* selection lists (k_octree) */                                                                  \
+  WORK(d_knode)        /* candidates' quadtree nodes (k_octree) */                                                       \
+  WORK(d_rowStart)     /* row offsets of the row-sorted stereo records (k_stereo_sort) */                                \
+  WORK(d_cellCount)    /* per-cell counts (k_detect) */                                                                  \
+  WORK(d_cellPrefix)   /* their prefix sums (k_octree) */                                                                \
+  WORK(d_candCount)    /* per-level candidate counts (k_octree) */                                                       \
+  WORK(d_selCount)     /* per-level selection counts (k_octree); k_describe reads ORBX_MAX_LEVELS of them per image */   \
+  WORK(d_slot)         /* output slots under a lapping area (k_slots) */                                                 \
+  WORK(d_nOut)         /* keypoint counts (k_slots / k_describe) */                                                      \
+  WORK(d_mono)         /* monocular counts (k_slots / k_describe) */                                                     \
+  UPLOAD(d_lap)        /* lapping areas, re-sent only when they differ from h_lap */                                     \
+  TABLE(d_yofs)        /* k_resize: source rows */                                                                       \
+  WORK(d_sad)          /* best SAD distance per left keypoint (stereo association) */                                    \
+  TABLE(d_yab)         /* k_resize: vertical weights */                                                                  \
+  TABLE(d_xtab)        /* k_resize: per-column table */                                                                  \
+  TABLE(d_rsRec)       /* k_resize: tile records */                                                                      \
+  TABLE(d_cellRec)     /* k_detect: per-cell records */                                                                  \
+  STATE(d_packCtr)     /* arrival counter of the single-frame gather, with packCtrDirty */                               \
+  TABLE(d_yrow)        /* k_resize: clamped source row pairs */                                                          \
+  WORK(d_srec)         /* row-sorted keypoint records of both eyes (k_stereo_sort) */                                    \
+  WORK(d_sdesc)        /* ... and their descriptors */                                                                   \
+  TABLE(d_tailBands)   /* fused small-level resize segments */                                                           \
+  TABLE(d_latBands)    /* single-frame cascade plans */                                                                  \
+  WORK(d_kps)          /* keypoints (k_describe) */                                                                      \
+  WORK(d_uR)           /* mvuRight (stereo association, RGB-D lookup) */                                                 \
+  WORK(d_depth)        /* mvDepth */                                                                                     \
+  UPLOAD(d_mapPos) UPLOAD(d_mapNormal) UPLOAD(d_mapMinD) UPLOAD(d_mapMaxD)   /* orbx_map_upload */                       \
+  UPLOAD(d_mapDesc) UPLOAD(d_mapFlags)                                                                                   \
+  UPLOAD(d_mapSkip)    /* the caller's skip flags of a device projection */                                              \
+  UPLOAD(d_poses)      /* its poses */                                                                                   \
+  WORK(d_views)        /* the view list it makes; read by the search that follows */                                     \
+  UPLOAD(d_lfPos) UPLOAD(d_lfAngle) UPLOAD(d_lfOct) UPLOAD(d_lfN) UPLOAD(d_lfDesc) UPLOAD(d_lfFlags)   /* orbx_last_frames_upload */ \
+  UPLOAD(d_posesQ)     /* poses of orbx_project_last_frames_batch */                                                     \
+  WORK(d_pviews)       /* its projections */                                                                             \
+  UPLOAD(d_scaleF)     /* mvScaleFactors, sent with them */                                                              \
+  UPLOAD(d_posesK)     /* poses of the stereo-fisheye projection */                                                      \
+  WORK(d_fviewsL) WORK(d_fviewsR)   /* its two view lists */                                                             \
+  WORK(d_bowWord) WORK(d_bowNode) WORK(d_bowStart) WORK(d_bowCounts)   /* bag of words: per feature, then assembled */   \
+  WORK(d_bowWeight) WORK(d_bowValues) WORK(d_bowWords) WORK(d_bowNodes) WORK(d_bowFeats)                                 \
+  WORK(d_fl2r) WORK(d_fr2l) WORK(d_fcnt) WORK(d_fcand) WORK(d_fdepth) WORK(d_fp3d)   /* batched fisheye association */
 
 // the vocabulary handle (orbx_api_bow.hip)
 struct orbx_vocabulary {

@@ -22,6 +22,7 @@ def test_library_exports_every_declared_symbol():
     lib = orbx.lib()
     syms = declared_symbols()
     assert len(syms) >= 18 and "orbx_debug_introsort_device" in syms and "orbx_debug_linalg" in syms
+    assert "orbx_debug_scratch_pool" in syms and "orbx_debug_fill_work_buffers" in syms
     for s in syms:
         assert hasattr(lib, s), "liborbx.so does not export " + s
     assert lib.orbx_abi_version() == 1

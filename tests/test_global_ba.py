@@ -336,9 +336,10 @@ def untouched_are_the_widened_inputs(name, d):
         assert np.array_equal(d["points"][j], sc["points"][j].astype(float)), (name, j)
 
 
-def against_v1(name, solver):
+def against_v1(name, solver, d=None):
+    """d: a device result of the scene under that solver made elsewhere (None: run it here)."""
     a = model(name, 0)
-    d = device(name, solver=solver)
+    d = device(name, solver=solver) if d is None else d
     again = device(name, solver=solver)
     for k in ("poses", "points", "chi2"):
         assert d[k].tobytes() == again[k].tobytes(), (name, k)

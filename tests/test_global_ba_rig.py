@@ -133,9 +133,10 @@ def bounds(name):
     return 4 * sp["R"] + EPS, 4 * sp["t"] + EPS, 4 * sp["X"] + EPS, 4 * sp["total"] + EPS
 
 
-def against_v1(name, solver):
+def against_v1(name, solver, d=None):
+    """d: a device result of the scene under that solver made elsewhere (None: run it here)."""
     a, sc = model(name, 0), scene(name)
-    d, again = call(sc, solver=solver), call(sc, solver=solver)
+    d, again = call(sc, solver=solver) if d is None else d, call(sc, solver=solver)
     for k in ("poses", "points", "chi2"):
         assert d[k].tobytes() == again[k].tobytes(), (name, k)
     assert all(d[k] == again[k] for k in COUNTERS + ("lambda", "chi2_initial", "chi2_final"))

@@ -453,10 +453,11 @@ def device(name, **kw):
     return orbx.LocalBundleAdjustment(sc["keyframes"], sc["n_local"], sc["points"], sc["edges"], **args)
 
 
-def against_v1(name, sp=None):
-    """One device run of a scene against V1; sp: the V1 / V2 spread the pose and point bounds are made of (None: the class's)."""
+def against_v1(name, sp=None, d=None):
+    """One device run of a scene against V1; sp: the V1 / V2 spread the pose and point bounds are made of (None: the class's);
+    d: a device result of the scene made elsewhere (None: run it here)."""
     a = model(name, 0)
-    d = device(name)
+    d = device(name) if d is None else d
     got = {k: d[k] for k in ("num_fixedKF", "num_OptKF", "num_MPs", "num_edges", "status", "iterations", "trials", "stop_reason")}
     print("scene %s device %s" % (name, got))
     for k, v in got.items():

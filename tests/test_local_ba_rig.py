@@ -341,9 +341,10 @@ def gpu():
     return True
 
 
-def against_v1(name):
+def against_v1(name, d=None):
+    """d: a device result of the scene made elsewhere (None: run it here)."""
     a, sc = model(name, 0), scene(name)
-    d = call(sc)
+    d = call(sc) if d is None else d
     got = {k: d[k] for k in COUNTERS}
     print("scene %s device %s" % (name, got))
     for k, v in got.items():

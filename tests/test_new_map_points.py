@@ -764,8 +764,9 @@ def device_sequence(ch):
     return rows, flags
 
 
-def assert_chain_equals_sequence(ch, label):
-    out = device_chain(ch)
+def assert_chain_equals_sequence(ch, label, out=None):
+    """out: the chain's result made elsewhere (None: run it here)."""
+    out = device_chain(ch) if out is None else out
     rows, flags = device_sequence(ch)
     n1 = len(ch["f1"]["kps"])
     for k, r in enumerate(rows):

@@ -322,11 +322,10 @@ def device(num, S12=None, matched=None):
                              s["th2"], s["fix_scale"], s["all_points"], s["cam1"], s["cam2"])
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("num", list(SCENES))
-def test_one_shot_against_v1(num):
+def check_one_shot(num, out):
+    """A device result of scene `num` (OptimizeSim3's tuple) against V1."""
     a = model(num, 0)
-    nin, S, m, H, res = device(num)
+    nin, S, m, H, res = out
     assert H is None if a["early_return"] else (H.shape == (7, 7) and not H.any())   # :2394 returns before :2401 zeroes it
     got = {k: int(res[k]) for k in ("n_in", "n_correspondences", "n_bad", "n_in_kf2", "n_out_kf2", "early_return", "trials")}
     print("scene %d device %s" % (num, got))
@@ -369,6 +368,12 @@ def test_one_shot_against_v1(num):
     assert eS <= bS, (num, eS, bS)
     if s["fix_scale"]:
         assert S["s"] == 1.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("num", list(SCENES))
+def test_one_shot_against_v1(num):
+    check_one_shot(num, device(num))
 
 
 def _batch_inputs(nums, with_empty=True):

@@ -423,11 +423,11 @@ def test_bad_arguments_are_rejected_before_any_device_is_touched():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def compare(kps, n_left, X, hp, q0, t0, rig, sig=None, label=""):
+def compare(kps, n_left, X, hp, q0, t0, rig, sig=None, label="", got=None):
     """One-shot entry vs the model.  Returns True when the frame had an edge within 1e-6 relative of 5.991 in a round (then
-    flags may differ and the pose is only checked loosely)."""
+    flags may differ and the pose is only checked loosely).  got: the entry's result made elsewhere (None: run it)."""
     sig = level_tables() if sig is None else sig
-    ng, qg, tg, og = run_gpu(kps, n_left, X, hp, q0, t0, rig, sig=sig)
+    ng, qg, tg, og = run_gpu(kps, n_left, X, hp, q0, t0, rig, sig=sig) if got is None else got
     nm, qm, tm, om, info = pose_optimization_kb8_model(kps, n_left, X, hp, sig, q0, t0, rig)
     near = any((m < 1e-6).any() for m in info["margins"])
     if near:

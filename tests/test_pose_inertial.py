@@ -90,9 +90,9 @@ def test_two_runs_are_bitwise_equal():
         assert a["raw"].tobytes() == b["raw"].tobytes() and a["outlier"].tobytes() == b["outlier"].tobytes(), cls
 
 
-@pytest.mark.parametrize("last_frame", [False, True])
-def test_batch_of_three_equals_the_one_shot_calls(last_frame):
-    """Three problems with different n, one of them without any edge: each has the bits of the one-shot entry."""
+def batch_of_three(last_frame):
+    """Three problems with different n, one of them without any edge, as one batch: (call() -> (results, outlier), the one-shot
+    scenes cut to their n, ns)."""
     pre = "lf_" if last_frame else "kf_"
     scs = [pc.scene(pre + "outliers", "mixed"), pc.scene(pre + "zero_edges", "mono"), pc.scene(pre + "recovery", "stereo")]
     ns = [48, 40, 33]   # different key point counts: the tails are cut off (and with them some of the points)
@@ -104,7 +104,7 @@ def test_batch_of_three_equals_the_one_shot_calls(last_frame):
     for p, (sc, n) in enumerate(zip(scs, ns)):
         cut = dict(sc, kps=sc["kps"][:n], u_right=sc["u_right"][:n], world_pos=sc["world_pos"][:n], has_point=sc["has_point"][:n],
                    track_depth=sc["track_depth"][:n], outlier_in=sc["outlier_in"][:n])
-        single.append(run_device(cut, last_frame))
+        single.append(cut)
         for f in sc["kps"].dtype.names:
             kps[f][p, :n] = sc["kps"][f][:n]
         ur[p, :n], wp[p, :n], has[p, :n], dep[p, :n] = sc["u_right"][:n], sc["world_pos"][:n], sc["has_point"][:n], sc["track_depth"][:n]
@@ -112,14 +112,30 @@ def test_batch_of_three_equals_the_one_shot_calls(last_frame):
         out_in[p, n:] = 7   # past n[p]: neither read nor written
         has[p, n:] = 1
     kw = dict(priors=[sc["prior"] for sc in scs], preintegrated_frame=[sc["preintegrated_frame"] for sc in scs]) if last_frame else {}
-    res, out = orbx.pose_inertial_optimization_batch(ns, kps, ur, wp, has, dep, pc.INV_LEVEL_SIGMA2, [sc["frame"] for sc in scs],
+
+    def call():
+        return orbx.pose_inertial_optimization_batch(ns, kps, ur, wp, has, dep, pc.INV_LEVEL_SIGMA2, [sc["frame"] for sc in scs],
                                                      [sc["prev_state" if last_frame else "keyframe"] for sc in scs],
                                                      [sc["preintegrated"] for sc in scs], [sc["rec_init"] for sc in scs],
                                                      outlier=out_in, **kw)
+    return call, single, ns
+
+
+def check_batch_of_three(last_frame, res, out, single, ns):
+    """Each problem of batch_of_three's result has the bits of the one-shot entry on its scene."""
+    single = [run_device(cut, last_frame) for cut in single]
     assert single[1]["n_good"] == 0 and single[0]["n_good"] > 20
     for p, n in enumerate(ns):
         assert res[p].tobytes() == single[p]["raw"].tobytes(), p
         assert np.array_equal(out[p, :n], single[p]["outlier"]) and (out[p, n:] == 7).all(), p
+
+
+@pytest.mark.parametrize("last_frame", [False, True])
+def test_batch_of_three_equals_the_one_shot_calls(last_frame):
+    """Three problems with different n, one of them without any edge: each has the bits of the one-shot entry."""
+    call, single, ns = batch_of_three(last_frame)
+    res, out = call()
+    check_batch_of_three(last_frame, res, out, single, ns)
 
 
 def test_frame_above_the_lds_staging_cap():

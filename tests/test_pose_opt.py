@@ -439,11 +439,11 @@ POSE_ROT_TOL = 2e-6     # rad
 POSE_T_TOL = 1e-5       # relative to 1 + |t|
 
 
-def compare(kps, ur, X, hp, q0, t0, sig=None, label=""):
+def compare(kps, ur, X, hp, q0, t0, sig=None, label="", got=None):
     """One-shot entry vs the model.  Returns True when the frame had an edge within 1e-6 relative of its threshold in a
-    round (then flags may differ and the pose is only checked loosely)."""
+    round (then flags may differ and the pose is only checked loosely).  got: the entry's result made elsewhere (None: run it)."""
     sig = level_tables() if sig is None else sig
-    ng, qg, tg, og = orbx.PoseOptimization(kps, ur, X, hp, sig, q0, t0, CAM)
+    ng, qg, tg, og = orbx.PoseOptimization(kps, ur, X, hp, sig, q0, t0, CAM) if got is None else got
     nm, qm, tm, om, info = pose_optimization_model(kps, ur, X, hp, sig, q0, t0, CAM)
     near = any((m < 1e-6).any() for m in info["margins"])
     if near:
