@@ -2065,8 +2065,19 @@ int orbx_debug_score_map(orbx_extractor* ex, int enable);
 int orbx_debug_score_level(orbx_extractor* ex, int image, int level, uint8_t* dst, ptrdiff_t dst_stride);
 /* The device's sinf / cosf of the descriptor steering (computeOrbDescriptor, src/ORBextractor.cc:106-107: libm cosf / sinf;
  * csrc/orbx_sincos.h restates glibc's two x86-64 ifunc variants): evaluates n angles (radians, host arrays) with the FMA
- * (fused != 0) or the SSE2 variant.  tests/ compare both with the host's libm bit for bit. */
+ * (fused == 1) or the SSE2 variant (fused == 0), or with k_describe's own branch-free restatement of the FMA variant
+ * (fused == 2: glibc_sincosf_sel, csrc/orbx_kernels.hip -- the form the product runs; the other two are its definition).  tests/
+ * compare all three with the host's libm bit for bit. */
 int orbx_debug_sincos(int device, const float* angles, int n, int fused, float* sin_out, float* cos_out);
+/* The device's cv::fastAtan2 of IC_Angle (src/ORBextractor.cc:98) in the branch-free form k_describe calls (fast_atan2_sel): n
+ * pairs (y[i], x[i]) from host arrays, degrees to out.  ORBX_E_BADARG (NULL array, n < 0) before any device is touched;
+ * ORBX_E_NODEVICE without a GPU. */
+int orbx_debug_fast_atan2(int device, const float* y, const float* x, int n, float* out);
+/* k_describe's launch plan for a batch of n_images width x height frames, exactly as the launch computes it (host only, no
+ * device): out[0] = nk, the selected slots of one (image, level) a wave walks; out[1] = tasks, the workgroups per image;
+ * out[2] = magic (as uint32: j / tasks == umulhi(j, magic) for every flat workgroup index j < n_images * tasks; 0 = no XCD
+ * remap); out[3 + l] = first task of level l (INT32_MAX past the last level), ORBX_MAX_LEVELS entries. */
+int orbx_debug_describe_plan(const orbx_params* p, int width, int height, int n_images, int32_t* out);
 /* Test hook of the memory the one-shot entries recycle.  Every one of them lays its inputs, scratch and outputs out in one
  * block of a per-device pool that caches hipMalloc blocks in power-of-two size classes and hands them back as they are, and
  * uploads its inputs through a per-thread page-locked staging buffer of which only the items' own bytes are rewritten.  A

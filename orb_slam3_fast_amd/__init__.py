@@ -240,6 +240,9 @@ def lib():
         L.orbx_debug_set_resize_tail.restype = None
         L.orbx_debug_resize_plan.argtypes = [vp, vp, vp, vp, i]
         L.orbx_debug_sincos.argtypes = [i, vp, i, i, vp, vp]
+        if hasattr(L, "orbx_debug_fast_atan2"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
+            L.orbx_debug_fast_atan2.argtypes = [i, vp, vp, i, vp]
+            L.orbx_debug_describe_plan.argtypes = [vp, i, i, i, vp]
         L.orbx_debug_score_map.argtypes = [vp, i]
         L.orbx_set_opencv_compat.argtypes = [vp, i]
         L.orbx_debug_score_level.argtypes = [vp, i, i, vp, C.c_ssize_t]
@@ -1989,11 +1992,22 @@ def PoseOptimizationFisheyeBatch(ex, first_left, first_right, n_frames, worldPos
 
 
 def debug_sincos(angles, fused=True, device=0):
-    """Test hook: the device's sinf / cosf (csrc/orbx_sincos.h: glibc's FMA or SSE2 variant) of angles in radians."""
+    """Test hook: the device's sinf / cosf (csrc/orbx_sincos.h: glibc's FMA or SSE2 variant; fused=2: k_describe's branch-free
+    restatement of the FMA variant, glibc_sincosf_sel) of angles in radians."""
     a = np.ascontiguousarray(angles, np.float32)
     sn, cs = np.zeros_like(a), np.zeros_like(a)
-    _check(lib().orbx_debug_sincos(device, _p(a), a.size, 1 if fused else 0, _p(sn), _p(cs)))
+    _check(lib().orbx_debug_sincos(device, _p(a), a.size, 2 if fused == 2 else (1 if fused else 0), _p(sn), _p(cs)))
     return sn, cs
+
+
+def debug_fast_atan2(y, x, device=0):
+    """Test hook: k_describe's branch-free cv::fastAtan2 (fast_atan2_sel) of the pairs (y[i], x[i]), in degrees."""
+    y, x = np.ascontiguousarray(y, np.float32).ravel(), np.ascontiguousarray(x, np.float32).ravel()
+    if y.size != x.size:
+        raise ValueError("y and x must have the same length")
+    out = np.zeros_like(y)
+    _check(lib().orbx_debug_fast_atan2(device, _p(y), _p(x), y.size, _p(out)))
+    return out
 
 
 def bf_knn2(descQ, descT, device=0):
@@ -2214,6 +2228,16 @@ def octree_plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, he
     nt, lds = np.zeros(int(nlevels), np.int32), np.zeros(int(nlevels), np.int32)
     _check(lib().orbx_debug_octree_plan(C.byref(prm), width, height, _p(nt), _p(lds)))
     return nt, lds
+
+
+def describe_plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, n_images):
+    """k_describe's launch plan for a batch of n_images frames of this size (orbx_debug_describe_plan; host only, no device):
+    (nk, tasks, magic, taskOff[nlevels]) -- keypoints per wave, workgroups per image, the multiplier of the XCD remap's division
+    (0 = no remap) and the first task of every level."""
+    prm = _Params(int(nfeatures), float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
+    out = np.zeros(3 + 12, np.int32)   # ORBX_MAX_LEVELS
+    _check(lib().orbx_debug_describe_plan(C.byref(prm), int(width), int(height), int(n_images), _p(out)))
+    return int(out[0]), int(out[1]), int(out[2:3].view(np.uint32)[0]), out[3:3 + int(nlevels)].copy()
 
 
 class ORBVocabulary:

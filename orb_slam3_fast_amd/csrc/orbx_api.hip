@@ -1999,4 +1999,35 @@ int orbx_debug_sincos(int device, const float* angles, int n, int fused, float* 
   return ORBX_OK;
 }
 
+int orbx_debug_fast_atan2(int device, const float* y, const float* x, int n, float* out) {
+  if (!y || !x || !out || n < 0) return fail(ORBX_E_BADARG, "bad argument");
+  if (n == 0) return ORBX_OK;
+  int rc = set_device(device);
+  if (rc != ORBX_OK) return rc;
+  ScratchBuf<float> d;
+  HIPC(d.alloc((size_t)3 * n));
+  hipError_t e = hipMemcpy(d.p, y, (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d.p + n, x, (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_debug_fast_atan2(d.p, d.p + n, n, d.p + 2 * (size_t)n, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d.p + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
+  return ORBX_OK;
+}
+
+int orbx_debug_describe_plan(const orbx_params* p, int width, int height, int n_images, int32_t* out) {
+  if (!p || !out || width < 1 || height < 1 || n_images < 1 || p->nlevels < 1 || p->nlevels > ORBX_MAX_LEVELS || p->nfeatures < 1 ||
+      !(p->scale_factor > 1.0f))
+    return fail(ORBX_E_BADARG, "bad argument");
+  std::unique_ptr<orbx_extractor> ex(new orbx_extractor());   // parameters and tables only: no device, no buffers
+  ex->prm = *p;
+  build_tables(ex.get());
+  Geom g;
+  std::string why;
+  const int rc = build_geom(ex.get(), width, height, g, why);
+  if (rc != ORBX_OK) return fail(rc, why);
+  debug_describe_plan(g, n_images, out);
+  return ORBX_OK;
+}
+
 }  // extern "C"

@@ -2832,18 +2832,39 @@ hipError_t prepare_kernels(const Geom& g) {
   return prepare_detect(g);
 }
 
-// Test entry: both glibc sinf/cosf variants on the device (compared with the host libm in tests).
+// Test entry: k_describe's plan exactly as launch_describe computes it (host only).  out: nk, tasks, magic, taskOff[ORBX_MAX_LEVELS]
+void debug_describe_plan(const Geom& g, int nimg, int32_t* out) {
+  const DescPlan dp = make_desc_plan(g, nimg);
+  out[0] = dp.nk;
+  out[1] = dp.tasks;
+  out[2] = (int32_t)dp.magic;
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) out[3 + l] = dp.taskOff[l];
+}
+
+// Test entry: glibc's sinf / cosf on the device (compared with the host libm in tests): fused = 0 / 1 the SSE2 / FMA variant of
+// orbx_sincos.h, fused = 2 glibc_sincosf_sel -- the branch-free form of the FMA variant, the one k_describe calls.
 __global__ void k_debug_sincos(const float* __restrict__ ang, int n, int fused, float* __restrict__ s, float* __restrict__ c) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float sv, cv;
-  if (fused) glibc_sincosf<true>(ang[i], sv, cv);
+  if (fused == 2) glibc_sincosf_sel(ang[i], sv, cv);
+  else if (fused) glibc_sincosf<true>(ang[i], sv, cv);
   else glibc_sincosf<false>(ang[i], sv, cv);
   s[i] = sv;
   c[i] = cv;
 }
 hipError_t launch_debug_sincos(const float* ang, int n, int fused, float* s, float* c, hipStream_t st) {
   hipLaunchKernelGGL(k_debug_sincos, dim3((n + 255) / 256), dim3(256), 0, st, ang, n, fused, s, c);
+  return hipGetLastError();
+}
+// Test entry: fast_atan2_sel, k_describe's branch-free cv::fastAtan2 (compared with the oracle's scalar restatement in tests).
+__global__ void k_debug_fast_atan2(const float* __restrict__ y, const float* __restrict__ x, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = fast_atan2_sel(y[i], x[i]);
+}
+hipError_t launch_debug_fast_atan2(const float* y, const float* x, int n, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_debug_fast_atan2, dim3((n + 255) / 256), dim3(256), 0, st, y, x, n, out);
   return hipGetLastError();
 }
 
