@@ -1924,6 +1924,10 @@ int orbx_debug_introsort_device(int device, uint64_t* v, int n);
  *   ORBX_LINALG_NULL_VECTOR_SYM9     A [16][9]  (one wave per item: lane l holds   v [4][9]: the result as lanes 0, 17, 34 and 63
  *   ORBX_LINALG_NULL_VECTOR_SYM12    A [16][12]  row l & 15, as the call sites)    v [4][12]  of the wave hold it
  *   ORBX_LINALG_SUM16                v [64], one value per lane of a wave          sum16(v) [64], as every lane holds it
+ *   ORBX_LINALG_HUBER                robust, chi2, delta                           rho0, rho1 (csrc/orbx_optim.h: huber)
+ *   ORBX_LINALG_LM_STEP              lambda, ni, curChi, iniChi, iter, qmax,       the seven state fields, then accepted (0 / 1), next
+ *                                    nbadR, tempChi, solveOk, scaleSum, maxIter    (0 retry, 1 next iteration, 2 stop), reason
+ *                                    (csrc/orbx_optim.h: lm_step; integers as doubles)   (ORBX_LBA_STOP_*, -1 unless next is 2)
  * A null pointer, n outside [1, ORBX_LINALG_MAX_ITEMS] and an unknown op are ORBX_E_BADARG before any device is touched. */
 #define ORBX_LINALG_RCP64 0
 #define ORBX_LINALG_RSQRT64 1
@@ -1936,7 +1940,9 @@ int orbx_debug_introsort_device(int device, uint64_t* v, int n);
 #define ORBX_LINALG_NULL_VECTOR_SYM9 8
 #define ORBX_LINALG_NULL_VECTOR_SYM12 9
 #define ORBX_LINALG_SUM16 10
-#define ORBX_LINALG_OPS 11
+#define ORBX_LINALG_HUBER 11
+#define ORBX_LINALG_LM_STEP 12
+#define ORBX_LINALG_OPS 13
 #define ORBX_LINALG_MAX_ITEMS 65536
 int orbx_debug_linalg(int device, int op, int n, const void* in, void* out);
 /* The camera models and the SE3 / Sim3 maps of the solvers (csrc/orbx_kb8.h, orbx_kb8_edge.h, orbx_pose.h, orbx_sim3opt.h,

@@ -1761,12 +1761,13 @@ def pose_graph_evaluate(vertices, fixed, edges, bFixScale, jacobians=True, devic
 
 # orbx_debug_linalg: ORBX_LINALG_* and, per operation, the numpy type and the elements of one item of `in` and of `out`
 (LINALG_RCP64, LINALG_RSQRT64, LINALG_JACOBI_CS, LINALG_SVD3, LINALG_NULL_VECTOR4, LINALG_LDLT6, LINALG_LDLT6_DAMPED, LINALG_LDLT7,
- LINALG_NULL_VECTOR_SYM9, LINALG_NULL_VECTOR_SYM12, LINALG_SUM16) = range(11)
-LINALG_OPS, LINALG_MAX_ITEMS = 11, 65536
+ LINALG_NULL_VECTOR_SYM9, LINALG_NULL_VECTOR_SYM12, LINALG_SUM16, LINALG_HUBER, LINALG_LM_STEP) = range(13)
+LINALG_OPS, LINALG_MAX_ITEMS = 13, 65536
 LINALG_ITEM = {LINALG_RCP64: (np.float64, 1, 1), LINALG_RSQRT64: (np.float64, 1, 1), LINALG_JACOBI_CS: (np.float64, 3, 3),
                LINALG_SVD3: (np.float64, 9, 21), LINALG_NULL_VECTOR4: (np.float32, 16, 4), LINALG_LDLT6: (np.float64, 27, 7),
                LINALG_LDLT6_DAMPED: (np.float64, 28, 7), LINALG_LDLT7: (np.float64, 36, 8), LINALG_NULL_VECTOR_SYM9: (np.float64, 144, 36),
-               LINALG_NULL_VECTOR_SYM12: (np.float64, 192, 48), LINALG_SUM16: (np.float64, 64, 64)}
+               LINALG_NULL_VECTOR_SYM12: (np.float64, 192, 48), LINALG_SUM16: (np.float64, 64, 64),
+               LINALG_HUBER: (np.float64, 3, 2), LINALG_LM_STEP: (np.float64, 11, 10)}
 
 
 def debug_linalg(op, items, prefill=0.0, device=0):

@@ -3,6 +3,7 @@
 // restated here.  One item per thread, except null_vector_sym and sum16, which take one item per wave in the call sites' layout.
 #include "orbx_host.h"
 #include "orbx_linalg.h"
+#include "orbx_optim.h"
 
 using namespace orbx_host;
 
@@ -96,9 +97,33 @@ __global__ __launch_bounds__(64) void k_la_sum16(const double* __restrict__ in, 
   out[i] = orbx::sum16(in[i]);
 }
 
+// item: robust, chi2, delta; out: rho0, rho1
+__global__ __launch_bounds__(64) void k_la_huber(int n, const double* __restrict__ in, double* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  double rho0, rho1;
+  orbx::huber(in[3 * i] != 0, in[3 * i + 1], in[3 * i + 2], rho0, rho1);
+  out[2 * i] = rho0;
+  out[2 * i + 1] = rho1;
+}
+
+// item: lambda, ni, curChi, iniChi, iter, qmax, nbadR, tempChi, solveOk, scaleSum, maxIter; out: the state's seven fields, then
+// accepted, next, reason
+__global__ __launch_bounds__(64) void k_la_lm_step(int n, const double* __restrict__ in, double* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const double* p = in + 11 * (size_t)i;
+  orbx::LmState s{p[0], p[1], p[2], p[3], (int)p[4], (int)p[5], (int)p[6], 0};
+  const orbx::LmVerdict v = orbx::lm_step(s, p[7], p[8] != 0, p[9], (int)p[10]);
+  double* o = out + 10 * (size_t)i;
+  o[0] = s.lambda; o[1] = s.ni; o[2] = s.curChi; o[3] = s.iniChi;
+  o[4] = s.iter; o[5] = s.qmax; o[6] = s.nbadR;
+  o[7] = v.accepted ? 1.0 : 0.0; o[8] = v.next; o[9] = v.reason;
+}
+
 // bytes of one item of `in` and of `out`, per operation
-constexpr size_t kInBytes[ORBX_LINALG_OPS] = {8, 8, 24, 72, 64, 27 * 8, 28 * 8, 36 * 8, 16 * 9 * 8, 16 * 12 * 8, 64 * 8};
-constexpr size_t kOutBytes[ORBX_LINALG_OPS] = {8, 8, 24, 21 * 8, 16, 7 * 8, 7 * 8, 8 * 8, 4 * 9 * 8, 4 * 12 * 8, 64 * 8};
+constexpr size_t kInBytes[ORBX_LINALG_OPS] = {8, 8, 24, 72, 64, 27 * 8, 28 * 8, 36 * 8, 16 * 9 * 8, 16 * 12 * 8, 64 * 8, 3 * 8, 11 * 8};
+constexpr size_t kOutBytes[ORBX_LINALG_OPS] = {8, 8, 24, 21 * 8, 16, 7 * 8, 7 * 8, 8 * 8, 4 * 9 * 8, 4 * 12 * 8, 64 * 8, 2 * 8, 10 * 8};
 
 }  // namespace
 
@@ -130,6 +155,8 @@ extern "C" int orbx_debug_linalg(int device, int op, int n, const void* in, void
     case ORBX_LINALG_LDLT7: hipLaunchKernelGGL((k_la_ldlt<7, true, true>), perThread, bs, 0, nullptr, n, di, dO); break;
     case ORBX_LINALG_NULL_VECTOR_SYM9: hipLaunchKernelGGL(k_la_null_sym<9>, perWave, bs, 0, nullptr, di, dO); break;
     case ORBX_LINALG_NULL_VECTOR_SYM12: hipLaunchKernelGGL(k_la_null_sym<12>, perWave, bs, 0, nullptr, di, dO); break;
+    case ORBX_LINALG_HUBER: hipLaunchKernelGGL(k_la_huber, perThread, bs, 0, nullptr, n, di, dO); break;
+    case ORBX_LINALG_LM_STEP: hipLaunchKernelGGL(k_la_lm_step, perThread, bs, 0, nullptr, n, di, dO); break;
     default: hipLaunchKernelGGL(k_la_sum16, perWave, bs, 0, nullptr, di, dO); break;
   }
   HIPC(hipGetLastError());

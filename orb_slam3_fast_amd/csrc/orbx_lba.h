@@ -3,6 +3,7 @@
 #ifndef ORBX_LBA_H
 #define ORBX_LBA_H
 #include "orbx_host.h"
+#include "orbx_optim.h"
 
 #include <vector>
 
@@ -18,8 +19,9 @@ struct LbaRigTrl { LbaPose T; double R[3][3]; };   // SE3Quat(Trl) normalised, a
 // The optimiser's state (optimization_algorithm_levenberg.cpp), written by k_lba_decide's thread 0 only.  `cur` names the copy
 // of the estimates and of the linear system (0 / 1) that belongs to the current estimate; a trial is built in the other copy.
 struct LbaState {
-  double lambda, ni, curChi, iniChi, chiInitial;
-  int cur, stage, iter, qmax, nbadR, trials, ok, running, stopReason, pad;
+  LmState lm;          // the Levenberg rule's own fields (orbx_optim.h)
+  double chiInitial;
+  int cur, stage, trials, ok, running, stopReason;
 };
 
 // What the step between the two optimisations of the map-merge bundle adjustment writes (k_lba_relevel, k_lba_relayout): round

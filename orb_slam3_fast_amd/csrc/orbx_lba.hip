@@ -36,19 +36,10 @@ using orbx::LbaState;
 using orbx::kLbaApp;
 using orbx::kLbaAll;
 using orbx::kLbaHpl;
+using orbx::block_tree;
 
 constexpr int kLbaBS = 256;
 constexpr int kSolveBS = 1024;
-
-__device__ __forceinline__ void quat_to_R(const double* q, double R[3][3]) {   // Eigen's toRotationMatrix
-  const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-  const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-  R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-  R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
-  R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
-}
 
 // SE3Quat::map of the edge's point, its error (rows: 2 mono, 3 stereo; the unused row is zero) and chi2 = e^T (info I) e
 __device__ __forceinline__ void lba_error(const orbx_lba_keyframe& K, const orbx_lba_edge& E, const LbaPose& P, const double* X, double Xc[3],
@@ -140,13 +131,8 @@ __device__ __forceinline__ void lba_edge_store(const LbaArgs& A, int ei, int tgt
   const bool mono = E.u_right < 0.f;
   // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91); without a kernel g2o weighs with the information alone: rho' = 1
   const double delta = mono ? A.deltaMono : A.deltaStereo;
-  const double dsqr = delta * delta;
-  double rho0 = chi, rho1 = 1.0;
-  if (A.robust && !(chi <= dsqr)) {
-    const double sq = sqrt(chi);
-    rho0 = 2 * sq * delta - dsqr;
-    rho1 = delta / sq;
-  }
+  double rho0, rho1;
+  huber(A.robust != 0, chi, delta, rho0, rho1);
   const double w = rho1 * (double)E.inv_sigma2;
   constexpr int rows = 3;   // a monocular edge's third row is zero: its terms add nothing
   A.chi2[ei] = chi;
@@ -356,19 +342,6 @@ __global__ __launch_bounds__(64) void k_lba_reduce_kfs(LbaArgs A) {
   }
 }
 
-// a strided serial sum per thread, then a fixed tree over the workgroup; every thread returns the result
-template <int kN>
-__device__ __forceinline__ double block_tree(double v, double* red, bool isMax) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = kN / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] = isMax ? fmax(red[threadIdx.x], red[threadIdx.x + off]) : red[threadIdx.x] + red[threadIdx.x + off];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(kLbaBS) void k_lba_decide(LbaArgs A) {
   __shared__ double red[kLbaBS];
   LbaState& st = *A.st;
@@ -391,7 +364,7 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_decide(LbaArgs A) {
     }
     aux = block_tree<kLbaBS>(m, red, true);
   } else {            // computeScale over all of x: sum x (lambda x + b), b of the system at the estimate
-    const double lambda = st.lambda;
+    const double lambda = st.lm.lambda;
     double sc = 0;
     for (int k = tid; k < A.n; k += kLbaBS) {
       const double x = A.xp[k];
@@ -407,53 +380,16 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_decide(LbaArgs A) {
   LbaState c = st;
   bool trial = false;
   if (stage == 0) {
-    c.curChi = chi;
-    c.iniChi = chi;
     c.chiInitial = chi;
-    c.lambda = A.lambdaInit > 0 ? A.lambdaInit : 1e-5 * aux;
-    c.ni = 2;
-    c.nbadR = 0;
-    c.qmax = 0;
+    lm_begin(c.lm, chi, A.lambdaInit > 0 ? A.lambdaInit : 1e-5 * aux);
     c.stage = 1;
     trial = true;
   } else {
     c.trials++;
-    double tempChi = chi;
-    if (!c.ok) tempChi = DBL_MAX;
-    double rho = c.curChi - tempChi;
-    const double scale = aux + 1e-3;
-    rho /= scale;
-    if (rho > 0 && isfinite(tempChi)) {
-      double alpha = 1. - pow(2 * rho - 1, 3);
-      alpha = fmin(alpha, 2. / 3.);
-      c.lambda *= fmax(1. / 3., alpha);
-      c.ni = 2;
-      c.curChi = tempChi;
-      c.cur ^= 1;
-    } else {
-      c.lambda *= c.ni;
-      c.ni *= 2;
-    }
-    c.qmax++;
-    if (rho < 0 && c.qmax < 10) {
-      trial = true;
-    } else {
-      int reason = -1;
-      if (c.qmax == 10) reason = ORBX_LBA_STOP_QMAX;
-      else if (rho == 0) reason = ORBX_LBA_STOP_RHO_ZERO;
-      if (reason < 0) {   // Raul's stop criterion
-        if ((c.iniChi - c.curChi) * 1e3 < c.iniChi) c.nbadR++; else c.nbadR = 0;
-        if (c.nbadR >= 3) reason = ORBX_LBA_STOP_SMALL_GAIN;
-      }
-      c.iter++;
-      if (reason < 0 && c.iter < A.maxIter) {   // next solve(): the errors and the system at the estimate are the ones held
-        c.iniChi = c.curChi;
-        c.qmax = 0;
-        trial = true;
-      } else {
-        c.stopReason = reason < 0 ? ORBX_LBA_STOP_ITERATIONS : reason;
-      }
-    }
+    const LmVerdict v = lm_step(c.lm, chi, c.ok != 0, aux, A.maxIter);
+    if (v.accepted) c.cur ^= 1;
+    trial = v.next != kLmStop;   // (the next solve(): the errors and the system at the estimate are the ones held)
+    if (!trial) c.stopReason = v.reason;
   }
   c.running = trial ? 1 : 0;
   st = c;
@@ -465,7 +401,7 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_dinv(LbaArgs A) {
   if (p >= A.nP) return;
   const LbaState& st = *A.st;
   const double* h = A.hll[st.cur] + (size_t)p * kLbaAll;
-  const double a = h[0] + st.lambda, b = h[1], c = h[2], d = h[3] + st.lambda, e = h[4], f = h[5] + st.lambda;
+  const double a = h[0] + st.lm.lambda, b = h[1], c = h[2], d = h[3] + st.lm.lambda, e = h[4], f = h[5] + st.lm.lambda;
   // Eigen's 3 x 3 inverse: cofactors over the determinant
   const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
   const double inv = 1.0 / (a * c00 + b * c01 + c * c02);
@@ -499,7 +435,7 @@ __device__ __forceinline__ void schur_write(const LbaArgs& A, const LbaState& st
     if (i == j) {
       const int lo = a < b ? a : b, hi = a < b ? b : a;
       v += A.hpp[cur][(size_t)i * kLbaApp + (lo * (13 - lo)) / 2 + (hi - lo)];
-      if (a == b) v += st.lambda;
+      if (a == b) v += st.lm.lambda;
       A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
     } else {
       A.S[(6 * (size_t)i + a) * n + 6 * j + b] = v;
@@ -772,10 +708,10 @@ __device__ __forceinline__ void lba_finish(const LbaArgs& A) {
       A.outPts[3 * (size_t)i + k] = active ? A.X[cur][3 * (size_t)i + k] : (double)A.points[3 * (size_t)i + k];
   }
   if (i == 0) {
-    A.outScalars[0] = st.lambda;
+    A.outScalars[0] = st.lm.lambda;
     A.outScalars[1] = st.chiInitial;
-    A.outScalars[2] = st.curChi;
-    A.outCounters[0] = st.iter;
+    A.outScalars[2] = st.lm.curChi;
+    A.outCounters[0] = st.lm.iter;
     A.outCounters[1] = st.trials;
     A.outCounters[2] = st.stopReason;
   }
@@ -834,8 +770,8 @@ __global__ __launch_bounds__(kLbaBS) void k_lba_relayout(LbaArgs A) {
     A.rl.counts[0] = n;
     A.rl.counts[1] = t;
     LbaState& st = *A.st;
-    A.rl.scalars[0] = st.lambda; A.rl.scalars[1] = st.chiInitial; A.rl.scalars[2] = st.curChi;
-    A.rl.counters[0] = st.iter; A.rl.counters[1] = st.trials; A.rl.counters[2] = st.stopReason;
+    A.rl.scalars[0] = st.lm.lambda; A.rl.scalars[1] = st.chiInitial; A.rl.scalars[2] = st.lm.curChi;
+    A.rl.counters[0] = st.lm.iter; A.rl.counters[1] = st.trials; A.rl.counters[2] = st.stopReason;
     LbaState s{};
     s.cur = st.cur;
     s.ok = 1;

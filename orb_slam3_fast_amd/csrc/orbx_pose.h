@@ -1,19 +1,27 @@
 // orbx_pose.h — what the two pose-optimisation kernels share: k_pose_opt (pinhole / rectified, orbx_pose.hip) and k_pose_opt_kb8
-// (KannalaBrandt8, orbx_pose_kb8.hip), and their C ABI (orbx_api_pose.hip): the per-frame argument records, SE3Quat and thread
-// 0's g2o Levenberg state machine (its 6 x 6 LDLT is orbx_linalg.h's, the wave reduction orbx_device.h's).
-// The kernels live in separate translation units so that the pinhole kernel compiles to the code it had before KB8 existed.
+// (KannalaBrandt8, orbx_pose_kb8.hip), and their C ABI (orbx_api_pose.hip): the per-frame argument records, SE3Quat, thread 0's
+// optimiser state machine (its Levenberg rule is orbx_optim.h's, its 6 x 6 LDLT orbx_linalg.h's, the wave reduction
+// orbx_device.h's) and the kernels' body, pose_opt_frame<Edges>; each kernel is an edge policy in its own translation unit (with
+// both in one file the pinhole kernel's register assignment moved).  Cam and stage_edges serve k_pose_inertial as well.
 #ifndef ORBX_POSE_H
 #define ORBX_POSE_H
 #include "orbx_device.h"
 #include "orbx_host.h"
 #include "orbx_linalg.h"
-#include <cfloat>
+#include "orbx_optim.h"
 
 namespace {
 
 using orbx::cross3;
 using orbx::ldlt6;
 using orbx::wave_sum;
+using orbx::huber;
+using orbx::jtwj_accum;
+using orbx::LmState;
+using orbx::LmVerdict;
+using orbx::lm_begin;
+using orbx::lm_step;
+using orbx::kLmStop;
 
 #ifndef ORBX_POSE_BS
 #define ORBX_POSE_BS 256
@@ -94,6 +102,15 @@ __device__ __forceinline__ void quat_from_R(const double R[3][3], double* q) {  
     else quat_from_R_diag<0>(R, q);
   }
 }
+__device__ __forceinline__ void quat_to_R(const double* q, double R[3][3]) {   // Eigen's toRotationMatrix: normalises nothing
+  const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+  const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+  R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+  R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+  R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+}
 // SE3Quat::exp(update) * P (VertexSE3Expmap::oplusImpl): rotation first in the update vector, small-angle branch R = I + W + W^2
 __device__ __forceinline__ void oplus(const double* x, const Pose& P, Pose& out) {
   const double w[3] = {x[0], x[1], x[2]}, u[3] = {x[3], x[4], x[5]};
@@ -130,14 +147,14 @@ enum : int { kEval = 0, kClassify = 1, kDone = 2 };
 struct Ctl {   // thread 0's optimiser state, in LDS
   Pose P0, P, T, L;                  // initial, current estimate, pose to evaluate / last trial, last evaluated trial
   double H[21], b[6], x[6];
-  double lambda, ni, curChi, iniChi;
-  int phase, stage, iter, qmax, nbadR, round, robust, nActive, trials, ok2;
+  LmState lm;
+  int phase, stage, round, robust, nActive, trials, ok2;
 };
 
 __device__ __forceinline__ void ctl_trial(Ctl& c) {   // push, H + lambda I, solve, update
   double x[6];
   for (int i = 0; i < 6; i++) x[i] = c.x[i];
-  c.ok2 = ldlt6<true>(c.H, c.b, x, c.lambda);
+  c.ok2 = ldlt6<true>(c.H, c.b, x, c.lm.lambda);
   for (int i = 0; i < 6; i++) c.x[i] = x[i];   // a failed solve leaves g2o's x as it was
   oplus(x, c.P, c.T);
   c.phase = kEval;
@@ -153,63 +170,182 @@ __device__ __forceinline__ void ctl_start_round(Ctl& c) {
   }
   c.T = c.P;
   c.stage = 0;
-  c.iter = 0;
   c.phase = kEval;
 }
 
 // after an evaluation pass: sums = H (21), b (6), robust chi2 at c.T
 __device__ __forceinline__ void ctl_after_eval(Ctl& c, const double* sums) {
   if (c.stage == 0) {   // solve(iteration 0): computeActiveErrors, buildSystem, lambda init
-    c.curChi = sums[27];
     for (int i = 0; i < 21; i++) c.H[i] = sums[i];
     for (int i = 0; i < 6; i++) c.b[i] = sums[21 + i];
-    c.iniChi = c.curChi;
     double maxDiag = 0;
     for (int j = 0, k = 0; j < 6; k += 6 - j, j++) maxDiag = fmax(fabs(c.H[k]), maxDiag);
-    c.lambda = 1e-5 * maxDiag;
-    c.ni = 2;
-    c.nbadR = 0;
-    c.qmax = 0;
+    lm_begin(c.lm, sums[27], 1e-5 * maxDiag);
     for (int i = 0; i < 6; i++) c.x[i] = 0;
     ctl_trial(c);
     return;
   }
   c.trials++;
   c.L = c.T;
-  double tempChi = sums[27];
-  if (!c.ok2) tempChi = DBL_MAX;
-  double rho = c.curChi - tempChi, scale = 0;
-  for (int j = 0; j < 6; j++) scale += c.x[j] * (c.lambda * c.x[j] + c.b[j]);
-  scale += 1e-3;
-  rho /= scale;
-  if (rho > 0 && isfinite(tempChi)) {
-    double alpha = 1. - pow(2 * rho - 1, 3);
-    alpha = fmin(alpha, 2. / 3.);
-    c.lambda *= fmax(1. / 3., alpha);
-    c.ni = 2;
-    c.curChi = tempChi;
+  double scale = 0;
+  for (int j = 0; j < 6; j++) scale += c.x[j] * (c.lm.lambda * c.x[j] + c.b[j]);
+  const LmVerdict v = lm_step(c.lm, sums[27], c.ok2 != 0, scale, 10);
+  if (v.accepted) {
     c.P = c.T;
     for (int i = 0; i < 21; i++) c.H[i] = sums[i];
     for (int i = 0; i < 6; i++) c.b[i] = sums[21 + i];
-  } else {
-    c.lambda *= c.ni;
-    c.ni *= 2;
   }
-  c.qmax++;
-  if (rho < 0 && c.qmax < 10) { ctl_trial(c); return; }
-  bool term = c.qmax == 10 || rho == 0;
-  if (!term) {   // Raul's stop criterion
-    if ((c.iniChi - c.curChi) * 1e3 < c.iniChi) c.nbadR++; else c.nbadR = 0;
-    term = c.nbadR >= 3;
+  if (v.next == kLmStop) c.phase = kClassify;
+  else ctl_trial(c);   // (the next solve(): errors and system at the estimate are the ones held)
+}
+
+// ---- what the frame kernels share: k_pose_opt, k_pose_opt_kb8 and (the staging, Cam) k_pose_inertial
+struct Cam { double fx, fy, cx, cy, bf; };
+
+// the observation of a pinhole / rectified frame's key point i: {u, v, uR (< 0: mono), 0}
+struct PinholeObs {
+  template <class Args>
+  __device__ static __forceinline__ float4 obs(const Args& A, int i, int& octave) {
+    const orbx_keypoint kp = A.kps[i];
+    octave = kp.octave;
+    return make_float4(kp.x, kp.y, A.uR ? A.uR[i] : -1.f, 0.f);
   }
-  c.iter++;
-  if (!term && c.iter < 10) {   // next solve(): errors and system at the estimate are the ones held
-    c.iniChi = c.curChi;
-    c.qmax = 0;
-    ctl_trial(c);
+};
+
+// stage a frame's edges: {Xw, invSigma2}, Obs::obs; eout != nullptr: mvbOutlier = false
+template <class Obs, class Args>
+__device__ __forceinline__ void stage_edges(const Args& A, float4* E, const float* __restrict__ invSigma2, int nlevels, uint8_t* eout) {
+  for (int k = threadIdx.x; k < A.nE; k += kBS) {
+    int octave;
+    const float4 B = Obs::obs(A, A.eidx[k], octave);
+    const int oct = min(max(octave, 0), nlevels - 1);
+    E[2 * k] = make_float4(A.wpos[3 * k], A.wpos[3 * k + 1], A.wpos[3 * k + 2], invSigma2[oct]);
+    E[2 * k + 1] = B;
+    if (eout) eout[k] = 0;
+  }
+}
+
+// Optimizer::PoseOptimization of one frame by one workgroup (the file comment of orbx_pose.hip has the scheme).  Edges is what an
+// edge is:
+//   Args, frame(A)         the argument record and its q / t carrying input record
+//   Rig, fill(rig, A)      the frame's constants in LDS, filled by thread 0
+//   Edges(A, dMono, dSt)   the call's constants in registers
+//   At, at(rig, T)         what a pass derives from the pose it evaluates
+//   accum(rig, at, a, b, robust, acc)   buildSystem's share of an edge and its robust chi2 (acc[27])
+//   bad(rig, at, a, b)     the classification's chi2, narrowed to float, against the edge's float threshold
+// and is also the Obs of stage_edges.
+template <class Edges>
+__device__ __forceinline__ void pose_opt_frame(const typename Edges::Args& A, const float* __restrict__ invSigma2, int nlevels,
+                                               double deltaMono, double deltaStereo) {
+  extern __shared__ __attribute__((aligned(16))) float4 lds_edges[];
+  __shared__ Ctl c;
+  __shared__ typename Edges::Rig rig;
+  __shared__ double red[kNW][kNSum];
+  __shared__ double sums[kNSum];
+  __shared__ int ired[kNW];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nE = A.nE;
+  float4* E = nE > kLdsEdges ? A.stage : lds_edges;
+  stage_edges<Edges>(A, E, invSigma2, nlevels, A.eout);
+  // (Edges::frame(A) is read where it is used: held in a reference from here on, its pointer costs k_pose_opt_kb8 two SGPR spills)
+  if (nE < 3) {   // nInitialCorrespondences < 3: return 0, the pose untouched
+    if (tid == 0) {
+      A.result[0] = 0;
+      A.result[1] = 0;
+      for (int i = 0; i < 4; i++) A.poseOut[i] = Edges::frame(A).q[i];
+      for (int i = 0; i < 3; i++) A.poseOut[4 + i] = Edges::frame(A).t[i];
+    }
     return;
   }
-  c.phase = kClassify;
+  const Edges ed(A, deltaMono, deltaStereo);
+  if (tid == 0) {
+    for (int i = 0; i < 4; i++) c.P0.q[i] = (double)Edges::frame(A).q[i];
+    for (int i = 0; i < 3; i++) c.P0.t[i] = (double)Edges::frame(A).t[i];
+    normalize_rotation(c.P0.q);
+    Edges::fill(rig, A);
+    c.round = 0;
+    c.robust = 1;
+    c.nActive = nE;
+    c.trials = 0;
+    ctl_start_round(c);
+  }
+  uint64_t outMask = 0;   // bit j: edge tid + j * kBS is an outlier (level 1)
+  int nBad = 0;
+  for (;;) {
+    __syncthreads();
+    const int phase = c.phase;
+    if (phase == kDone) break;
+    if (phase == kEval) {
+      const typename Edges::At T = Edges::at(rig, c.T);
+      const bool robust = c.robust != 0;
+      double acc[kNSum];
+#pragma unroll
+      for (int i = 0; i < kNSum; i++) acc[i] = 0;
+      for (int k = tid, j = 0; k < nE; k += kBS, j++) {
+        if ((outMask >> j) & 1) continue;
+        ed.accum(rig, T, E[2 * k], E[2 * k + 1], robust, acc);
+      }
+#pragma unroll
+      for (int i = 0; i < kNSum; i++) {
+        const double v = wave_sum(acc[i]);
+        if (lane == 0) red[wid][i] = v;
+      }
+      __syncthreads();
+      if (tid < kNSum) {
+        double v = red[0][tid];
+        for (int w = 1; w < kNW; w++) v += red[w][tid];
+        sums[tid] = v;
+      }
+      __syncthreads();
+      if (tid == 0) ctl_after_eval(c, sums);
+    } else {   // classify at the round's end (Optimizer.cc:1005-1092)
+      const typename Edges::At P = Edges::at(rig, c.P), L = Edges::at(rig, c.L);
+      nBad = 0;
+      uint64_t mask = 0;
+      for (int k = tid, j = 0; k < nE; k += kBS, j++) {
+        const bool wasOut = (outMask >> j) & 1;
+        if (ed.bad(rig, wasOut ? P : L, E[2 * k], E[2 * k + 1])) { mask |= 1ull << j; nBad++; }
+      }
+      outMask = mask;
+      const int v = wave_sum(nBad);
+      if (lane == 0) ired[wid] = v;
+      __syncthreads();
+      if (tid == 0) {
+        int tot = 0;
+        for (int w = 0; w < kNW; w++) tot += ired[w];
+        c.nActive = nE - tot;
+        if (c.round == 2) c.robust = 0;
+        c.round++;
+        if (nE < 10 || c.round == 4) {   // optimizer.edges().size() < 10, or the fourth round done
+          // Sophus::SE3f(q.cast<float>(), t.cast<float>()): the SO3f constructor normalises in float
+          float q[4];
+          for (int i = 0; i < 4; i++) q[i] = (float)c.P.q[i];
+          const float len = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+          for (int i = 0; i < 4; i++) A.poseOut[i] = q[i] / len;
+          for (int i = 0; i < 3; i++) A.poseOut[4 + i] = (float)c.P.t[i];
+          A.result[0] = nE - tot;
+          A.result[1] = c.trials;
+          c.phase = kDone;
+        } else {
+          ctl_start_round(c);
+        }
+      }
+    }
+  }
+  for (int k = tid, j = 0; k < nE; k += kBS, j++) A.eout[k] = (outMask >> j) & 1;
+}
+
+// the launch of a frame kernel: one workgroup per record, the staged edges in dynamic LDS; deltas: the Huber deltas the kernel
+// takes, as the reference holds them (floats)
+inline double huber_delta(double chi2Gate) { return (float)std::sqrt(chi2Gate); }
+template <class Args, class... Deltas>
+hipError_t launch_pose_frames(void (*kernel)(const Args*, const float*, int, Deltas...), const void* d_frames, int nFrames, size_t lds,
+                              const float* d_invSigma2, int nlevels, Deltas... deltas) {
+  if (lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(nFrames), dim3(kBS), lds, nullptr, static_cast<const Args*>(d_frames), d_invSigma2, nlevels, deltas...);
+  return hipGetLastError();
 }
 
 }  // namespace

@@ -20,7 +20,6 @@ using namespace orbx;
 constexpr int kNV = 27;                      // visual sums: H upper triangle (21), b (6)
 constexpr double kG = (double)9.81f;         // IMU::GRAVITY_VALUE is a float (include/ImuTypes.h:42); g = (0, 0, -kG)
 
-struct Cam { double fx, fy, cx, cy, bf; };
 struct VPose { double Rcw[9], tcw[3], Rcb[9], tbc[3]; };
 
 struct ICtl {   // the optimiser's state, in LDS
@@ -85,21 +84,9 @@ __device__ __forceinline__ double vis_accum(const VPose& P, const Cam& K, const 
                                             double* acc) {
   double e[M], J[M][6], chi2;
   vis_eval<M, true>(P, K, A, B, e, chi2, J);
-  double rho1 = 1.0;
-  if (robust && !(chi2 <= delta * delta)) rho1 = delta / sqrt(chi2);   // RobustKernelHuber (robust_kernel_impl.cpp:78-91)
-  const double w = rho1 * (double)A.w;
-#pragma unroll
-  for (int r = 0; r < M; r++) {
-    double wj[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) wj[a] = J[r][a] * w;
-#pragma unroll
-    for (int a = 0, q = 0; a < 6; a++) {
-#pragma unroll
-      for (int b = a; b < 6; b++, q++) acc[q] += wj[a] * J[r][b];
-      acc[21 + a] -= wj[a] * e[r];
-    }
-  }
+  double rho0, rho1;   // (a Gauss-Newton step reads no chi2: rho0 is unused)
+  huber(robust, chi2, delta, rho0, rho1);
+  jtwj_accum<M, 6>(J, e, rho1 * (double)A.w, acc);
   return chi2;
 }
 
@@ -406,13 +393,7 @@ __global__ __launch_bounds__(kBS) void k_pose_inertial(const PoseInertialArgs* _
   const PoseInertialArgs& A = frames[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nE = A.nE;
   float4* E = nE > kLdsEdges ? A.stage : lds_edges;
-  for (int k = tid; k < nE; k += kBS) {   // stage: {Xw, invSigma2}, {u, v, uR (< 0: mono), the held chi2}; mvbOutlier = false
-    const int i = A.eidx[k];
-    const orbx_keypoint kp = A.kps[i];
-    const int oct = min(max(kp.octave, 0), nlevels - 1);
-    E[2 * k] = make_float4(A.wpos[3 * k], A.wpos[3 * k + 1], A.wpos[3 * k + 2], invSigma2[oct]);
-    E[2 * k + 1] = make_float4(kp.x, kp.y, A.uR ? A.uR[i] : -1.f, 0.f);
-  }
+  stage_edges<PinholeObs>(A, E, invSigma2, nlevels, nullptr);   // B.w: the chi2 the edge holds
   const orbx_pose_inertial_frame& F = *A.frame;
   const Cam K{(double)F.fx, (double)F.fy, (double)F.cx, (double)F.cy, (double)F.bf};
   // ---- the vertices, the constants of the call and the information matrices

@@ -3,6 +3,7 @@
 #ifndef ORBX_POSEGRAPH_H
 #define ORBX_POSEGRAPH_H
 #include "orbx_host.h"
+#include "orbx_optim.h"
 #include "orbx_sim3opt.h"
 
 namespace orbx {
@@ -19,8 +20,9 @@ constexpr double kPgDelta = 1e-6;        // step of the central differences (g2o
 // names the copy of the estimates (0 / 1) that is the current estimate; a trial is built in the other copy.  needLin: the next
 // chain starts a g2o iteration (computeActiveErrors + buildSystem at the estimate); otherwise it is a further trial of the same.
 struct PgState {
-  double lambda, ni, curChi, iniChi, chiInitial;
-  int cur, iter, qmax, nbad, trials, ok, running, stopReason, needLin, pad;
+  LmState lm;          // the Levenberg rule's own fields (orbx_optim.h)
+  double chiInitial;
+  int cur, trials, ok, running, stopReason, needLin;
 };
 
 struct PgArgs {
@@ -67,16 +69,6 @@ hipError_t launch_pg_evaluate(const PgArgs& a); // k_pg_linearize alone, errors 
 
 namespace {
 
-__device__ __forceinline__ void sim3_quat_to_R(const double* q, double R[3][3]) {   // Eigen's toRotationMatrix: normalises nothing
-  const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-  const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-  R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-  R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
-  R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
-}
-
 // W u = t by Gaussian elimination with partial pivoting (Eigen's PartialPivLU of a 3 x 3: W.lu().solve(t))
 __device__ __forceinline__ void lu3_solve(double W[3][3], const double* t, double* u) {
   double b[3] = {t[0], t[1], t[2]};
@@ -108,7 +100,7 @@ __device__ __forceinline__ void lu3_solve(double W[3][3], const double* t, doubl
 __device__ __forceinline__ void sim3_log(const Sim3& S, double* out) {
   const double sigma = log(S.s);
   double R[3][3];
-  sim3_quat_to_R(S.q, R);
+  quat_to_R(S.q, R);
   const double d = 0.5 * (R[0][0] + R[1][1] + R[2][2] - 1);
   const double dR[3] = {R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1]};   // deltaR (se3_ops.hpp)
   const double eps = 0.00001;

@@ -137,18 +137,6 @@ __global__ __launch_bounds__(kPgBS) void k_pg_assemble_off(PgArgs A) {
   A.ho[idx] = v;
 }
 
-// a strided serial sum per thread, then a fixed tree over the workgroup; every thread returns the result
-__device__ __forceinline__ double pg_block_sum(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = kPgBS / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // solve()'s head (optimization_algorithm_levenberg.cpp:75-101): currentChi = iniChi = the chi2 at the estimate, qmax = 0, and in
 // iteration 0 computeLambdaInit (the user's value: the entry requires one), ni = 2, nBad = 0
 __global__ __launch_bounds__(kPgBS) void k_pg_begin(PgArgs A) {
@@ -157,17 +145,16 @@ __global__ __launch_bounds__(kPgBS) void k_pg_begin(PgArgs A) {
   if (!st.needLin) return;
   double part = 0;
   for (int e = threadIdx.x; e < A.nE; e += kPgBS) part += A.eChi[e];
-  const double chi = pg_block_sum(part, red);
+  const double chi = block_tree<kPgBS>(part, red, false);
   if (threadIdx.x != 0) return;
   PgState c = st;
-  c.curChi = chi;
-  c.iniChi = chi;
-  c.qmax = 0;
-  if (c.iter == 0) {
+  if (c.lm.iter == 0) {
     c.chiInitial = chi;
-    c.lambda = A.lambdaInit;
-    c.ni = 2;
-    c.nbad = 0;
+    lm_begin(c.lm, chi, A.lambdaInit);
+  } else {   // (lm_step left iniChi = curChi of the trial's sum; the chi2 of this linearisation replaces both)
+    c.lm.curChi = chi;
+    c.lm.iniChi = chi;
+    c.lm.qmax = 0;
   }
   c.needLin = 0;
   st = c;
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(kPgBS) void k_pg_scatter(PgArgs A) {
     const int s = idx / kPgDiag, t = idx % kPgDiag;
     if (t < kPgBlk) {
       const int r = t / kPgDim, c = t % kPgDim;
-      if (c <= r) A.S[(size_t)(kPgDim * s + r) * n + kPgDim * s + c] = A.hd[idx] + (r == c ? A.st->lambda : 0.0);
+      if (c <= r) A.S[(size_t)(kPgDim * s + r) * n + kPgDim * s + c] = A.hd[idx] + (r == c ? A.st->lm.lambda : 0.0);
     } else {
       A.bs[kPgDim * s + (t - kPgBlk)] = A.hd[idx];
     }
@@ -222,51 +209,22 @@ __global__ __launch_bounds__(kPgBS) void k_pg_decide(PgArgs A) {
   const int tid = threadIdx.x;
   double part = 0;
   for (int e = tid; e < A.nE; e += kPgBS) part += A.tChi[e];
-  const double chi = pg_block_sum(part, red);
-  const double lambda = st.lambda;
+  const double chi = block_tree<kPgBS>(part, red, false);
+  const double lambda = st.lm.lambda;
   double sc = 0;
   for (int k = tid; k < A.n; k += kPgBS) {   // computeScale: sum x (lambda x + b)
     const double x = A.x[k];
     sc += x * (lambda * x + A.hd[(size_t)(k / kPgDim) * kPgDiag + kPgBlk + k % kPgDim]);
   }
-  const double scale = pg_block_sum(sc, red) + 1e-3;
+  const double scaleSum = block_tree<kPgBS>(sc, red, false);
   if (tid != 0) return;
   PgState c = st;
-  bool trial = false;
   c.trials++;
-  double tempChi = chi;
-  if (!c.ok) tempChi = DBL_MAX;
-  const double rho = (c.curChi - tempChi) / scale;
-  if (rho > 0 && isfinite(tempChi)) {
-    double alpha = 1. - pow(2 * rho - 1, 3);
-    alpha = fmin(alpha, 2. / 3.);
-    c.lambda *= fmax(1. / 3., alpha);
-    c.ni = 2;
-    c.curChi = tempChi;
-    c.cur ^= 1;
-  } else {
-    c.lambda *= c.ni;
-    c.ni *= 2;
-  }
-  c.qmax++;
-  if (rho < 0 && c.qmax < 10) {
-    trial = true;
-  } else {
-    int reason = -1;
-    if (c.qmax == 10) reason = ORBX_LBA_STOP_QMAX;
-    else if (rho == 0) reason = ORBX_LBA_STOP_RHO_ZERO;
-    if (reason < 0) {   // Raul's stop criterion
-      if ((c.iniChi - c.curChi) * 1e3 < c.iniChi) c.nbad++; else c.nbad = 0;
-      if (c.nbad >= 3) reason = ORBX_LBA_STOP_SMALL_GAIN;
-    }
-    c.iter++;
-    if (reason < 0 && c.iter < A.maxIter) {
-      c.needLin = 1;
-      trial = true;
-    } else {
-      c.stopReason = reason < 0 ? ORBX_LBA_STOP_ITERATIONS : reason;
-    }
-  }
+  const LmVerdict v = lm_step(c.lm, chi, c.ok != 0, scaleSum, A.maxIter);
+  if (v.accepted) c.cur ^= 1;
+  const bool trial = v.next != kLmStop;
+  if (v.next == kLmNextIteration) c.needLin = 1;
+  if (!trial) c.stopReason = v.reason;
   c.running = trial ? 1 : 0;
   st = c;
   *A.status = c.running;
@@ -289,9 +247,9 @@ __global__ __launch_bounds__(kPgBS) void k_pg_finish(PgArgs A) {
   }
   if (idx < A.nE) A.outChi[idx] = pg_edge_chi(A, idx, est);
   if (idx == 0) {
-    A.outScalars[0] = st.lambda;
+    A.outScalars[0] = st.lm.lambda;
     A.outScalars[1] = st.chiInitial;
-    A.outCounters[0] = st.iter;
+    A.outCounters[0] = st.lm.iter;
     A.outCounters[1] = st.trials;
     A.outCounters[2] = st.stopReason;
   }
@@ -302,7 +260,7 @@ __global__ __launch_bounds__(kPgBS) void k_pg_final_chi(PgArgs A) {
   __shared__ double red[kPgBS];
   double part = 0;
   for (int e = threadIdx.x; e < A.nE; e += kPgBS) part += A.outChi[e];
-  const double chi = pg_block_sum(part, red);
+  const double chi = block_tree<kPgBS>(part, red, false);
   if (threadIdx.x == 0) {
     A.outScalars[2] = chi;
     if (A.nOpt == 0) A.outScalars[1] = chi;   // nothing to optimise: no iteration ran

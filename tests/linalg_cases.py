@@ -734,3 +734,174 @@ def sum16_xor_tree(v):
     for off in (8, 4, 2, 1):
         v = v + v[:, lane ^ off]
     return v
+
+
+# ------------------------------------------------------------------------------------------------ huber (csrc/orbx_optim.h)
+DELTA_MONO = float(np.float32(np.sqrt(5.991)))          # the project's two Huber deltas, as the reference holds them: floats
+DELTA_STEREO = float(np.float32(np.sqrt(7.815)))
+
+
+@functools.lru_cache(None)
+def huber_items():
+    """Rows of (robust, chi2, delta): chi2 at delta^2 and its two neighbours, 0, inf, NaN, ordinary values on both sides, and a
+    large chi2 without a kernel, for both deltas."""
+    rows = []
+    for d in (DELTA_MONO, DELTA_STEREO):
+        d2 = d * d
+        for chi in (d2, np.nextafter(d2, np.inf), np.nextafter(d2, -np.inf), 0.0, np.inf, np.nan, 0.37, 2.0 * d2, 1234.5678, 1e300, TINY):
+            rows.append((1.0, chi, d))
+        rows += [(0.0, 1e12, d), (0.0, np.nextafter(d2, np.inf), d), (0.0, np.nan, d)]
+    return np.array(rows)
+
+
+def huber_reference(items):
+    """RobustKernelHuber::robustify in double, operation by operation: each one is correctly rounded here and on the device."""
+    out = np.empty((len(items), 2))
+    with np.errstate(all="ignore"):
+        for i, (robust, chi, d) in enumerate(items):
+            rho0, rho1 = np.float64(chi), np.float64(1.0)
+            dsqr = np.float64(d) * np.float64(d)
+            if robust != 0 and not chi <= dsqr:
+                sq = np.sqrt(np.float64(chi))
+                rho0 = np.float64(2.0) * sq * np.float64(d) - dsqr
+                rho1 = np.float64(d) / sq
+            out[i] = rho0, rho1
+    return out
+
+
+def same_bits(a, b):
+    """Equal bit for bit; a NaN equals any NaN (its sign and payload are not arithmetic)."""
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    nan = np.isnan(a)
+    return a.shape == b.shape and np.array_equal(nan, np.isnan(b)) and a[~nan].tobytes() == b[~nan].tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ lm_step (csrc/orbx_optim.h)
+LM_RETRY, LM_NEXT, LM_STOP = 0, 1, 2
+STOP_ITERATIONS, STOP_QMAX, STOP_RHO_ZERO, STOP_SMALL_GAIN = 0, 1, 2, 3
+LM_CLAMP_EDGES = ((1 + (1 / 3) ** (1 / 3)) / 2, (1 + (2 / 3) ** (1 / 3)) / 2)       # rho at alpha = 2/3 and at alpha = 1/3
+LM_POW_BOUND = 3e-14          # 64 ulp of pow on p in [1/3, 2/3] through 1 - p: 64 * 2^-52 * p / (1 - p) <= 2.9e-14
+DBL_MAX = HUGE
+
+
+def lm_step_reference(item):
+    """optimization_algorithm_levenberg.cpp:123-168 and the test of optimize()'s loop on one item of ORBX_LINALG_LM_STEP, in double."""
+    f = np.float64
+    lam, ni, cur, ini = (f(v) for v in item[:4])
+    it, qmax, nbad = (int(v) for v in item[4:7])
+    temp, ok, scale_sum, max_iter = f(item[7]), item[8] != 0, f(item[9]), int(item[10])
+    with np.errstate(all="ignore"):
+        if not ok:
+            temp = f(DBL_MAX)
+        rho = (cur - temp) / (scale_sum + f(1e-3))
+        accepted = bool(rho > 0 and np.isfinite(temp))
+        if accepted:
+            alpha = f(1.0) - np.power(f(2.0) * rho - f(1.0), 3)
+            alpha = min(alpha, f(2.0) / f(3.0))
+            lam = lam * max(f(1.0) / f(3.0), alpha)
+            ni = f(2.0)
+            cur = temp
+        else:
+            lam = lam * ni
+            ni = ni * f(2.0)
+        qmax += 1
+        nxt, reason = LM_STOP, -1
+        if rho < 0 and qmax < 10:
+            nxt = LM_RETRY
+        else:
+            if qmax == 10:
+                reason = STOP_QMAX
+            elif rho == 0:
+                reason = STOP_RHO_ZERO
+            if reason < 0:
+                nbad = nbad + 1 if (ini - cur) * f(1e3) < ini else 0
+                if nbad >= 3:
+                    reason = STOP_SMALL_GAIN
+            it += 1
+            if reason < 0 and it < max_iter:
+                ini, qmax, nxt = cur, 0, LM_NEXT
+            elif reason < 0:
+                reason = STOP_ITERATIONS
+    return np.array([lam, ni, cur, ini, it, qmax, nbad, 1.0 if accepted else 0.0, nxt, reason], float), float(rho)
+
+
+@functools.lru_cache(None)
+def lm_step_cases():
+    """(name, item, expected) per branch and per side of every comparison of the rule.  expected: accepted, next, reason and,
+    where the clamp or the rejection decides it, the factor lambda takes (None: between the clamp edges, held to LM_POW_BOUND)."""
+    cases = []
+
+    def add(name, rho=None, temp=None, ok=1, scale_sum=0.5, lam=1e-3, ni=2.0, cur=1000.0, ini=None, it=0, qmax=0, nbad=0, max_iter=10,
+            accepted=None, nxt=None, reason=-1, factor=None):
+        if temp is None:
+            temp = cur - rho * (scale_sum + 1e-3)
+        ini = cur if ini is None else ini
+        cases.append((name, np.array([lam, ni, cur, ini, it, qmax, nbad, temp, ok, scale_sum, max_iter], float),
+                      dict(accepted=accepted, next=nxt, reason=reason, factor=factor)))
+
+    big = dict(cur=1000.0, ini=1000.0)      # a trial that gains far more than 1e-3 of iniChi needs a scale to match
+    for rho in (-2.0, 0.1, 0.5, 0.8, LM_CLAMP_EDGES[0] - 2e-3):
+        if rho > 0:
+            add("accepted, factor clamped to 2/3, rho %.4f" % rho, rho, scale_sum=500.0, accepted=1, nxt=LM_NEXT, factor=2 / 3, **big)
+    for rho in (LM_CLAMP_EDGES[1] + 2e-3, 0.95, 1.0, 5.0):
+        add("accepted, factor clamped to 1/3, rho %.4f" % rho, rho, scale_sum=100.0, accepted=1, nxt=LM_NEXT, factor=1 / 3, **big)
+    for rho in (0.85, 0.87, 0.9, 0.93):
+        add("accepted, between the clamp edges, rho %.2f" % rho, rho, scale_sum=300.0, accepted=1, nxt=LM_NEXT, **big)
+    add("accepted resets ni", 0.5, scale_sum=500.0, ni=16.0, accepted=1, nxt=LM_NEXT, factor=2 / 3)
+    # rho's sign: one ulp of the chi2 on either side, and zero
+    add("rho just above zero", temp=float(np.nextafter(1000.0, 0)), accepted=1, nxt=LM_NEXT, factor=2 / 3)
+    add("rho == 0", temp=1000.0, accepted=0, nxt=LM_STOP, reason=STOP_RHO_ZERO, factor=2.0)
+    add("rho just below zero", temp=float(np.nextafter(1000.0, np.inf)), accepted=0, nxt=LM_RETRY, factor=2.0)
+    add("rejected, ni 2 -> 4", -2.0, accepted=0, nxt=LM_RETRY, factor=2.0)
+    add("rejected, ni 8 -> 16", -2.0, ni=8.0, qmax=3, accepted=0, nxt=LM_RETRY, factor=8.0)
+    add("rejected, qmax 8 -> 9: retry", -2.0, qmax=8, accepted=0, nxt=LM_RETRY, factor=2.0)
+    add("rejected, qmax 9 -> 10: stop", -2.0, qmax=9, accepted=0, nxt=LM_STOP, reason=STOP_QMAX, factor=2.0)
+    add("accepted at qmax 9 -> 10: stop all the same", 0.5, scale_sum=500.0, qmax=9, accepted=1, nxt=LM_STOP, reason=STOP_QMAX, factor=2 / 3)
+    add("rho == 0 at qmax 9 -> 10: QMAX comes first", temp=1000.0, qmax=9, accepted=0, nxt=LM_STOP, reason=STOP_QMAX, factor=2.0)
+    # a failed solve: tempChi is DBL_MAX whatever the pass summed
+    add("solve failed", temp=3.0, ok=0, accepted=0, nxt=LM_RETRY, factor=2.0)
+    add("solve failed at qmax 9", temp=3.0, ok=0, qmax=9, accepted=0, nxt=LM_STOP, reason=STOP_QMAX, factor=2.0)
+    add("solve failed under a negative scale: DBL_MAX is finite and rho positive", temp=3.0, ok=0, scale_sum=-1.0, accepted=1, nxt=LM_NEXT,
+        factor=1 / 3)
+    # a chi2 that is not finite is never accepted
+    add("tempChi +inf: rho -inf", temp=np.inf, accepted=0, nxt=LM_RETRY, factor=2.0)
+    add("tempChi +inf under a negative scale: rho +inf", temp=np.inf, scale_sum=-1.0, accepted=0, nxt=LM_NEXT, factor=2.0)
+    add("tempChi -inf: rho +inf", temp=-np.inf, accepted=0, nxt=LM_NEXT, factor=2.0)
+    add("tempChi NaN: no comparison holds", temp=np.nan, accepted=0, nxt=LM_NEXT, factor=2.0)
+    add("tempChi NaN at qmax 9", temp=np.nan, qmax=9, accepted=0, nxt=LM_STOP, reason=STOP_QMAX, factor=2.0)
+    # Raul's criterion: (iniChi - curChi) * 1e3 < iniChi, three times in a row
+    small = dict(rho=0.5, scale_sum=1.0 - 1e-3, accepted=1, factor=2 / 3)      # gains 0.5 of 1000
+    add("small gain, nbadR 0 -> 1", nbad=0, nxt=LM_NEXT, **small)
+    add("small gain, nbadR 1 -> 2", nbad=1, nxt=LM_NEXT, **small)
+    add("small gain, nbadR 2 -> 3: stop", nbad=2, nxt=LM_STOP, reason=STOP_SMALL_GAIN, **small)
+    add("gain of exactly 1e-3 iniChi resets nbadR", temp=999.0, scale_sum=2.0 - 1e-3, nbad=2, accepted=1, nxt=LM_NEXT, factor=2 / 3)
+    add("gain just under 1e-3 iniChi counts", temp=float(np.nextafter(999.0, np.inf)), scale_sum=2.0 - 1e-3, nbad=1, accepted=1, nxt=LM_NEXT,
+        factor=2 / 3)
+    add("large gain resets nbadR", 0.5, scale_sum=500.0, nbad=2, accepted=1, nxt=LM_NEXT, factor=2 / 3)
+    add("rejected with rho NaN and a small gain counts too", temp=np.nan, nbad=2, accepted=0, nxt=LM_STOP, reason=STOP_SMALL_GAIN, factor=2.0)
+    # optimize()'s loop
+    add("iter reaches maxIter - 1", 0.5, scale_sum=500.0, it=3, max_iter=5, accepted=1, nxt=LM_NEXT, factor=2 / 3)
+    add("iter reaches maxIter", 0.5, scale_sum=500.0, it=4, max_iter=5, accepted=1, nxt=LM_STOP, reason=STOP_ITERATIONS, factor=2 / 3)
+    add("maxIter 1", 0.5, scale_sum=500.0, it=0, max_iter=1, accepted=1, nxt=LM_STOP, reason=STOP_ITERATIONS, factor=2 / 3)
+    add("small gain at the last iteration: SMALL_GAIN comes first", it=9, nbad=2, nxt=LM_STOP, reason=STOP_SMALL_GAIN, **small)
+    add("a retry leaves iter alone at the cap", -2.0, it=9, accepted=0, nxt=LM_RETRY, factor=2.0)
+    return tuple(cases)
+
+
+def lm_step_items():
+    return np.stack([c[1] for c in lm_step_cases()])
+
+
+def lm_step_check(out, what=""):
+    """The reference and (where stated) the expectation of every case against `out` [n][10]: everything exact except lambda between
+    the clamp edges, which is held to LM_POW_BOUND (relative)."""
+    for (name, item, exp), o in zip(lm_step_cases(), out):
+        ref, rho = lm_step_reference(item)
+        assert same_bits(o[1:], ref[1:]), (what, name, o.tolist(), ref.tolist())
+        assert (o[7], o[8], o[9]) == (exp["accepted"], exp["next"], exp["reason"]), (what, name, o.tolist())
+        if exp["factor"] is not None:
+            assert o[0].tobytes() == ref[0].tobytes() == np.float64(item[0] * exp["factor"]).tobytes(), (what, name, o[0], ref[0])
+            assert min(abs(rho - e) for e in LM_CLAMP_EDGES) >= 1e-3 or not exp["accepted"], (name, rho)
+        else:
+            assert LM_CLAMP_EDGES[0] + 1e-3 < rho < LM_CLAMP_EDGES[1] - 1e-3 and 1 / 3 < ref[0] / item[0] < 2 / 3, (name, rho)
+            assert abs(o[0] - ref[0]) <= LM_POW_BOUND * abs(ref[0]), (what, name, o[0], ref[0])

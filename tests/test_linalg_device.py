@@ -42,11 +42,11 @@ def test_symbol_exported_constants_mirrored_and_header_compiles_as_c99(tmp_path)
     assert hasattr(orbx.lib(), "orbx_debug_linalg")
     h = open(os.path.join(ROOT, "include", "orbx.h")).read()
     defs = {k: int(v) for k, v in re.findall(r"#define ORBX_LINALG_(\w+) (\d+)", h)}
-    assert len(defs) == 13 and defs.pop("OPS") == orbx.LINALG_OPS == 11 and defs.pop("MAX_ITEMS") == orbx.LINALG_MAX_ITEMS
-    assert sorted(defs.values()) == list(range(11)) and all(getattr(orbx, "LINALG_" + k) == v for k, v in defs.items())
+    assert len(defs) == 15 and defs.pop("OPS") == orbx.LINALG_OPS == 13 and defs.pop("MAX_ITEMS") == orbx.LINALG_MAX_ITEMS
+    assert sorted(defs.values()) == list(range(13)) and all(getattr(orbx, "LINALG_" + k) == v for k, v in defs.items())
     src = tmp_path / "abi.c"
     src.write_text('#include "orbx.h"\nint (*entry)(int, int, int, const void*, void*) = orbx_debug_linalg;\n'
-                   "typedef char a0[ORBX_LINALG_SUM16 + 1 == ORBX_LINALG_OPS ? 1 : -1];\nint main(void) { return 0; }\n")
+                   "typedef char a0[ORBX_LINALG_LM_STEP + 1 == ORBX_LINALG_OPS ? 1 : -1];\nint main(void) { return 0; }\n")
     subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Werror", "-Wall", "-I", os.path.join(ROOT, "include"), "-c", str(src),
                            "-o", str(tmp_path / "abi.o")])
     # the item sizes of the Python mirror are the kernels'
@@ -62,6 +62,7 @@ def test_debug_kernels_call_the_header_and_restate_nothing():
     assert '#include "orbx_linalg.h"' in hip
     for fn in ("rcp64", "rsqrt64", "jacobi_cs", "svd3", "null_vector4", "ldlt6<true>", "ldlt6<false>", "ldlt7", "null_vector_sym<NC>", "sum16"):
         assert "orbx::" + fn + "(" in hip, fn
+    assert '#include "orbx_optim.h"' in hip and "orbx::huber(" in hip and "orbx::lm_step(" in hip
     for word in ("__builtin_amdgcn_rcp", "__builtin_amdgcn_rsq", "__shfl", "sqrt("):
         assert word not in hip, word
     assert "orbx_api_linalg.hip" in open(os.path.join(CSRC, "Makefile")).read()
@@ -263,6 +264,45 @@ def test_sum16_reference_depends_on_the_order():
     for l in range(16):
         seq = seq + v.reshape(len(v), 4, 16)[:, :, l]
     assert (t[:, ::16] != seq).any() or (t[:, ::16] != serial).any()          # another order gives other bits somewhere
+
+
+def test_huber_items_and_reference():
+    """The items the shared Huber weight is pinned at, and the double restatement on them."""
+    items = lc.huber_items()
+    ref = lc.huber_reference(items)
+    assert {lc.DELTA_MONO, lc.DELTA_STEREO} == set(items[:, 2]) and lc.DELTA_MONO == float(np.float32(np.sqrt(5.991)))
+    for d in (lc.DELTA_MONO, lc.DELTA_STEREO):
+        at = {chi: r for (rob, chi, dd), r in zip(items, ref) if rob and dd == d and not np.isnan(chi)}
+        d2 = d * d
+        assert tuple(at[d2]) == (d2, 1.0) and tuple(at[float(np.nextafter(d2, 0))]) == (float(np.nextafter(d2, 0)), 1.0)      # not robustified
+        above = at[float(np.nextafter(d2, np.inf))]
+        assert above[1] < 1.0 or above[0] != float(np.nextafter(d2, np.inf))                                                      # the kernel's branch
+        assert tuple(at[0.0]) == (0.0, 1.0) and tuple(at[np.inf]) == (np.inf, 0.0)
+    nan = ref[np.isnan(items[:, 1]) & (items[:, 0] != 0)]
+    assert len(nan) == 2 and np.isnan(nan).all()                      # a NaN takes the kernel's branch: rho' is NaN, not 1
+    off = ref[(items[:, 0] == 0) & ~np.isnan(items[:, 1])]
+    assert (off[:, 1] == 1.0).all() and (off[:, 0] > lc.DELTA_MONO ** 2).all() and off[:, 0].max() == 1e12      # no kernel: the chi2 and the weight 1
+    assert lc.same_bits(ref, ref) and not lc.same_bits(ref, np.nextafter(ref, np.inf))
+
+
+def test_lm_step_cases_reach_every_branch_and_the_reference_meets_their_expectations():
+    cases = lc.lm_step_cases()
+    assert 35 <= len(cases) <= 48 and len({c[0] for c in cases}) == len(cases)
+    out = np.stack([lc.lm_step_reference(item)[0] for _, item, _ in cases])
+    lc.lm_step_check(out, "reference")
+    seen = {(int(o[7]), int(o[8]), int(o[9])) for o in out}
+    for accepted in (0, 1):
+        for verdict in ((lc.LM_NEXT, -1), (lc.LM_STOP, lc.STOP_QMAX), (lc.LM_STOP, lc.STOP_SMALL_GAIN)):
+            assert (accepted,) + verdict in seen, (accepted, verdict)
+    assert {(0, lc.LM_RETRY, -1), (0, lc.LM_STOP, lc.STOP_RHO_ZERO), (1, lc.LM_STOP, lc.STOP_ITERATIONS)} <= seen
+    assert sum(1 for c in cases if c[2]["factor"] is None) == 4
+    assert sorted({o[6] for o in out}) == [0.0, 1.0, 2.0, 3.0] and {9.0, 10.0} <= {o[5] for o in out}
+    # a result one ulp off in lambda, or off by one in a counter, is seen
+    for col, delta in ((0, None), (1, 2.0), (4, 1.0), (5, 1.0), (6, 1.0), (8, 1.0)):
+        bad = out.copy()
+        bad[3, col] = np.nextafter(bad[3, col], np.inf) if delta is None else bad[3, col] + delta
+        with pytest.raises(AssertionError):
+            lc.lm_step_check(bad, "mutated")
 
 
 # ------------------------------------------------------------------------------------------------ the device
@@ -483,3 +523,29 @@ def test_the_last_item_of_a_part_filled_wave_is_computed_and_nothing_past_it_is_
         out = np.full(66, 7.0)
         assert orbx.lib().orbx_debug_linalg(0, orbx.LINALG_RCP64, n, orbx._p(x), orbx._p(out)) == 0
         assert (out[n:] == 7.0).all() and np.abs(out[:n] * x[:n] - 1).max() <= 4 * EPS, n
+
+
+@pytest.mark.gpu
+def test_huber(gpu):
+    """csrc/orbx_optim.h's huber, bit for bit the double restatement: every operation of both sides is correctly rounded."""
+    items = lc.huber_items()
+    out = orbx.debug_linalg(orbx.LINALG_HUBER, items, 7.0)
+    ref = lc.huber_reference(items)
+    for it, o, r in zip(items, out, ref):
+        print("huber(robust %d, chi2 %r, delta %r) -> %r, %r" % (it[0], float(it[1]), float(it[2]), float(o[0]), float(o[1])))
+        assert lc.same_bits(o, r), (it.tolist(), o.tolist(), r.tolist())
+
+
+@pytest.mark.gpu
+def test_lm_step(gpu):
+    """csrc/orbx_optim.h's lm_step on one item per branch and per side of every comparison: the state and the verdict exact, lambda
+    exact wherever the clamp or a rejection decides it and within linalg_cases.LM_POW_BOUND between the clamp edges."""
+    items = lc.lm_step_items()
+    out = orbx.debug_linalg(orbx.LINALG_LM_STEP, items, 7.0)
+    assert out.tobytes() == orbx.debug_linalg(orbx.LINALG_LM_STEP, items, 7.0).tobytes()
+    for (name, item, exp), o in zip(lc.lm_step_cases(), out):
+        ref = lc.lm_step_reference(item)[0]
+        if exp["factor"] is None:
+            print("%s: lambda %r, reference %r, relative difference %.3g of %.3g" % (name, float(o[0]), float(ref[0]),
+                                                                                    abs(o[0] - ref[0]) / abs(ref[0]), lc.LM_POW_BOUND))
+    lc.lm_step_check(out, "device")
