@@ -432,7 +432,11 @@ int orbx_bow_download(orbx_extractor* ex, int image, uint32_t* word_ids, double*
  * concatenated for two-camera rigs), mDescriptors and kf_valid[i] = (vpMapPointsKF[i] && !isBad()); f_* = F.mFeatVec,
  * F's keypoints and descriptors, n_left_f = F.Nleft (-1 for monocular / rectified frames).  matches[i] = index of the
  * keyframe feature whose map point F's feature i received, or -1 (vpMapPointMatches).  nnratio = mfNNratio,
- * check_orientation = mbCheckOrientation.  Returns nmatches or a negative error. */
+ * check_orientation = mbCheckOrientation.  Returns nmatches or a negative error.
+ * Limit: a vocabulary node that both feature vectors contain may hold at most 4096 features of F (their "already matched"
+ * marks are kept on chip; a node of ORBvoc.txt at levelsup 4 holds about 15 of a 1500-feature frame).  A larger one is refused
+ * with ORBX_E_UNSUPPORTED -- there is no slower path -- and every entry of matches is then -1.  A node of any size that
+ * pKF does not have is never looked at.  pKF's side of a node has no limit. */
 int orbx_search_by_bow(int device, const uint32_t* kf_node_ids, const int32_t* kf_node_start, const uint32_t* kf_feature_idx,
                        int n_kf_nodes, const orbx_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_valid, int n_kf,
                        const uint32_t* f_node_ids, const int32_t* f_node_start, const uint32_t* f_feature_idx, int n_f_nodes,
@@ -444,7 +448,9 @@ int orbx_search_by_bow(int device, const uint32_t* kf_node_ids, const int32_t* k
  * kf_feature_idx / kf_kps / kf_desc / kf_valid [n_frames][kf_stride](x 32) with n_kf_nodes[f] / n_kf[f] valid entries.
  * matches is [n_frames][cap] (cap = orbx_batch_results_device's cap; -1 past a frame's keypoints), n_matches [n_frames].
  * Every kernel runs ONCE for all pairs (blockIdx.y = pair); results are those of n_frames separate calls.
- * Returns the total number of matches or a negative error. */
+ * Returns the total number of matches or a negative error.  The limit of 4096 frame features per shared vocabulary node holds
+ * for every pair: if one pair exceeds it the call returns ORBX_E_UNSUPPORTED, every entry of matches (all pairs) is -1 and
+ * n_matches[f] is -1 for the pairs over the limit and 0 for the others. */
 int orbx_search_by_bow_batch(orbx_extractor* ex, int first_image, int n_frames, const uint32_t* kf_node_ids,
                              const int32_t* kf_node_start, const int32_t* n_kf_nodes, int nodes_stride,
                              const uint32_t* kf_feature_idx, const orbx_keypoint* kf_kps, const uint8_t* kf_desc,
@@ -681,7 +687,9 @@ int orbx_search_for_triangulation_rig(int device, const uint32_t* node_ids1, con
  * (vpMapPoints[i] && !vpMapPoints[i]->isBad() && !(NLeft != -1 && i >= mvKeysUn.size())) (:799-806,:817-825).  matches12[idx1] =
  * the feature of pKF2 whose map point vpMatches12[idx1] receives, or -1: per vocabulary node, pKF1's features in list order, best
  * and second best over the partner node's features that are valid and not taken yet (vbMatched2), accepted if bestDist1 < TH_LOW
- * (strict) and bestDist1 < nnratio * bestDist2; then the rotation-consistency cull.  Returns nmatches or a negative error. */
+ * (strict) and bestDist1 < nnratio * bestDist2; then the rotation-consistency cull.  Returns nmatches or a negative error.
+ * Limit: a vocabulary node that both key frames contain may hold at most 4096 features of pKF2 (valid or not); a larger one is
+ * refused with ORBX_E_UNSUPPORTED and every entry of matches12 is then -1.  pKF1's side of a node has no limit. */
 int orbx_search_by_bow_keyframes(int device, const uint32_t* node_ids1, const int32_t* node_start1, const uint32_t* feature_idx1,
                                  int n_nodes1, const orbx_keypoint* kps1, const uint8_t* desc1, const uint8_t* valid1, int n1,
                                  const uint32_t* node_ids2, const int32_t* node_start2, const uint32_t* feature_idx2, int n_nodes2,

@@ -252,7 +252,10 @@ int orbx_search_by_bow(int device, const uint32_t* kf_node_ids, const int32_t* k
   int n = 0;
   if (e == hipSuccess) e = fetch_result(pk, oOut, n_f, matches, &n);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  if (n < 0) return fail(ORBX_E_UNSUPPORTED, "a vocabulary node holds more than 4096 frame features");
+  if (n < 0) {  // the other nodes' waves have written their matches by now: the caller gets none of them
+    for (int i = 0; i < n_f; i++) matches[i] = -1;
+    return fail(ORBX_E_UNSUPPORTED, "a vocabulary node holds more than 4096 frame features");
+  }
   return n;
 }
 
@@ -344,7 +347,11 @@ int orbx_search_by_bow_batch(orbx_extractor* ex, int first_image, int n_frames, 
       }
   }
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));
-  if (tooLarge) return fail(ORBX_E_UNSUPPORTED, "a vocabulary node holds more than 4096 frame features");
+  if (tooLarge) {  // no partial results: every pair's matches are -1, n_matches tells which pairs were over the limit
+    for (size_t i = 0; i < (size_t)F * cap; i++) matches[i] = -1;
+    for (int f = 0; f < F; f++) n_matches[f] = n_matches[f] < 0 ? -1 : 0;
+    return fail(ORBX_E_UNSUPPORTED, "a vocabulary node holds more than 4096 frame features");
+  }
   return total;
 }
 

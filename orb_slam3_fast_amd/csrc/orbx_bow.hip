@@ -231,7 +231,9 @@ hipError_t launch_bow_transform(const BowArgs& a, int nimg, hipStream_t s) {
 // (the "already matched" gate makes that walk order dependent); its lanes score the node's frame features, best / second
 // by the serial rule (first minimum; an equal later distance becomes the second).  The right-eye branch keeps the
 // reference's "|| true" (:363-365): no ratio test, and only inside "bestDist1 <= TH_LOW".
-constexpr int kBowNodeCap = 4096;  // frame features of one node tracked in LDS (a node above this: serial fallback on lane 0)
+// kBowNodeCap: the scored features of one node whose "taken" marks fit in LDS.  A shared node above it raises flags[32], the
+// result word becomes -1 and the entries refuse the call with ORBX_E_UNSUPPORTED (there is no slower path; include/orbx.h).
+constexpr int kBowNodeCap = 4096;
 // Kernel-argument views: the one-shot call passes its argument block by value; orbx_search_by_bow_batch (round 5) launches every
 // kernel ONCE for all frames of an extraction batch with blockIdx.y = frame and the argument blocks in a device array.
 struct BowVal {
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(64) void k_bow_match(R ar) {
   if (lo >= a.nFNodes || a.fNodes[lo] != node) return;
   const int f0 = a.fStart[lo], nfl = a.fStart[lo + 1] - f0;
   const int k0 = a.kfStart[ia], k1 = a.kfStart[ia + 1];
-  if (nfl > kBowNodeCap) {  // never with a real vocabulary (levelsup 4 of 6: 100 nodes); keep the exact semantics anyway
+  if (nfl > kBowNodeCap) {  // never with a real vocabulary (levelsup 4 of 6: 100 nodes): the call is refused
     if (lane == 0) a.flags[32] = 1;
     return;
   }
