@@ -2018,6 +2018,11 @@ int orbx_debug_octree_plan(const orbx_params* p, int width, int height, int32_t*
  * k_stereo_sort launch in front --, larger ones the row-sorted form.  Default 1 (the single-frame path); 0 = never; < 0
  * restores the default.  Environment: ORBX_STEREO_DIRECT_PAIRS. */
 void orbx_debug_set_stereo_direct(int max_pairs);
+/* Test hook of k_stereo_sort: what the row-sorted form of the handle's last association left for `pair` -- row_start
+ * [2][height + 1] (CSR row tables of the left and the right eye), records [2][cap][4] ({x, y, octave | index << 8,
+ * minr | maxr << 16}) and descriptors [2][cap][8], the first `cap` sorted slots of each eye.  Returns the slots per image of
+ * the sorted arrays (cap may not exceed it).  The direct form does not write these arrays.  Synchronises the stream. */
+int orbx_debug_stereo_sort(orbx_extractor* left, int pair, int32_t* row_start, uint32_t* records, uint32_t* descriptors, int cap);
 /* Test hook of orbx_clahe's two apply forms (cv::CLAHE::apply, Examples/Stereo/stereo_tum_vi.cc:100,142-143): 1 (default) = one
  * workgroup per interpolation cell with the cell's table in LDS where the geometry allows it, 0 = the per-pixel table gathers
  * everywhere. */

@@ -227,6 +227,8 @@ def lib():
             L.orbx_debug_octree_plan.argtypes = [vp, i, i, vp, vp]
         L.orbx_debug_set_stereo_direct.argtypes = [i]
         L.orbx_debug_set_stereo_direct.restype = None
+        if hasattr(L, "orbx_debug_stereo_sort"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
+            L.orbx_debug_stereo_sort.argtypes = [vp, i, vp, vp, vp, i]
         L.orbx_debug_set_clahe_cell_kernel.argtypes = [i]
         L.orbx_debug_set_clahe_cell_kernel.restype = None
         L.orbx_debug_upload_results.argtypes = [vp, i, vp, vp, i, i]

@@ -1799,6 +1799,24 @@ int orbx_debug_upload_results(orbx_extractor* ex, int image, const orbx_keypoint
   return ORBX_OK;
 }
 
+int orbx_debug_stereo_sort(orbx_extractor* left, int pair, int32_t* row_start, uint32_t* records, uint32_t* descriptors, int cap) {
+  if (!left || pair < 0 || pair >= left->lastStereoPairs)
+    return fail(ORBX_E_BADARG, "no such pair in the stereo association run since the handle's last extraction");
+  if (!row_start || !records || !descriptors) return fail(ORBX_E_BADARG, "null argument");
+  HIPC(hipSetDevice(left->device));
+  HIPC(hipStreamSynchronize(left->stream));
+  // (the strides of enqueue_stereo_match: imgH + 1 rows, max(capL, capR) slots; stereoPairs was sized with the right handle's too)
+  const size_t rows = (size_t)left->curH + 1, slots = left->d_srec.n / ((size_t)left->stereoPairs * 2);
+  if (cap < 0 || (size_t)cap > slots) return fail(ORBX_E_BADARG, "cap outside the sorted arrays' slots per image");
+  HIPC(hipMemcpy(row_start, left->d_rowStart.p + (size_t)pair * 2 * rows, 2 * rows * sizeof(int), hipMemcpyDeviceToHost));
+  for (int eye = 0; eye < 2 && cap > 0; eye++) {
+    const size_t img = (size_t)pair * 2 + eye;
+    HIPC(hipMemcpy(records + (size_t)eye * cap * 4, left->d_srec.p + img * slots, (size_t)cap * 16, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(descriptors + (size_t)eye * cap * 8, left->d_sdesc.p + img * slots * 2, (size_t)cap * 32, hipMemcpyDeviceToHost));
+  }
+  return (int)slots;
+}
+
 int orbx_fisheye_results_device(const orbx_extractor* left, const int32_t** d_left_to_right, const int32_t** d_right_to_left,
                                 const float** d_depth, const float** d_points3d, const int32_t** d_counts) {
   if (!left || left->fisheyePairs == 0) return fail(ORBX_E_BADARG, "no fisheye association has been run on this handle");

@@ -1,7 +1,5 @@
 // orbx_stereo.hip — association kernels of liborbx: Frame::ComputeStereoMatches (src/Frame.cc:921-1084), BFMatcher kNN-2
 // (:1293-1302) and ComputeStereoFishEyeMatches with the KannalaBrandt8 triangulation (:1273-1331).
-#include <mutex>
-
 #include "orbx_matching.h"
 #include "orbx_linalg.h"
 #include "orbx_kb8.h"
@@ -10,12 +8,25 @@ namespace orbx {
 
 // ================================================================================================ stereo
 
+__device__ __forceinline__ uint32_t stereo_right_band(float x, float y, int oct, const float* lvS) {  // minr | maxr << 16 (:943-948)
+  const float r = __fmul_rn(2.0f, lvS[oct]);
+  int maxr = (int)ceilf(__fadd_rn(y, r));
+  const int minr = (int)floorf(__fsub_rn(y, r));
+  if (y == 0.0f && x == 0.0f) maxr = -1;
+  return ((uint32_t)minr & 0xFFFFu) | ((uint32_t)maxr << 16);
+}
 // Both eyes' keypoints sorted by integer row (counting sort, one block per (pair, eye)): the analogue of the reference's
 // vRowIndices table (src/Frame.cc:930-949).  Next to the CSR row table the block writes what the matcher reads, in row
 // order: one 16-byte record per keypoint {x, y, octave | index << 8, minr | maxr << 16} -- [minr, maxr] = the +-2*scale row
 // band of a RIGHT keypoint (:944-948); maxr = -1 marks the (0,0) points the reference skips (:943) -- and its descriptor.
 // A band of left rows then finds its own keypoints and its candidates as two contiguous, coalesced ranges.
-constexpr int kSortNT = 512, kSortItems = 4;  // register-resident path: up to 2048 keypoints per image
+// The row histogram (2.9 KB at 720 rows) is all the LDS there is: every keypoint goes straight from k_describe's arrays (in
+// L2) to its sorted slot, three scattered 16-byte stores.  Rounds 3 - 10 permuted the payloads through 96 KB of LDS to store
+// linearly: 10.2 us alone against 9.1, but a 101 KB workgroup fits on no CU beside k_detect's cells (134 KB of 160), and under
+// four handles the launch waited 43 - 52 us for one to drain (now 18).  A u16 index permutation in LDS with a gather behind it
+// (7 KB, linear stores) costs a third memory round trip: 12.5 us alone, 22 under four handles
+// (profiles/stereo_sort_lds/variants.txt).
+constexpr int kSortNT = 512;
 __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   int* hist = reinterpret_cast<int*>(smem);  // imgH + 1 counters, then running offsets
@@ -36,36 +47,13 @@ __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
   int* rowStart = a.rowStart + (long long)(pair * 2 + eye) * (a.imgH + 1);
   uint4* rec = a.srec + (long long)(pair * 2 + eye) * a.cap;
   uint4* sd = a.sdesc + (long long)(pair * 2 + eye) * a.cap * 2;
-  // everything the scatter needs is requested up front, beside the load of n (one memory round trip for the whole kernel
-  // when n <= 2048)
   __shared__ float lvS[ORBX_MAX_LEVELS];
   if (tid < g.nlevels) lvS[tid] = g.lv[tid].scale;
-  float kx[kSortItems], ky[kSortItems];
-  int ko[kSortItems];
-  uint4 kd0[kSortItems], kd1[kSortItems];
-  {
-#pragma unroll
-    for (int j = 0; j < kSortItems; j++) {
-      const int i = min(tid + j * kSortNT, cap - 1);  // (entries past n are inside the buffer and never used)
-      kx[j] = kp[i].x;
-      ky[j] = kp[i].y;
-      ko[j] = kp[i].octave;
-      kd0[j] = dsc[2 * i];
-      kd1[j] = dsc[2 * i + 1];
-    }
-  }
   SS_MK();
   for (int r = tid; r <= a.imgH; r += kSortNT) hist[r] = 0;
-  const bool inRegs = n <= kSortNT * kSortItems;
   __syncthreads();
   auto row_of = [&](float y) { return min(max((int)y, 0), a.imgH - 1); };
-  if (inRegs) {
-#pragma unroll
-    for (int j = 0; j < kSortItems; j++)
-      if (tid + j * kSortNT < n) atomicAdd(&hist[row_of(ky[j])], 1);
-  } else {
-    for (int i = tid; i < n; i += kSortNT) atomicAdd(&hist[row_of(kp[i].y)], 1);
-  }
+  for (int i = tid; i < n; i += kSortNT) atomicAdd(&hist[row_of(kp[i].y)], 1);
   SS_MK();
   __syncthreads();
   SS_MK();
@@ -88,61 +76,26 @@ __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
   SS_MK();
   __syncthreads();
   SS_MK();
-  // the permutation happens in LDS (when n <= 2048): 16-byte stores scattered over global memory, three per keypoint, were
-  // half of the kernel's time; the sorted arrays then leave as linear, coalesced copies
-  uint4* srecL = reinterpret_cast<uint4*>(smem + (((size_t)(a.imgH + 2) * 4 + 15) & ~(size_t)15));  // [kSortNT * kSortItems]
-  uint4* sdL = srecL + kSortNT * kSortItems;                                                          // [.. * 2]
-  auto emit = [&](int i, float x, float y, int oct, const uint4& d0, const uint4& d1, uint4* orec, uint4* odesc) {
-    const int pos = atomicAdd(&hist[row_of(y)], 1);
-    const float r = __fmul_rn(2.0f, lvS[oct]);
-    int maxr = (int)ceilf(__fadd_rn(y, r)), minr = (int)floorf(__fsub_rn(y, r));
-    if (y == 0.0f && x == 0.0f) maxr = -1;
-    orec[pos] = make_uint4(__float_as_uint(x), __float_as_uint(y), (uint32_t)oct | ((uint32_t)i << 8),
-                           ((uint32_t)minr & 0xFFFFu) | ((uint32_t)maxr << 16));
-    odesc[2 * pos] = d0;
-    odesc[2 * pos + 1] = d1;
-  };
-  if (inRegs) {
-#pragma unroll
-    for (int j = 0; j < kSortItems; j++)
-      if (tid + j * kSortNT < n) emit(tid + j * kSortNT, kx[j], ky[j], ko[j], kd0[j], kd1[j], srecL, sdL);
-    __syncthreads();
-    for (int i = tid; i < n; i += kSortNT) rec[i] = srecL[i];
-    for (int i = tid; i < 2 * n; i += kSortNT) sd[i] = sdL[i];
-  } else {
-    for (int i = tid; i < n; i += kSortNT) {
-      const orbx_keypoint k = kp[i];
-      emit(i, k.x, k.y, k.octave, dsc[2 * i], dsc[2 * i + 1], rec, sd);
-    }
+  for (int i = tid; i < n; i += kSortNT) {
+    const orbx_keypoint k = kp[i];
+    const int pos = atomicAdd(&hist[row_of(k.y)], 1);
+    rec[pos] = make_uint4(__float_as_uint(k.x), __float_as_uint(k.y), (uint32_t)k.octave | ((uint32_t)i << 8),
+                          stereo_right_band(k.x, k.y, k.octave, lvS));
+    sd[2 * pos] = dsc[2 * i];
+    sd[2 * pos + 1] = dsc[2 * i + 1];
   }
   SS_MK();
 #ifdef ST_PROF
   if (tid == 0 && blockIdx.x == 9) {
     printf("k_stereo_sort n %d:", n);
     for (int i = 1; i < nsq; i++) printf(" %d", (int)(sq[i] - sq[i - 1]));
-    printf("  (x10 ns: issue loads | zero+hist | bar | scan | bar | scatter)\n");
+    printf("  (x10 ns: level table | zero+hist | bar | scan | bar | scatter)\n");
   }
 #endif
 }
 
 hipError_t launch_stereo_sort(const Geom& g, const StereoArgs& a, int npairs, hipStream_t s) {
-  const size_t lds = (((size_t)(a.imgH + 2) * 4 + 15) & ~(size_t)15) + (size_t)kSortNT * kSortItems * 48;
-  // > 64 KB of dynamic LDS needs the attribute, and the attribute is PER DEVICE (a process may hold handles on several GPUs):
-  // one flag per device, set under a lock (two threads call the matcher concurrently)
-  {
-    static std::mutex mu;
-    static bool prepared[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev < 0 || dev >= 64 || !prepared[dev]) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_stereo_sort), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) prepared[dev] = true;
-    }
-  }
-  hipLaunchKernelGGL(k_stereo_sort, dim3(2 * npairs), dim3(kSortNT), lds, s, g, a);
+  hipLaunchKernelGGL(k_stereo_sort, dim3(2 * npairs), dim3(kSortNT), (size_t)(a.imgH + 1) * sizeof(int), s, g, a);
   return hipGetLastError();
 }
 
@@ -281,13 +234,6 @@ __device__ __forceinline__ void stereo_filter_pair(const StereoArgs& a, int pair
 // the unique keys (dist, iR), results are written by iL.  In a 0.2 ms frame the sort was 7.6 us of dependent launch; in a batch
 // it is shared by the pair's 30 workgroups and stays.
 constexpr int kStereoSelCap = 4096;  // per-image keypoint capacity the direct form's index lists hold
-__device__ __forceinline__ uint32_t stereo_right_band(float x, float y, int oct, const float* lvS) {  // minr | maxr << 16 (:943-948)
-  const float r = __fmul_rn(2.0f, lvS[oct]);
-  int maxr = (int)ceilf(__fadd_rn(y, r));
-  const int minr = (int)floorf(__fsub_rn(y, r));
-  if (y == 0.0f && x == 0.0f) maxr = -1;
-  return ((uint32_t)minr & 0xFFFFu) | ((uint32_t)maxr << 16);
-}
 // Workgroups behind the last band (direct form, rp.hKps != nullptr): the single-frame entry's gather of both eyes' keypoints and
 // descriptors into the page-locked result block (k_result_pack's sections 0 - 3, orbx_kernels.hip) -- 180 KB of PCIe writes that do
 // not depend on the association and so leave beside it instead of behind it, in the frame's last launch.
