@@ -2085,7 +2085,7 @@ int orbx_debug_score_level(orbx_extractor* ex, int image, int level, uint8_t* ds
 /* The device's sinf / cosf of the descriptor steering (computeOrbDescriptor, src/ORBextractor.cc:106-107: libm cosf / sinf;
  * csrc/orbx_sincos.h restates glibc's two x86-64 ifunc variants): evaluates n angles (radians, host arrays) with the FMA
  * (fused == 1) or the SSE2 variant (fused == 0), or with k_describe's own branch-free restatement of the FMA variant
- * (fused == 2: glibc_sincosf_sel, csrc/orbx_kernels.hip -- the form the product runs; the other two are its definition).  tests/
+ * (fused == 2: glibc_sincosf_sel, csrc/orbx_describe.hip -- the form the product runs; the other two are its definition).  tests/
  * compare all three with the host's libm bit for bit. */
 int orbx_debug_sincos(int device, const float* angles, int n, int fused, float* sin_out, float* cos_out);
 /* The device's cv::fastAtan2 of IC_Angle (src/ORBextractor.cc:98) in the branch-free form k_describe calls (fast_atan2_sel): n

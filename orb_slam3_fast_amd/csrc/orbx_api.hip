@@ -1,6 +1,6 @@
 // orbx_api.hip — C ABI of liborbx (include/orbx.h): handles, buffers, geometry, launch sequencing.
 // Host-side restatement of the ORBextractor constructor tables (src/ORBextractor.cc:408-469) and of the
-// OpenCV resize coefficient tables; all pixel/bit work is in orbx_kernels.hip.
+// OpenCV resize coefficient tables; all pixel/bit work is in the kernel files (stage map: orbx_kernels.hip).
 #include "orbx_host.h"
 #include "orbx_rgbd.h"
 
@@ -391,7 +391,7 @@ void build_tail_plans(const Geom& g, const std::vector<int>& yofs, std::vector<T
   plans.clear();
   bands.clear();
   static const bool envRead = [] {  // diagnostic knob, same meaning as the hook: ORBX_RESIZE_TAIL=first[,levels[,rows]]
-    if (const char* e = getenv("ORBX_RESIZE_TAIL")) {
+    if (const char* e = env_str("ORBX_RESIZE_TAIL")) {
       int a = -1, b = 0, c = 0;
       if (sscanf(e, "%d,%d,%d", &a, &b, &c) >= 1) {
         g_tail_first = a;
@@ -440,14 +440,14 @@ void build_latency_plans(const Geom& g, const std::vector<int>& yofs, std::vecto
   plans.clear();
   bands.clear();
   static const bool envRead = [] {
-    if (const char* e = getenv("ORBX_LAT_TAIL")) {
+    if (const char* e = env_str("ORBX_LAT_TAIL")) {
       int a = -1, b = 0;
       if (sscanf(e, "%d,%d", &a, &b) >= 1) {
         g_lat_levels = a;
         if (b > 0) g_lat_rows = b;
       }
     }
-    if (const char* e = getenv("ORBX_LAT_MAX_IMAGES")) g_lat_max_images = atoi(e);
+    g_lat_max_images = env_int("ORBX_LAT_MAX_IMAGES", g_lat_max_images);
     return true;
   }();
   (void)envRead;
@@ -657,7 +657,7 @@ int enqueue_extract(orbx_extractor* ex, const uint8_t* d_images, int n, int w, i
   // SLOWER than the plain launches -- one 1280x720 eye 0.487 vs 0.310 ms, a stereo frame 0.823 vs 0.711 ms (640x480:
   // 0.263 vs 0.247 ms per eye) -- so it stays off by default.  Never used while profiling (the stage events are not
   // captured) nor for device batches (their image pointer is the caller's and changes from call to call).
-  static const bool useGraph = getenv("ORBX_GRAPH") && atoi(getenv("ORBX_GRAPH")) != 0;
+  static const bool useGraph = env_int("ORBX_GRAPH", 0) != 0;
   if (useGraph && n == 1 && d_images == ex->d_stage.p && !ex->profiling && !ex->graphOff) {
     if (ex->graphW != w || ex->graphH != h) {
       drop_graphs(ex);
@@ -705,7 +705,7 @@ int record_pipeline(orbx_extractor* ex, int n, bool lapTrivial, bool capturing, 
   // k_detect fills every VALU of the chip by itself: two of them side by side (two handles in flight) only stretch
   // each other.  A per-device token orders the k_detect launches of all handles one after the other, while each still
   // overlaps the other handles' quadtree / describe / stereo / resize work.
-  static const bool noToken = getenv("ORBX_NO_DETECT_TOKEN") && atoi(getenv("ORBX_NO_DETECT_TOKEN")) != 0;   // measurement aid
+  static const bool noToken = env_int("ORBX_NO_DETECT_TOKEN", 0) != 0;   // measurement aid
   // (a graph cannot wait on it; a launch of one or two images does not fill the chip: no ordering, no event record between
   // k_detect and k_octree of a single frame)
   DetectToken* tok = (!capturing && !noToken && n > g_lat_max_images) ? detect_token(ex->device) : nullptr;
@@ -1041,7 +1041,7 @@ static size_t host_pyr_image_bytes(const orbx_extractor* ex) {
 // copy of the pyramid is kept -- the event its copies wait for, then k_detect .. k_describe.  (The hipGraph replay of
 // ORBX_GRAPH=1 keeps the plain order of enqueue_extract; its host copies start behind the frame's last kernel.)
 static int enqueue_frame(orbx_extractor* ex, int n, bool lapTrivial, const int32_t* lap) {
-  static const bool useGraph = getenv("ORBX_GRAPH") && atoi(getenv("ORBX_GRAPH")) != 0;
+  static const bool useGraph = env_int("ORBX_GRAPH", 0) != 0;
   hipStream_t st = ex->stream;
   if (ex->keepHostPyr && !ex->evPyr) HIPC(hipEventCreateWithFlags(&ex->evPyr, hipEventDisableTiming));
   if (useGraph && n == 1) {
@@ -1091,25 +1091,20 @@ static int enqueue_host_pyramid(orbx_extractor* ex, int nimg, hipEvent_t after, 
   // levels 1.. : one DMA copy per image of its block of the device pyramid (4 MB per 1280x720 stereo frame: the ~100 us
   // between the pyramid and the frame's last kernel are just enough for them on a PCIe 5 x16 link).  The HOST waits for the
   // pyramid event (polling: it has nothing else to do until the frame's synchronisation) and then issues the copies --
-  // a hipStreamWaitEvent on the copy stream was resolved ~90 us late by this runtime (the copies started when the frame's
-  // kernels were over: +82 us per frame, profiles/r5b_host_pyramid.txt).
-  static const bool streamWait = getenv("ORBX_PYR_STREAM_WAIT") != nullptr;  // (the measured alternative)
-  if (streamWait) {
-    HIPC(hipStreamWaitEvent(ex->streamPyr, after, 0));
-  } else {
-    // bounded poll: ~200 us of polling with a pause between the queries -- four frames' worth of kernels --, then
-    // the blocking wait (a wedged stream must not spin a core forever; two eye threads poll at once in the reference's flow)
-    hipError_t q = hipErrorNotReady;
-    const auto tp0 = std::chrono::steady_clock::now();
-    for (unsigned spin = 1; (q = hipEventQuery(after)) == hipErrorNotReady; spin++) {
-      cpu_pause();
-      if ((spin & 63u) == 0 && std::chrono::steady_clock::now() - tp0 > std::chrono::microseconds(200)) {
-        q = hipEventSynchronize(after);
-        break;
-      }
+  // a hipStreamWaitEvent on the copy stream, the measured alternative (removed, see HISTORY.md), was resolved ~90 us late by this
+  // runtime (the copies started when the frame's kernels were over: +82 us per frame, profiles/r5b_host_pyramid.txt).
+  // bounded poll: ~200 us of polling with a pause between the queries -- four frames' worth of kernels --, then
+  // the blocking wait (a wedged stream must not spin a core forever; two eye threads poll at once in the reference's flow)
+  hipError_t q = hipErrorNotReady;
+  const auto tp0 = std::chrono::steady_clock::now();
+  for (unsigned spin = 1; (q = hipEventQuery(after)) == hipErrorNotReady; spin++) {
+    cpu_pause();
+    if ((spin & 63u) == 0 && std::chrono::steady_clock::now() - tp0 > std::chrono::microseconds(200)) {
+      q = hipEventSynchronize(after);
+      break;
     }
-    if (q != hipSuccess) return fail(ORBX_E_HIP, std::string("pyramid event: ") + hipGetErrorString(q));
   }
+  if (q != hipSuccess) return fail(ORBX_E_HIP, std::string("pyramid event: ") + hipGetErrorString(q));
   for (int i = 0; i < nimg; i++)
     if (restBytes)
       HIPC(hipMemcpyAsync(ex->hostPyrAll + (size_t)i * per + restDst, ex->pyr.pyr + (long long)i * g.pyrImg + restOff, restBytes,
@@ -1293,14 +1288,8 @@ int orbx_extract_stereo(orbx_extractor* ex, const uint8_t* img_left, const uint8
   bool lapTrivial = true;
   rc = prepare_extract(ex, ex->d_stage.p, 2, w, h, pitch, (ptrdiff_t)imgBytes, lap, lapTrivial);
   if (rc != ORBX_OK) return rc;
-  static const bool copy1d = getenv("ORBX_UPLOAD_1D") != nullptr;   // measurement aid
-  if (copy1d && stride_left == w && stride_right == w && pitch == w) {
-    HIPC(hipMemcpyAsync(ex->d_stage.p, img_left, imgBytes, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(ex->d_stage.p + imgBytes, img_right, imgBytes, hipMemcpyHostToDevice, st));
-  } else {
-    HIPC(hipMemcpy2DAsync(ex->d_stage.p, pitch, img_left, stride_left, w, h, hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpy2DAsync(ex->d_stage.p + imgBytes, pitch, img_right, stride_right, w, h, hipMemcpyHostToDevice, st));
-  }
+  HIPC(hipMemcpy2DAsync(ex->d_stage.p, pitch, img_left, stride_left, w, h, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpy2DAsync(ex->d_stage.p + imgBytes, pitch, img_right, stride_right, w, h, hipMemcpyHostToDevice, st));
   rc = enqueue_frame(ex, 2, lapTrivial, lap);
   if (rc != ORBX_OK) return rc;
   const bool stereo = bf > 0.f;   // (uright / depth NULL: the results stay in the host block, orbx_host_results)
@@ -1334,15 +1323,14 @@ int orbx_extract_stereo(orbx_extractor* ex, const uint8_t* img_left, const uint8
     rc = enqueue_host_pyramid(ex, 2, ex->evPyr, hi, hs);
     if (rc != ORBX_OK) return rc;
   }
-  static const bool latTimes = getenv("ORBX_LAT_TIMES") != nullptr;   // measurement aid: host-side phases of the call
+  static const bool latTimes = env_set("ORBX_LAT_TIMES");   // measurement aid: host-side phases of the call
   const auto tq1 = std::chrono::steady_clock::now();
   // Keypoints and descriptors reach the host block with the association's launch (launch_stereo_match's gather workgroups), two
   // launches before the frame ends: a caller that wants them in its own arrays gets them copied WHILE the association and the
   // median cut run (7 us of reads from memory the GPU has just written, off the end of the call).  The block's sequence word is
   // the gather's last write; the stream is polled beside it so that a failed launch cannot leave this thread spinning.
   bool copiedEarly = false;
-  static const bool earlyOut = !(getenv("ORBX_EARLY_COPYOUT") && atoi(getenv("ORBX_EARLY_COPYOUT")) == 0);
-  if (kpsPacked && earlyOut && (kps_left || desc_left || kps_right || desc_right)) {
+  if (kpsPacked && (kps_left || desc_left || kps_right || desc_right)) {
     const volatile uint32_t* flag = reinterpret_cast<const volatile uint32_t*>(H + hr_flag());
     const uint32_t want = ex->packSeq;
     bool seen = false;

@@ -13,10 +13,8 @@ struct Knobs {
 };
 const Knobs& knobs() {
   static const Knobs k = [] {
-    const char* cap = getenv("ORBX_PROJ_CAND_CAP");
-    const char* blind = getenv("ORBX_PROJ_BLIND");
-    const char* serial = getenv("ORBX_PROJ_SERIAL");
-    return Knobs{cap ? atoi(cap) : 0, blind ? std::min(48, std::max(1, atoi(blind))) : 16, serial && atoi(serial) != 0};
+    return Knobs{env_int("ORBX_PROJ_CAND_CAP", 0), std::min(48, std::max(1, env_int("ORBX_PROJ_BLIND", 16))),
+                 env_int("ORBX_PROJ_SERIAL", 0) != 0};
   }();
   return k;
 }

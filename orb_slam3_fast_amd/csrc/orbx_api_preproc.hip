@@ -256,8 +256,7 @@ int orbx_preproc_create(const orbx_preproc_params* p, int max_batch, int device,
     if (e == hipSuccess) chk(hipMemcpy(pp->d_xab.p, xab.data(), xab.size() * sizeof(short), hipMemcpyHostToDevice));
     if (e == hipSuccess) chk(hipMemcpy(pp->d_yab.p, yab.data(), yab.size() * sizeof(short), hipMemcpyHostToDevice));
     // single-channel frames: the same cv::resize through the pyramid's tiled kernel (tables of a two-level geometry)
-    static const bool plainOff = getenv("ORBX_RESIZE_PLAIN") && atoi(getenv("ORBX_RESIZE_PLAIN")) == 0;   // A / B switch
-    if (cn == 1 && !plainOff && p->out_w >= 4 && resize_plain_lds(p->src_w, p->src_h, p->out_w, p->out_h) <= 60 * 1024) {
+    if (cn == 1 && p->out_w >= 4 && resize_plain_lds(p->src_w, p->src_h, p->out_w, p->out_h) <= 60 * 1024) {
       Geom g2{};
       g2.nlevels = 2;
       g2.lv[0].w = p->src_w; g2.lv[0].h = p->src_h;

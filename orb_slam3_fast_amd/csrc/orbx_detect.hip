@@ -3,6 +3,7 @@
 // ORBextractor::ComputeKeyPointsOctTree's cell loop (src/ORBextractor.cc:892-971 of the reference): per-cell cv::FAST with
 // non-max suppression at iniThFAST, minThFAST for cells that come out empty.  SURVEY A3 / B3.
 #include "orbx_device.h"
+#include "orbx_prof.h"
 
 namespace orbx {
 
@@ -124,6 +125,21 @@ __device__ __forceinline__ uint64_t low_lanes_pos(int n) {  // n >= 1
 }
 
 
+// Shader-clock measurement aid (-DDET_CLK): cycles per 10 ns tick over the life of a few waves, printed when the kernel returns.
+// (off: an empty, trivially destructible object -- a destructor, even an empty one, changes how the kernel's returns are laid out)
+template <bool kOn>
+struct ClkPrint {};
+template <>
+struct ClkPrint<true> {
+  const long long c0 = clock64(), w0 = wall_clock64();
+  __device__ ~ClkPrint() {
+    if (threadIdx.x == 0 && blockIdx.y == 31 && (blockIdx.x % 400) == 7) {
+      const long long dc = clock64() - c0, dw = wall_clock64() - w0;
+      printf("det wave: %lld shader cycles in %lld x 10 ns -> %.3f GHz\n", dc, dw, dw ? (double)dc / (double)dw / 10.0 : 0.0);
+    }
+  }
+};
+
 // One wave per FAST cell (workgroup = 64 threads, so __syncthreads() is a wave barrier).
 // Pass 1 runs at iniThFAST; only a cell whose post-NMS set is empty is redone at minThFAST (:942-959).
 // The NMS needs no threshold masking: a neighbour that is not a corner at t has score < t <= the centre's.
@@ -141,26 +157,9 @@ __global__ __launch_bounds__(64) void k_detect(DetectArgs g, Pyr p, const CellRe
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x;
   const int img = blockIdx.y;
-#ifdef DET_CLK  // shader-clock measurement aid: cycles per 10 ns tick over the life of a few waves
-  const long long clk0 = clock64(), wall0 = wall_clock64();
-  struct ClkPrint {
-    long long c0, w0;
-    int on;
-    __device__ ~ClkPrint() {
-      if (on) {
-        const long long dc = clock64() - c0, dw = wall_clock64() - w0;
-        printf("det wave: %lld shader cycles in %lld x 10 ns -> %.3f GHz\n", dc, dw, dw ? (double)dc / (double)dw / 10.0 : 0.0);
-      }
-    }
-  } clkPrint{clk0, wall0, (int)(lane == 0 && blockIdx.y == 31 && (blockIdx.x % 400) == 7)};
-#endif
-#ifdef DET_PROF  // measurement aid (make prof PROF_FLAGS=-DDET_PROF): the life of a few cell-waves inside one launch, x10 ns
-  long long dq_[8]; int ndq_ = 0;
-#define DET_MK() do { if (ndq_ < 8) dq_[ndq_++] = wall_clock64(); } while (0)
-#else
-#define DET_MK() do {} while (0)
-#endif
-  DET_MK();
+  [[maybe_unused]] ClkPrint<kDetClk> clkPrint;
+  SectionClock<8, kDetProf> clk;  // measurement aid (make prof PROF_FLAGS=-DDET_PROF): the life of a few cell-waves inside one launch, x10 ns
+  PROF_MARK(clk);
   // Runs of xcdRun horizontally consecutive cells share an XCD and therefore the L2 lines of their common halo
   // columns (HBM-side fetch 410 -> 151 MB per 64-image launch; same duration, the kernel is VALU-bound).
   const int cell = g.cellBegin + xcd_run_remap<kDetectXcdRun>(blockIdx.x, gridDim.x, blockIdx.y);
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(64) void k_detect(DetectArgs g, Pyr p, const CellRe
       }
     }
   }
-  DET_MK();
+  PROF_MARK(clk);
   uint32_t* out = cellCand + (long long)img * g.cellImg + rec.outOff;
   int kept = 0;
   // a round of 64 quads advances a lane by dq rows and rq quads (no division per round)
@@ -314,7 +313,7 @@ __global__ __launch_bounds__(64) void k_detect(DetectArgs g, Pyr p, const CellRe
     // clear the score tile (16-byte stores; its zero ring is part of it).  The barrier also publishes the image tile.
     for (int i = lane; i < nScore16; i += 64) reinterpret_cast<uint4*>(score)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
-    if (pass == 0) DET_MK();
+    if (pass == 0) PROF_MARK(clk);
     // dense corner test, 4 pixels per lane; corners are compacted into an LDS list and scored with dense
     // lanes (the score needs ~40 min/max ops: running it under per-lane divergence would dominate).
     // Stage 1 (4 pixels per lane, registers): compass pre-test -> survivor list.
@@ -436,9 +435,9 @@ __global__ __launch_bounds__(64) void k_detect(DetectArgs g, Pyr p, const CellRe
         }
       }
     }
-    if (pass == 0) DET_MK();
+    if (pass == 0) PROF_MARK(clk);
     flush_survivors();
-    if (pass == 0) DET_MK();
+    if (pass == 0) PROF_MARK(clk);
     const int nCorners = nList;
     // 3x3 non-max suppression (strict '>') inside the cell + emission
     if (TAP && pass == 0) {  // test tap (orbx_debug_score_map): the cell's FAST scores at iniThFAST, 0 = no corner
@@ -519,14 +518,16 @@ __global__ __launch_bounds__(64) void k_detect(DetectArgs g, Pyr p, const CellRe
     __syncthreads();
   }
   if (lane == 0) *myCount = min(kept, cellCap);
-#ifdef DET_PROF
-  DET_MK();
-  if (lane == 0 && (blockIdx.x % 16) == 3) printf("detw %d %d %lld %lld\n", (int)((rec.flags >> 8) & 15u), kept, dq_[0] % 100000000, dq_[ndq_ - 1] % 100000000);
-  if (lane == 0 && ((blockIdx.x % 293) == 7 || blockIdx.x + 1 == gridDim.x || blockIdx.x == 0) && ndq_ >= 6)
-    printf("det img %d blk %4d level %d start %6lld: issue tile loads %d | tile in LDS + clear %d | stage 1 %d | flush (stage 2) %d | "
-           "NMS + emit%s %d | total %d  kept %d\n", img, (int)blockIdx.x, (int)((rec.flags >> 8) & 15u), dq_[0] % 1000000, (int)(dq_[1] - dq_[0]), (int)(dq_[2] - dq_[1]),
-           (int)(dq_[3] - dq_[2]), (int)(dq_[4] - dq_[3]), ndq_ > 6 ? " + pass 2" : "", (int)(dq_[ndq_ - 1] - dq_[4]), (int)(dq_[ndq_ - 1] - dq_[0]), kept);
-#endif
+  PROF_MARK(clk);
+  if constexpr (kDetProf) {
+    const long long* dq_ = clk.t;
+    const int ndq_ = clk.n;
+    if (lane == 0 && (blockIdx.x % 16) == 3) printf("detw %d %d %lld %lld\n", (int)((rec.flags >> 8) & 15u), kept, dq_[0] % 100000000, dq_[ndq_ - 1] % 100000000);
+    if (lane == 0 && ((blockIdx.x % 293) == 7 || blockIdx.x + 1 == gridDim.x || blockIdx.x == 0) && ndq_ >= 6)
+      printf("det img %d blk %4d level %d start %6lld: issue tile loads %d | tile in LDS + clear %d | stage 1 %d | flush (stage 2) %d | "
+             "NMS + emit%s %d | total %d  kept %d\n", img, (int)blockIdx.x, (int)((rec.flags >> 8) & 15u), dq_[0] % 1000000, (int)(dq_[1] - dq_[0]), (int)(dq_[2] - dq_[1]),
+             (int)(dq_[3] - dq_[2]), (int)(dq_[4] - dq_[3]), ndq_ > 6 ? " + pass 2" : "", (int)(dq_[ndq_ - 1] - dq_[4]), clk.total(), kept);
+  }
 }
 
 static int g_detect_list_cap = kListTotal;  // test hook: a smaller list forces the flush / carry / corner-overflow paths

@@ -104,6 +104,13 @@ __device__ __forceinline__ int xcd_run_remap(int bx, int nbx, int by) {
   return c0 + (r & 7) * K + (r >> 3) - o;
 }
 
+// BORDER_REFLECT_101 (k_blur and k_describe's window loader)
+__device__ __forceinline__ int reflect101(int p, int n) {
+  if (p < 0) p = -p;
+  if (p >= n) p = 2 * n - 2 - p;
+  return p;
+}
+
 __device__ __forceinline__ int hamming256(const uint32_t* a, const uint32_t* b) {
   int d = 0;
 #pragma unroll

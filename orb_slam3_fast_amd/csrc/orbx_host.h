@@ -1,5 +1,6 @@
 // orbx_host.h — host-side internals shared by the C-ABI translation units of liborbx (orbx_api*.hip): error state, device
-// buffers, the per-call scratch pool and packed staging, and the extractor handle.
+// buffers, the per-call scratch pool and packed staging, and the extractor handle.  The environment helpers (env_int, env_set,
+// env_str) are also what the launchers in the kernel units read their knobs with.
 #ifndef ORBX_HOST_H
 #define ORBX_HOST_H
 #if defined(__x86_64__) || defined(__i386__)
@@ -23,6 +24,17 @@ static inline void cpu_pause() {}
 
 #include "orbx_internal.h"
 
+namespace orbx {
+// Environment knobs (the list: README.md, include/orbx.h).  Every site keeps its value in a function-local or file static, so a
+// knob is read once per process.  This is the library's only reader of the environment.
+inline const char* env_str(const char* name) { return getenv(name); }                 // nullptr: not set
+inline bool env_set(const char* name) { return env_str(name) != nullptr; }           // set at all, whatever the value
+inline int env_int(const char* name, int dflt) {
+  const char* e = env_str(name);
+  return e ? atoi(e) : dflt;
+}
+}  // namespace orbx
+
 using namespace orbx;
 
 namespace orbx_host {
@@ -39,9 +51,9 @@ inline int fail(int code, const std::string& msg) {
   return code;
 }
 // ORBX_TRACE_SLOW=<ms>: report every wrapped HIP call / launch sequence that blocks the host longer than that (debug aid
-// for enqueue stalls; one getenv at first use, two clock reads per call only when it is set).
+// for enqueue stalls; read at first use, two clock reads per call only when it is set).
 inline double trace_slow_ms() {
-  static const double v = getenv("ORBX_TRACE_SLOW") ? atof(getenv("ORBX_TRACE_SLOW")) : 0.0;
+  static const double v = env_set("ORBX_TRACE_SLOW") ? atof(env_str("ORBX_TRACE_SLOW")) : 0.0;
   return v;
 }
 #define HIPC(expr)                                                                                     \

@@ -123,8 +123,8 @@ hipError_t launch_resize_tail(const Geom& g, const Pyr& p, const TailPlan& tp, c
 hipError_t prepare_resize_tail(unsigned ldsBytes);
 hipError_t raise_dynamic_lds(const void* fn, size_t bytes);   // per-device running maximum of a kernel's dynamic-LDS limit
 
-// Launch wrappers (orbx_kernels.hip).  All enqueue on `s` and return the HIP status.
-// whole single-channel frames through the pyramid's resize kernel (pre-processing plans; orbx_kernels.hip)
+// Launch wrappers (orbx_resize / orbx_octree / orbx_blur / orbx_describe / orbx_kernels .hip).  All enqueue on `s` and return the HIP status.
+// whole single-channel frames through the pyramid's resize kernel (pre-processing plans; orbx_resize.hip)
 size_t resize_plain_lds(int sw, int sh, int dw, int dh);
 hipError_t prepare_resize_plain(int sw, int sh, int dw, int dh);
 hipError_t launch_resize_plain(const uint8_t* src, int sw, int sh, long long sp, long long sip, uint8_t* dst, int dw, int dh,
@@ -134,7 +134,7 @@ hipError_t launch_resize_plain(const uint8_t* src, int sw, int sh, long long sp,
 hipError_t launch_resize(const Geom& g, const Pyr& p, int nimg, int level, const uint4* xtab, const uint32_t* yofs /* clamped row pairs */,
                          const short* yab, const uint32_t* records, hipStream_t s);
 int resize_records_layout(const Geom& g, int level, int& tileOff, int& rowOff);
-constexpr uint32_t kTileFast = 1u, kTileWhole = 2u;   // flags of a tile record (k_resize, orbx_kernels.hip)
+constexpr uint32_t kTileFast = 1u, kTileWhole = 2u;   // flags of a tile record (k_resize, orbx_resize.hip)
 hipError_t launch_detect(const Geom& g, const Pyr& p, const CellRec* cellRec, int nimg, uint32_t* cellCand, int* cellCount,
                          int level0, int level1, uint8_t* dbgScore, hipStream_t s);
 // levels [level0, level1) with blocks of nt threads (128 / 256 / 512); its dynamic LDS is sized for that level range
@@ -578,6 +578,8 @@ hipError_t launch_proj_fisheye_batch(const ProjArgs* d_sides, const ProjFeArgs* 
                                      int checkOri, int rounds, hipStream_t s);
 hipError_t prepare_kernels(const Geom& g);                             // raises the dynamic-LDS limits
 hipError_t prepare_detect(const Geom& g);                              // (orbx_detect.hip)
+hipError_t prepare_octree(const Geom& g);                              // (orbx_octree.hip)
+hipError_t prepare_resize(const Geom& g);                              // (orbx_resize.hip)
 void debug_introsort_host(uint64_t* v, int n);
 void debug_set_detect_list_cap(int cap);
 void debug_set_clahe_cell_kernel(int on);

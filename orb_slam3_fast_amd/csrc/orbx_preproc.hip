@@ -1,6 +1,7 @@
 // orbx_preproc.hip — image pre-processing in front of the extractor (gray, resize, cv::remap, CLAHE) and
 // Frame::UndistortKeyPoints (src/Frame.cc:853-919).
 #include "orbx_device.h"
+#include "orbx_host.h"   // env_int
 #include "orbx_undistort.h"
 #include <algorithm>
 #include <cmath>
@@ -75,8 +76,7 @@ __global__ __launch_bounds__(256) void k_cvt_gray16(const uint8_t* __restrict__ 
 
 int cvt_gray_segs(const uint8_t* src, int w, long long sp, long long sip, int cn, const uint8_t* dst, long long dp, long long dip) {
   const bool aligned = !(((uintptr_t)src | (uintptr_t)dst | (uintptr_t)sp | (uintptr_t)sip | (uintptr_t)dp | (uintptr_t)dip) & 15);
-  static const bool naive = getenv("ORBX_GRAY_NAIVE") && atoi(getenv("ORBX_GRAY_NAIVE")) != 0;   // A / B switch: the per-pixel kernel everywhere
-  return aligned && !naive && (cn == 3 || cn == 4) ? w / 16 : 0;
+  return aligned && (cn == 3 || cn == 4) ? w / 16 : 0;
 }
 hipError_t launch_cvt_gray(const uint8_t* src, int w, int h, long long sp, long long sip, int cn, int rgb, uint8_t* dst,
                            long long dp, long long dip, int nimg, hipStream_t s) {
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(256, 8) void k_remap1(RemapArgs a, int nimg, int xb
     }
   }
 }
-static int g_remap_lds = [] { const char* e = getenv("ORBX_REMAP_LDS"); return e ? atoi(e) : 1; }();   // test / A-B hook
+static int g_remap_lds = env_int("ORBX_REMAP_LDS", 1);   // test / A-B hook
                                         // (orbx_debug_set_remap_lds, ORBX_REMAP_LDS): 0 = the plans keep k_remap1
 void debug_set_remap_lds(int on) { g_remap_lds = on; }
 // ---------------------------------------------------------------------------------------------------------------- round 6b
@@ -341,9 +341,6 @@ void debug_set_remap_lds(int on) { g_remap_lds = on; }
 // group per trip, the next trip's loads in flight under the current blends -- and the windows come from LDS.
 // Used by the pre-processing plans whose every tile fits kRemapLdsDwords (rectification maps do; a plan with a wider tile, an
 // unaligned source or cn != 1 keeps k_remap1 / k_remap).  Results are bit-identical: the taps, weights and blends are k_remap1's.
-#ifndef REMAP_ABLATE
-#define REMAP_ABLATE 0
-#endif
 #ifndef REMAP_ROWMAJOR
 #define REMAP_ROWMAJOR 0
 #endif
@@ -448,9 +445,6 @@ __global__ __launch_bounds__(256) void k_remap_lds(RemapArgs a, int nimg, int nb
   auto blend = [&](const uint32_t* st) -> uint32_t {
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(st);
     uint32_t packed = 0;
-#if REMAP_ABLATE == 2   // timing only: no blend
-    return *reinterpret_cast<const uint32_t*>(sb + lw0);
-#endif
     if (allFast) {
       const uint32_t* q0 = reinterpret_cast<const uint32_t*>(sb + lw0);
       const uint32_t* q1 = reinterpret_cast<const uint32_t*>(sb + lw1);
@@ -483,9 +477,6 @@ __global__ __launch_bounds__(256) void k_remap_lds(RemapArgs a, int nimg, int nb
     return packed;
   };
   auto put = [&](int img, uint32_t packed) {
-#if REMAP_ABLATE == 1   // timing only: no stores
-    if (packed != 0x12345678u) return;
-#endif
     if (!rowIn || x0 >= a.dw) return;
     uint8_t* D = dst + (long long)img * a.dstImgPitch + (long long)y * a.dstPitch + x0;
     if (full && a.dstVec4) {
@@ -506,7 +497,7 @@ __global__ __launch_bounds__(256) void k_remap_lds(RemapArgs a, int nimg, int nb
   auto fetch = [&](int trip, uint4& xa, uint4& xb) {
     const int tc = min(trip, ntrips - 1);   // (behind the last trip: a repeat of it, never staged)
     const int imgA = m + a.nMaps * (first + 2 * tc), imgB = m + a.nMaps * (first + min(2 * tc + 1, count - 1));
-    if (sIn && REMAP_ABLATE != 3) {
+    if (sIn) {
       xa = *reinterpret_cast<const uint4*>(src + (long long)imgA * a.srcImgPitch + sOff);
       xb = *reinterpret_cast<const uint4*>(src + (long long)imgB * a.srcImgPitch + sOff);
     }
@@ -600,7 +591,7 @@ hipError_t launch_remap(const RemapArgs& a, int nimg, hipStream_t s) {
   if (form == 2) {
     // images per workgroup: the taps and weights of a tile are built once per group, so larger groups halve that share of the
     // vector work -- as long as the launch keeps a few workgroups per CU slot
-    static const int gforce = [] { const char* e = getenv("ORBX_REMAP_GROUP"); return e ? atoi(e) : 0; }();
+    static const int gforce = env_int("ORBX_REMAP_GROUP", 0);
     const int perMap = (nimg + a.nMaps - 1) / a.nMaps, tiles = a.tilesX * a.tilesY * a.nMaps;
     int gsz = 8;
     while (gsz < 32 && gsz < perMap && (long long)tiles * ((perMap + 2 * gsz - 1) / (2 * gsz)) >= 1500) gsz *= 2;

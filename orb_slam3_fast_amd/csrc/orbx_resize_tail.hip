@@ -10,6 +10,7 @@
 // Arithmetic = k_resize's = cv::resize INTER_LINEAR 8U: t = S[sx]*a0 + S[sx+1]*a1 from the same per-column
 // table (build_coefs), D = (((b0*(t0>>4))>>16) + ((b1*(t1>>4))>>16) + 2) >> 2 with the same per-row table.
 #include "orbx_device.h"
+#include "orbx_prof.h"
 
 namespace orbx {
 
@@ -31,14 +32,8 @@ __global__ __launch_bounds__(kTailNT) void k_resize_tail(Geom g, Pyr p, TailPlan
   // (tile offsets, not a pointer array: pointers selected at run time decay to generic addresses and the tile reads
   // become flat_load instead of ds_read)
   uint4* rtab = reinterpret_cast<uint4*>(smem + tp.tileBytes[0] + tp.tileBytes[1]);
-#ifdef RT_PROF  // phase timing of a few workgroups (tools/resize_prof.py, build with -DRT_PROF): 10 ns ticks
-  long long tq[32];
-  int nq_ = 0;
-#define RT_MK() do { if (nq_ < 32) tq[nq_++] = wall_clock64(); } while (0)
-#else
-#define RT_MK() do {} while (0)
-#endif
-  RT_MK();
+  SectionClock<32, kRtProf> clk;  // phase timing of one band (tools/resize_tail_prof.py, build with -DRT_PROF): 10 ns ticks
+  PROF_MARK(clk);
   // ---- the rows of level lA-1 this band depends on: 16-byte loads, all of a thread's loads in flight before its first
   // LDS store (the level's buffer is 64-byte aligned with a 64-byte pitch: whole uint4s up to align_up(w, 16) exist)
   {
@@ -98,7 +93,7 @@ __global__ __launch_bounds__(kTailNT) void k_resize_tail(Geom g, Pyr p, TailPlan
     for (int j = 0; j < 4; j++) cnext[j] = xtab[D.xcoef + 4 * q + j];  // (padded to whole 256-column blocks: always valid)
   };
   fetch_coefs(0);
-  RT_MK();
+  PROF_MARK(clk);
   for (int t = 0; t < tp.nT; t++) {
     const int l = tp.lA + t;
     const LevelDev D = g.lv[l];
@@ -118,9 +113,9 @@ __global__ __launch_bounds__(kTailNT) void k_resize_tail(Geom g, Pyr p, TailPlan
       coef[j] = cnext[j].w;
     }
     if (t + 1 < tp.nT) fetch_coefs(t + 1);
-    RT_MK();
+    PROF_MARK(clk);
     __syncthreads();  // (also: the source tile is complete)
-    RT_MK();
+    PROF_MARK(clk);
     uint8_t* gdst = p.pyr + (long long)img * g.pyrImg + D.off;
     const bool keep = t + 1 < tp.nT;
     if (ph < nPh) {
@@ -175,17 +170,16 @@ __global__ __launch_bounds__(kTailNT) void k_resize_tail(Geom g, Pyr p, TailPlan
         if (dFirst + r < ownEnd) *reinterpret_cast<uint32_t*>(gdst + (long long)(dFirst + r) * D.pitch + 4 * q) = outw;
       }
     }
-    RT_MK();
+    PROF_MARK(clk);
     __syncthreads();  // the next level reads the destination tile and overwrites rtab / the old source tile
-    RT_MK();
+    PROF_MARK(clk);
   }
-#ifdef RT_PROF
-  if (tid == 0 && img == 0 && band == 1) {  // load + tables | per level: {barrier, rows, barrier}
-    printf("k_resize_tail L%d..%d band 1:", tp.lA, tp.lA + tp.nT - 1);
-    for (int i = 1; i < nq_; i++) printf(" %d", (int)(tq[i] - tq[i - 1]));
-    printf("  (x10 ns; workgroup %d)\n", (int)(tq[nq_ - 1] - tq[0]));
+  if constexpr (kRtProf) {
+    if (tid == 0 && img == 0 && band == 1) {  // load + tables | per level: {barrier, rows, barrier}
+      clk.print("k_resize_tail L%d..%d band 1:", tp.lA, tp.lA + tp.nT - 1);
+      printf("  (x10 ns; workgroup %d)\n", clk.total());
+    }
   }
-#endif
 }
 
 hipError_t launch_resize_tail(const Geom& g, const Pyr& p, const TailPlan& tp, const TailBand* bands, int img0, int nimg,

@@ -15,7 +15,7 @@
 //
 // Valid for |y| < 120 (the path produces y = fastAtan2(..) * (pi/180) in [0, 2 pi]); glibc's reduce_large is not restated.
 // Host + device: one source; the tests run both variants on the device against the host libm (orbx_debug_sincos).
-// k_describe itself calls glibc_sincosf_sel (orbx_kernels.hip), a branch-free restatement of the FMA variant; the same entry
+// k_describe itself calls glibc_sincosf_sel (orbx_describe.hip), a branch-free restatement of the FMA variant; the same entry
 // evaluates it (fused == 2) on the same angles.  glibc_sincosf<> below is the definition it is held to.
 #ifndef ORBX_SINCOS_H
 #define ORBX_SINCOS_H

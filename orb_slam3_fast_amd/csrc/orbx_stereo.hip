@@ -1,8 +1,10 @@
 // orbx_stereo.hip — association kernels of liborbx: Frame::ComputeStereoMatches (src/Frame.cc:921-1084), BFMatcher kNN-2
 // (:1293-1302) and ComputeStereoFishEyeMatches with the KannalaBrandt8 triangulation (:1273-1331).
 #include "orbx_matching.h"
+#include "orbx_host.h"   // env_int
 #include "orbx_linalg.h"
 #include "orbx_kb8.h"
+#include "orbx_prof.h"
 
 namespace orbx {
 
@@ -32,13 +34,8 @@ __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
   int* hist = reinterpret_cast<int*>(smem);  // imgH + 1 counters, then running offsets
   __shared__ int wsum[kSortNT / 64];
   const int tid = threadIdx.x, pair = blockIdx.x >> 1, eye = blockIdx.x & 1;
-#ifdef ST_PROF
-  long long sq[12]; int nsq = 0;
-#define SS_MK() do { if (nsq < 12) sq[nsq++] = wall_clock64(); } while (0)
-#else
-#define SS_MK() do {} while (0)
-#endif
-  SS_MK();
+  SectionClock<12, kStProf> clk;
+  PROF_MARK(clk);
   const int img = (eye ? a.firstR : a.firstL) + pair;
   const int cap = eye ? a.capR : a.capL;
   const int n = (eye ? a.nR : a.nL)[img];
@@ -49,14 +46,14 @@ __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
   uint4* sd = a.sdesc + (long long)(pair * 2 + eye) * a.cap * 2;
   __shared__ float lvS[ORBX_MAX_LEVELS];
   if (tid < g.nlevels) lvS[tid] = g.lv[tid].scale;
-  SS_MK();
+  PROF_MARK(clk);
   for (int r = tid; r <= a.imgH; r += kSortNT) hist[r] = 0;
   __syncthreads();
   auto row_of = [&](float y) { return min(max((int)y, 0), a.imgH - 1); };
   for (int i = tid; i < n; i += kSortNT) atomicAdd(&hist[row_of(kp[i].y)], 1);
-  SS_MK();
+  PROF_MARK(clk);
   __syncthreads();
-  SS_MK();
+  PROF_MARK(clk);
   // exclusive prefix over the rows: a contiguous chunk per thread, wave scans of the chunk sums, wave totals through LDS
   const int per = (a.imgH + kSortNT) / kSortNT;
   const int b = min(tid * per, a.imgH + 1), e = min(b + per, a.imgH + 1);
@@ -73,9 +70,9 @@ __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
     rowStart[r] = run;
     run += c;
   }
-  SS_MK();
+  PROF_MARK(clk);
   __syncthreads();
-  SS_MK();
+  PROF_MARK(clk);
   for (int i = tid; i < n; i += kSortNT) {
     const orbx_keypoint k = kp[i];
     const int pos = atomicAdd(&hist[row_of(k.y)], 1);
@@ -84,14 +81,13 @@ __global__ __launch_bounds__(kSortNT) void k_stereo_sort(Geom g, StereoArgs a) {
     sd[2 * pos] = dsc[2 * i];
     sd[2 * pos + 1] = dsc[2 * i + 1];
   }
-  SS_MK();
-#ifdef ST_PROF
-  if (tid == 0 && blockIdx.x == 9) {
-    printf("k_stereo_sort n %d:", n);
-    for (int i = 1; i < nsq; i++) printf(" %d", (int)(sq[i] - sq[i - 1]));
-    printf("  (x10 ns: level table | zero+hist | bar | scan | bar | scatter)\n");
+  PROF_MARK(clk);
+  if constexpr (kStProf) {
+    if (tid == 0 && blockIdx.x == 9) {
+      clk.print("k_stereo_sort n %d:", n);
+      printf("  (x10 ns: level table | zero+hist | bar | scan | bar | scatter)\n");
+    }
   }
-#endif
 }
 
 hipError_t launch_stereo_sort(const Geom& g, const StereoArgs& a, int npairs, hipStream_t s) {
@@ -285,13 +281,8 @@ __global__ __launch_bounds__(NT) void k_stereo_band(Geom g, Pyr pl, Pyr pr, Ster
   __shared__ float lvS[ORBX_MAX_LEVELS];
   const int tid = threadIdx.x;
   const int pair = blockIdx.y, r0 = blockIdx.x * kStereoBand;
-#ifdef ST_PROF
-  long long tq[16]; int nq_ = 0;
-#define ST_MK() do { if (nq_ < 16) tq[nq_++] = wall_clock64(); } while (0)
-#else
-#define ST_MK() do {} while (0)
-#endif
-  ST_MK();
+  SectionClock<16, kStProf> clk;
+  PROF_MARK(clk);
   const int imgL = a.firstL + pair, imgR = a.firstR + pair;
   int jLb, jLe, jRb, jRe;
   const uint4 *recL = nullptr, *recR = nullptr, *sdL, *sdR;
@@ -358,7 +349,7 @@ __global__ __launch_bounds__(NT) void k_stereo_band(Geom g, Pyr pl, Pyr pr, Ster
     jRe = cntSel[1];
     if (jLe == 0) return;  // no left keypoint in these rows
   }
-  ST_MK();
+  PROF_MARK(clk);
   for (int lc = jLb; lc < jLe; lc += kStereoLC) {
     const int nl = min(kStereoLC, jLe - lc);
     __syncthreads();  // (the previous trip's SAD stage has read Lrec / Lbest)
@@ -396,9 +387,9 @@ __global__ __launch_bounds__(NT) void k_stereo_band(Geom g, Pyr pl, Pyr pr, Ster
         const int c = i >> 1, k0 = (i & 1) * 4;
         Rdesc[k0][c] = d.x; Rdesc[k0 + 1][c] = d.y; Rdesc[k0 + 2][c] = d.z; Rdesc[k0 + 3][c] = d.w;
       }
-      ST_MK();
+      PROF_MARK(clk);
       __syncthreads();
-      ST_MK();
+      PROF_MARK(clk);
       // 16 lanes per left keypoint (four keypoints per wave side by side), lane s takes candidates s, s + 16, ...
       for (int li = tid >> 4; li < nl; li += NT / 16) {
         const uint4 lr = Lrec[li];
@@ -443,9 +434,9 @@ __global__ __launch_bounds__(NT) void k_stereo_band(Geom g, Pyr pl, Pyr pr, Ster
         }
       }
     }
-    ST_MK();
+    PROF_MARK(clk);
     __syncthreads();
-    ST_MK();
+    PROF_MARK(clk);
     // ---- left keypoints without an ORB match are finished; the others queue for the SAD refinement
     {
       const bool matched = tid < nl && (int)(Lbest[min(tid, kStereoLC - 1)] >> 16) < 75;  // thOrbDist = (TH_HIGH + TH_LOW) / 2
@@ -567,16 +558,15 @@ __global__ __launch_bounds__(NT) void k_stereo_band(Geom g, Pyr pl, Pyr pr, Ster
         a.sad[o] = sad_out;
       }
     }
-    ST_MK();
+    PROF_MARK(clk);
   }
-#ifdef ST_PROF
-  if (tid == 0 && ((pair % 8) == 5 || gridDim.y == 1) && (blockIdx.x % 9) == 4) {
-    char buf[200]; (void)buf;
-    printf("band %2d pair %2d nL %2d nR %2d start %5lld: tab %d | stage %d bar %d match %d bar %d queue+SAD %d  (x10 ns; total %d)\n", (int)blockIdx.x, pair,
-           jLe - jLb, jRe - jRb, tq[0] % 100000, (int)(tq[1] - tq[0]), (int)(tq[2] - tq[1]), (int)(tq[3] - tq[2]), (int)(tq[4] - tq[3]),
-           (int)(tq[5] - tq[4]), (int)(tq[6] - tq[5]), (int)(tq[nq_ - 1] - tq[0]));
+  if constexpr (kStProf) {
+    const long long* tq = clk.t;
+    if (tid == 0 && ((pair % 8) == 5 || gridDim.y == 1) && (blockIdx.x % 9) == 4)
+      printf("band %2d pair %2d nL %2d nR %2d start %5lld: tab %d | stage %d bar %d match %d bar %d queue+SAD %d  (x10 ns; total %d)\n", (int)blockIdx.x, pair,
+             jLe - jLb, jRe - jRb, tq[0] % 100000, (int)(tq[1] - tq[0]), (int)(tq[2] - tq[1]), (int)(tq[3] - tq[2]), (int)(tq[4] - tq[3]),
+             (int)(tq[5] - tq[4]), (int)(tq[6] - tq[5]), clk.total());
   }
-#endif
 }
 
 __global__ __launch_bounds__(256) void k_stereo_filter(StereoArgs a) {
@@ -635,7 +625,7 @@ hipError_t launch_stereo_filter_pack(const StereoArgs& sa, const ResultPack& a, 
 }
 
 // pairs per call up to which the direct form runs (default 1: the single-frame path; ORBX_STEREO_DIRECT_PAIRS / test hook)
-static int g_stereo_direct_pairs = getenv("ORBX_STEREO_DIRECT_PAIRS") ? atoi(getenv("ORBX_STEREO_DIRECT_PAIRS")) : 1;
+static int g_stereo_direct_pairs = env_int("ORBX_STEREO_DIRECT_PAIRS", 1);
 void debug_set_stereo_direct(int max_pairs) { g_stereo_direct_pairs = max_pairs < 0 ? 1 : max_pairs; }
 bool stereo_direct_ok(const StereoArgs& a, int npairs) {
   return npairs <= g_stereo_direct_pairs && a.capL <= kStereoSelCap && a.capR <= kStereoSelCap;
@@ -653,7 +643,7 @@ hipError_t launch_stereo_match(const Geom& g, const Pyr& pl, const Pyr& pr, cons
   // SHORTER with them, 0.4853 vs 0.4895 ms: small workgroups get scheduled between k_detect's one-wave cells, large ones
   // wait for it to drain; not adopted, the single-frame latency matters more than 0.8 %)
 #ifdef ORBX_BAND_SWEEP   // measurement aid (make prof PROF_FLAGS=-DORBX_BAND_SWEEP): band shapes of the direct form, ORBX_BAND_SHAPE=0..5
-  static const int shape = getenv("ORBX_BAND_SHAPE") ? atoi(getenv("ORBX_BAND_SHAPE")) : 0;
+  static const int shape = env_int("ORBX_BAND_SHAPE", 0);
   if (direct && shape == 1) ORBX_SB(12, 256, 256, 64);
   else if (direct && shape == 2) ORBX_SB(24, 512, 256, 128);
   else if (direct && shape == 3) ORBX_SB(12, 512, 256, 64);
@@ -936,9 +926,6 @@ hipError_t launch_tri_match_rig(const TriArgs& a, hipStream_t s) {
 // Keys keep the stable first-minimum order of BFMatcher::knnMatch; the lanes and waves that share a query merge their lists at the
 // end (lexicographic keys: any merge order gives the serial scan's result).  The accepted (query, train) pairs go to a compact
 // list, so the double-precision triangulation runs with full waves in its own launch instead of one sparse wave per workgroup.
-#ifndef FE_ABLATE
-#define FE_ABLATE 0
-#endif
 typedef int orbx_v4i_s __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ orbx_v4i_s expand16(uint32_t h) {   // bit j of h -> byte j (0 / 1) of the 16-byte operand
   orbx_v4i_s v;
@@ -991,11 +978,7 @@ __global__ __launch_bounds__(kFeThreads, 4) void k_fisheye_scan(FisheyeBatchArgs
     }
   }
   uint32_t k0[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, k1[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};  // (distance << 16 | train index), nT < 65536
-#if FE_ABLATE == 5   // timing only: no sub-tiles (the workgroup's fixed part alone)
-  const int nSub = nT < 0 ? 1 : 0;
-#else
   const int nSub = (nT + kFeSub - 1) / kFeSub;
-#endif
   // the workgroup expands dword e >> 7 (wave-uniform) of train e & 127 of the sub-tile, e = tid (+ kFeThreads)
   // The raw dwords travel kFePF sub-tiles ahead in registers: a sub-tile's compute (a few hundred cycles) is far shorter than the
   // latency of its loads (descriptors written by another XCD's k_describe come from the memory side), and one workgroup or two
@@ -1010,7 +993,6 @@ __global__ __launch_bounds__(kFeThreads, 4) void k_fisheye_scan(FisheyeBatchArgs
     }
   };
   auto expand_sub = [&](const uint32_t (&x)[kItems], int buf) {
-#if FE_ABLATE != 2   // (2: timing only, no expansion)
 #pragma unroll
     for (int u = 0; u < kItems; u++) {
       const int e = tid + u * kFeThreads, ei = e & 127, ed = e >> 7;
@@ -1019,7 +1001,6 @@ __global__ __launch_bounds__(kFeThreads, 4) void k_fisheye_scan(FisheyeBatchArgs
       dst[0] = make_uint4((uint32_t)lo[0], (uint32_t)lo[1], (uint32_t)lo[2], (uint32_t)lo[3]);
       dst[16] = make_uint4((uint32_t)hi[0], (uint32_t)hi[1], (uint32_t)hi[2], (uint32_t)hi[3]);
     }
-#endif
   };
   if (nSub > 0) {
 #pragma unroll
@@ -1076,20 +1057,12 @@ __global__ __launch_bounds__(kFeThreads, 4) void k_fisheye_scan(FisheyeBatchArgs
           for (int ks = 0; ks < 4; ks++) {
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-#if FE_ABLATE == 4   // timing only: no MFMA
-              acc[h][ks] ^= av4[u & 1][ks][0] ^ av4[u & 1][ks][1] ^ av4[u & 1][ks][2] ^ av4[u & 1][ks][3] ^ bq[h][ks][0];
-#else
               acc[h] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av4[u & 1][ks], bq[h][ks], acc[h], 0, 0, 0);
-#endif
             }
           }
           // acc[h][r] = |a| + a" . b = the distance of query (h, n) and train tg + 4 g + r
 #pragma unroll
           for (int h = 0; h < 2; h++) {
-#if FE_ABLATE == 3   // timing only: no top-2 epilogue
-            k0[h] ^= (uint32_t)(acc[h][0] + acc[h][1] + acc[h][2] + acc[h][3]);
-            continue;
-#endif
 #pragma unroll
             for (int r = 0; r < 4; r++) top2_insert(k0[h], k1[h], ((uint32_t)acc[h][r] << 16) | tr[r]);
           }

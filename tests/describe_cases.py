@@ -1,4 +1,4 @@
-"""Scenes and the census for k_describe (csrc/orbx_kernels.hip): which of its three window loaders a keypoint takes, at which
+"""Scenes and the census for k_describe (csrc/orbx_describe.hip): which of its three window loaders a keypoint takes, at which
 misalignment, over which reflected sides, and what follows what inside a wave.
 
 The restatement below is the kernel's own classification (the `win` lambda): for a level (w, h, pitch, level) and a key (X, Y)

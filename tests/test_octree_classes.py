@@ -14,7 +14,7 @@ from orb_slam3_fast_amd import synth
 
 CLASSES = (128, 256, 512, 0)   # orbx_debug_set_octree_class: 0 = the plan
 PATHS = (0, 1, 2)              # orbx_debug_set_octree_global: histogram variant, global-memory candidates, per-pass sweeps
-OCT_KMAX = 32                  # register-resident candidates per thread (orbx_kernels.hip)
+OCT_KMAX = 32                  # register-resident candidates per thread (orbx_octree.hip)
 
 
 @pytest.fixture(scope="module")

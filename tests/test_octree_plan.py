@@ -1,5 +1,5 @@
 """k_octree's plan (orbx_debug_octree_plan; host only): the class of every level (the threads of its workgroup that work) and the
-dynamic LDS of the batch's launch.  The LDS lower bound is a Python copy of oct_layout (orbx_kernels.hip) evaluated for the level alone, with the level
+dynamic LDS of the batch's launch.  The LDS lower bound is a Python copy of oct_layout (orbx_octree.hip) evaluated for the level alone, with the level
 quotas of ORBextractor's constructor (src/ORBextractor.cc:431-445) and the FAST cell grid of ComputeKeyPointsOctTree (:888-894)."""
 import numpy as np
 import pytest

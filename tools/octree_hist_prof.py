@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Section timing of k_octree's histogram variant (the product path); build liborbx_prof.so with -DOCT_PROF (see
-tools/octree_prof.py) and run with ORBX_OCTREE_PROF_LEVEL=<level> (level 0 cannot be selected: use -1 via the env
+"""Section timing of k_octree's histogram variant (the product path); build liborbx_prof.so with
+make -C orb_slam3_fast_amd/csrc prof PROF_FLAGS=-DOCT_PROF and run with ORBX_OCTREE_PROF_LEVEL=<level> (level 0 cannot be selected: use -1 via the env
 ORBX_OCTREE_PROF_LEVEL0=1)."""
 import sys, os
 sys.path.insert(0, '.')

@@ -2,11 +2,9 @@
 """Section timing inside k_octree (profiling aid, not part of the product).
 
 Build the instrumented library first:
-  cd orb_slam3_fast_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -DOCT_PROF \
-      -shared -o ../liborbx_prof.so orbx_kernels.hip orbx_stereo.hip orbx_guided.hip orbx_preproc.hip orbx_bow.hip orbx_api.hip \
-      -Wl,-rpath,/opt/rocm/lib
+  make -C orb_slam3_fast_amd/csrc prof PROF_FLAGS=-DOCT_PROF
 then   ORBX_OCTREE_PROF_LEVEL=0 python tools/octree_prof.py      (pyramid level)
-prints, for image 0, the 10 ns ticks between the MK() markers of the per-pass variant (octree_body; this script forces it
+prints, for image 0, the 10 ns ticks between the section marks of the per-pass variant (octree_body; this script forces it
 with the test hook, the product path is the histogram variant): gather, roots, then per phase-1 pass {count sweep, node
 loop, scan, node loop, relabel sweep}, per phase-2 round {sort, rest}, final selection.
 """

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase timing inside k_resize (profiling aid, not part of the product).  Build the instrumented library with
--DRS_PROF (same command as tools/octree_prof.py, output ../liborbx_prof.so), then run this script on the GPU box: a few
+make -C orb_slam3_fast_amd/csrc prof PROF_FLAGS=-DRS_PROF (output liborbx_prof.so), then run this script on the GPU box: a few
 blocks of image 7 print the 10 ns ticks spent in {footprint load, barrier, horizontal pass, barrier, vertical pass}.
 """
 import sys, os

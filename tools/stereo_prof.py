@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Phase timing inside k_stereo_band (profiling aid, not part of the product).  Build the instrumented library:
-  cd orb_slam3_fast_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -DST_PROF -shared \
-      -o ../liborbx_prof.so *.hip -ldl -Wl,-rpath,/opt/rocm/lib
+  make -C orb_slam3_fast_amd/csrc prof PROF_FLAGS=-DST_PROF
 then run this on the GPU box: a few workgroups of pair 5 print the 10 ns ticks of {row-table reads, record staging, barrier,
 match, barrier, SAD}."""
 import sys, os
