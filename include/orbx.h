@@ -226,6 +226,26 @@ int orbx_host_pyramid_level(const orbx_extractor* ex, int image, int level, cons
  * unspecified order (x, y relative to the (16,16) window origin as in src/ORBextractor.cc:965-967;
  * response = FAST score).  Returns the count or a negative error; copies at most cap entries. */
 int orbx_debug_candidates(orbx_extractor* ex, int image, int level, int32_t* xys, int cap);
+/* k_octree alone on the caller's candidates (tests/test_octree_rules.py): DistributeOctTree of n_images images of width x height,
+ * every level, with the launch an extraction of that batch makes -- the plan's launch for batches above two images, 512 threads
+ * otherwise, under orbx_debug_set_octree_class / orbx_debug_set_octree_global.  No pyramid, no FAST: the candidates are written
+ * into k_detect's per-cell store in the FAST cell each belongs to (cell = (y - 3) / hCell, (x - 3) / wCell), in the caller's
+ * order inside a cell -- ties between equal responses are broken by (cell row, cell column, y, x), never by that order.
+ *   counts[image * nlevels + level]   candidates of the (image, level)
+ *   xyr                               their (x, y, response) triples back to back, image-major, then level; x, y relative to
+ *                                     the (16,16) window origin as orbx_debug_candidates returns them
+ *   sel_counts[image * nlevels + level], sel[((image * nlevels + level) * sel_cap + i) * 3 ..]   the selected keys in list
+ *                                     order as (x, y, response), x, y in level coordinates
+ * Sets the handle's geometry and image count like an extraction (orbx_debug_candidates and orbx_level_stats work afterwards;
+ * pyramid, keypoints and descriptors of the handle are NOT those of this call).  ORBX_E_CAPACITY when a level selects more than
+ * sel_cap keys.  Everything orbx_debug_octree_check rejects is rejected here before anything is written or launched. */
+int orbx_debug_octree(orbx_extractor* ex, int width, int height, int n_images, const int32_t* counts, const int32_t* xyr,
+                      int32_t* sel_counts, int32_t* sel, int sel_cap);
+/* The argument check of orbx_debug_octree (host only, no device), for an extractor of parameters p: ORBX_E_BADARG for a
+ * coordinate outside the level's detectable window (3 <= x < 3 + min(W - 6, nCols * wCell) with W = level width - 32, likewise
+ * y), a response outside 1 .. 255, a pixel given twice, a FAST cell with more candidates than its slots (cellCap), a level with
+ * more than its dense list holds (candCap) -- no crafted input makes the kernel index outside its tables. */
+int orbx_debug_octree_check(const orbx_params* p, int width, int height, int n_images, const int32_t* counts, const int32_t* xyr);
 
 /* ---- ORBmatcher / Frame matching -------------------------------------------------------------------- */
 
@@ -1917,6 +1937,11 @@ int orbx_copy_probe(int device, size_t bytes, int iters, double* gbps);
 void orbx_debug_introsort(uint64_t* v, int n);
 /* The wave-cooperative device version the quadtree kernel actually runs (n <= 4000). */
 int orbx_debug_introsort_device(int device, uint64_t* v, int n);
+/* The same with the workgroup named: nt = 64 is the single-wave form (introsort_wave), 128 / 256 / 512 the workgroup form
+ * (introsort_block) with that many threads -- the three classes k_octree runs; the waves per round and the lanes per element of
+ * the final rank (4 / 2 / 1, by 4 n <= nt and 2 n <= nt) depend on it.  (orbx_debug_introsort_device alternates 512 and 64
+ * from call to call.) */
+int orbx_debug_introsort_device_nt(int device, uint64_t* v, int n, int nt);
 /* The small dense linear algebra of the geometric solvers (csrc/orbx_linalg.h), each function alone on n items of the caller's:
  * the kernels load an item, call the header's function and store what it returns.  in / out are packed arrays of items, doubles
  * unless stated.  out is read as well as written: where a function leaves an output untouched (jacobi_cs returning false, a

@@ -209,6 +209,10 @@ def lib():
         L.orbx_debug_introsort.argtypes = [vp, i]
         L.orbx_debug_introsort.restype = None
         L.orbx_debug_introsort_device.argtypes = [i, vp, i]
+        if hasattr(L, "orbx_debug_octree"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
+            L.orbx_debug_introsort_device_nt.argtypes = [i, vp, i, i]
+            L.orbx_debug_octree.argtypes = [vp, i, i, i, vp, vp, vp, vp, i]
+            L.orbx_debug_octree_check.argtypes = [vp, i, i, i, vp, vp]
         L.orbx_debug_linalg.argtypes = [i, i, i, vp, vp]
         L.orbx_debug_geometry.argtypes = [i, i, i, vp, vp]
         L.orbx_pose_inertial_optimization_last_keyframe.argtypes = [i, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, vp, vp]
@@ -655,6 +659,18 @@ class ORBextractor:
         out = np.zeros((cap, 3), np.int32)
         n = _check(lib().orbx_debug_candidates(self._h, image, level, _p(out), cap))
         return out[:n].copy()
+
+    def debug_octree(self, width, height, candidates):
+        """k_octree alone on the caller's candidates (orbx_debug_octree): candidates[image][level] = (n, 3) integers (x, y,
+        response), x, y relative to the (16,16) window origin, in any order.  Returns selected[image][level] = (m, 3) int32 (x, y,
+        response) in list order, level coordinates.  The launch is the one an extraction of len(candidates) images makes."""
+        counts, flat = _octree_candidates(candidates, self.nlevels)
+        n = len(candidates)
+        cap = int(self._nfeat.max()) + 64
+        nsel = np.zeros(n * self.nlevels, np.int32)
+        sel = np.zeros((n, self.nlevels, cap, 3), np.int32)
+        _check(lib().orbx_debug_octree(self._h, int(width), int(height), n, _p(counts), _p(flat), _p(nsel), _p(sel), cap))
+        return [[sel[i, l, :nsel[i * self.nlevels + l]].copy() for l in range(self.nlevels)] for i in range(n)]
 
     def debug_fill_work_buffers(self, byte):
         """Test hook: every device buffer of the handle that a call produces before it reads it set to `byte`
@@ -2231,6 +2247,36 @@ def octree_plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, he
     nt, lds = np.zeros(int(nlevels), np.int32), np.zeros(int(nlevels), np.int32)
     _check(lib().orbx_debug_octree_plan(C.byref(prm), width, height, _p(nt), _p(lds)))
     return nt, lds
+
+
+def _octree_candidates(candidates, nlevels):
+    """candidates[image][level] -> (counts[image * nlevels + level], the triples back to back) as orbx_debug_octree takes them."""
+    counts, parts = [], [np.zeros((0, 3), np.int32)]
+    for per_level in candidates:
+        if len(per_level) != nlevels:
+            raise ValueError("one candidate array per level")
+        for c in per_level:
+            c = np.asarray(c, np.int32).reshape(-1, 3)
+            counts.append(len(c))
+            parts.append(c)
+    return np.array(counts, np.int32), np.ascontiguousarray(np.concatenate(parts))
+
+
+def octree_check(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, candidates):
+    """The argument check of ORBextractor.debug_octree (orbx_debug_octree_check; host only, no device): raises OrbxError(E_BADARG)
+    for a candidate outside the detectable window, a response outside 1 .. 255, a pixel given twice, a FAST cell or a level with
+    more candidates than it holds."""
+    prm = _Params(int(nfeatures), float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
+    counts, flat = _octree_candidates(candidates, int(nlevels))
+    _check(lib().orbx_debug_octree_check(C.byref(prm), int(width), int(height), len(candidates), _p(counts), _p(flat)))
+
+
+def introsort_device(v, nt, device=0):
+    """orbx_debug_introsort_device_nt: the device's std::sort replica on a copy of the uint64 array v; nt = 64 (one wave) or the
+    workgroup form with 128 / 256 / 512 threads."""
+    a = np.array(v, np.uint64)
+    _check(lib().orbx_debug_introsort_device_nt(int(device), _p(a), len(a), int(nt)))
+    return a
 
 
 def describe_plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, n_images):

@@ -1516,6 +1516,124 @@ int orbx_debug_candidates(orbx_extractor* ex, int image, int level, int32_t* xys
   return n;
 }
 
+// orbx_debug_octree's argument check against the geometry g (host only).  cellOf (optional) receives every candidate's FAST cell.
+static int check_octree_candidates(const Geom& g, int n_images, const int32_t* counts, const int32_t* xyr, std::vector<int>* cellOf) {
+  if (n_images < 1 || !counts) return fail(ORBX_E_BADARG, "bad argument");
+  long long total = 0;
+  for (int i = 0; i < n_images * g.nlevels; i++) {
+    if (counts[i] < 0) return fail(ORBX_E_BADARG, "negative candidate count");
+    if (counts[i] > g.lv[i % g.nlevels].candCap) return fail(ORBX_E_BADARG, "more candidates than the level's dense list holds (candCap)");
+    total += counts[i];
+  }
+  if (total > 0 && !xyr) return fail(ORBX_E_BADARG, "bad argument");
+  if (cellOf) cellOf->assign((size_t)total, 0);
+  std::vector<int> perCell;
+  std::vector<uint32_t> seen;
+  size_t k = 0;
+  for (int img = 0; img < n_images; img++)
+    for (int l = 0; l < g.nlevels; l++) {
+      const LevelDev& L = g.lv[l];
+      const int n = counts[img * g.nlevels + l];
+      // the detectable pixels of the level's cells (build_cell_records), relative to the (16,16) window origin
+      const int x1 = 3 + std::min(L.w - 2 * kBorder - 6, L.nCols * L.wCell), y1 = 3 + std::min(L.h - 2 * kBorder - 6, L.nRows * L.hCell);
+      perCell.assign((size_t)L.nCols * L.nRows, 0);
+      seen.clear();
+      for (int i = 0; i < n; i++, k++) {
+        const int x = xyr[3 * k], y = xyr[3 * k + 1], r = xyr[3 * k + 2];
+        if (x < 3 || x >= x1 || y < 3 || y >= y1) return fail(ORBX_E_BADARG, "candidate outside the level's detectable window");
+        if (r < 1 || r > 255) return fail(ORBX_E_BADARG, "candidate response outside 1 .. 255");
+        const int cell = ((y - 3) / L.hCell) * L.nCols + (x - 3) / L.wCell;
+        if (++perCell[cell] > L.cellCap) return fail(ORBX_E_BADARG, "more candidates in one FAST cell than it has slots (cellCap)");
+        seen.push_back((uint32_t)y << 12 | (uint32_t)x);
+        if (cellOf) (*cellOf)[k] = cell;
+      }
+      std::sort(seen.begin(), seen.end());
+      if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(ORBX_E_BADARG, "candidate pixel given twice");
+    }
+  return ORBX_OK;
+}
+
+int orbx_debug_octree_check(const orbx_params* p, int width, int height, int n_images, const int32_t* counts, const int32_t* xyr) {
+  if (!p || width < 1 || height < 1 || p->nlevels < 1 || p->nlevels > ORBX_MAX_LEVELS || p->nfeatures < 1 || !(p->scale_factor > 1.0f))
+    return fail(ORBX_E_BADARG, "bad argument");
+  std::unique_ptr<orbx_extractor> ex(new orbx_extractor());   // parameters and tables only: no device, no buffers
+  ex->prm = *p;
+  build_tables(ex.get());
+  Geom g;
+  std::string why;
+  const int rc = build_geom(ex.get(), width, height, g, why);
+  if (rc != ORBX_OK) return fail(rc, why);
+  return check_octree_candidates(g, n_images, counts, xyr, nullptr);
+}
+
+int orbx_debug_octree(orbx_extractor* ex, int width, int height, int n_images, const int32_t* counts, const int32_t* xyr,
+                      int32_t* sel_counts, int32_t* sel, int sel_cap) {
+  if (!ex || !sel_counts || !sel || sel_cap < 0 || n_images < 1 || n_images > ex->maxB || width < 1 || height < 1)
+    return fail(ORBX_E_BADARG, "bad argument");
+  {  // the whole check on a geometry of the host's, before the handle or the device is touched
+    const int rc = orbx_debug_octree_check(&ex->prm, width, height, n_images, counts, xyr);
+    if (rc != ORBX_OK) return rc;
+  }
+  HIPC(hipSetDevice(ex->device));
+  int rc = configure(ex, width, height);
+  if (rc != ORBX_OK) return rc;
+  const Geom& g = ex->g;
+  std::vector<int> cellOf;
+  rc = check_octree_candidates(g, n_images, counts, xyr, &cellOf);   // (the handle's geometry is the one just checked)
+  if (rc != ORBX_OK) return rc;
+  hipStream_t s = ex->stream;
+  HIPC(hipStreamSynchronize(s));
+  ex->lastN = n_images;   // per-extraction state, as prepare_extract resets it
+  ex->lastEvValid = false;
+  ex->blurValid = false;
+  ex->lastStereoPairs = 0;
+  ex->hostPyrImages = 0;
+  // k_detect's output: per-cell counts and slots, strided by the handle's maximum geometry (g.totalCells, g.cellImg)
+  std::vector<int> cnt((size_t)n_images * g.totalCells, 0);
+  std::vector<uint32_t> slots((size_t)n_images * g.cellImg, 0u);
+  size_t k = 0;
+  for (int img = 0; img < n_images; img++)
+    for (int l = 0; l < g.nlevels; l++) {
+      const LevelDev& L = g.lv[l];
+      for (int i = 0; i < counts[img * g.nlevels + l]; i++, k++) {
+        const int cell = cellOf[k];
+        int& c = cnt[(size_t)img * g.totalCells + L.cellStart + cell];
+        slots[(size_t)img * g.cellImg + L.cellOff + (size_t)cell * L.cellCap + c++] = pack_key(xyr[3 * k], xyr[3 * k + 1], xyr[3 * k + 2]);
+      }
+    }
+  HIPC(hipMemcpy(ex->d_cellCount.p, cnt.data(), cnt.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!slots.empty()) HIPC(hipMemcpy(ex->d_cellCand.p, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  {  // the launch decision of record_pipeline
+    const int forced = debug_octree_class();
+    if (!forced && n_images > g_lat_max_images) {
+      HIPC(launch_octree_mixed(g, ex->octPlan, n_images, ex->d_cellCand.p, ex->d_cellCount.p, ex->d_cand.p, ex->d_candCount.p,
+                               ex->d_knode.p, ex->d_sel.p, ex->d_selCount.p, s));
+    } else {
+      HIPC(launch_octree(g, n_images, ex->d_cellCand.p, ex->d_cellCount.p, ex->d_cellPrefix.p, ex->d_cand.p, ex->d_candCount.p,
+                         ex->d_knode.p, ex->d_sel.p, ex->d_selCount.p, 0, g.nlevels, forced ? forced : 512, s));
+    }
+  }
+  HIPC(hipStreamSynchronize(s));
+  const int L = g.nlevels;
+  HIPC(hipMemcpy(sel_counts, ex->d_selCount.p, (size_t)n_images * L * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> hs((size_t)n_images * g.selImg);
+  HIPC(hipMemcpy(hs.data(), ex->d_sel.p, hs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int img = 0; img < n_images; img++)
+    for (int l = 0; l < L; l++) {
+      const int n = sel_counts[img * L + l];
+      if (n < 0 || n > g.lv[l].selCap) return fail(ORBX_E_HIP, "k_octree returned a count outside the level's slots");
+      if (n > sel_cap) return fail(ORBX_E_CAPACITY, "a level selected more keys than sel_cap");
+      for (int i = 0; i < n; i++) {
+        const uint32_t key = hs[(size_t)img * g.selImg + g.lv[l].selOff + i];
+        int32_t* o = sel + ((size_t)(img * L + l) * sel_cap + i) * 3;
+        o[0] = key_x(key);
+        o[1] = key_y(key);
+        o[2] = key_r(key);
+      }
+    }
+  return ORBX_OK;
+}
+
 int orbx_debug_front_tables(const orbx_params* p, int width, int height, uint32_t* cells, int cells_cap, uint32_t* tiles,
                             int tiles_cap, int32_t info[4]) {
   if (!p || !info || width < 1 || height < 1 || cells_cap < 0 || tiles_cap < 0 || (cells_cap && !cells) || (tiles_cap && !tiles) ||
@@ -1912,14 +2030,20 @@ int orbx_debug_resize_plan(const orbx_extractor* ex, int32_t* first_level, int32
   return n;
 }
 int orbx_debug_introsort_device(int device, uint64_t* v, int n) {
+  static int flip = 0;  // alternate the workgroup and the single-wave version: the test calls this many times
   if (!v || n < 0 || n > 4000) return fail(ORBX_E_BADARG, "bad argument");
+  if (n == 0) return ORBX_OK;
+  return orbx_debug_introsort_device_nt(device, v, n, (flip++ & 1) ? 64 : 512);
+}
+int orbx_debug_introsort_device_nt(int device, uint64_t* v, int n, int nt) {
+  if (!v || n < 0 || n > 4000 || (nt != 64 && nt != 128 && nt != 256 && nt != 512)) return fail(ORBX_E_BADARG, "bad argument");
   if (n == 0) return ORBX_OK;
   int rc = set_device(device);
   if (rc != ORBX_OK) return rc;
   ScratchBuf<uint64_t> d;
   HIPC(d.alloc(n));
   hipError_t e = hipMemcpy(d.p, v, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_debug_sort(d.p, n, nullptr);
+  if (e == hipSuccess) e = launch_debug_sort(d.p, n, nt, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(v, d.p, (size_t)n * 8, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(ORBX_E_HIP, hipGetErrorString(e));

@@ -586,7 +586,7 @@ void debug_set_clahe_cell_kernel(int on);
 void debug_set_octree_global(int on);
 void debug_set_octree_class(int nt);   // test hook: 0 = the plan, 128 / 256 / 512 = that block size for every level, one launch
 int debug_octree_class();
-hipError_t launch_debug_sort(uint64_t* d_v, int n, hipStream_t s);
+hipError_t launch_debug_sort(uint64_t* d_v, int n, int nt /* 64 = one wave, 128 / 256 / 512 */, hipStream_t s);
 hipError_t launch_debug_sincos(const float* ang, int n, int fused, float* s, float* c, hipStream_t st);
 hipError_t launch_debug_fast_atan2(const float* y, const float* x, int n, float* out, hipStream_t st);
 void debug_describe_plan(const Geom& g, int nimg, int32_t* out);   // nk, tasks, magic, taskOff[ORBX_MAX_LEVELS] of launch_describe

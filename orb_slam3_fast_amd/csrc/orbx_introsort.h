@@ -9,7 +9,7 @@
 // __unguarded_partition_pivot, __final_insertion_sort; bits/stl_heap.h).
 //
 // Elements are uint64; `Less` compares the KEY part only (the payload bits ride along), which is exactly
-// how equivalent elements behave under std::sort.  tests/test_host_logic.py checks this replica against
+// how equivalent elements behave under std::sort.  tests/test_abi.py checks this replica against
 // std::sort on tie-heavy inputs through orbx_debug_introsort.
 #pragma once
 #include <stdint.h>

@@ -350,8 +350,8 @@ __device__ __forceinline__ void introsort_block(uint64_t* a, int n, uint64_t* tm
   }
 }
 
-// Test entry: sort n elements (one block, dynamic LDS): 512 threads = the workgroup version the quadtree runs,
-// 64 threads = the single-wave version.
+// Test entry: sort n elements (one block, dynamic LDS): 128 / 256 / 512 threads = the workgroup version the quadtree runs with
+// its three classes, 64 threads = the single-wave version.
 __global__ __launch_bounds__(512) void k_debug_sort(uint64_t* v, int n) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint64_t* a = reinterpret_cast<uint64_t*>(smem);
@@ -367,13 +367,13 @@ __global__ __launch_bounds__(512) void k_debug_sort(uint64_t* v, int n) {
   __syncthreads();
   for (int i = tid; i < n; i += blockDim.x) v[i] = a[i];
 }
-hipError_t launch_debug_sort(uint64_t* d_v, int n, hipStream_t s) {
+hipError_t launch_debug_sort(uint64_t* d_v, int n, int nt, hipStream_t s) {
+  if (nt != 64 && nt != 128 && nt != 256 && nt != 512) return hipErrorInvalidValue;
   const size_t lds = (size_t)n * 16 + 516 * 4 + (size_t)(2 * n + 16) * 2 + 64;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_debug_sort),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  static int flip = 0;  // alternate the two versions: the test calls this many times
-  hipLaunchKernelGGL(k_debug_sort, dim3(1), dim3((flip++ & 1) ? 64 : 512), lds, s, d_v, n);
+  hipLaunchKernelGGL(k_debug_sort, dim3(1), dim3(nt), lds, s, d_v, n);
   return hipGetLastError();
 }
 

@@ -462,6 +462,38 @@ def test_sim3_ransac_parameters(args, expect):
     assert orbx.lib().orbx_sim3_ransac_parameters(*args, None) == 0
 
 
+def _octree_grid(n, x0=3, y0=3, w=50):
+    """n distinct pixels, row by row from (x0, y0) in rows of w."""
+    return [(x0 + i % w, y0 + i // w, 20) for i in range(n)]
+
+
+# orbx_debug_octree (k_octree alone on the caller's candidates): everything it rejects is rejected by orbx_debug_octree_check, on the
+# host, before a handle or the device is touched.  Window 100 x 38 (frame 132 x 70, one level): 2 x 1 FAST cells of 50 x 38 px with
+# 25 * 19 = 475 slots each, a dense list of 52 * 21 = 1092 candidates, detectable pixels 3 <= x < 97, 3 <= y < 35.
+@pytest.mark.parametrize("cand,msg", [
+    ([(2, 10, 20)], "candidate outside the level's detectable window"),
+    ([(97, 10, 20)], "candidate outside the level's detectable window"),
+    ([(10, 2, 20)], "candidate outside the level's detectable window"),
+    ([(10, 35, 20)], "candidate outside the level's detectable window"),
+    ([(-1, 10, 20)], "candidate outside the level's detectable window"),
+    ([(10, 10, 0)], "candidate response outside 1 .. 255"),
+    ([(10, 10, 256)], "candidate response outside 1 .. 255"),
+    ([(10, 10, 20), (11, 10, 20), (10, 10, 21)], "candidate pixel given twice"),
+    (_octree_grid(476), "more candidates in one FAST cell than it has slots (cellCap)"),
+    (_octree_grid(1093, w=94), "more candidates than the level's dense list holds (candCap)"),
+])
+def test_debug_octree_rejections(cand, msg):
+    with pytest.raises(orbx.OrbxError) as e:
+        orbx.octree_check(40, 1.2, 1, 20, 7, 132, 70, [[np.zeros((0, 3), np.int32)], [cand]])   # (in the second image of two)
+    assert e.value.code == E_BADARG and orbx.lib().orbx_last_error().decode() == msg
+
+
+def test_debug_octree_accepts_the_limits():
+    edge = [(3, 3, 1), (96, 34, 255), (96, 3, 255), (3, 34, 1)]
+    orbx.octree_check(40, 1.2, 1, 20, 7, 132, 70, [[edge], [_octree_grid(475)], [_octree_grid(475) + _octree_grid(475, x0=53, w=44)]])
+    orbx.octree_check(40, 1.2, 1, 20, 7, 132, 70, [[[]]])
+
+
 def test_ransac_parameters_negative_count():
     rejected(orbx.lib().orbx_mlpnp_ransac_parameters(-1, 0.99, 8, 300, 6, 0.4, None, None, None), "negative count")
     rejected(orbx.lib().orbx_sim3_ransac_parameters(-1, 0.99, 6, 300, None), "negative count")
