@@ -2085,6 +2085,26 @@ int orbx_debug_remap_footprints(const float* map_x, const float* map_y, ptrdiff_
  * ORBX_E_CAPACITY when a cap (in dwords) is too small. */
 int orbx_debug_front_tables(const orbx_params* p, int width, int height, uint32_t* cells, int cells_cap, uint32_t* tiles,
                             int tiles_cap, int32_t info[4]);
+/* The lane tables of k_resize_stream (the batched path's pyramid kernel for the levels k_resize_tail does not fuse: one-wave
+ * workgroups, a lane per destination quad) as orbx_extractor_configure builds them for a width x height frame, for strips of
+ * `quads` quads (32 or 64).  Host only: touches no device and works without one.  Per level >= 1 and strip, three blocks of `quads`
+ * entries of four dwords, one entry per lane: {v_perm selectors of the quad's four columns: byte of S[sx] | 0x0c000c00 | byte of
+ * S[sx + 1] << 16 within the lane's 8 loaded bytes}, {a0 | a1 << 16 of the four columns}, {byte offset of the lane's 8-byte load
+ * in a source row, 4 * quad (the first destination column; 0xFFFFFFFF for a lane past the level's last quad, which repeats its
+ * entries), 0, 0}.  level_off[ORBX_MAX_LEVELS] receives each level's first dword, -1 for level 0 and for a level that cannot
+ * stream (a quad's source bytes span more than 8, or its source level is narrower than 8 pixels: it stays with k_resize).
+ * Returns the dwords of the tables; lanes may be NULL (size and offsets only); ORBX_E_CAPACITY when lanes_cap (in dwords) is too
+ * small. */
+int orbx_debug_resize_stream_tables(const orbx_params* p, int width, int height, int quads, uint32_t* lanes, int lanes_cap,
+                                    int32_t* level_off);
+/* Test hook of k_resize_stream: builds levels 1 .. nlevels - 1 of n_images frames in device memory (any byte address for kernel
+ * 1; row_pitch >= w) into the handle's pyramid with ONE kernel for every level -- kernel 1 = k_resize_stream with strips of `quads`
+ * quads (32 / 64, 0 = what the batched path uses) and bands of `band` destination rows (0 = likewise), whatever the batch size;
+ * kernel 0 = the tiled k_resize (4-byte aligned frames and pitches) -- and synchronises.  orbx_pyramid_download then returns the
+ * levels.  Changes no setting of the handle: its extractions launch what they launched before.  ORBX_E_UNSUPPORTED when a level
+ * cannot stream. */
+int orbx_debug_resize_stream(orbx_extractor* ex, const uint8_t* d_images, int n_images, int w, int h, ptrdiff_t row_pitch,
+                             ptrdiff_t image_pitch, int kernel, int quads, int band);
 /* What a pre-processing plan decided at creation and what its LAST enqueue (orbx_preproc_run / _run_device,
  * orbx_extract_batch_raw_device) launched, from the expressions that pick the launch:
  *   info[0] k_remap_lds table built (0 / 1)          info[1] single-channel resize fast path prepared (0 / 1)

@@ -242,6 +242,9 @@ def lib():
         L.orbx_debug_preproc_plan.argtypes = [vp, vp]
         if hasattr(L, "orbx_debug_front_tables"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
             L.orbx_debug_front_tables.argtypes = [vp, i, i, vp, i, vp, i, vp]
+        if hasattr(L, "orbx_debug_resize_stream"):   # (ORBX_LIB_NAME may name an older build in A/B runs)
+            L.orbx_debug_resize_stream_tables.argtypes = [vp, i, i, i, vp, i, vp]
+            L.orbx_debug_resize_stream.argtypes = [vp, vp, i, i, i, C.c_ssize_t, C.c_ssize_t, i, i, i]
         L.orbx_debug_set_resize_tail.argtypes = [i, i, i]
         L.orbx_debug_set_resize_tail.restype = None
         L.orbx_debug_resize_plan.argtypes = [vp, vp, vp, vp, i]
@@ -671,6 +674,13 @@ class ORBextractor:
         sel = np.zeros((n, self.nlevels, cap, 3), np.int32)
         _check(lib().orbx_debug_octree(self._h, int(width), int(height), n, _p(counts), _p(flat), _p(nsel), _p(sel), cap))
         return [[sel[i, l, :nsel[i * self.nlevels + l]].copy() for l in range(self.nlevels)] for i in range(n)]
+
+    def debug_resize_stream(self, d_images_ptr, n_images, w, h, row_pitch, image_pitch, kernel=1, quads=0, band=0):
+        """Test hook (orbx_debug_resize_stream): levels 1.. of n_images device frames into the handle's pyramid with one kernel
+        for every level -- kernel 1 = k_resize_stream (strips of `quads` quads, bands of `band` rows; 0 = the batched path's),
+        kernel 0 = the tiled k_resize -- whatever the batch size; synchronises.  pyramid_download(i) returns the levels."""
+        _check(lib().orbx_debug_resize_stream(self._h, C.c_void_p(d_images_ptr), int(n_images), int(w), int(h), int(row_pitch),
+                                              int(image_pitch), int(kernel), int(quads), int(band)))
 
     def debug_fill_work_buffers(self, byte):
         """Test hook: every device buffer of the handle that a call produces before it reads it set to `byte`
@@ -2238,6 +2248,19 @@ def front_tables(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, h
     _check(lib().orbx_debug_front_tables(C.byref(prm), width, height, _p(cells), cells.size, _p(tiles) if tiles.size else None,
                                          tiles.size, _p(info)))
     return cells, tiles, int(info[2]), int(info[3])
+
+
+def resize_stream_tables(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height, quads=64):
+    """k_resize_stream's lane tables at this frame size (orbx_debug_resize_stream_tables; host only, no device): a list with
+    one uint32 array [strips, 3, quads, 4] per level (None for level 0 and for a level that cannot stream)."""
+    prm = _Params(int(nfeatures), float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
+    off = np.zeros(12, np.int32)   # ORBX_MAX_LEVELS
+    n = _check(lib().orbx_debug_resize_stream_tables(C.byref(prm), width, height, quads, None, 0, _p(off)))
+    tab = np.zeros(n, np.uint32)
+    _check(lib().orbx_debug_resize_stream_tables(C.byref(prm), width, height, quads, _p(tab) if n else None, n, _p(off)))
+    ends = sorted([int(o) for o in off if o >= 0] + [n])
+    return [tab[o:ends[ends.index(int(o)) + 1]].reshape(-1, 3, quads, 4) if l < nlevels and o >= 0 else None
+            for l, o in enumerate(off[:nlevels])]
 
 
 def octree_plan(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, width, height):

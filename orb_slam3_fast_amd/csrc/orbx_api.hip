@@ -230,6 +230,45 @@ void build_resize_records(const Geom& g, const std::vector<uint4>& xtab, const s
   }
 }
 
+// The lane tables of k_resize_stream for strips of `quads` quads (64 or 32): per level l >= 1 and strip, three blocks of `quads`
+// uint4 (StreamLv::lanes).  laneOff[l] = the level's first uint4 in `tab`, -1 where the level cannot stream (a quad's source bytes
+// span more than 8, or the source level is narrower than 8): such a level stays with k_resize.
+void build_resize_stream(const Geom& g, const std::vector<uint4>& xtab, int quads, std::vector<uint4>& tab, int* laneOff) {
+  tab.clear();
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) laneOff[l] = -1;
+  for (int l = 1; l < g.nlevels; l++) {
+    const LevelDev &D = g.lv[l], &S = g.lv[l - 1];
+    const int nq = (D.w + 3) / 4, nStrips = (nq + quads - 1) / quads;
+    if (S.w < 8) continue;
+    std::vector<uint4> lv((size_t)nStrips * 3 * quads);
+    bool ok = true;
+    for (int qi = 0; qi < nStrips * quads && ok; qi++) {
+      const int qv = std::min(qi, nq - 1);            // lanes past the last quad: its entries again, marked "no store"
+      const uint4* e = &xtab[(size_t)D.xcoef + 4 * qv];   // (each level of xtab is padded to whole 256-column blocks with its last column)
+      int lo = (int)e[0].x, hi = lo;
+      for (int j = 0; j < 4; j++) {
+        lo = std::min(lo, (int)e[j].x);
+        hi = std::max(hi, std::min((int)e[j].x + 1, S.w - 1));
+      }
+      const int off = std::min(lo, S.w - 8);
+      if (hi - off > 7) { ok = false; break; }
+      uint32_t sel[4], cf[4];
+      for (int j = 0; j < 4; j++) {
+        const uint32_t b0 = (uint32_t)((int)e[j].x - off), b1 = (uint32_t)(std::min((int)e[j].x + 1, S.w - 1) - off);
+        sel[j] = b0 | 0x0c000c00u | (b1 << 16);       // v_perm: {S0, 0, S1, 0} from the 8 loaded bytes
+        cf[j] = e[j].w;
+      }
+      uint4* o = &lv[(size_t)(qi / quads) * 3 * quads + qi % quads];
+      o[0] = make_uint4(sel[0], sel[1], sel[2], sel[3]);
+      o[quads] = make_uint4(cf[0], cf[1], cf[2], cf[3]);
+      o[2 * quads] = make_uint4((uint32_t)off, qi < nq ? (uint32_t)(4 * qi) : 0xFFFFFFFFu, 0u, 0u);
+    }
+    if (!ok) continue;
+    laneOff[l] = (int)tab.size();
+    tab.insert(tab.end(), lv.begin(), lv.end());
+  }
+}
+
 // ---- k_detect's per-cell records: the cell loop's bounds (src/ORBextractor.cc:892-919) and the constants of the stage-1 rounds
 // for every FAST cell of the size, in the order of the cell numbers (level, cell row, cell column).
 void build_cell_records(const Geom& g, std::vector<CellRec>& recs) {
@@ -505,6 +544,10 @@ int configure(orbx_extractor* ex, int w, int h) {
     build_resize_records(g, xtab, yrow, yab, rec);
     if (ex->d_rsRec.n < rec.size()) HIPC(ex->d_rsRec.alloc(rec.size()));
     if (!rec.empty()) HIPC(hipMemcpy(ex->d_rsRec.p, rec.data(), rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    std::vector<uint4> lanes;
+    build_resize_stream(g, xtab, kStreamQuads, lanes, ex->rsStreamOff);
+    if (ex->d_rsStream.n < lanes.size()) return fail(ORBX_E_CAPACITY, "lane tables larger than the handle's maximum size allows");
+    if (!lanes.empty()) HIPC(hipMemcpy(ex->d_rsStream.p, lanes.data(), lanes.size() * sizeof(uint4), hipMemcpyHostToDevice));
   }
   HIPC(hipMemcpy(ex->d_yab.p, yab.data(), yab.size() * sizeof(short), hipMemcpyHostToDevice));
   {
@@ -639,7 +682,12 @@ static int enqueue_pyramid(orbx_extractor* ex, hipStream_t s, int img0, int n) {
       HIPC(launch_resize_tail(g, ex->pyr, tp, ex->d_tailBands.p + tp.bandOff, 0, n, ex->d_xtab.p, ex->d_yofs.p, ex->d_yab.p, s));
       l += tp.nT;
     } else {
-      HIPC(launch_resize(g, ex->pyr, n, l, ex->d_xtab.p, ex->d_yrow.p, ex->d_yab.p, ex->d_rsRec.p, s));
+      // batches: streaming waves (no LDS, no barrier); up to g_lat_max_images images without a cascade plan: the tile kernel
+      if (n > g_lat_max_images && resize_stream_ok(g, ex->pyr, l, kStreamQuads, ex->rsStreamOff))
+        HIPC(launch_resize_stream(g, ex->pyr, n, l, ex->d_rsStream.p + ex->rsStreamOff[l], kStreamQuads, kStreamBand, ex->d_yrow.p,
+                                  ex->d_yab.p, s));
+      else
+        HIPC(launch_resize(g, ex->pyr, n, l, ex->d_xtab.p, ex->d_yrow.p, ex->d_yab.p, ex->d_rsRec.p, s));
       l++;
     }
   }
@@ -834,6 +882,11 @@ int orbx_extractor_create(const orbx_params* p, int max_width, int max_height, i
       trows += (m.lv[l].h + 15) / 16 + 1;
     }
     ok(ex->d_rsRec.alloc((size_t)8 * tiles + 64 * trows + 64));
+  }
+  {  // k_resize_stream's lane tables: no level of a smaller size is wider than the same level of the largest one (+ one strip of rounding)
+    size_t lanes = 0;
+    for (int l = 1; l < m.nlevels; l++) lanes += (size_t)(((m.lv[l].w + 3) / 4 + kStreamQuads - 1) / kStreamQuads + 1) * 3 * kStreamQuads;
+    ok(ex->d_rsStream.alloc(lanes + 64));
   }
   ok(ex->d_yofs.alloc(ny + 64));
   ok(ex->d_yrow.alloc(ny + 64));
@@ -1664,6 +1717,76 @@ int orbx_debug_front_tables(const orbx_params* p, int width, int height, uint32_
     if (rec.size() > (size_t)tiles_cap) return fail(ORBX_E_CAPACITY, "tile records larger than tiles_cap");
     std::memcpy(tiles, rec.data(), rec.size() * sizeof(uint32_t));
   }
+  return ORBX_OK;
+}
+
+int orbx_debug_resize_stream_tables(const orbx_params* p, int width, int height, int quads, uint32_t* lanes, int lanes_cap,
+                                    int32_t* level_off) {
+  if (!p || !level_off || width < 1 || height < 1 || lanes_cap < 0 || (lanes_cap && !lanes) || (quads != 32 && quads != 64) ||
+      p->nlevels < 1 || p->nlevels > ORBX_MAX_LEVELS || p->nfeatures < 1 || !(p->scale_factor > 1.0f))
+    return fail(ORBX_E_BADARG, "bad argument");
+  std::unique_ptr<orbx_extractor> ex(new orbx_extractor());   // parameters and tables only: no device, no buffers
+  ex->prm = *p;
+  build_tables(ex.get());
+  Geom g;
+  std::string why;
+  const int rc = build_geom(ex.get(), width, height, g, why);
+  if (rc != ORBX_OK) return fail(rc, why);
+  std::vector<uint4> xtab, tab;
+  std::vector<int> yofs;
+  std::vector<short> yab;
+  int off[ORBX_MAX_LEVELS];
+  build_coefs(g, xtab, yofs, yab);
+  build_resize_stream(g, xtab, quads, tab, off);
+  for (int l = 0; l < ORBX_MAX_LEVELS; l++) level_off[l] = off[l] < 0 ? -1 : 4 * off[l];
+  if (lanes) {
+    if (tab.size() * 4 > (size_t)lanes_cap) return fail(ORBX_E_CAPACITY, "lane tables larger than lanes_cap");
+    if (!tab.empty()) std::memcpy(lanes, tab.data(), tab.size() * sizeof(uint4));
+  }
+  return (int)(tab.size() * 4);
+}
+
+int orbx_debug_resize_stream(orbx_extractor* ex, const uint8_t* d_images, int n_images, int w, int h, ptrdiff_t row_pitch,
+                             ptrdiff_t image_pitch, int kernel, int quads, int band) {
+  if (!ex) return fail(ORBX_E_BADARG, "null handle");
+  if (!d_images || n_images <= 0 || w <= 0 || h <= 0) return fail(ORBX_E_EMPTY, "empty image");
+  if (n_images > ex->maxB) return fail(ORBX_E_CAPACITY, "batch larger than max_batch");
+  if (row_pitch < w || (kernel != 0 && kernel != 1)) return fail(ORBX_E_BADARG, "bad argument");
+  if (kernel == 0 && (((uintptr_t)d_images & 3) || (row_pitch & 3) || (image_pitch & 3)))
+    return fail(ORBX_E_BADARG, "k_resize needs 4-byte aligned images and pitches");
+  if (quads == 0) quads = kStreamQuads;
+  if (band == 0) band = kStreamBand;
+  if ((quads != 32 && quads != 64) || band < 1 || band > 4096) return fail(ORBX_E_BADARG, "strips of 32 or 64 quads, bands of 1 .. 4096 rows");
+  int rc = set_device(ex->device);
+  if (rc != ORBX_OK) return rc;
+  bool lapTrivial = true;
+  rc = prepare_extract(ex, d_images, n_images, w, h, row_pitch, image_pitch, nullptr, lapTrivial);
+  if (rc != ORBX_OK) return rc;
+  const Geom& g = ex->g;
+  hipStream_t s = ex->stream;
+  DevBuf<uint4> d_lanes;   // (freed behind the synchronisation below)
+  int off[ORBX_MAX_LEVELS];
+  if (kernel == 1) {
+    std::vector<uint4> xtab, tab;
+    std::vector<int> yofs;
+    std::vector<short> yab;
+    build_coefs(g, xtab, yofs, yab);
+    build_resize_stream(g, xtab, quads, tab, off);
+    for (int l = 1; l < g.nlevels; l++)
+      if (!resize_stream_ok(g, ex->pyr, l, quads, off)) return fail(ORBX_E_UNSUPPORTED, "level " + std::to_string(l) + " cannot stream");
+    if (!tab.empty()) {
+      HIPC(d_lanes.alloc(tab.size()));
+      HIPC(hipMemcpyAsync(d_lanes.p, tab.data(), tab.size() * sizeof(uint4), hipMemcpyHostToDevice, s));
+      HIPC(hipStreamSynchronize(s));   // (tab is pageable and leaves scope)
+    }
+  }
+  for (int l = 1; l < g.nlevels; l++) {
+    if (kernel == 1)
+      HIPC(launch_resize_stream(g, ex->pyr, n_images, l, d_lanes.p + off[l], quads, band, ex->d_yrow.p, ex->d_yab.p, s));
+    else
+      HIPC(launch_resize(g, ex->pyr, n_images, l, ex->d_xtab.p, ex->d_yrow.p, ex->d_yab.p, ex->d_rsRec.p, s));
+  }
+  HIPC(hipStreamSynchronize(s));
   return ORBX_OK;
 }
 

@@ -46,6 +46,7 @@ void build_cell_records(const Geom& g, std::vector<CellRec>& recs);   // orbx_ap
 void build_yrow(const Geom& g, const std::vector<int>& yofs, std::vector<uint32_t>& yrow);   // k_resize's clamped source row pairs
 void build_resize_records(const Geom& g, const std::vector<uint4>& xtab, const std::vector<uint32_t>& yrow, const std::vector<short>& yab,
                           std::vector<uint32_t>& tab);   // orbx_api.hip: k_resize's per-tile and per-tile-row records
+void build_resize_stream(const Geom& g, const std::vector<uint4>& xtab, int quads, std::vector<uint4>& tab, int* laneOff);   // k_resize_stream's lane tables
 inline int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
@@ -446,6 +447,8 @@ struct orbx_extractor {
   DevBuf<short> d_yab;
   DevBuf<uint4> d_xtab;  // k_resize's per-column table (build_coefs)
   DevBuf<uint32_t> d_rsRec;  // k_resize's tile records and tile-row blocks of the configured size (build_resize_records)
+  DevBuf<uint4> d_rsStream;  // k_resize_stream's lane tables of the configured size (build_resize_stream, strips of kStreamQuads quads)
+  int rsStreamOff[ORBX_MAX_LEVELS] = {};   // ... each level's first entry, -1 = the level stays with k_resize
   DevBuf<orbx::CellRec> d_cellRec;  // k_detect's per-cell records of the configured size (build_cell_records)
   orbx::OctPlan octPlan{};          // k_octree's class per level at the configured size (build_octree_plan)
   DevBuf<int> d_packCtr;    // arrival counter of the single-frame gather workgroups (launch_stereo_match)
@@ -562,6 +565,7 @@ struct orbx_extractor {
   TABLE(d_yab)         /* k_resize: vertical weights */                                                                  \
   TABLE(d_xtab)        /* k_resize: per-column table */                                                                  \
   TABLE(d_rsRec)       /* k_resize: tile records */                                                                      \
+  TABLE(d_rsStream)    /* k_resize_stream: lane tables */                                                                \
   TABLE(d_cellRec)     /* k_detect: per-cell records */                                                                  \
   STATE(d_packCtr)     /* arrival counter of the single-frame gather, with packCtrDirty */                               \
   TABLE(d_yrow)        /* k_resize: clamped source row pairs */                                                          \

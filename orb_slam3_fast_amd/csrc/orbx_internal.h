@@ -134,6 +134,12 @@ hipError_t launch_resize_plain(const uint8_t* src, int sw, int sh, long long sp,
 hipError_t launch_resize(const Geom& g, const Pyr& p, int nimg, int level, const uint4* xtab, const uint32_t* yofs /* clamped row pairs */,
                          const short* yab, const uint32_t* records, hipStream_t s);
 int resize_records_layout(const Geom& g, int level, int& tileOff, int& rowOff);
+// k_resize_stream (orbx_resize.hip): one-wave workgroups without LDS, for the levels of a batch.  lanes: the level's lane table
+// (build_resize_stream) for strips of `quads` quads; band: destination rows per wave
+constexpr int kStreamQuads = 32, kStreamBand = 16;   // what the batched path launches (profiles/resize_stream/variants.txt)
+bool resize_stream_ok(const Geom& g, const Pyr& p, int level, int quads, const int* laneOff);
+hipError_t launch_resize_stream(const Geom& g, const Pyr& p, int nimg, int level, const uint4* lanes, int quads, int band,
+                                const uint32_t* yrow, const short* yab, hipStream_t s);
 constexpr uint32_t kTileFast = 1u, kTileWhole = 2u;   // flags of a tile record (k_resize, orbx_resize.hip)
 hipError_t launch_detect(const Geom& g, const Pyr& p, const CellRec* cellRec, int nimg, uint32_t* cellCand, int* cellCount,
                          int level0, int level1, uint8_t* dbgScore, hipStream_t s);

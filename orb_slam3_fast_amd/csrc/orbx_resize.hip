@@ -1,5 +1,6 @@
 // orbx_resize.hip — k_resize: ComputePyramid (src/ORBextractor.cc:1108-1145), cv::resize INTER_LINEAR 8U, one
-// launch per level; also the whole-frame resize of the pre-processing plans (resize_plain_*).
+// launch per level; also the whole-frame resize of the pre-processing plans (resize_plain_*).  k_resize_stream (second half of
+// the file) is the form the level launches of a batch of more than two images take.
 #include "orbx_device.h"
 #include "orbx_prof.h"
 
@@ -407,6 +408,143 @@ hipError_t prepare_resize(const Geom& g) {
   hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<0, true>), lds);
   if (e == hipSuccess) e = raise_dynamic_lds(reinterpret_cast<const void*>(k_resize<kResizeNdw, true>), lds);
   return e;
+}
+
+// ================================================================================================ resize, streaming waves
+// k_resize_stream: the same cv::resize as k_resize without its block.  A workgroup is ONE wave, it uses no LDS and no barrier.
+// The wave owns a strip of QS destination quads and a band of destination rows; a lane owns one quad (four adjacent destination
+// pixels) for the whole walk.  The source bytes of a quad, S[sx(x0)] .. S[sx(x0 + 3) + 1], span at most 8 bytes (scale factors up
+// to ~1.6: build_resize_stream refuses the level otherwise), so a lane takes ONE 8-byte load per source row at any byte address
+// (as k_detect's tile loader: the memory pipeline runs in unaligned-access mode).  A load never leaves its source row: near the
+// right edge it starts at W - 8 and the byte selectors carry the difference.  The lane's load offset, v_perm selectors and
+// a0 | a1 << 16 come from the level's lane table (built beside the tile records, from the same xtab entries) and stay in registers.
+// The wave walks the source rows of its band in order, kStreamRows rows of loads in flight behind the rows being used; per source
+// row it forms the u16 quad (S0*a0 + S1*a1) >> 4 -- what k_resize's horizontal pass leaves in LDS -- and keeps the current and the
+// previous one.  When the next destination row's lower source row is the current row (wave-uniform; the row constants are scalar
+// loads from k_resize's row tables, fetched one destination row ahead) it blends the two with vblend4 and stores one dword.
+// QS = 32: the two half-waves take the same strip and band of two consecutive images (same tables, same control flow; the image
+// shows only in the lanes' 32-bit offsets), which fills the last strip of a level better; an odd batch idles the last half-wave.
+struct __attribute__((packed, aligned(1))) ResizeU64Unaligned { uint32_t x, y; };
+struct StreamLv {
+  const uint8_t* src; long long srcImg; int sp;      // level l-1 of image 0, bytes between images, row pitch
+  uint8_t* dst; long long dstImg; int dpitch;        // level l of image 0
+  int dh, ycoef;                                     // destination rows; the level's first entry in the row tables
+  int nStrips, band, nimg;                           // strips per band, destination rows per band, images
+  const uint4* lanes;                                // [strip][3][QS]: {sel x 4}, {a0 | a1 << 16 x 4}, {load offset, 4 * quad or ~0, 0, 0}
+};
+constexpr int kStreamRows = 4;   // source rows per batch of loads; two batches alternate (one in use, one in flight)
+template <int QS>
+__global__ __launch_bounds__(64) void k_resize_stream(StreamLv a, const uint32_t* __restrict__ yrow, const uint32_t* __restrict__ yab) {
+  static_assert(QS == 64 || QS == 32, "a strip is a wave or a half-wave of quads");
+  constexpr int K = kStreamRows;
+  const int lane = threadIdx.x;
+  const int q = lane & (QS - 1), half = QS == 32 ? lane >> 5 : 0;
+  const int tIdx = xcd_run_remap<kResizeXcdRun>((int)blockIdx.x, (int)gridDim.x, (int)blockIdx.z);
+  const int bandI = __builtin_amdgcn_readfirstlane((int)(((float)tIdx + 0.5f) * __builtin_amdgcn_rcpf((float)a.nStrips)));
+  const int strip = tIdx - bandI * a.nStrips;
+  const int img0 = (int)blockIdx.z * (64 / QS);
+  const uint4* lt = a.lanes + (size_t)strip * (3 * QS) + q;
+  const uint4 sel = lt[0], coef = lt[QS], misc = lt[2 * QS];
+  // lanes past the level's last quad, and the second half-wave past an odd batch's last image, have nothing to do (no barrier
+  // follows: they leave)
+  if (misc.y == 0xFFFFFFFFu || img0 + half >= a.nimg) return;
+  const uint32_t soff = misc.x + (uint32_t)half * (uint32_t)a.srcImg;   // (launch_resize_stream: both fit 32 bits)
+  const uint32_t doff = misc.y + (uint32_t)half * (uint32_t)a.dstImg;
+  const int y0 = bandI * a.band, y1 = min(y0 + a.band, a.dh) - 1;
+  const uint32_t* yr = yrow + a.ycoef;
+  const uint32_t* yb = yab + a.ycoef;
+  const int rb = (int)(yr[y0] & 0xFFFFu), re = (int)(yr[y1] >> 16);   // source rows of the band (clamped to the level by build_yrow)
+  const uint8_t* srcImg = a.src + (long long)img0 * a.srcImg;
+  uint8_t* dstRow = a.dst + (long long)img0 * a.dstImg + (long long)y0 * a.dpitch;
+  uint32_t kRound = 0x20000u;   // vblend4's "+ 2" (a VGPR: the products' one scalar operand is the row's coefficient pair)
+  asm volatile("" : "+v"(kRound));
+  // row constants of the next destination row to emit (n0) and of the one after it (n1: in flight while n0 is used)
+  int dy = y0;
+  uint32_t n0rr = yr[y0], n0bb = yb[y0];
+  uint32_t n1rr = yr[min(y0 + 1, y1)], n1bb = yb[min(y0 + 1, y1)];
+  uint2 cur = make_uint2(0u, 0u), prev = cur;
+  auto load = [&](uint2 (&v)[K], int r) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {   // rows past the band's last one: that row again (inside the level; never used)
+      // scalar image base + 32-bit lane offset (row offset added per lane in 32 bits: launch_resize_stream checks that it fits)
+      const uint32_t o = soff + (uint32_t)(min(r + k, re) * a.sp);
+      const ResizeU64Unaligned t = *reinterpret_cast<const ResizeU64Unaligned*>(srcImg + o);
+      v[k] = make_uint2(t.x, t.y);
+    }
+  };
+  auto use = [&](const uint2 (&v)[K], int r) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const int rk = r + k;
+      if (rk > re) break;
+      const uint32_t t0 = udot2_u16(__builtin_amdgcn_perm(v[k].y, v[k].x, sel.x), coef.x, 0u);
+      const uint32_t t1 = udot2_u16(__builtin_amdgcn_perm(v[k].y, v[k].x, sel.y), coef.y, 0u);
+      const uint32_t t2 = udot2_u16(__builtin_amdgcn_perm(v[k].y, v[k].x, sel.z), coef.z, 0u);
+      const uint32_t t3 = udot2_u16(__builtin_amdgcn_perm(v[k].y, v[k].x, sel.w), coef.w, 0u);
+      prev = cur;
+      cur.x = t0 >> 4;   // (t >> 4) as u16 pairs, as k_resize's horizontal pass packs them
+      cur.y = t2 >> 4;
+      asm("v_lshrrev_b32_sdwa %0, 4, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(cur.x) : "v"(t1));
+      asm("v_lshrrev_b32_sdwa %0, 4, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(cur.y) : "v"(t3));
+      // The scale factor is above 1: a source row closes at most one destination row, except where the level's last row is the
+      // clamped lower row of more than one (the tables decide).  Upper row = lower row only under that clamp.
+      while (dy <= y1 && (int)(n0rr >> 16) == rk) {
+        const bool same = (n0rr & 0xFFFFu) == (n0rr >> 16);
+        const uint32_t outw = vblend4(same ? cur : prev, cur, n0bb, kRound);
+        asm volatile("global_store_dword %0, %1, %2" : : "v"(doff), "v"(outw), "s"(dstRow) : "memory");
+        dstRow += a.dpitch;
+        dy++;
+        n0rr = n1rr, n0bb = n1bb;
+        const int nx = min(dy + 1, y1);
+        n1rr = yr[nx], n1bb = yb[nx];
+      }
+    }
+  };
+  // Two batches alternate, one in use and one in flight; the band's last batch is used with nothing behind it, so that no
+  // batch is loaded past the band (a batch loaded for nothing cost a third of the band's loads at 21 rows in batches of 4).
+  uint2 A[K], B[K];
+  load(A, rb);
+  for (int r = rb;; r += 2 * K) {
+    if (r + K > re) { use(A, r); break; }
+    load(B, r + K);
+    use(A, r);
+    if (r + 2 * K > re) { use(B, r + K); break; }
+    load(A, r + 2 * K);
+    use(B, r + K);
+  }
+}
+
+// May level `level` of this batch go through k_resize_stream?  The lanes add their image's and their row's offset in 32 bits.
+bool resize_stream_ok(const Geom& g, const Pyr& p, int level, int quads, const int* laneOff) {
+  if (level < 1 || level >= g.nlevels || laneOff[level] < 0) return false;
+  const long long sp = level == 1 ? p.l0Row : g.lv[level - 1].pitch, si = level == 1 ? p.l0Img : g.pyrImg;
+  const long long lim = 1ll << 31;
+  if (sp < 0 || sp * g.lv[level - 1].h >= lim) return false;
+  if (quads == 32 && (si < 0 || si + sp * g.lv[level - 1].h >= lim || g.pyrImg + (long long)g.lv[level].pitch * g.lv[level].h >= lim)) return false;
+  return true;
+}
+
+hipError_t launch_resize_stream(const Geom& g, const Pyr& p, int nimg, int level, const uint4* lanes, int quads, int band,
+                                const uint32_t* yrow, const short* yab, hipStream_t s) {
+  const LevelDev &D = g.lv[level], &S = g.lv[level - 1];
+  StreamLv a;
+  if (level == 1) {
+    a.src = p.l0; a.srcImg = p.l0Img; a.sp = (int)p.l0Row;
+  } else {
+    a.src = p.pyr + S.off; a.srcImg = g.pyrImg; a.sp = S.pitch;
+  }
+  a.dst = p.pyr + D.off; a.dstImg = g.pyrImg; a.dpitch = D.pitch;
+  a.dh = D.h; a.ycoef = D.ycoef;
+  a.nStrips = ((D.w + 3) / 4 + quads - 1) / quads;
+  a.band = band;
+  a.nimg = nimg;
+  a.lanes = lanes;
+  const int nBands = (D.h + band - 1) / band;
+  const dim3 grid(a.nStrips * nBands, 1, quads == 32 ? (nimg + 1) / 2 : nimg);
+  const uint32_t* yabw = reinterpret_cast<const uint32_t*>(yab);
+  if (quads == 32) hipLaunchKernelGGL(k_resize_stream<32>, grid, dim3(64), 0, s, a, yrow, yabw);
+  else hipLaunchKernelGGL(k_resize_stream<64>, grid, dim3(64), 0, s, a, yrow, yabw);
+  return hipGetLastError();
 }
 
 }  // namespace orbx
